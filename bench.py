@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""bench.py -- frames/s of the ORB front end (N-camera extract + match) on MI355X, with the matcher rooflines and the
-CPU baseline in the same run.
+"""bench.py -- frames/s of the ORB front end (N-camera extract + match) on MI355X; with --full also the oracle parity gate,
+the other timing legs, the matcher rooflines, the drop-in class path and the CPU baseline in the same run.
 
-  python bench.py --gpus N --steps K --warmup W [--config 1|2|3|4]
+  python bench.py --gpus N --steps K --warmup W [--config 1|2|3|4] [--dump-outputs DIR] [--full]
   (N > 1: one rank per GPU over RCCL -- launched by torch.distributed.run, or, when run as a plain process, by bench.py
   itself: the parent starts N rank processes before it touches a GPU and relays rank 0's line)
 
@@ -18,10 +18,15 @@ HBM before the timed region.  --config selects the BASELINE.json workload:
 With N > 1 the cross-camera matcher sees every rank's descriptors through ONE RCCL all-gather per step, issued natively
 from inside the step.  `value` = rig timesteps per second of the whole job (weak: summed over the ranks' rigs).
 
-Timing: W warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + device synchronisation, repeated until
-at least --min-time seconds have been timed (so that a short K still gives a stable figure); `ms_per_step` is the median
-block, per-step median / p5 / p95 come from host timestamps of the individual step calls (each ends with the step's single
-synchronisation).  Before anything is timed the GPU results are compared bit for bit with the CPU oracle.
+Timing: W warm-up steps, then ONE block of exactly K steps, bracketed by barrier + device synchronisation; `ms_per_step` is
+the block's time over K, per-step median / p5 / p95 come from host timestamps of the individual step calls (each ends with
+the step's single synchronisation).  --dump-outputs DIR writes the arrays the last timed step handed its caller as
+DIR/<name>.npy (float32 / float64; the inputs are the same synthetic stream in every run with the same arguments).
+
+A plain run does nothing else.  --full adds, as separate legs: the parity gate before anything is timed (the GPU results
+compared bit for bit with the CPU oracle), the loop fed from page-locked host memory, the loop inside the library, the
+isolated-step latencies, the extractor's stage times, the rooflines, the drop-in class path and the CPU baseline
+(--min-time sets how long each of the repeated legs is timed).
 """
 import argparse
 import json
@@ -82,10 +87,13 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=None, help="GPUs = rank processes.  Under a launcher (WORLD_SIZE set) it must equal the "
                     "world size; on its own `--gpus N` with N > 1 starts the N ranks itself.  Default: WORLD_SIZE, else 1")
     ap.add_argument("--plan-only", action="store_true", help="no GPU: launch / rendezvous (gloo) / sharding plan only, one JSON line")
-    ap.add_argument("--steps", type=int, default=None, help="steps per timed block (default 2000; 100 for --config 4)")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 2000; 100 for --config 4)")
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", type=int, default=1, choices=sorted(CONFIGS))
-    ap.add_argument("--min-time", type=float, default=0.25, help="keep timing blocks of --steps steps until this many seconds are covered")
+    ap.add_argument("--full", action="store_true", help="also the parity gate, the other timing legs, rooflines, drop-in and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--min-time", type=float, default=0.25, help="--full legs: keep timing blocks of --steps steps until this many seconds are covered")
     ap.add_argument("--no-overlap", action="store_true", help="every step extracts its own images first (no orbf_prefetch)")
     ap.add_argument("--ahead", type=int, default=3, choices=[1, 2, 3],
                     help="timesteps whose images the front end knows ahead of the step it matches (orbf_prefetch); default 3")
@@ -101,6 +109,8 @@ def parse(argv=None):
         a.steps = 100 if a.config == 4 else 2000
     if a.warmup is None:
         a.warmup = 10 if a.config == 4 else 200
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     return a
 
 
@@ -377,6 +387,40 @@ def extract_alg_bytes(width, height, nfeatures, nlevels=8, scale=1.2):
     return b + 60.0 * nfeatures
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(r, outdir, prefix="", limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: the arrays FrontEnd.step handed its caller in the last timed step -> outdir/<prefix><name>.npy.  Float
+    fields and descriptor bytes as float32, integer fields as float64 (both exact); the keypoint record one file per field.  Above
+    `limit` bytes the per-feature arrays keep the same seeded sample of rows (sorted), whose indices go to feature_index.npy.
+    Returns {name: shape}."""
+    import numpy as np
+    arrs = {"counts": np.asarray(r["counts"]), "n_temporal": np.asarray([r["n_temporal"]]), "n_cross": np.asarray([r["n_cross"]])}
+    kps = np.asarray(r["kps"])
+    for f in kps.dtype.names:
+        arrs["kps_" + f] = kps[f]
+    for k in ("desc", "uright", "depth", "un_x", "un_y", "match_of_feature"):
+        arrs[k] = np.asarray(r[k])
+    if "cross" in r:
+        for k, v in zip(("cross_best_idx", "cross_best_dist", "cross_second_dist"), r["cross"]):
+            arrs[k] = np.asarray(v)
+    arrs = {k: v.astype(np.float32 if v.dtype.kind == "f" or v.dtype.itemsize == 1 else np.float64) for k, v in arrs.items()}
+    n = len(kps)
+    per_feature = [k for k, v in arrs.items() if v.ndim >= 1 and len(v) == n and k not in ("counts", "n_temporal", "n_cross")]
+    total = sum(v.nbytes for v in arrs.values())
+    if total > limit and n > 0:
+        row = sum(arrs[k].nbytes for k in per_feature) / float(n)
+        keep = max(0, min(n, int((limit - (total - row * n)) // (row + 8.0))))     # (+ 8 B per row: its float64 index)
+        idx = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        arrs = {k: (v[idx] if k in per_feature else v) for k, v in arrs.items()}
+        arrs["feature_index"] = idx.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(outdir, prefix + k + ".npy"), np.ascontiguousarray(v))
+    return {k: list(v.shape) for k, v in arrs.items()}
+
+
 # ------------------------------------------------------------------------------------------------ main
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -492,50 +536,52 @@ def main(argv=None):
             if transport != "peer":
                 dist.barrier(device_ids=[local])
 
-    # ---- parity gate, on EVERY rank of any world size: this rank's cameras bit for bit against the CPU oracle on the call
-    # pattern of the timed loop (keypoint records, descriptors, stereo, undistorted positions, the temporal search with its
-    # rotation histogram), and the rig-wide cross-camera top-2 of this rank's features against the oracle's brute force over
-    # the descriptors of every OTHER camera of the job -- which the oracle extracts itself from the other ranks' synthetic
-    # images (nothing a GPU produced goes into the expectation).  One host thread per camera (the oracle's C entry points
-    # release the GIL).
-    from oracle_pipeline import OracleFrontEnd, assert_same_step
-    import oracle
-    from concurrent.futures import ThreadPoolExecutor
-    job_cams = list(range(world * P["rig_cams"])) if P["scaling"] == "weak" else list(range(P["rig_cams"]))
-    if not use_dist or world == 1:
-        job_cams = list(gcam)
-    other_g = [g for g in job_cams if g not in gcam]
-    n_gate = 2 if a.config == 4 else 5
-    t_gate = time.perf_counter()
-    ofe = OracleFrontEnd(params, W, H, gcam, cam_threads=True)
-    pool = ThreadPoolExecutor(max(1, min(len(other_g), 16))) if other_g else None
     AHEAD = max(1, min(a.ahead, fe.fe.ahead_depth))
-    if overlap:
-        for k in range(1, AHEAD):
-            fe.announce(frame_args(k), resident=True)
-    for t in range(n_gate):   # AHEAD future steps are announced (orbf_prefetch), as in the timed loop
-        got = fe.step(frame_args(t), resident=True, next_images=frame_args(t + AHEAD) if overlap else None)
-        desc_of = {}
-        if other_g:
-            ext = lambda g: oracle.extract(synth.image(g, t % RING, W, H), nfeatures=NFEAT)[1]
-            desc_of = dict(zip(other_g, pool.map(ext, other_g)))
-        seen_own = {}
+    parity = None
+    if a.full:
+        # ---- parity gate, on EVERY rank of any world size: this rank's cameras bit for bit against the CPU oracle on the call
+        # pattern of the timed loop (keypoint records, descriptors, stereo, undistorted positions, the temporal search with its
+        # rotation histogram), and the rig-wide cross-camera top-2 of this rank's features against the oracle's brute force over
+        # the descriptors of every OTHER camera of the job -- which the oracle extracts itself from the other ranks' synthetic
+        # images (nothing a GPU produced goes into the expectation).  One host thread per camera (the oracle's C entry points
+        # release the GIL).
+        from oracle_pipeline import OracleFrontEnd, assert_same_step
+        import oracle
+        from concurrent.futures import ThreadPoolExecutor
+        job_cams = list(range(world * P["rig_cams"])) if P["scaling"] == "weak" else list(range(P["rig_cams"]))
+        if not use_dist or world == 1:
+            job_cams = list(gcam)
+        other_g = [g for g in job_cams if g not in gcam]
+        n_gate = 2 if a.config == 4 else 5
+        t_gate = time.perf_counter()
+        ofe = OracleFrontEnd(params, W, H, gcam, cam_threads=True)
+        pool = ThreadPoolExecutor(max(1, min(len(other_g), 16))) if other_g else None
+        if overlap:
+            for k in range(1, AHEAD):
+                fe.announce(frame_args(k), resident=True)
+        for t in range(n_gate):   # AHEAD future steps are announced (orbf_prefetch), as in the timed loop
+            got = fe.step(frame_args(t), resident=True, next_images=frame_args(t + AHEAD) if overlap else None)
+            desc_of = {}
+            if other_g:
+                ext = lambda g: oracle.extract(synth.image(g, t % RING, W, H), nfeatures=NFEAT)[1]
+                desc_of = dict(zip(other_g, pool.map(ext, other_g)))
+            seen_own = {}
 
-        def others(c):
-            return [desc_of[g] if g in desc_of else seen_own[g] for g in job_cams if g != gcam[c]]
-        # the oracle front end extracts this rank's cameras first and then asks for the others per camera
-        own_hook = lambda per_cam: seen_own.update({g: per_cam[i][1] for i, g in enumerate(gcam)})
-        exp = ofe.step(host_frames[t % RING], other_descs=others if other_g else None, on_extracted=own_hook)
-        assert_same_step(got, exp)
-    if pool is not None:
-        pool.shutdown()
-    if hasattr(ofe, "pool") and ofe.pool is not None:
-        ofe.pool.shutdown()
-    parity = ("bit-exact vs oracle on %d steps, all %d camera(s) of this rank at full size (keypoints, descriptors, stereo, temporal "
-              "matches incl. rotation histogram) + the complete cross-camera top-2 against the oracle's brute force over %d camera(s) "
-              "of the job; every rank runs the gate (%.1f s on rank 0)" % (n_gate, NC, len(job_cams), time.perf_counter() - t_gate))
-    fe.reset()
-    sync_all(long_wait=True)      # a rank whose gate failed has raised by now: its exit stops the job
+            def others(c):
+                return [desc_of[g] if g in desc_of else seen_own[g] for g in job_cams if g != gcam[c]]
+            # the oracle front end extracts this rank's cameras first and then asks for the others per camera
+            own_hook = lambda per_cam: seen_own.update({g: per_cam[i][1] for i, g in enumerate(gcam)})
+            exp = ofe.step(host_frames[t % RING], other_descs=others if other_g else None, on_extracted=own_hook)
+            assert_same_step(got, exp)
+        if pool is not None:
+            pool.shutdown()
+        if hasattr(ofe, "pool") and ofe.pool is not None:
+            ofe.pool.shutdown()
+        parity = ("bit-exact vs oracle on %d steps, all %d camera(s) of this rank at full size (keypoints, descriptors, stereo, temporal "
+                  "matches incl. rotation histogram) + the complete cross-camera top-2 against the oracle's brute force over %d camera(s) "
+                  "of the job; every rank runs the gate (%.1f s on rank 0)" % (n_gate, NC, len(job_cams), time.perf_counter() - t_gate))
+        fe.reset()
+        sync_all(long_wait=True)      # a rank whose gate failed has raised by now: its exit stops the job
 
     ahead = [0]   # index of the youngest timestep announced so far
     stamps = []   # host timestamps after every step call of the current block
@@ -549,6 +595,7 @@ def main(argv=None):
             for k in range(max(ahead[0] + 1, t0 + 1), t0 + AHEAD):
                 fe.announce(frame_args(k, pinned), resident=res); ahead[0] = k
         pc = time.perf_counter
+        r = None
         for i in range(nsteps):
             if overlap:
                 ahead[0] = t0 + i + AHEAD
@@ -557,16 +604,20 @@ def main(argv=None):
                 stamps.append(pc())
                 if not overlap:              # (the library's own clock is only read for the isolated-latency figures)
                     native_us.append(r["host_us"])
+        return r          # the last step's result (consumed in place: valid until the next step)
+
+    last = [None]   # result of the last step timed_blocks ran
 
     def timed_blocks(K, t0, min_time, overlap=overlap, pinned=False):
-        """blocks of exactly K steps, barrier + synchronise on both sides of each; -> (block seconds [max over ranks], per-step s)"""
+        """blocks of exactly K steps, barrier + synchronise on both sides of each, until min_time is covered (one block for
+        min_time 0); -> (block seconds [max over ranks], per-step s)"""
         blocks, per_step, covered, t = [], [], 0.0, t0
         n_blocks = None
         while True:
             sync_all()
             del stamps[:]
             t_start = time.perf_counter()
-            run(K, t, overlap, pinned, record=True)
+            last[0] = run(K, t, overlap, pinned, record=True)
             # closing bracket: this rank's work has drained (synchronise), its clock is read, and the MAX over the ranks -- the
             # moment the slowest rank was done -- is the block's time; the reduction itself is the closing barrier and stays
             # outside the clock (a barrier's own latency is not the path's)
@@ -604,73 +655,82 @@ def main(argv=None):
     import gc
     gc.collect(); gc.freeze(); gc.disable()
     run(a.warmup, 0)
-    blocks, per_step, t_next = timed_blocks(a.steps, a.warmup, a.min_time)
+    # the headline: exactly --steps timed steps, in one block
+    blocks, per_step, t_next = timed_blocks(a.steps, a.warmup, 0.0)
     med_block = pct(blocks, 50)
     rigs = P["rigs"]
     value = rigs * a.steps / med_block
+    dumped = None
+    if a.dump_outputs:
+        # what the last timed step handed its caller, written before any other step reuses the buffers it lies in
+        dumped = dump_outputs(last[0], a.dump_outputs, "" if world == 1 else "rank%d_" % rank)
+    last[0] = None
 
-    # ---- the same loop fed from page-locked HOST memory: the H2D copy of every image (PCIe) is inside the timed region
-    h2d = None
-    if world == 1:
+    if a.full:
+        # ---- the same loop fed from page-locked HOST memory: the H2D copy of every image (PCIe) is inside the timed region
+        h2d = None
+        if world == 1:
+            fe.reset(); ahead[0] = 0
+            run(min(a.warmup, 50), 0, overlap, pinned=True)
+            b2, ps2, _ = timed_blocks(a.steps, min(a.warmup, 50), a.min_time, overlap, pinned=True)
+            h2d = {"value": round(rigs * a.steps / pct(b2, 50), 2), "ms_per_step": round(1e3 * pct(b2, 50) / a.steps, 4),
+                   "bytes_per_step": NC * W * H, "source": "page-locked host memory, hipMemcpy2DAsync inside the step"}
+        # ---- the same overlapped loop inside the library (orbf_run_stream: prefetch + orbf_step_motion + the accepted-match count per
+        # step, one native call per block): the stream as a C or C++ host would drive it, without the Python binding around every step
+        c_abi_loop = None
+        if world == 1:
+            from multi_orb_slam_amd.matcher import TH_LOW
+            fe.reset(); ahead[0] = 0
+            ring = [[(dev_frames[t][c].ptr, W, H, W, 1) for c in range(NC)] for t in range(RING)]
+            motion = (pipeline.MOTION[0], pipeline.MOTION[1], pipeline.TH_PROJ)
+            la = AHEAD if overlap else 0
+            upto, t_loop = -1, 0
+            _st, upto = fe.fe.run_stream(ring, t_loop, min(a.warmup, 50), la, upto, motion, TH_LOW, pipeline.BOW_RATIO); t_loop += min(a.warmup, 50)
+            blk, covered = [], 0.0
+            while True:
+                sync_all()
+                t_start = time.perf_counter()
+                _st, upto = fe.fe.run_stream(ring, t_loop, a.steps, la, upto, motion, TH_LOW, pipeline.BOW_RATIO)
+                sync_all()
+                el = time.perf_counter() - t_start
+                blk.append(el); covered += el; t_loop += a.steps
+                if covered >= a.min_time or len(blk) >= 200:
+                    break
+            c_abi_loop = {"value": round(rigs * a.steps / pct(blk, 50), 2), "ms_per_step": round(1e3 * pct(blk, 50) / a.steps, 4), "blocks": len(blk),
+                          "what": "orbf_run_stream: the same steps (%d announced ahead, accepted-match count included) driven from inside the library" % la}
+        # ---- one isolated timestep: no look-ahead, every step extracts its own images first (what a live rig sees as latency)
         fe.reset(); ahead[0] = 0
-        run(min(a.warmup, 50), 0, overlap, pinned=True)
-        b2, ps2, _ = timed_blocks(a.steps, min(a.warmup, 50), a.min_time, overlap, pinned=True)
-        h2d = {"value": round(rigs * a.steps / pct(b2, 50), 2), "ms_per_step": round(1e3 * pct(b2, 50) / a.steps, 4),
-               "bytes_per_step": NC * W * H, "source": "page-locked host memory, hipMemcpy2DAsync inside the step"}
-    # ---- the same overlapped loop inside the library (orbf_run_stream: prefetch + orbf_step_motion + the accepted-match count per
-    # step, one native call per block): the stream as a C or C++ host would drive it, without the Python binding around every step
-    c_abi_loop = None
-    if world == 1:
-        from multi_orb_slam_amd.matcher import TH_LOW
+        n_iso = max(20, min(200, a.steps))
+        run(min(20, a.warmup), 0, False)
+        del native_us[:]
+        _b3, ps3, _ = timed_blocks(n_iso, 20, min(a.min_time, 0.1), overlap=False)
+        iso = latency(ps3, native_us)
+        # ---- the live-rig number: the same isolated step with the images in page-locked HOST memory -- no look-ahead, the H2D
+        # copies of all cameras inside the step (what Frame::Frame, src/Frame.cc:148-288, would wait for on a rig that delivers
+        # host images)
         fe.reset(); ahead[0] = 0
-        ring = [[(dev_frames[t][c].ptr, W, H, W, 1) for c in range(NC)] for t in range(RING)]
-        motion = (pipeline.MOTION[0], pipeline.MOTION[1], pipeline.TH_PROJ)
-        la = AHEAD if overlap else 0
-        upto, t_loop = -1, 0
-        _st, upto = fe.fe.run_stream(ring, t_loop, min(a.warmup, 50), la, upto, motion, TH_LOW, pipeline.BOW_RATIO); t_loop += min(a.warmup, 50)
-        blk, covered = [], 0.0
-        while True:
-            sync_all()
-            t_start = time.perf_counter()
-            _st, upto = fe.fe.run_stream(ring, t_loop, a.steps, la, upto, motion, TH_LOW, pipeline.BOW_RATIO)
-            sync_all()
-            el = time.perf_counter() - t_start
-            blk.append(el); covered += el; t_loop += a.steps
-            if covered >= a.min_time or len(blk) >= 200:
-                break
-        c_abi_loop = {"value": round(rigs * a.steps / pct(blk, 50), 2), "ms_per_step": round(1e3 * pct(blk, 50) / a.steps, 4), "blocks": len(blk),
-                      "what": "orbf_run_stream: the same steps (%d announced ahead, accepted-match count included) driven from inside the library" % la}
-    # ---- one isolated timestep: no look-ahead, every step extracts its own images first (what a live rig sees as latency)
-    fe.reset(); ahead[0] = 0
-    n_iso = max(20, min(200, a.steps))
-    run(min(20, a.warmup), 0, False)
-    del native_us[:]
-    _b3, ps3, _ = timed_blocks(n_iso, 20, min(a.min_time, 0.1), overlap=False)
-    iso = latency(ps3, native_us)
-    # ---- the live-rig number: the same isolated step with the images in page-locked HOST memory -- no look-ahead, the H2D
-    # copies of all cameras inside the step (what Frame::Frame, src/Frame.cc:148-288, would wait for on a rig that delivers
-    # host images)
-    fe.reset(); ahead[0] = 0
-    run(min(20, a.warmup), 0, False, pinned=True)
-    del native_us[:]
-    _b4, ps4, _ = timed_blocks(n_iso, 20, min(a.min_time, 0.1), overlap=False, pinned=True)
-    iso_h2d = latency(ps4, native_us)
-    iso_h2d["bytes_per_step"] = NC * W * H
-    fe.reset(); ahead[0] = 0
-    gc.enable(); gc.unfreeze()
+        run(min(20, a.warmup), 0, False, pinned=True)
+        del native_us[:]
+        _b4, ps4, _ = timed_blocks(n_iso, 20, min(a.min_time, 0.1), overlap=False, pinned=True)
+        iso_h2d = latency(ps4, native_us)
+        iso_h2d["bytes_per_step"] = NC * W * H
+        fe.reset(); ahead[0] = 0
+        gc.enable(); gc.unfreeze()
 
-    # per-stage GPU time of the extractor (HIP events): median over several profiled isolated steps (a single probe is noisy)
-    fe.ex.set_profiling(True)
-    probes = []
-    for t in range(12):
-        fe.step(frame_args(t), resident=True)
-        if t >= 2:
-            probes.append(fe.ex.stage_times_us())
-    fe.ex.set_profiling(False)
-    stages = {k: pct([p[k] for p in probes], 50) for k in probes[0]}
-    ex_us = sum(stages[k] for k in ("pyramid", "fast_cells", "compact", "quadtree", "describe"))
-    ex_bytes = NC * extract_alg_bytes(W, H, NFEAT)
-    ex_ach = ex_bytes / (ex_us * 1e-6) / 1e9 if ex_us > 0 else 0.0
+        # per-stage GPU time of the extractor (HIP events): median over several profiled isolated steps (a single probe is noisy)
+        fe.ex.set_profiling(True)
+        probes = []
+        for t in range(12):
+            fe.step(frame_args(t), resident=True)
+            if t >= 2:
+                probes.append(fe.ex.stage_times_us())
+        fe.ex.set_profiling(False)
+        stages = {k: pct([p[k] for p in probes], 50) for k in probes[0]}
+        ex_us = sum(stages[k] for k in ("pyramid", "fast_cells", "compact", "quadtree", "describe"))
+        ex_bytes = NC * extract_alg_bytes(W, H, NFEAT)
+        ex_ach = ex_bytes / (ex_us * 1e-6) / 1e9 if ex_us > 0 else 0.0
+    else:
+        gc.enable(); gc.unfreeze()
 
     # (ranks that share a device -- the peer transport's rehearsal on a box with fewer GPUs than ranks -- are not GPUs that worked)
     n_gpus_used = world if not (use_dist and world > 1 and shared_devices) else ndev
@@ -686,22 +746,10 @@ def main(argv=None):
                                          "max": round(1e3 * max(blocks) / a.steps, 4)},
                    "step_ms": {"median": round(1e3 * pct(per_step, 50), 4), "p5": round(1e3 * pct(per_step, 5), 4),
                                "p95": round(1e3 * pct(per_step, 95), 4), "n": len(per_step)}},
-        "value_c_abi_loop": c_abi_loop["value"] if c_abi_loop else None, "c_abi_loop": c_abi_loop,
-        "latency_ms_isolated": iso["median"], "latency_isolated": iso,
-        "latency_ms_isolated_h2d": iso_h2d["median"], "latency_isolated_h2d": iso_h2d,
-        "value_isolated": round(rigs * 1e3 / iso["median"], 2),
-        "value_h2d_inclusive": h2d["value"] if h2d else None, "h2d_inclusive": h2d,
-        "parity": parity,
+        "full": a.full, "dumped_outputs": dumped,
         "ahead": AHEAD if overlap else 0,
         "overlap": ("the extractions of timesteps t+1 .. t+%d run next to the matching of timestep t (orbf_prefetch); `value` needs "
                     "the images %d steps ahead, `latency_ms_isolated` / `value_isolated` do not" % (AHEAD, AHEAD)) if overlap else "off",
-        "extractor_stage_us": {k: round(v, 1) for k, v in stages.items()},
-        "roofline_extract": {"kernel": "extraction chain (k_pyramid_tiled [k_ingest], k_fast_cells, k_octree, k_describe)", "bound": "hbm",
-                             "achieved": round(ex_ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ex_ach / HBM_PEAK_GBS, 5),
-                             "alg_bytes_per_image": extract_alg_bytes(W, H, NFEAT), "images": NC, "chain_us": round(ex_us, 1),
-                             "traffic": _pmc_extract_bytes(a.config), "traffic_unit": "HBM bytes per image of THIS configuration (stored counter passes)",
-                             "note": "SURVEY 8(d): W*H + 2*sum(levels>=1) + 60*N per image over the GPU time of one isolated extraction "
-                                     "chain (HIP events, median of 10 steps); a latency chain of small launches, not a bandwidth kernel"},
         "exchange": ("none (one rank)" if not use_dist else
                      ("peer transport: every rank writes its descriptor block straight into every other rank's IPC-mapped arena (one put kernel + "
                       "one wait kernel per step, no RCCL), issued at the tail of the step's extraction chain; %d rank process(es) on %d GPU(s)%s"
@@ -714,7 +762,23 @@ def main(argv=None):
                      if getattr(fe, "native_exchange", False) else
                      "one RCCL all-gather of the step's descriptor block per step through torch.distributed"),
     }
-    if rank == 0 and not a.no_roofline:
+    if a.full:
+        out.update({
+            "value_c_abi_loop": c_abi_loop["value"] if c_abi_loop else None, "c_abi_loop": c_abi_loop,
+            "latency_ms_isolated": iso["median"], "latency_isolated": iso,
+            "latency_ms_isolated_h2d": iso_h2d["median"], "latency_isolated_h2d": iso_h2d,
+            "value_isolated": round(rigs * 1e3 / iso["median"], 2),
+            "value_h2d_inclusive": h2d["value"] if h2d else None, "h2d_inclusive": h2d,
+            "parity": parity,
+            "extractor_stage_us": {k: round(v, 1) for k, v in stages.items()},
+            "roofline_extract": {"kernel": "extraction chain (k_pyramid_tiled [k_ingest], k_fast_cells, k_octree, k_describe)", "bound": "hbm",
+                                 "achieved": round(ex_ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ex_ach / HBM_PEAK_GBS, 5),
+                                 "alg_bytes_per_image": extract_alg_bytes(W, H, NFEAT), "images": NC, "chain_us": round(ex_us, 1),
+                                 "traffic": _pmc_extract_bytes(a.config), "traffic_unit": "HBM bytes per image of THIS configuration (stored counter passes)",
+                                 "note": "SURVEY 8(d): W*H + 2*sum(levels>=1) + 60*N per image over the GPU time of one isolated extraction "
+                                         "chain (HIP events, median of 10 steps); a latency chain of small launches, not a bandwidth kernel"},
+        })
+    if a.full and rank == 0 and not a.no_roofline:
         out["roofline"] = matcher_roofline(rt, m, fe.stream, a.matrix_n)
         live = None if a.no_live_traffic else live_matrix_traffic(a.matrix_n)
         if live and live.get("hbm_bytes_per_launch"):
@@ -725,11 +789,11 @@ def main(argv=None):
             out["roofline"]["traffic_source"] = {"source": "stored counter passes (profiles/pmc_traffic.json)", "live": live}
         out["roofline_m1"] = top2_roofline(rt, m, fe.stream, a.matrix_n)
         out["roofline_m3"] = project_roofline(m)
-    if rank == 0 and world == 1 and not a.no_dropin and a.config == 1:
+    if a.full and rank == 0 and world == 1 and not a.no_dropin and a.config == 1:
         import dropin_leg       # tests/dropin_leg.py: the C++ classes with the reference's signatures, reference call pattern
         out["dropin"] = dropin_leg.bench(W, H, NFEAT)
         out["dropin_fps"] = out["dropin"]["dropin_fps"]
-    if rank == 0 and not a.no_cpu:
+    if a.full and rank == 0 and not a.no_cpu:
         # the CPU baseline of the unit `value` counts: one rig timestep.  Weak configurations: this rank's own rig; strong
         # ones: the WHOLE rig (all cameras, whichever rank owns them), so the figure is the same at every N.
         cpu_cams = list(gcam) if P["scaling"] == "weak" else list(range(P["rig_cams"]))

@@ -4,6 +4,8 @@
 `make -C oracle ref` in the build container) for seeded synthetic inputs.  The inputs are regenerated from the seeds by
 multi_orb_slam_amd.synth at test time; the per-feature (word id, weight, node id) fed to the reference classes come from the
 oracle's descent (the descent itself cannot be built from the reference here), and are stored too.
+Also tests/golden/dbow2_ref_live.npz: the same for the cases of test_oracle_matches_reference_classes_live (LIVE_SEEDS x
+LIVE_LEVELSUP), so that the test needs no reference build.
 Run from the repo root:  python tests/golden/make_dbow2_golden.py"""
 import ctypes as C
 import os
@@ -21,6 +23,10 @@ CASES = [dict(k=10, L=3, seed=11, ragged=False, stop_every=0, n=1500, fseed=3, l
          dict(k=4, L=5, seed=23, ragged=False, stop_every=3, n=2500, fseed=1, levelsup=4),
          dict(k=10, L=2, seed=2, ragged=False, stop_every=0, n=40, fseed=4, levelsup=1),
          dict(k=3, L=3, seed=8, ragged=True, stop_every=2, n=300, fseed=6, levelsup=5)]
+
+LIVE_SEEDS = [101, 102, 103, 104]
+LIVE_LEVELSUP = (0, 1, 2, 6)
+LIVE_KEYS = ("word", "node", "weight", "bow_id", "bow_val", "fv_node", "fv_start", "fv_items")
 
 
 def ref_lib():
@@ -45,6 +51,26 @@ def case_inputs(c):
     return voc, feats
 
 
+def live_inputs(seed):
+    voc = synth.vocabulary(k=3 + seed % 7, L=3 + seed % 2, seed=seed, ragged=bool(seed & 1), stop_every=(0, 5, 2, 9)[seed % 4])
+    feats = synth.vocabulary_words(voc, 700 + 100 * (seed % 5), seed=seed, flip_p=0.1)
+    return voc, feats
+
+
+def live_vectors(L):
+    """{"s<seed>_l<levelsup>_<key>": array} for the live cases: the oracle's descent and the reference classes' vectors built from it"""
+    out = {}
+    for seed in LIVE_SEEDS:
+        voc, feats = live_inputs(seed)
+        V = oracle.Vocabulary(voc)
+        for levelsup in LIVE_LEVELSUP:
+            word, node, weight = V.transform(feats, levelsup)
+            ref = ref_build(L, np.ascontiguousarray(word), np.ascontiguousarray(weight), np.ascontiguousarray(node))
+            for k, v in zip(LIVE_KEYS, (word, node, weight) + ref):
+                out["s%d_l%d_%s" % (seed, levelsup, k)] = v
+    return out
+
+
 def main():
     L = ref_lib()
     out = {"n_cases": np.int32(len(CASES))}
@@ -58,6 +84,7 @@ def main():
                     "c%d_fv_node" % i: fn, "c%d_fv_start" % i: fs, "c%d_fv_items" % i: fi})
         print("case %d: %d features -> %d words, %d nodes" % (i, c["n"], len(bid), len(fn)))
     np.savez_compressed(os.path.join(ROOT, "tests", "golden", "dbow2_ref_vectors.npz"), **out)
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "dbow2_ref_live.npz"), **live_vectors(L))
 
 
 if __name__ == "__main__":

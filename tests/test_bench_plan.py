@@ -146,3 +146,60 @@ def test_settled_launches_times_only_behind_the_transient():
     rt = _FakeClockRt([0.5 - 0.0005 * i for i in range(1000)])
     ms, used, hist = bench._settled_launches(rt, rt.launch, None, iters=10, max_groups=12)
     assert used == 120 and 0.0 < ms < 0.5
+
+
+def test_plain_run_is_lean_and_full_is_opt_in():
+    a = bench.parse(["--gpus", "1", "--steps", "30", "--warmup", "5"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 30
+    a = bench.parse(["--gpus", "1", "--steps", "30", "--warmup", "5", "--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def _fake_step(n, ncam=2, seed=1):
+    import numpy as np
+    from multi_orb_slam_amd import KP_DTYPE
+    rng = np.random.default_rng(seed)
+    kps = np.zeros(n, KP_DTYPE)
+    for f in ("x", "y", "size", "angle", "response"):
+        kps[f] = rng.random(n, np.float32) * 100
+    kps["octave"] = rng.integers(0, 8, n)
+    kps["class_id"] = -1
+    return {"counts": [n - n // 2, n // 2], "n_temporal": 17, "n_cross": 5, "kps": kps,
+            "desc": rng.integers(0, 256, (n, 32), dtype=np.uint8), "uright": rng.random(n, np.float32),
+            "depth": rng.random(n, np.float32), "un_x": rng.random(n, np.float32), "un_y": rng.random(n, np.float32),
+            "match_of_feature": rng.integers(-1, n, n, dtype=np.int32),
+            "cross": tuple(rng.integers(0, 256, n, dtype=np.int32) for _ in range(3)), "host_us": (1.0, 2.0, 3.0, 4.0)}
+
+
+def test_dump_outputs_writes_every_array_exactly_as_float(tmp_path):
+    import numpy as np
+    r = _fake_step(500)
+    shapes = bench.dump_outputs(r, str(tmp_path))
+    names = {p.name[:-4] for p in tmp_path.iterdir()}
+    assert names == set(shapes) and "host_us" not in names and "feature_index" not in names
+    for name in names:
+        assert np.load(tmp_path / (name + ".npy")).dtype in (np.float32, np.float64), name
+    assert np.array_equal(np.load(tmp_path / "desc.npy"), r["desc"].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "kps_octave.npy"), r["kps"]["octave"])
+    assert np.load(tmp_path / "kps_x.npy").tobytes() == r["kps"]["x"].tobytes()
+    assert np.array_equal(np.load(tmp_path / "match_of_feature.npy"), r["match_of_feature"])
+    assert np.array_equal(np.load(tmp_path / "cross_second_dist.npy"), r["cross"][2])
+    assert list(np.load(tmp_path / "counts.npy")) == r["counts"] and np.load(tmp_path / "n_cross.npy")[0] == 5
+
+
+def test_dump_outputs_keeps_a_seeded_sample_within_the_limit(tmp_path):
+    import numpy as np
+    r = _fake_step(4000)
+    limit = 100_000
+    bench.dump_outputs(r, str(tmp_path / "a"), limit=limit)
+    bench.dump_outputs(r, str(tmp_path / "b"), limit=limit)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert sum((tmp_path / "a" / f).stat().st_size - 128 for f in files) <= limit      # (128 B: the .npy header)
+    idx = np.load(tmp_path / "a" / "feature_index.npy").astype(np.int64)
+    assert 0 < len(idx) < 4000 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "desc.npy"), r["desc"][idx].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "uright.npy"), r["uright"][idx])
+    for f in files:   # the same sample in every run
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f

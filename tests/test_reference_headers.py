@@ -10,7 +10,8 @@ lacks, is stood in for by host/cv_compat.h through the include shim host/cv_shim
      (ORBVocabulary::score / size), src/MapPoint.cc (ORBmatcher::DescriptorDistance), src/Map.cc -- must compile UNCHANGED.
      (Frame.cc / KeyFrame.cc / Tracking.cc need Eigen and Pangolin, which are absent: not attempted, not faked.)
 
-Skipped when /root/reference is absent (the GPU box)."""
+The compile checks are skipped where the reference checkout is absent (the GPU box); the container types of the stand-ins are
+checked everywhere."""
 import os
 import subprocess
 
@@ -21,7 +22,8 @@ HOST = os.path.join(ROOT, "multi_orb_slam_amd", "host")
 REF = "/root/reference"
 OURS = ["ORBmatcher.cc", "ORBextractor.cc", "ORBVocabulary.cc"]
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "include")), reason="reference checkout not present")
+HAVE_REF = os.path.isdir(os.path.join(REF, "include"))
+needs_ref = pytest.mark.skipif(not HAVE_REF, reason="reference checkout not present")
 
 
 def _syntax_only(src, includes):
@@ -34,6 +36,7 @@ def _syntax_only(src, includes):
     return p.returncode, errors
 
 
+@needs_ref
 @pytest.mark.parametrize("src", OURS)
 def test_host_sources_compile_against_the_reference_headers_in_place(src):
     rc, errors = _syntax_only(os.path.join(HOST, src),
@@ -54,6 +57,7 @@ def _replaced_tree(tmp_path):
     return str(inc)
 
 
+@needs_ref
 @pytest.mark.parametrize("src", OURS + ["ref:src/KeyFrameDatabase.cc", "ref:src/MapPoint.cc", "ref:src/Map.cc"])
 def test_replaced_headers_serve_our_sources_and_the_reference_consumers(tmp_path, src):
     inc = _replaced_tree(tmp_path)
@@ -64,9 +68,9 @@ def test_replaced_headers_serve_our_sources_and_the_reference_consumers(tmp_path
 
 def test_stand_in_types_are_the_reference_types():
     """slam_types.h must declare the two index maps with the reference's container type (include/Frame.h:256,261,
-    include/KeyFrame.h:243,248)."""
+    include/KeyFrame.h:243,248: std::unordered_map<size_t, int>); the reference's headers are read too where they are present."""
     import re
     want = re.compile(r"std::unordered_map<size_t,\s*int>\s+keypoint_to_cam")
-    for hdr in ("Frame.h", "KeyFrame.h"):
+    for hdr in ("Frame.h", "KeyFrame.h") if HAVE_REF else ():
         assert want.search(open(os.path.join(REF, "include", hdr)).read()), hdr
     assert len(want.findall(open(os.path.join(HOST, "slam_types.h")).read())) == 2

@@ -12,23 +12,23 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$ROUND/final; mkdir -p $O
 cd $R
 if [ "$1" != "prof-only" ]; then
 python -m pytest tests -m gpu -x -q 2>&1 | grep -E "passed|failed" > $O/pytest.txt
-python bench.py > $O/bench.json 2> $O/bench.err
-for c in 2 3 4; do python bench.py --config $c --no-roofline > $O/bench_c$c.json 2> $O/bench_c$c.err; done
+python bench.py --full > $O/bench.json 2> $O/bench.err
+for c in 2 3 4; do python bench.py --full --config $c --no-roofline > $O/bench_c$c.json 2> $O/bench_c$c.err; done
 # the per-rank step of a multi-GPU job, forced on this one GPU (world-1 RCCL group: one all-gather + rig-wide top-2 per step): at the
 # tail of the step's extraction chain (the default, with and without the issuer thread) and behind the step's search (rounds 2-4)
-MORB_FORCE_DIST=1 python bench.py --no-dropin --no-roofline --no-cpu > $O/bench_forced_exchange.json 2> $O/bench_forced_exchange.err
+MORB_FORCE_DIST=1 python bench.py --full --no-dropin --no-roofline --no-cpu > $O/bench_forced_exchange.json 2> $O/bench_forced_exchange.err
 # the N > 1 job rehearsed as rank PROCESSES on this one GPU (peer transport: direct writes into IPC-mapped arenas, gloo control plane)
-python bench.py --gpus 2 --no-dropin --no-roofline --no-cpu > $O/bench_2ranks_1gpu_config1_peer.json 2> $O/bench_2ranks_1gpu_config1_peer.err
-python bench.py --gpus 2 --config 3 --no-roofline --no-cpu > $O/bench_2ranks_1gpu_config3_peer.json 2> $O/bench_2ranks_1gpu_config3_peer.err
-python bench.py --gpus 4 --config 3 --no-roofline --no-cpu > $O/bench_4ranks_1gpu_config3_peer.json 2> $O/bench_4ranks_1gpu_config3_peer.err
-MORB_FORCE_DIST=1 MORB_EXCHANGE_PLACEMENT=inline python bench.py --no-dropin --no-roofline --no-cpu > $O/bench_forced_exchange_inline.json 2> $O/bench_forced_exchange_inline.err
+python bench.py --full --gpus 2 --no-dropin --no-roofline --no-cpu > $O/bench_2ranks_1gpu_config1_peer.json 2> $O/bench_2ranks_1gpu_config1_peer.err
+python bench.py --full --gpus 2 --config 3 --no-roofline --no-cpu > $O/bench_2ranks_1gpu_config3_peer.json 2> $O/bench_2ranks_1gpu_config3_peer.err
+python bench.py --full --gpus 4 --config 3 --no-roofline --no-cpu > $O/bench_4ranks_1gpu_config3_peer.json 2> $O/bench_4ranks_1gpu_config3_peer.err
+MORB_FORCE_DIST=1 MORB_EXCHANGE_PLACEMENT=inline python bench.py --full --no-dropin --no-roofline --no-cpu > $O/bench_forced_exchange_inline.json 2> $O/bench_forced_exchange_inline.err
 fi
 cd /tmp && export TMPDIR=/tmp
 export MORB_NO_BAR_STAGING=1
 export MORB_CHAIN_GRAPH=0
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o bench -- python3 $R/bench.py --no-dropin --no-live-traffic > $O/bench_under_rocprof.json 2> $O/prof_bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o bench -- python3 $R/bench.py --full --no-dropin --no-live-traffic > $O/bench_under_rocprof.json 2> $O/prof_bench.err
 if [ "$1" != "prof-only" ]; then
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c4 -o c4 -- python3 $R/bench.py --config 4 --no-roofline --no-cpu > $O/bench_c4_under_rocprof.json 2> $O/prof_c4.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c4 -o c4 -- python3 $R/bench.py --full --config 4 --no-roofline --no-cpu > $O/bench_c4_under_rocprof.json 2> $O/prof_c4.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_matcher -o matcher -- python3 $R/tools/profile_matcher.py > $O/prof_matcher.out 2> $O/prof_matcher.err
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o pmc_fetch -- python3 $R/tools/profile_matcher.py > /dev/null 2> $O/pmc_fetch.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o pmc_write -- python3 $R/tools/profile_matcher.py > /dev/null 2> $O/pmc_write.err
