@@ -145,6 +145,32 @@ int orbv_search_for_triangulation_resident(orbv_workspace* w, const orbv_keyfram
                                            const uint8_t* flags_b, const orbv_triangulation* t, int th_low, int check_orientation,
                                            int32_t* match, int* nmatches);
 
+/* Resident keyframe database: KeyFrameDatabase's inverted-file walk and the scores behind it (reference src/KeyFrameDatabase.cc:132-153,
+ * :187, :429-446, :477; LoopClosing::DetectLoop's minScore loop, src/LoopClosing.cc:150-170) without an inverted file.  Every BowVector
+ * added stays in HBM (word ids strictly ascending, values double); one pass of k_db_query over all of them gives, per entry, the number
+ * of words shared with the query, the smallest shared word and L1Scoring::score(query, entry) -- bit-identical to orbv_score_l1.
+ * One handle = one stream + scratch, one calling thread at a time.  Word ids >= n_words, unsorted or duplicate ids, n < 0 or
+ * n > 65535: ORB_E_ARG. */
+typedef struct orbv_database orbv_database;
+int orbv_db_create(int n_words, int device, orbv_database** out);
+void orbv_db_destroy(orbv_database* db);
+/* key already present: ORB_E_ARG (the database is unchanged).  n == 0 is accepted: an empty BowVector is stored (it counts in
+ * orbv_db_count and can be erased) and is never returned by a query.  The call returns after the upload has completed. */
+int orbv_db_add(orbv_database* db, uint64_t key, const uint32_t* id, const double* val, int n);
+/* unknown key: no-op, returns 0 (reference :63-97).  The arena is compacted once dead words exceed half of it. */
+int orbv_db_erase(orbv_database* db, uint64_t key);
+int orbv_db_clear(orbv_database* db);
+int orbv_db_count(const orbv_database* db); /* alive entries */
+/* Per query q: the entries that share at least one word with it, in the order the reference's lKFsSharingWords has them (ascending
+ * smallest shared word, then add order), as rows of `capacity` in key / common / score; n_hits[q] = their number.  A query with more
+ * hits than `capacity` is ORB_E_ARG, never a truncated answer (capacity = orbv_db_count() always suffices).  At most
+ * ORBV_DB_MAX_QUERIES queries per call, and n_queries x orbv_db_count() <= 2^26 (16 B per pair come back): more is ORB_E_ARG. */
+enum { ORBV_DB_MAX_QUERIES = 1024 };
+int orbv_db_query(orbv_database* db, int n_queries, const uint32_t* const* id, const double* const* val, const int* n, int capacity,
+                  uint64_t* key, int32_t* common, double* score, int* n_hits);
+/* L1 score of one query against the named entries (score[k] for keys[k]); a key that is not in the database: ORB_E_ARG. */
+int orbv_db_score(orbv_database* db, const uint32_t* id, const double* val, int n, const uint64_t* keys, int n_keys, double* score);
+
 #ifdef __cplusplus
 }
 #endif

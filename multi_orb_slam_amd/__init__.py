@@ -8,4 +8,4 @@ the tests, the benchmark and the multi-GPU driver; it contains no compute and no
 from ._lib import lib, build, LIB_PATH, OrbError, KP_DTYPE, QUERY_DTYPE  # noqa: F401
 from .extractor import Extractor, ExtractorParams, tables  # noqa: F401
 from .matcher import Matcher, FrameData, descriptor_distance, three_maxima  # noqa: F401
-from .vocabulary import Vocabulary, BowSearch, Side as BowSide, FeatureVector, score_l1  # noqa: F401
+from .vocabulary import Vocabulary, BowSearch, Side as BowSide, FeatureVector, score_l1, KeyFrameDatabase  # noqa: F401

@@ -228,6 +228,14 @@ def lib():
     L.orbf_export_features.argtypes = [vp, vp]
     L.orbv_search_by_bow_resident.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, i32, vp, vp]
     L.orbv_search_for_triangulation_resident.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
+    L.orbv_db_create.argtypes = [i32, i32, vp]
+    L.orbv_db_destroy.argtypes = [vp]; L.orbv_db_destroy.restype = None
+    L.orbv_db_add.argtypes = [vp, C.c_uint64, vp, vp, i32]
+    L.orbv_db_erase.argtypes = [vp, C.c_uint64]
+    L.orbv_db_clear.argtypes = [vp]
+    L.orbv_db_count.argtypes = [vp]
+    L.orbv_db_query.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.orbv_db_score.argtypes = [vp, vp, vp, i32, vp, i32, vp]
     _lib = L
     return L
 

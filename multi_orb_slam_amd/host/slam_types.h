@@ -134,6 +134,25 @@ public:
     std::vector<float> mvInvLevelSigma2;
     float mbf = 0, mfLogScaleFactor = 0; int mnScaleLevels = 0;
     float mnMinX = 0, mnMaxX = 0, mnMinY = 0, mnMaxY = 0;
+
+    // members KeyFrameDatabase reads or writes (include/KeyFrame.h:73-79, :172-178).  The reference's constructor initialises the two ids
+    // and the two counts to 0 (src/KeyFrame.cc:35) and leaves the two scores uninitialised: 0 here.
+    long unsigned int mnLoopQuery = 0;
+    int mnLoopWords = 0;
+    float mLoopScore = 0;
+    long unsigned int mnRelocQuery = 0;
+    int mnRelocWords = 0;
+    float mRelocScore = 0;
+    std::set<KeyFrame*> GetConnectedKeyFrames() { return mConnectedKeyFrames; }
+    std::set<KeyFrame*> GetConnectedKeyFrames_cam1() { return mConnectedKeyFrames_cam1; }
+    std::vector<KeyFrame*> GetBestCovisibilityKeyFrames(const int& N) { return FirstN(mvpOrderedConnectedKeyFrames, N); }
+    std::vector<KeyFrame*> GetBestCovisibilityKeyFrames_cam1(const int& N) { return FirstN(mvpOrderedConnectedKeyFrames_cam1, N); }
+    // the covisibility graph itself is not modelled: plain containers the caller fills (ordered: best covisibility first)
+    std::set<KeyFrame*> mConnectedKeyFrames, mConnectedKeyFrames_cam1;
+    std::vector<KeyFrame*> mvpOrderedConnectedKeyFrames, mvpOrderedConnectedKeyFrames_cam1;
+    static std::vector<KeyFrame*> FirstN(const std::vector<KeyFrame*>& v, int N) {   // src/KeyFrame.cc GetBestCovisibilityKeyFrames
+        return (int)v.size() < N ? v : std::vector<KeyFrame*>(v.begin(), v.begin() + N);
+    }
 };
 
 }  // namespace ORB_SLAM2

@@ -73,6 +73,59 @@ def score_l1(a, b):
     return _lib.lib().orbv_score_l1(ptr(ia), ptr(va), len(ia), ptr(ib), ptr(vb), len(ib))
 
 
+def _bow(b):
+    return np.ascontiguousarray(b[0], np.uint32), np.ascontiguousarray(b[1], np.float64)
+
+
+class KeyFrameDatabase:
+    """Resident keyframe database (orbv_database): BowVectors stay in HBM, a query returns the reference's lKFsSharingWords."""
+
+    def __init__(self, n_words, device=0):
+        self._h = C.c_void_p()
+        check(_lib.lib().orbv_db_create(int(n_words), device, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().orbv_db_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def add(self, key, bow):
+        ids, vals = _bow(bow)
+        check(_lib.lib().orbv_db_add(self._h, int(key), ptr(ids), ptr(vals), len(ids)))
+
+    def erase(self, key):
+        check(_lib.lib().orbv_db_erase(self._h, int(key)))
+
+    def clear(self):
+        check(_lib.lib().orbv_db_clear(self._h))
+
+    def __len__(self):
+        return _lib.lib().orbv_db_count(self._h)
+
+    def query(self, bows, capacity=None):
+        """-> per query (keys, common, score) of the entries sharing a word with it, in the order of the reference's list."""
+        qs = [_bow(b) for b in bows]
+        Q = len(qs)
+        cap = len(self) if capacity is None else int(capacity)
+        pid = (C.c_void_p * max(Q, 1))(*[a[0].ctypes.data for a in qs]); pval = (C.c_void_p * max(Q, 1))(*[a[1].ctypes.data for a in qs])
+        n = np.array([len(a[0]) for a in qs] + [0], np.int32)
+        keys, common = np.zeros(max(Q * cap, 1), np.uint64), np.zeros(max(Q * cap, 1), np.int32)
+        score, hits = np.zeros(max(Q * cap, 1), np.float64), np.zeros(max(Q, 1), np.int32)
+        check(_lib.lib().orbv_db_query(self._h, Q, pid, pval, ptr(n), cap, ptr(keys), ptr(common), ptr(score), ptr(hits)))
+        return [(keys[q * cap:q * cap + hits[q]].copy(), common[q * cap:q * cap + hits[q]].copy(), score[q * cap:q * cap + hits[q]].copy())
+                for q in range(Q)]
+
+    def score(self, bow, keys):
+        """L1 score of `bow` against the named entries."""
+        ids, vals = _bow(bow)
+        keys = np.ascontiguousarray(keys, np.uint64)
+        out = np.zeros(max(len(keys), 1), np.float64)
+        check(_lib.lib().orbv_db_score(self._h, ptr(ids), ptr(vals), len(ids), ptr(keys), len(keys), ptr(out)))
+        return out[:len(keys)]
+
+
 class Side:
     """One frame / keyframe for the BoW searches (orbv_side); keeps the arrays alive."""
 
