@@ -13,10 +13,13 @@
  *   Frame::AssignFeaturesToGrid / GetFeaturesInArea(cam, ...)
  *        reference src/Frame.cc:348-395, :574-629                                     -> orbm_frame_create / orbm_features_in_area
  *   ORBmatcher::ComputeThreeMaxima   reference src/ORBmatcher.cc:3948-3989             -> orbm_three_maxima
+ *   Tracking::SearchLocalPoints from its second loop on: Frame::isInFrustum + that SearchByProjection
+ *        reference src/Tracking.cc:1730-1768, src/Frame.cc:443-499                    -> orbm_points_*, orbm_search_local_points
  *
  * No Frame* / MapPoint* crosses the ABI: the C++ wrapper (multi_orb_slam_amd/host/ORBmatcher.h) packs flat
  * arrays.  The 3-D projection of map points stays on the host (it is cv::Mat float algebra in the reference,
- * src/ORBmatcher.cc:3513-3528); queries arrive already projected.
+ * src/ORBmatcher.cc:3513-3528); queries arrive already projected -- except for the local map, whose points can stay in HBM
+ * and are projected there (orbm_search_local_points).
  *
  * A matcher handle owns one HIP stream and scratch; use one handle per thread (the reference constructs an
  * ORBmatcher on the stack per use and calls it from three threads).  No global mutable state.
@@ -244,6 +247,67 @@ int orbm_project_best(orbm_matcher* m, const orbm_frame* f, const orbm_query* q,
 int orbm_search_by_projection_points(orbm_matcher* m, const orbm_frame* cur, const orbm_query* q, int nq,
                                      const uint8_t* occupied, float nnratio, int th_high,
                                      int32_t* match_of_feature, int* nmatches);
+
+/* -- local-map tracking: Frame::isInFrustum fused with the search ---------------------------------------------
+ * Tracking::SearchLocalPoints from its second loop on (reference src/Tracking.cc:1730-1768): Frame::isInFrustum
+ * (src/Frame.cc:443-499) per point, MapPoint::PredictScale (src/MapPoint.cc:602-617), the query of
+ * SearchByProjection(F, vpMapPoints, th) (src/ORBmatcher.cc:62-157) and its top-2 search, over a table of map points that
+ * stays in HBM between frames.  Neither the points nor the queries cross the bus per frame: the caller rewrites the rows
+ * that changed (orbm_points_write) and hands in the pose. */
+typedef struct orbm_points orbm_points;
+
+typedef struct orbm_point {        /* what isInFrustum and the search read of one MapPoint */
+    float pos[3];                  /* GetWorldPos()                                        */
+    float normal[3];               /* GetNormal()                                          */
+    float min_dist, max_dist;      /* mfMinDistance, mfMaxDistance (NOT yet * 0.8 / 1.2)   */
+    int32_t blocks;                /* Observations() > 0                                   */
+    uint8_t desc[32];              /* GetDescriptor()                                      */
+} orbm_point;                      /* 68 bytes */
+
+typedef struct orbm_view {         /* the Frame members isInFrustum reads */
+    float Rcw[9], tcw[3], Ow[3];   /* mRcw row-major, mtcw, mOw                            */
+    float fx, fy, cx, cy, mbf;
+    float min_x, max_x, min_y, max_y;
+    float viewing_cos_limit;       /* 0.5 in SearchLocalPoints                             */
+    float th;                      /* SearchByProjection's th (1, 3 or 5)                  */
+    float log_scale_factor; int32_t n_levels;   /* mfLogScaleFactor, mnScaleLevels (1 .. ORBM_MAX_LEVELS) */
+    const float* scale_factors;    /* mvScaleFactors, n_levels (host)                      */
+} orbm_view;
+
+typedef struct orbm_track {        /* what isInFrustum leaves in the MapPoint */
+    float proj_x, proj_y, proj_xr, view_cos;   /* mTrackProjX, mTrackProjY, mTrackProjXR, mTrackViewCos */
+    int32_t level;                 /* mnTrackScaleLevel                                    */
+    int32_t in_view;               /* mbTrackInView; 0 also for skipped points (the other fields are 0 then) */
+} orbm_track;
+
+enum { ORBM_MAX_LEVELS = 32, ORBM_MAX_POINTS = 65535 };
+
+int orbm_points_create(orbm_matcher* m, int capacity, orbm_points** out);
+void orbm_points_destroy(orbm_points* p);
+/* rows [first, first + n) of the table; any sub-range inside the capacity.  Returns when the rows are in HBM. */
+int orbm_points_write(orbm_matcher* m, orbm_points* p, int first, int n, const orbm_point* src);
+int orbm_points_count(const orbm_points* p);   /* high-water mark: one past the last row ever written */
+/* Frustum test, scale prediction, query construction and the top-2 search of the first n rows of the table against `cur`.
+ * skip[i] != 0 (n entries, may be NULL) is the reference's `mnLastFrameSeen == mnId || isBad()`: the point is neither tested
+ * nor searched.  occupied / nnratio / th_high as in orbm_search_by_projection_points.  track (n entries, may be NULL)
+ * receives what isInFrustum writes; match_of_feature[g] is an index into the TABLE (0 .. n-1) or -1; *n_to_match = points
+ * that passed the test (the reference's nToMatch); *nmatches = SearchByProjection's return value.  Points claim in table
+ * order.  n beyond orbm_points_count or ORBM_MAX_POINTS: ORB_E_CAPACITY.
+ * One deviation from the reference: a non-finite projection (PcZ == 0) is out of view; the reference lets it through its
+ * bound checks into an int cast. */
+int orbm_search_local_points(orbm_matcher* m, const orbm_frame* cur, const orbm_points* pts, int n, const orbm_view* view,
+                             const uint8_t* skip, const uint8_t* occupied, float nnratio, int th_high, orbm_track* track,
+                             int32_t* match_of_feature, int* n_to_match, int* nmatches);
+/* (test / inspection hooks, like orbm_debug_*: not needed by a caller of orbm_search_local_points)
+ * Host: the level thresholds the kernel uses in place of a logarithm.  out[k], k = 0 .. n_levels-2, is the largest float
+ * ratio r with ceil(logf(r) / log_scale_factor) <= k under the C library's logf; the predicted level of a ratio is the number
+ * of thresholds it exceeds.  Verifies that the predicate flips exactly once around every threshold; ORB_E_ARG otherwise. */
+int orbm_level_thresholds(float log_scale_factor, int n_levels, float* out);
+/* (test / inspection hook) Host: the same arithmetic as the kernel, operation for operation, for n points in host memory (the exact fallback of the
+ * search uses it; a test can hold it against a model without a device).  track and q (n entries each, either may be NULL):
+ * q[i] is the query of point i, with cam = -1 (no window) where the point is not in view. */
+int orbm_frustum_host(const orbm_point* pts, int n, const orbm_view* view, const uint8_t* skip, orbm_track* track,
+                      orbm_query* q, int* n_to_match);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,11 @@ QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("radius", "<f4"), ("ur", "<
                         ("desc", "u1", (32,))])
 WINDOW_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("radius", "<f4"), ("cam", "<i4"), ("min_level", "<i4"), ("max_level", "<i4")])
 assert KP_DTYPE.itemsize == 28 and QUERY_DTYPE.itemsize == 68 and WINDOW_DTYPE.itemsize == 24
+POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_dist", "<f4"), ("max_dist", "<f4"),
+                        ("blocks", "<i4"), ("desc", "u1", (32,))])
+TRACK_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
+                        ("in_view", "<i4")])
+assert POINT_DTYPE.itemsize == 68 and TRACK_DTYPE.itemsize == 24
 
 ORB_OK, ORB_E_ARG, ORB_E_HIP, ORB_E_CAPACITY, ORB_E_NO_DEVICE, ORB_E_TIMEOUT = 0, -1, -2, -3, -4, -5
 
@@ -68,6 +73,13 @@ class FrameDesc(C.Structure):  # orbm_frame_desc
                 ("octave", C.c_void_p), ("angle", C.c_void_p), ("uright", C.c_void_p), ("cam_of", C.c_void_p),
                 ("local_of", C.c_void_p), ("desc", C.c_void_p), ("min_x", C.c_float), ("min_y", C.c_float),
                 ("max_x", C.c_float), ("max_y", C.c_float)]
+
+
+class View(C.Structure):  # orbm_view
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3)] + \
+               [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "mbf", "min_x", "max_x", "min_y", "max_y",
+                                         "viewing_cos_limit", "th", "log_scale_factor")] + \
+               [("n_levels", C.c_int32), ("scale_factors", C.c_void_p)]
 
 
 class DeviceFeatures(C.Structure):  # orbf_device_features
@@ -206,6 +218,13 @@ def lib():
     L.orbm_search_by_projection_windows.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, vp, vp]
     L.orbm_debug_time_project.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     L.orbm_search_by_projection_points.argtypes = [vp, vp, vp, i32, vp, f32, i32, vp, vp]
+    L.orbm_points_create.argtypes = [vp, i32, vp]
+    L.orbm_points_destroy.argtypes = [vp]; L.orbm_points_destroy.restype = None
+    L.orbm_points_write.argtypes = [vp, vp, i32, i32, vp]
+    L.orbm_points_count.argtypes = [vp]
+    L.orbm_search_local_points.argtypes = [vp, vp, vp, i32, vp, vp, vp, f32, i32, vp, vp, vp, vp]
+    L.orbm_level_thresholds.argtypes = [f32, i32, vp]
+    L.orbm_frustum_host.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     f64 = C.c_double
     L.orbv_create.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp]
     L.orbv_load_text.argtypes = [C.c_char_p, i32, vp]

@@ -1105,6 +1105,13 @@ int ORBmatcher::SearchByProjection(Frame& F, const std::vector<MapPoint*>& vpMap
     return nmatches;
 }
 
+bool ORBmatcher::GetLocalSearchContext(Frame& F, LocalSearchContext* out) {
+    out->handle = Handle(); out->nnratio = mfNNratio; out->frame = nullptr;
+    if (!out->handle) return false;
+    out->frame = device_frame(out->handle, F, true);
+    return out->frame != nullptr;
+}
+
 // reference src/ORBmatcher.cc:3448-3641
 int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th, const bool bMono,
                                    cv::Mat CalibMatrix) {

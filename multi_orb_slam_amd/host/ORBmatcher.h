@@ -17,6 +17,7 @@
 #include "slam_types.h"
 
 struct orbm_matcher;
+struct orbm_frame;
 struct orbv_workspace;
 
 namespace ORB_SLAM2 {
@@ -133,6 +134,11 @@ public:
     // test hook: R * x + t (3x3, 3x1 CV_32F) through the scalar routine the per-frame tracking search uses instead of three
     // cv::Mat temporaries per point; host/test_host `rt` compares it with the cv::Mat expression bit for bit
     static void DebugApplyRt(const cv::Mat& R, const cv::Mat& t, const float* x, float* out);
+    // internal hook, not part of the reference's class: for host/LocalMapSearch.cc (Tracking::SearchLocalPoints on the device): the calling thread's matcher handle, the camera-1
+    // view of F on the device (uploaded or found in the thread's frame cache, as SearchByProjection(F, vpMapPoints, th) does)
+    // and this object's ratio.  false (failure reported as every search reports it) when there is no device.
+    struct LocalSearchContext { orbm_matcher* handle; orbm_frame* frame; float nnratio; };
+    bool GetLocalSearchContext(Frame& F, LocalSearchContext* out);
 
 private:
     // The device state (matcher handle with its stream and scratch, BoW workspace, cache of uploaded frames) belongs to the

@@ -37,6 +37,10 @@ public:
     bool mbTrackInView = false;
     int mnTrackScaleLevel = 0;
     float mTrackViewCos = 1.f;
+    // bookkeeping of Tracking::SearchLocalPoints (src/Tracking.cc:1702-1770; include/MapPoint.h, src/MapPoint.cc:IncreaseVisible)
+    long unsigned int mnLastFrameSeen = 0;
+    void IncreaseVisible(int n = 1) { mnVisible += n; }
+    int mnVisible = 1;
 
     // members the remaining projection searches read (src/MapPoint.cc:559-617)
     cv::Mat GetNormal() { return mNormalVector; }
@@ -91,6 +95,44 @@ public:
     DBoW2::FeatureVector mFeatVec_cam1;
     std::vector<cv::KeyPoint> mvKeys;   // camera 1, distorted
     float mfLogScaleFactor = 0; int mnScaleLevels = 0;
+
+    // pose members (include/Frame.h:82-99, src/Frame.cc:420-499)
+    void SetPose(cv::Mat Tcw) { mTcw = Tcw.clone(); UpdatePoseMatrices(); }
+    void UpdatePoseMatrices() {
+        mRcw = mTcw.rowRange(0, 3).colRange(0, 3);
+        mRwc = mRcw.t();
+        mtcw = mTcw.rowRange(0, 3).col(3);
+        mOw = -mRcw.t() * mtcw;
+    }
+    cv::Mat GetCameraCenter() { return mOw.clone(); }
+    // Frame::isInFrustum (src/Frame.cc:443-499), camera 1: the same tests in the same order on the same cv::Mat expressions --
+    // cv_compat.h evaluates them as OpenCV does (R*P + t is ONE small-path gemm; norm and dot accumulate in double) -- and the same
+    // six scratch fields written on success.  This is the checker of the device form (csrc/frustum.hip).
+    // One deviation: a projection that is not finite (depth exactly 0) is out of view.
+    bool isInFrustum(MapPoint* pMP, float viewingCosLimit) {
+        pMP->mbTrackInView = false;
+        const cv::Mat world = pMP->GetWorldPos();
+        const cv::Mat cam = mRcw * world + mtcw;
+        const float depth = cam.at<float>(2);
+        if (depth < 0.0f) return false;
+        const float inv_depth = 1.0f / depth;
+        const float u = fx * cam.at<float>(0) * inv_depth + cx, v = fy * cam.at<float>(1) * inv_depth + cy;
+        if (!std::isfinite(u) || !std::isfinite(v)) return false;
+        if (u < mnMinX || u > mnMaxX || v < mnMinY || v > mnMaxY) return false;
+        const cv::Mat ray = world - mOw;
+        const float range = cv::norm(ray);
+        if (range < pMP->GetMinDistanceInvariance() || range > pMP->GetMaxDistanceInvariance()) return false;
+        const float cosine = ray.dot(pMP->GetNormal()) / range;   // (double / float, rounded once)
+        if (cosine < viewingCosLimit) return false;
+        pMP->mnTrackScaleLevel = pMP->PredictScale(range, this);
+        pMP->mTrackProjX = u; pMP->mTrackProjY = v; pMP->mTrackProjXR = u - mbf * inv_depth;
+        pMP->mTrackViewCos = cosine;
+        pMP->mbTrackInView = true;
+        return true;
+    }
+
+private:
+    cv::Mat mRcw, mtcw, mRwc, mOw;   // private in the reference too (include/Frame.h:263-282): read them through mTcw / GetCameraCenter()
 };
 
 // KeyFrame members the BoW-gated searches read (include/KeyFrame.h:53-59, :104-113, :218-219 and the Frame copies of

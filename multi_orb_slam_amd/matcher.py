@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import KP_DTYPE, QUERY_DTYPE, CamFeatures, FrameDesc, check, ptr
+from ._lib import KP_DTYPE, QUERY_DTYPE, POINT_DTYPE, TRACK_DTYPE, CamFeatures, FrameDesc, check, ptr
 
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30  # reference src/ORBmatcher.cc:37-39
 
@@ -17,6 +17,80 @@ def three_maxima(sizes):
     sizes = np.ascontiguousarray(sizes, np.int32); ind = np.zeros(3, np.int32)
     _lib.lib().orbm_three_maxima(ptr(sizes), len(sizes), ptr(ind))
     return tuple(int(i) for i in ind)
+
+
+class View:
+    """The Frame members Frame::isInFrustum reads (orbm_view): pose, intrinsics, image bounds, the scale pyramid and the
+    `th` of SearchByProjection(F, vpMapPoints, th).  Rcw 3x3 row-major, tcw and Ow 3-vectors, bounds = (min_x, min_y, max_x, max_y)."""
+
+    def __init__(self, Rcw, tcw, Ow, fx, fy, cx, cy, mbf, bounds, scale_factors, log_scale_factor, th=1.0, viewing_cos_limit=0.5):
+        self.scale_factors = np.ascontiguousarray(scale_factors, np.float32)
+        c = self.c = _lib.View()
+        c.Rcw[:] = np.asarray(Rcw, np.float32).reshape(9).tolist()
+        c.tcw[:] = np.asarray(tcw, np.float32).reshape(3).tolist()
+        c.Ow[:] = np.asarray(Ow, np.float32).reshape(3).tolist()
+        c.fx, c.fy, c.cx, c.cy, c.mbf = float(fx), float(fy), float(cx), float(cy), float(mbf)
+        c.min_x, c.min_y, c.max_x, c.max_y = (float(b) for b in bounds)
+        c.viewing_cos_limit = float(viewing_cos_limit); c.th = float(th)
+        c.log_scale_factor = float(log_scale_factor); c.n_levels = len(self.scale_factors)
+        c.scale_factors = self.scale_factors.ctypes.data
+
+
+def level_thresholds(log_scale_factor, n_levels):
+    """orbm_level_thresholds: the largest ratio of every level under the C library's logf (host only)."""
+    out = np.zeros(max(n_levels - 1, 1), np.float32)
+    check(_lib.lib().orbm_level_thresholds(float(log_scale_factor), int(n_levels), ptr(out)))
+    return out[:max(n_levels - 1, 0)]
+
+
+def frustum_host(points, view, skip=None):
+    """orbm_frustum_host: the library's host restatement of the frustum kernel -> (n_to_match, track, queries)."""
+    points = np.ascontiguousarray(points, POINT_DTYPE); n = len(points)
+    sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+    assert sk is None or len(sk) == n
+    track = np.zeros(max(n, 1), TRACK_DTYPE); q = np.zeros(max(n, 1), QUERY_DTYPE); cnt = C.c_int()
+    check(_lib.lib().orbm_frustum_host(ptr(points), n, C.byref(view.c), None if sk is None else ptr(sk), ptr(track), ptr(q),
+                                       C.byref(cnt)))
+    return cnt.value, track[:n], q[:n]
+
+
+class LocalPoints:
+    """A table of map points resident in HBM (orbm_points): what isInFrustum and the search read of each MapPoint."""
+
+    def __init__(self, matcher, capacity):
+        self._m = matcher; self.capacity = int(capacity)
+        self._h = C.c_void_p()
+        check(_lib.lib().orbm_points_create(matcher._h, self.capacity, C.byref(self._h)))
+
+    def write(self, first, points):
+        """Rows [first, first + len(points)) of the table (POINT_DTYPE); any sub-range."""
+        points = np.ascontiguousarray(points, POINT_DTYPE)
+        check(_lib.lib().orbm_points_write(self._m._h, self._h, int(first), len(points), ptr(points)))
+
+    @property
+    def count(self):
+        """High-water mark: one past the last row ever written (orbm_points_count)."""
+        n = int(_lib.lib().orbm_points_count(self._h))
+        if n < 0:
+            raise _lib.OrbError(n, "orbm_points_count on a closed table")
+        return n
+
+    def close(self):
+        if getattr(self, "_h", None):
+            try:
+                _lib.lib().orbm_points_destroy(self._h)
+            except Exception:
+                pass
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
 
 class FrameData:
@@ -314,3 +388,20 @@ class Matcher:
                                                           None if occ is None else ptr(occ), self.nnratio, th_high,
                                                           ptr(m), C.byref(n)))
         return n.value, m[:frame.data.n_total]
+
+    def SearchLocalPoints(self, frame, points, view, skip=None, occupied=None, th_high=TH_HIGH, n=None, want_track=True):
+        """Tracking::SearchLocalPoints from its second loop on (reference src/Tracking.cc:1730-1768) over the first n rows
+        (default: all written rows) of a LocalPoints table: Frame::isInFrustum, scale prediction and
+        SearchByProjection(F, vpMapPoints, th) on the device.  -> (n_to_match, nmatches, match_of_feature, track);
+        match_of_feature[g] indexes the table."""
+        n = points.count if n is None else int(n)
+        m = np.zeros(max(frame.data.n_total, 1), np.int32); nm = C.c_int(); nt = C.c_int()
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        occ = None if occupied is None else np.ascontiguousarray(occupied, np.uint8)
+        assert sk is None or len(sk) >= n
+        assert occ is None or len(occ) >= frame.data.n_total
+        track = np.zeros(max(n, 1), TRACK_DTYPE) if want_track else None
+        check(_lib.lib().orbm_search_local_points(self._h, frame._h, points._h, n, C.byref(view.c), None if sk is None else ptr(sk),
+                                                  None if occ is None else ptr(occ), self.nnratio, th_high,
+                                                  None if track is None else ptr(track), ptr(m), C.byref(nt), C.byref(nm)))
+        return nt.value, nm.value, m[:frame.data.n_total], (None if track is None else track[:max(n, 0)])
