@@ -5,8 +5,8 @@ include/orbx.h, orbm.h, orbf.h and orbv.h) plus the C++ host classes in `host/` 
 ORB_SLAM2::ORBextractor / ORBmatcher signatures.  This Python package is a thin ctypes mirror of that ABI used by
 the tests, the benchmark and the multi-GPU driver; it contains no compute and no CPU fallback.
 """
-from ._lib import lib, build, LIB_PATH, OrbError, KP_DTYPE, QUERY_DTYPE, POINT_DTYPE, TRACK_DTYPE  # noqa: F401
+from ._lib import lib, build, LIB_PATH, OrbError, KP_DTYPE, QUERY_DTYPE, POINT_DTYPE, TRACK_DTYPE, REFRESH_DTYPE  # noqa: F401
 from .extractor import Extractor, ExtractorParams, tables  # noqa: F401
 from .matcher import Matcher, FrameData, LocalPoints, View, descriptor_distance, three_maxima  # noqa: F401
-from .matcher import frustum_host, level_thresholds  # noqa: F401
+from .matcher import frustum_host, level_thresholds, RefreshBatch, refresh_points_host  # noqa: F401
 from .vocabulary import Vocabulary, BowSearch, Side as BowSide, FeatureVector, score_l1, KeyFrameDatabase  # noqa: F401

@@ -21,6 +21,10 @@ POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_dis
 TRACK_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
                         ("in_view", "<i4")])
 assert POINT_DTYPE.itemsize == 68 and TRACK_DTYPE.itemsize == 24
+REFRESH_DTYPE = np.dtype([("desc", "u1", (32,)), ("normal", "<f4", (3,)), ("min_dist", "<f4"), ("max_dist", "<f4"),
+                          ("best_obs", "<i4"), ("best_median", "<i4")])   # orbm_refresh_out
+assert REFRESH_DTYPE.itemsize == 60
+REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH, REFRESH_CAP = 1, 2, 256
 
 ORB_OK, ORB_E_ARG, ORB_E_HIP, ORB_E_CAPACITY, ORB_E_NO_DEVICE, ORB_E_TIMEOUT = 0, -1, -2, -3, -4, -5
 
@@ -80,6 +84,12 @@ class View(C.Structure):  # orbm_view
                [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "mbf", "min_x", "max_x", "min_y", "max_y",
                                          "viewing_cos_limit", "th", "log_scale_factor")] + \
                [("n_levels", C.c_int32), ("scale_factors", C.c_void_p)]
+
+
+class RefreshIn(C.Structure):  # orbm_refresh_in
+    _fields_ = [("n_points", C.c_int32), ("n_obs", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("first", "obs_desc", "obs_centre", "obs_alive", "pos", "ref_centre", "ref_level", "what",
+                                          "scale_factors")] + [("n_levels", C.c_int32)]
 
 
 class DeviceFeatures(C.Structure):  # orbf_device_features
@@ -225,6 +235,9 @@ def lib():
     L.orbm_search_local_points.argtypes = [vp, vp, vp, i32, vp, vp, vp, f32, i32, vp, vp, vp, vp]
     L.orbm_level_thresholds.argtypes = [f32, i32, vp]
     L.orbm_frustum_host.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.orbm_refresh_points.argtypes = [vp, vp, vp]
+    L.orbm_refresh_points_host.argtypes = [vp, vp]
+    L.orbm_debug_last_refresh.argtypes = [vp, vp]
     f64 = C.c_double
     L.orbv_create.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp]
     L.orbv_load_text.argtypes = [C.c_char_p, i32, vp]

@@ -1,6 +1,6 @@
 // matcher_internal.h -- types and internal entry points shared by the translation units of the matcher / front end
 // (hamming.hip: all-pairs kernels; frame.hip: frame assembly; search.hip: projection search + resolve; matcher.hip: handle
-// + host helpers; exchange.hip: RCCL / loopback transport; frontend.hip: orbf_*).  Not part of the C ABI.
+// + host helpers; exchange.hip: RCCL / loopback transport; frontend.hip: orbf_*; mappoint.hip: map-point refresh).  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <condition_variable>
@@ -101,6 +101,12 @@ struct orbm_matcher {
     bool foreign_work = false;     // something other than a step's own search was put on the stream (orbf_step_end then waits for all of it)
     DevBuf<int32_t> d_mergecnt;    // running count of the merging workgroups that rode in resolve launches (MergeJob)
     bool merge_ready = false; unsigned merge_target = 0;
+    // orbm_refresh_points (mappoint.hip): the packed inputs of a call (host-written, read in place by the kernels), the records the
+    // kernels write (mapped pinned, dense in worklist order) and where the points of the last call went
+    morb::StageBuf stage_r;
+    PinnedBuf<orbm_refresh_out> h_refresh;
+    std::vector<int32_t> refresh_list;
+    int last_refresh[5] = {0, 0, 0, 0, 0};
 };
 namespace morb { hipStream_t side_stream(orbm_matcher* m); }   // (lazily created; NULL after a reported failure)
 

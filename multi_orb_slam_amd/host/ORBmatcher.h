@@ -139,6 +139,9 @@ public:
     // and this object's ratio.  false (failure reported as every search reports it) when there is no device.
     struct LocalSearchContext { orbm_matcher* handle; orbm_frame* frame; float nnratio; };
     bool GetLocalSearchContext(Frame& F, LocalSearchContext* out);
+    // internal hook for host/MapPointRefresh.cc: the calling thread's matcher handle; NULL (failure reported as every search
+    // reports it) when there is no device
+    orbm_matcher* GetDeviceHandle() { return Handle(); }
 
 private:
     // The device state (matcher handle with its stream and scratch, BoW workspace, cache of uploaded frames) belongs to the

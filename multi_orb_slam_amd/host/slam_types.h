@@ -58,6 +58,14 @@ public:
     int GetIndexInKeyFrame_cam1(KeyFrame* pKF) { auto it = mObservations.find(pKF); return it != mObservations.end() ? (int)it->second : -1; }
     void AddObservation(KeyFrame* pKF, size_t idx) { if (mObservations.count(pKF)) return; mObservations[pKF] = idx; nObs++; }
     void Replace(MapPoint* pMP) { if (pMP == this) return; mpReplaced = pMP; mbBad = true; }
+    // members host/MapPointRefresh.cc reads (include/MapPoint.h:50-52) and the two writers an integration adds for it
+    std::map<KeyFrame*, size_t> GetObservations() { return mObservations; }
+    KeyFrame* GetReferenceKeyFrame() { return mpRefKF; }
+    void SetDistinctiveDescriptor(const cv::Mat& d) { mDescriptor = d.clone(); }
+    void SetNormalAndDepth(const cv::Mat& normal, float minDistance, float maxDistance) {
+        mNormalVector = normal.clone(); mfMinDistance = minDistance; mfMaxDistance = maxDistance;
+    }
+    KeyFrame* mpRefKF = nullptr;
 
     cv::Mat mWorldPos;    // 3x1 CV_32F
     cv::Mat mDescriptor;  // 1x32 CV_8U
@@ -151,6 +159,8 @@ public:
     cv::Mat GetTranslation_cam2() { return Tcw_cam2.rowRange(0, 3).col(3).clone(); }
     cv::Mat GetCameraCenter() { return -(GetRotation().t() * GetTranslation()); }
     cv::Mat GetCameraCenter_cam2() { return -(GetRotation_cam2().t() * GetTranslation_cam2()); }
+    bool isBad() { return mbBad; }
+    bool mbBad = false;
 
     std::vector<cv::KeyPoint> mvKeysUn_total;
     std::vector<float> mvuRight_total;

@@ -2,7 +2,7 @@
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import KP_DTYPE, QUERY_DTYPE, POINT_DTYPE, TRACK_DTYPE, CamFeatures, FrameDesc, check, ptr
+from ._lib import KP_DTYPE, QUERY_DTYPE, POINT_DTYPE, TRACK_DTYPE, REFRESH_DTYPE, CamFeatures, FrameDesc, check, ptr
 
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30  # reference src/ORBmatcher.cc:37-39
 
@@ -52,6 +52,38 @@ def frustum_host(points, view, skip=None):
     check(_lib.lib().orbm_frustum_host(ptr(points), n, C.byref(view.c), None if sk is None else ptr(sk), ptr(track), ptr(q),
                                        C.byref(cnt)))
     return cnt.value, track[:n], q[:n]
+
+
+class RefreshBatch:
+    """The inputs of a map-point refresh (orbm_refresh_in): P points whose observations arrive as a CSR list.  first[P + 1];
+    obs_desc n_obs x 32, obs_centre n_obs x 3 (centre of the observing camera), obs_alive n_obs (the keyframe is not bad); pos and
+    ref_centre P x 3, ref_level P (octave of the point's keypoint in its reference keyframe), what P (bit 0: distinctive
+    descriptor, bit 1: normal and depth); scale_factors = mvScaleFactors."""
+
+    def __init__(self, first, obs_desc, obs_centre, obs_alive, pos, ref_centre, ref_level, what, scale_factors):
+        self.first = np.ascontiguousarray(first, np.int32)
+        self.n_points = len(self.first) - 1; self.n_obs = int(self.first[-1])
+        self.obs_desc = np.ascontiguousarray(obs_desc, np.uint8).reshape(-1, 32)
+        self.obs_centre = np.ascontiguousarray(obs_centre, np.float32).reshape(-1, 3)
+        self.obs_alive = np.ascontiguousarray(obs_alive, np.uint8)
+        self.pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        self.ref_centre = np.ascontiguousarray(ref_centre, np.float32).reshape(-1, 3)
+        self.ref_level = np.ascontiguousarray(ref_level, np.int32)
+        self.what = np.ascontiguousarray(what, np.uint8)
+        self.scale_factors = np.ascontiguousarray(scale_factors, np.float32)
+        assert self.n_points >= 0 and len(self.obs_desc) == len(self.obs_centre) == len(self.obs_alive) == self.n_obs
+        assert len(self.pos) == len(self.ref_centre) == len(self.ref_level) == len(self.what) == self.n_points
+        self.c = _lib.RefreshIn(self.n_points, self.n_obs, *[a.ctypes.data for a in (
+            self.first, self.obs_desc, self.obs_centre, self.obs_alive, self.pos, self.ref_centre, self.ref_level, self.what,
+            self.scale_factors)], len(self.scale_factors))
+
+
+def refresh_points_host(batch):
+    """orbm_refresh_points_host: MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth for every point of a RefreshBatch,
+    entirely on the host (no device needed) -> REFRESH_DTYPE records."""
+    out = np.zeros(max(batch.n_points, 1), REFRESH_DTYPE)
+    check(_lib.lib().orbm_refresh_points_host(C.byref(batch.c), ptr(out)))
+    return out[:batch.n_points]
 
 
 class LocalPoints:
@@ -388,6 +420,20 @@ class Matcher:
                                                           None if occ is None else ptr(occ), self.nnratio, th_high,
                                                           ptr(m), C.byref(n)))
         return n.value, m[:frame.data.n_total]
+
+    def RefreshPoints(self, batch):
+        """MapPoint::ComputeDistinctiveDescriptors + MapPoint::UpdateNormalAndDepth (reference src/MapPoint.cc:325-438, :480-528)
+        for every point of a RefreshBatch in one device call (orbm_refresh_points) -> REFRESH_DTYPE records."""
+        out = np.zeros(max(batch.n_points, 1), REFRESH_DTYPE)
+        check(_lib.lib().orbm_refresh_points(self._h, C.byref(batch.c), ptr(out)))
+        return out[:batch.n_points]
+
+    def last_refresh(self):
+        """Points of the last RefreshPoints by path: (16-lane groups, one wavefront, one workgroup, host routine because of more than
+        REFRESH_CAP observations, no work) (orbm_debug_last_refresh)."""
+        out = (C.c_int * 5)()
+        check(_lib.lib().orbm_debug_last_refresh(self._h, out))
+        return tuple(out)
 
     def SearchLocalPoints(self, frame, points, view, skip=None, occupied=None, th_high=TH_HIGH, n=None, want_track=True):
         """Tracking::SearchLocalPoints from its second loop on (reference src/Tracking.cc:1730-1768) over the first n rows
