@@ -145,6 +145,81 @@ int orbv_search_for_triangulation_resident(orbv_workspace* w, const orbv_keyfram
                                            const uint8_t* flags_b, const orbv_triangulation* t, int th_low, int check_orientation,
                                            int32_t* match, int* nmatches);
 
+/* ---- Triangulation and gating of new map points: the loop over the matched pairs in LocalMapping::CreateNewMapPoints (reference
+ * src/LocalMapping.cc:388-669) with KeyFrame::UnprojectStereo (src/KeyFrame.cc:985-1012), up to, not including, `new MapPoint`.
+ * One statement sequence (csrc/triangulate.hip) serves the kernel and the host routine; DESIGN.md section 2 lists the operators at
+ * the OpenCV boundary whose parity is unpinned (the Jacobi SVD, its hypot replacement, the weighted row difference, v / w). */
+typedef struct orbv_tri_keyframe {
+    float Tcw[2][12];          /* per camera [R|t], 3x4 row-major: GetRotation / GetTranslation and their _cam2 forms         */
+    float centre[2][3];        /* GetCameraCenter, GetCameraCenter_cam2                                                      */
+    float Twc[12];             /* Twc.rowRange(0,3), 3x4 row-major (UnprojectStereo)                                         */
+    float Rcam12[9], tcam12[3];/* mRcam12, mtcam12 (UnprojectStereo, camera 2)                                               */
+    float fx, fy, cx, cy, invfx, invfy, mbf;
+    int n_levels;
+    const float* scale_factors;/* mvScaleFactors, n_levels                                                                   */
+    const float* level_sigma2; /* mvLevelSigma2, n_levels                                                                    */
+    int n;                     /* features (N_total)                                                                         */
+    int n_cam1;                /* the reference's N: UnprojectStereo takes camera 2 for i >= N                               */
+    /* per feature, n entries each.  The resident calls ignore these nine and read the keyframe's own arrays instead.        */
+    const float* x;            /* mvKeysUn_total[i].pt                                                                       */
+    const float* y;
+    const float* xd;           /* mvKeys_total[i].pt (distorted: what UnprojectStereo reads)                                 */
+    const float* yd;
+    const int32_t* octave;     /* mvKeysUn_total[i].octave                                                                   */
+    const float* uright;       /* mvuRight_total                                                                             */
+    const float* depth;        /* mvDepth_total                                                                              */
+    const float* cos_stereo;   /* orbv_cos_stereo(mb, depth): read where uright >= 0 only                                    */
+    const int32_t* cam_of;     /* keypoint_to_cam, or NULL = (i >= n_cam1)                                                   */
+} orbv_tri_keyframe;
+
+enum { ORBV_TRI_NONE = 0,         /* no pair (the fused call's record where match[i] < 0)   */
+       ORBV_TRI_ACCEPTED = 1,     /* reached `new MapPoint`                                  */
+       ORBV_TRI_CAM_OFF = 2,      /* istrian[camIdx1] == false                         :414  */
+       ORBV_TRI_LOW_PARALLAX = 3, /* no stereo and very low parallax                   :515  */
+       ORBV_TRI_W_ZERO = 4,       /* x3D.at<float>(3) == 0                             :491  */
+       ORBV_TRI_Z1 = 5,           /* z1 <= 0                                           :527  */
+       ORBV_TRI_Z2 = 6,           /* z2 <= 0                                           :530  */
+       ORBV_TRI_REPROJ1 = 7,      /* chi-square test in the current keyframe           :577  */
+       ORBV_TRI_REPROJ2 = 8,      /* chi-square test in the neighbour                  :620  */
+       ORBV_TRI_ZERO_DIST = 9,    /* dist1 == 0 || dist2 == 0                          :657  */
+       ORBV_TRI_SCALE = 10 };     /* scale consistency                                 :668  */
+enum { ORBV_TRI_PATH_NONE = 0, ORBV_TRI_PATH_SVD = 1, ORBV_TRI_PATH_UNPROJECT1 = 2, ORBV_TRI_PATH_UNPROJECT2 = 3 };
+typedef struct orbv_tri_out {
+    float x3D[3];              /* the point whenever one was computed, also for a rejected pair (w == 0: the first three
+                                  components of the null vector); a NaN is written as 0xffc00000                              */
+    int32_t outcome;           /* ORBV_TRI_*                                                                                  */
+    int32_t path;              /* ORBV_TRI_PATH_*                                                                             */
+} orbv_tri_out;
+
+/* cos(2*atan2(mb/2, depth[i])) as the reference's translation unit evaluates it (float overloads: atan2f, cosf), for every feature.
+ * Host libm; the device never evaluates it. */
+int orbv_cos_stereo(float mb, const float* depth, int n, float* cos_stereo);
+/* pairs: n_pairs x 2 int32 (idx1 in kf1 = the current keyframe, idx2 in kf2); cam_enabled: the reference's istrian, 2 bytes;
+ * ratio_factor = 1.5f * mfScaleFactor.  ORB_E_ARG (the offender named in orb_last_error()): an index out of range, an octave outside
+ * n_levels, a camera id outside cam_enabled, a stereo feature (uright >= 0) whose depth is not positive (the reference's
+ * UnprojectStereo returns an empty matrix there and the caller faults), a null array.  Needs no device. */
+int orbv_triangulate_pairs_host(const orbv_tri_keyframe* kf1, const orbv_tri_keyframe* kf2, const uint8_t* cam_enabled, const int32_t* pairs,
+                                int n_pairs, float ratio_factor, orbv_tri_out* out);
+/* The same on the workspace's stream: one lane per pair, one synchronisation. */
+int orbv_triangulate_pairs(orbv_workspace* w, const orbv_tri_keyframe* kf1, const orbv_tri_keyframe* kf2, const uint8_t* cam_enabled,
+                           const int32_t* pairs, int n_pairs, float ratio_factor, orbv_tri_out* out);
+/* Adds to a resident keyframe (built with the triangulation arrays) the per-feature arrays this stage reads beyond them:
+ * orbv_keyframe_count(k) entries each, copied from the host; the searches on the keyframe are unaffected. */
+int orbv_keyframe_set_geometry(orbv_workspace* w, orbv_keyframe* k, const float* uright, const float* depth, const float* cos_stereo,
+                               const float* xd, const float* yd);
+typedef struct orbv_tri_geometry {
+    orbv_tri_keyframe kf1, kf2;   /* poses, intrinsics, level tables, n_cam1; the per-feature pointers and n are ignored */
+    uint8_t cam_enabled[2];
+    float ratio_factor;
+} orbv_tri_geometry;
+/* orbv_search_for_triangulation_resident followed by the triangulation of its pairs, the match words read where the search leaves
+ * them in HBM: one synchronisation.  match[] / the return of the search as there; out[i] (a->n records) belongs to the pair
+ * (i, match[i]) and is all zero where match[i] < 0; *n_accepted counts ORBV_TRI_ACCEPTED.  Both keyframes need
+ * orbv_keyframe_set_geometry.  A device-built keyframe's octaves are vouched for by the caller, as in the search. */
+int orbv_create_new_points_resident(orbv_workspace* w, const orbv_keyframe* a, const uint8_t* flags_a, const orbv_keyframe* b,
+                                    const uint8_t* flags_b, const orbv_triangulation* t, const orbv_tri_geometry* geometry, int th_low,
+                                    int check_orientation, int32_t* match, orbv_tri_out* out, int* n_accepted);
+
 /* Resident keyframe database: KeyFrameDatabase's inverted-file walk and the scores behind it (reference src/KeyFrameDatabase.cc:132-153,
  * :187, :429-446, :477; LoopClosing::DetectLoop's minScore loop, src/LoopClosing.cc:150-170) without an inverted file.  Every BowVector
  * added stays in HBM (word ids strictly ascending, values double); one pass of k_db_query over all of them gives, per entry, the number

@@ -10,3 +10,4 @@ from .extractor import Extractor, ExtractorParams, tables  # noqa: F401
 from .matcher import Matcher, FrameData, LocalPoints, View, descriptor_distance, three_maxima  # noqa: F401
 from .matcher import frustum_host, level_thresholds, RefreshBatch, refresh_points_host  # noqa: F401
 from .vocabulary import Vocabulary, BowSearch, Side as BowSide, FeatureVector, score_l1, KeyFrameDatabase  # noqa: F401
+from .vocabulary import TriKeyframe, TRI_OUT_DTYPE, cos_stereo, triangulate_pairs_host  # noqa: F401

@@ -113,6 +113,17 @@ class Triangulation(C.Structure):  # orbv_triangulation
                 ("ey", C.c_float * 8), ("scale_factors", C.c_void_p), ("level_sigma2", C.c_void_p)]
 
 
+class TriKeyframe(C.Structure):  # orbv_tri_keyframe
+    _fields_ = [("Tcw", (C.c_float * 12) * 2), ("centre", (C.c_float * 3) * 2), ("Twc", C.c_float * 12), ("Rcam12", C.c_float * 9),
+                ("tcam12", C.c_float * 3)] + [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "invfx", "invfy", "mbf")] + \
+               [("n_levels", C.c_int32), ("scale_factors", C.c_void_p), ("level_sigma2", C.c_void_p), ("n", C.c_int32), ("n_cam1", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("x", "y", "xd", "yd", "octave", "uright", "depth", "cos_stereo", "cam_of")]
+
+
+class TriGeometry(C.Structure):  # orbv_tri_geometry
+    _fields_ = [("kf1", TriKeyframe), ("kf2", TriKeyframe), ("cam_enabled", C.c_uint8 * 2), ("ratio_factor", C.c_float)]
+
+
 def build(verbose=False):
     """Compile every HIP source for gfx950 into lib/libmorb.so (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-C", CSRC] + ([] if verbose else ["-s"])
@@ -260,6 +271,11 @@ def lib():
     L.orbf_export_features.argtypes = [vp, vp]
     L.orbv_search_by_bow_resident.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, i32, vp, vp]
     L.orbv_search_for_triangulation_resident.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
+    L.orbv_cos_stereo.argtypes = [f32, vp, i32, vp]
+    L.orbv_triangulate_pairs_host.argtypes = [vp, vp, vp, vp, i32, f32, vp]
+    L.orbv_triangulate_pairs.argtypes = [vp, vp, vp, vp, vp, i32, f32, vp]
+    L.orbv_keyframe_set_geometry.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.orbv_create_new_points_resident.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     L.orbv_db_create.argtypes = [i32, i32, vp]
     L.orbv_db_destroy.argtypes = [vp]; L.orbv_db_destroy.restype = None
     L.orbv_db_add.argtypes = [vp, C.c_uint64, vp, vp, i32]

@@ -20,14 +20,18 @@
 #include <vector>
 #include "../../include/orbv.h"
 #include "orb_common.h"
+#include "bow_internal.h"
 
 using morb::DevBuf;
 using morb::PinnedBuf;
+using morb::SideDev;
+using morb::TriDev;
+using morb::JoinWork;
+using morb::MAX_LEVELS;
 
 namespace {
 
 constexpr int HISTO = 30;        // ORBmatcher::HISTO_LENGTH, src/ORBmatcher.cc:39
-constexpr int MAX_LEVELS = 32;   // pyramid levels a triangulation search may name
 constexpr int JOIN_MAX_NODE = 32768;  // candidates of one node (one LDS byte each)
 constexpr int JOIN_LDS_BYTES = 65536; // dynamic LDS of one join workgroup: claimed bytes + staged descriptors
 
@@ -138,24 +142,6 @@ __global__ void k_side_misc(int n, CamStarts C, const float* __restrict__ uright
     cam_of[i] = c;
     flags[i] = (uint8_t)(1 | ((uright && uright[i] >= 0) ? 2 : 0));
 }
-
-struct SideDev {
-    int n, n_nodes;
-    const uint4* desc; const float* angle; const uint8_t* flags; const uint32_t* node_id; const int32_t* node_start;
-    const uint32_t* items; const float* x; const float* y; const int32_t* octave; const int32_t* cam_of;
-};
-
-struct TriDev {
-    float F12[ORBV_MAX_CAMS][9];
-    float ex[ORBV_MAX_CAMS], ey[ORBV_MAX_CAMS];
-    float scale[MAX_LEVELS], sigma2[MAX_LEVELS];
-};
-
-struct JoinWork {
-    int32_t* match;    // n_out
-    uint8_t* bin_of;   // n_out: histogram bin of an accepted match
-    int* hist;         // HISTO bins, then [HISTO] = accepted matches
-};
 
 __global__ void k_bow_init(JoinWork W, int n_out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -362,7 +348,9 @@ __global__ __launch_bounds__(64 * NW) void k_bow_join(SideDev A, SideDev B, TriD
 // Every workgroup works the three maxima out for itself (30 bins from L2) and filters its own 256 results: no single
 // workgroup walking the whole array through sixteen dependent trips to memory.  The match count is taken by the host while it
 // copies the array out (it touches every word anyway).
-__global__ __launch_bounds__(256) void k_bow_finish(JoinWork W, int n_out, int check_ori, int32_t* __restrict__ h_match) {
+// d_final (may be NULL): the filtered words once more, in HBM, for a kernel enqueued behind this one (triangulate.hip); it may be
+// W.match itself -- every thread reads and writes its own word only.
+__global__ __launch_bounds__(256) void k_bow_finish(JoinWork W, int n_out, int check_ori, int32_t* __restrict__ h_match, int32_t* d_final) {
     __shared__ int s_keep[3];
     __shared__ int s_hist[HISTO];
     if (threadIdx.x < HISTO) s_hist[threadIdx.x] = W.hist[threadIdx.x];
@@ -389,6 +377,7 @@ __global__ __launch_bounds__(256) void k_bow_finish(JoinWork W, int n_out, int c
         if (b != s_keep[0] && b != s_keep[1] && b != s_keep[2]) mt = -1;
     }
     h_match[i] = mt;
+    if (d_final) d_final[i] = mt;
 }
 
 inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
@@ -410,14 +399,6 @@ struct orbv_vocabulary {
     DevBuf<uint32_t> d_out;
     PinnedBuf<uint32_t> h_out;
     PinnedBuf<uint8_t> h_feat;
-};
-
-struct orbv_workspace {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    PinnedBuf<uint8_t> h_stage;
-    DevBuf<uint8_t> d_stage, d_work;
-    PinnedBuf<int32_t> h_match;
 };
 
 extern "C" {
@@ -652,7 +633,7 @@ void orbv_workspace_destroy(orbv_workspace* w) {
     if (!w) return;
     (void)hipSetDevice(w->device);
     if (w->stream) { (void)hipStreamSynchronize(w->stream); (void)hipStreamDestroy(w->stream); }
-    w->h_stage.release(); w->d_stage.release(); w->d_work.release(); w->h_match.release();
+    w->h_stage.release(); w->d_stage.release(); w->d_work.release(); w->h_match.release(); w->h_tri.release(); w->tri_const.release();
     delete w;
 }
 
@@ -715,9 +696,10 @@ int max_node_of(const orbv_side* s) {
     return m;
 }
 
-// init + join + finish on the workspace's stream, one synchronisation, results out of pinned memory
-int launch_join(orbv_workspace* w, const SideDev& A, const SideDev& B, int max_nc, int mode, const TriDev& T, int th_low, float nnratio,
-                int check_ori, int32_t* match, int* nmatches) {
+// init + join + finish enqueued on the workspace's stream, no synchronisation.  *d_final (may be NULL) receives the device address of
+// the n_out filtered match words, valid for work enqueued behind this on the same stream until the workspace's next search.
+int enqueue_join(orbv_workspace* w, const SideDev& A, const SideDev& B, int max_nc, int mode, const TriDev& T, int th_low, float nnratio,
+                 int check_ori, const int32_t** d_final) {
     const int n_out = mode == 0 ? B.n : A.n;
     if (max_nc > JOIN_MAX_NODE) { morb::set_error("a vocabulary node holds %d features (limit %d)", max_nc, JOIN_MAX_NODE); return ORB_E_CAPACITY; }
     int rc;
@@ -744,12 +726,26 @@ int launch_join(orbv_workspace* w, const SideDev& A, const SideDev& B, int max_n
         else if (mode == 1) k_bow_join<1, 1><<<A.n_nodes, 64, lds, st>>>(A, B, T, th_low, nnratio, check_ori, W, claimed_bytes, lds_cand);
         else k_bow_join<2, 1><<<A.n_nodes, 64, lds, st>>>(A, B, T, th_low, nnratio, check_ori, W, claimed_bytes, lds_cand);
     }
-    k_bow_finish<<<(n_out + 255) / 256, 256, 0, st>>>(W, n_out, check_ori, w->h_match.dp);
+    k_bow_finish<<<(n_out + 255) / 256, 256, 0, st>>>(W, n_out, check_ori, w->h_match.dp, d_final ? W.match : nullptr);
     MORB_HIP(hipGetLastError());
-    MORB_HIP(hipStreamSynchronize(st));
+    if (d_final) *d_final = W.match;
+    return ORB_OK;
+}
+
+// after the synchronisation: the words out of pinned memory, counted on the way
+void collect_join(orbv_workspace* w, int n_out, int32_t* match, int* nmatches) {
     int nm = 0;
     for (int i = 0; i < n_out; ++i) { const int v = w->h_match.p[i]; match[i] = v; nm += v >= 0; }
     *nmatches = nm;   // == accepted - removed by the rotation filter: every accepted match owns one output word
+}
+
+// init + join + finish on the workspace's stream, one synchronisation, results out of pinned memory
+int launch_join(orbv_workspace* w, const SideDev& A, const SideDev& B, int max_nc, int mode, const TriDev& T, int th_low, float nnratio,
+                int check_ori, int32_t* match, int* nmatches) {
+    int rc = enqueue_join(w, A, B, max_nc, mode, T, th_low, nnratio, check_ori, nullptr);
+    if (rc) return rc;
+    MORB_HIP(hipStreamSynchronize(w->stream));
+    collect_join(w, mode == 0 ? B.n : A.n, match, nmatches);
     return ORB_OK;
 }
 
@@ -784,19 +780,13 @@ int run_join(orbv_workspace* w, const orbv_side* a, const orbv_side* b, int mode
 
 // One frame / keyframe resident in HBM for any number of searches (descriptors, angles, FeatureVector, and the triangulation
 // arrays when given): a keyframe is searched against ~20 covisible neighbours by LocalMapping alone (src/LocalMapping.cc).
-struct orbv_keyframe {
-    int device = 0;
-    DevBuf<uint8_t> block;
-    SideDev D;
-    int max_node = 1, max_cam = 0, max_octave = 0;
-    bool tri = false;
-    const uint32_t* d_word = nullptr; const uint32_t* d_node = nullptr;   // per-feature descent results (device-built keyframes)
-};
-
+// (struct orbv_keyframe: bow_internal.h)
 namespace {
 
-int run_join_resident(orbv_workspace* w, const orbv_keyframe* a, const uint8_t* flags_a, const orbv_keyframe* b, const uint8_t* flags_b,
-                      int mode, const orbv_triangulation* t, int th_low, float nnratio, int check_ori, int32_t* match, int* nmatches) {
+// validation, the per-call flags and the enqueue of a resident search.  *enqueued = 0: an empty side, match[] is complete (all -1).
+int prepare_join_resident(orbv_workspace* w, const orbv_keyframe* a, const uint8_t* flags_a, const orbv_keyframe* b, const uint8_t* flags_b,
+                          int mode, const orbv_triangulation* t, int th_low, float nnratio, int check_ori, int32_t* match, int* nmatches,
+                          int* enqueued, const int32_t** d_final) {
     MORB_ARG(w != nullptr && a != nullptr && b != nullptr && nmatches != nullptr && mode >= 0 && mode <= 2);
     MORB_ARG(a->device == w->device && b->device == w->device);
     const int n_out = mode == 0 ? b->D.n : a->D.n;
@@ -808,7 +798,7 @@ int run_join_resident(orbv_workspace* w, const orbv_keyframe* a, const uint8_t* 
         if ((rc = tri_params(t, T))) return rc;
         MORB_ARG(a->max_cam < t->n_cams && b->max_octave < t->n_levels);
     }
-    *nmatches = 0;
+    *nmatches = 0; *enqueued = 0;
     for (int i = 0; i < n_out; ++i) match[i] = -1;
     if (a->D.n_nodes == 0 || b->D.n_nodes == 0 || a->D.n == 0 || b->D.n == 0) return ORB_OK;
     MORB_HIP(hipSetDevice(w->device));
@@ -820,10 +810,31 @@ int run_join_resident(orbv_workspace* w, const orbv_keyframe* a, const uint8_t* 
         if (flags_b) { memcpy(w->h_stage.p + na, flags_b, (size_t)B.n); B.flags = w->d_stage.p + na; }
         MORB_HIP(hipMemcpyAsync(w->d_stage.p, w->h_stage.p, na + nb, hipMemcpyHostToDevice, w->stream));
     }
-    return launch_join(w, A, B, b->max_node, mode, T, th_low, nnratio, check_ori, match, nmatches);
+    if ((rc = enqueue_join(w, A, B, b->max_node, mode, T, th_low, nnratio, check_ori, d_final))) return rc;
+    *enqueued = 1;
+    return ORB_OK;
+}
+
+int run_join_resident(orbv_workspace* w, const orbv_keyframe* a, const uint8_t* flags_a, const orbv_keyframe* b, const uint8_t* flags_b,
+                      int mode, const orbv_triangulation* t, int th_low, float nnratio, int check_ori, int32_t* match, int* nmatches) {
+    int enqueued = 0;
+    int rc = prepare_join_resident(w, a, flags_a, b, flags_b, mode, t, th_low, nnratio, check_ori, match, nmatches, &enqueued, nullptr);
+    if (rc || !enqueued) return rc;
+    MORB_HIP(hipStreamSynchronize(w->stream));
+    collect_join(w, mode == 0 ? b->D.n : a->D.n, match, nmatches);
+    return ORB_OK;
 }
 
 }  // namespace
+
+namespace morb {
+int bow_triangulation_search_enqueue(orbv_workspace* w, const orbv_keyframe* a, const uint8_t* flags_a, const orbv_keyframe* b,
+                                     const uint8_t* flags_b, const orbv_triangulation* t, int th_low, int check_ori, int32_t* match,
+                                     int* nmatches, int* enqueued, const int32_t** d_final) {
+    return prepare_join_resident(w, a, flags_a, b, flags_b, 2, t, th_low, 0.f, check_ori, match, nmatches, enqueued, d_final);
+}
+void bow_search_collect(orbv_workspace* w, int n_out, int32_t* match, int* nmatches) { collect_join(w, n_out, match, nmatches); }
+}  // namespace morb
 
 extern "C" {
 
@@ -865,7 +876,7 @@ int orbv_keyframe_create(orbv_workspace* w, const orbv_side* s, orbv_keyframe** 
 void orbv_keyframe_destroy(orbv_keyframe* k) {
     if (!k) return;
     (void)hipSetDevice(k->device);
-    k->block.release();
+    k->block.release(); k->geometry.release();
     delete k;
 }
 

@@ -142,6 +142,9 @@ public:
     // internal hook for host/MapPointRefresh.cc: the calling thread's matcher handle; NULL (failure reported as every search
     // reports it) when there is no device
     orbm_matcher* GetDeviceHandle() { return Handle(); }
+    // internal hook for host/NewMapPoints.cc: the calling thread's BoW workspace (stream + scratch of the searches and of the
+    // triangulation stage); NULL (failure reported as every search reports it) when there is no device
+    orbv_workspace* GetBowWorkspace() { return Bow(); }
 
 private:
     // The device state (matcher handle with its stream and scratch, BoW workspace, cache of uploaded frames) belongs to the

@@ -174,6 +174,18 @@ public:
     float fx = 0, fy = 0, cx = 0, cy = 0;
     cv::Mat Tcw, Tcw_cam2;           // 4x4 CV_32F
 
+    // members host/NewMapPoints.cc reads (include/KeyFrame.h:52, :186-211, :226; src/KeyFrame.cc SetPose for Twc = [Rwc | Ow])
+    cv::Mat GetPoseInverse() {
+        cv::Mat Twc = cv::Mat::eye(4, 4, CV_32F);
+        const cv::Mat Rwc = GetRotation().t(), Ow = GetCameraCenter();
+        for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) Twc.at<float>(r, c) = Rwc.at<float>(r, c); Twc.at<float>(r, 3) = Ow.at<float>(r); }
+        return Twc;
+    }
+    float invfx = 0, invfy = 0, mb = 0, mfScaleFactor = 0;
+    cv::Mat mRcam12, mtcam12;                        // 3x3, 3x1 CV_32F
+    std::vector<cv::KeyPoint> mvKeys_total;          // distorted (what UnprojectStereo reads)
+    std::vector<float> mvDepth_total;
+
     // members the remaining projection searches read
     std::vector<MapPoint*> GetMapPointMatches_cam1() { return std::vector<MapPoint*>(mvpMapPoints.begin(), mvpMapPoints.begin() + N); }
     void AddMapPoint(MapPoint* pMP, const size_t& idx) { mvpMapPoints[idx] = pMP; }

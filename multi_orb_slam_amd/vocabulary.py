@@ -2,7 +2,12 @@
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import BowSide, Triangulation, check, ptr
+from ._lib import BowSide, Triangulation, TriGeometry, check, ptr
+
+# orbv_tri_out: the record of one pair of the triangulation stage
+TRI_OUT_DTYPE = np.dtype([("x3D", np.float32, 3), ("outcome", np.int32), ("path", np.int32)])
+TRI_NONE, TRI_ACCEPTED, TRI_CAM_OFF, TRI_LOW_PARALLAX, TRI_W_ZERO, TRI_Z1, TRI_Z2, TRI_REPROJ1, TRI_REPROJ2, TRI_ZERO_DIST, TRI_SCALE = range(11)
+TRI_PATH_NONE, TRI_PATH_SVD, TRI_PATH_UNPROJECT1, TRI_PATH_UNPROJECT2 = range(4)
 
 
 class FeatureVector:
@@ -126,6 +131,73 @@ class KeyFrameDatabase:
         return out[:len(keys)]
 
 
+def cos_stereo(mb, depth):
+    """cos(2*atan2(mb/2, depth)) per feature with the float overloads of the reference's statement (orbv_cos_stereo, host libm)."""
+    d = np.ascontiguousarray(depth, np.float32)
+    out = np.zeros(len(d), np.float32)
+    check(_lib.lib().orbv_cos_stereo(float(np.float32(mb)), ptr(d), len(d), ptr(out)))
+    return out
+
+
+class TriKeyframe:
+    """One keyframe as the triangulation stage reads it (orbv_tri_keyframe); keeps the arrays alive.  Tcw: (2, 3, 4) per camera
+    [R|t]; centre: (2, 3); Twc: (3, 4); the per-feature arrays may be left out for the resident calls."""
+
+    FEATURE_ARRAYS = (("x", np.float32), ("y", np.float32), ("xd", np.float32), ("yd", np.float32), ("octave", np.int32),
+                      ("uright", np.float32), ("depth", np.float32), ("cos_stereo", np.float32), ("cam_of", np.int32))
+
+    def __init__(self, Tcw, centre, Twc, Rcam12, tcam12, fx, fy, cx, cy, invfx, invfy, mbf, scale_factors, level_sigma2, n_cam1, n=None,
+                 **arrays):
+        f32 = lambda a, shape: np.ascontiguousarray(a, np.float32).reshape(shape)
+        self.Tcw, self.centre, self.Twc = f32(Tcw, (2, 12)), f32(centre, (2, 3)), f32(Twc, 12)
+        self.Rcam12, self.tcam12 = f32(Rcam12, 9), f32(tcam12, 3)
+        self.scalars = [float(np.float32(v)) for v in (fx, fy, cx, cy, invfx, invfy, mbf)]
+        self.scale_factors = np.ascontiguousarray(scale_factors, np.float32)
+        self.level_sigma2 = np.ascontiguousarray(level_sigma2, np.float32)
+        self.n_levels = len(self.scale_factors)     # (set n_levels afterwards to describe a table shorter than the array)
+        self.n_cam1 = int(n_cam1)
+        for name, dt in self.FEATURE_ARRAYS:
+            a = arrays.pop(name, None)
+            setattr(self, name, None if a is None else np.ascontiguousarray(a, dt))
+        assert not arrays, "unknown arrays: %s" % sorted(arrays)
+        self.n = int(n) if n is not None else (len(self.x) if self.x is not None else 0)
+
+    def c(self):
+        k = _lib.TriKeyframe()
+        for cam in range(2):
+            for j in range(12):
+                k.Tcw[cam][j] = float(self.Tcw[cam, j])
+            for j in range(3):
+                k.centre[cam][j] = float(self.centre[cam, j])
+        for j in range(12):
+            k.Twc[j] = float(self.Twc[j])
+        for j in range(9):
+            k.Rcam12[j] = float(self.Rcam12[j])
+        for j in range(3):
+            k.tcam12[j] = float(self.tcam12[j])
+        k.fx, k.fy, k.cx, k.cy, k.invfx, k.invfy, k.mbf = self.scalars
+        k.n_levels = self.n_levels; k.scale_factors = self.scale_factors.ctypes.data; k.level_sigma2 = self.level_sigma2.ctypes.data
+        k.n = self.n; k.n_cam1 = self.n_cam1
+        for name, _ in self.FEATURE_ARRAYS:
+            a = getattr(self, name)
+            setattr(k, name, None if a is None else a.ctypes.data)
+        return k
+
+
+def _pairs(pairs):
+    p = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    return p, np.zeros(max(len(p), 1), TRI_OUT_DTYPE)
+
+
+def triangulate_pairs_host(kf1, kf2, cam_enabled, pairs, ratio_factor):
+    """The pair loop of LocalMapping::CreateNewMapPoints on the host (orbv_triangulate_pairs_host; needs no device) -> TRI_OUT_DTYPE records."""
+    p, out = _pairs(pairs)
+    c1, c2 = kf1.c(), kf2.c()
+    en = np.ascontiguousarray(cam_enabled, np.uint8)
+    check(_lib.lib().orbv_triangulate_pairs_host(C.byref(c1), C.byref(c2), ptr(en), ptr(p), len(p), float(np.float32(ratio_factor)), ptr(out)))
+    return out[:len(p)]
+
+
 class Side:
     """One frame / keyframe for the BoW searches (orbv_side); keeps the arrays alive."""
 
@@ -219,6 +291,29 @@ class BowSearch:
                                                                 C.byref(T), th_low, int(check_orientation), ptr(match), C.byref(nm)))
         return nm.value, match[:a.n]
 
+    def triangulate_pairs(self, kf1, kf2, cam_enabled, pairs, ratio_factor):
+        """triangulate_pairs_host on the device: one lane per pair (orbv_triangulate_pairs)."""
+        p, out = _pairs(pairs)
+        c1, c2 = kf1.c(), kf2.c()
+        en = np.ascontiguousarray(cam_enabled, np.uint8)
+        check(_lib.lib().orbv_triangulate_pairs(self._h, C.byref(c1), C.byref(c2), ptr(en), ptr(p), len(p), float(np.float32(ratio_factor)), ptr(out)))
+        return out[:len(p)]
+
+    def create_new_points_resident(self, a, b, F12, ex, ey, scale_factors, level_sigma2, kf1, kf2, cam_enabled, ratio_factor, flags_a=None,
+                                   flags_b=None, th_low=50, check_orientation=True):
+        """search_for_triangulation_resident and the triangulation of its pairs in one call, one synchronisation
+        (orbv_create_new_points_resident) -> (match per feature of a, TRI_OUT_DTYPE record per feature of a, accepted)."""
+        T, keep = self._tri(F12, ex, ey, scale_factors, level_sigma2)
+        G = TriGeometry()
+        G.kf1, G.kf2 = kf1.c(), kf2.c()
+        G.cam_enabled[0], G.cam_enabled[1] = int(bool(cam_enabled[0])), int(bool(cam_enabled[1]))
+        G.ratio_factor = float(np.float32(ratio_factor))
+        match = np.full(max(a.n, 1), -1, np.int32); out = np.zeros(max(a.n, 1), TRI_OUT_DTYPE); acc = C.c_int()
+        fa, fb = self._flags(flags_a), self._flags(flags_b)
+        check(_lib.lib().orbv_create_new_points_resident(self._h, a._h, None if fa is None else ptr(fa), b._h, None if fb is None else ptr(fb),
+                                                         C.byref(T), C.byref(G), th_low, int(check_orientation), ptr(match), ptr(out), C.byref(acc)))
+        return match[:a.n], out[:a.n], acc.value
+
     @staticmethod
     def _tri(F12, ex, ey, scale_factors, level_sigma2):
         T = Triangulation()
@@ -257,6 +352,12 @@ class Keyframe:
         self._h = C.c_void_p(); self.n = side.n; self._search = search
         cs = side.c()
         check(_lib.lib().orbv_keyframe_create(search._h, C.byref(cs), C.byref(self._h)))
+
+    def set_geometry(self, uright, depth, cos_stereo, xd, yd):
+        """The per-feature arrays the triangulation stage reads beyond the search's (orbv_keyframe_set_geometry)."""
+        a = [np.ascontiguousarray(v, np.float32) for v in (uright, depth, cos_stereo, xd, yd)]
+        assert all(len(v) == self.n for v in a)
+        check(_lib.lib().orbv_keyframe_set_geometry(self._search._h, self._h, *[ptr(v) for v in a]))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -1,0 +1,232 @@
+"""Generated and hand-built inputs of the triangulation stage (orbv_tri_keyframe pairs) for tests/test_triangulate_model.py and
+tests/test_gpu_triangulate.py, and the condition the generated worlds must meet before anything is compared on them."""
+import functools
+
+import numpy as np
+
+import triangulate_model as tm
+
+f32 = np.float32
+N_LEVELS = 8
+FX = FY = 520.0
+CX, CY = 320.0, 240.0
+MBF = 40.0
+N_PAIRS = 3000
+# translation of keyframe 2 (metres) and its rotation (degrees about an oblique axis)
+WORLDS = {"25cm": ((0.25, 0.02, 0.1), 3.0, 11), "90cm": ((0.9, 0.05, 0.6), 3.0, 12), "5cm": ((0.05, 0.0, 0.06), 3.0, 13)}
+
+
+def scale_factors(n_levels=N_LEVELS, factor=1.2):
+    """mvScaleFactors as ORBextractor builds them: a running float product."""
+    s = np.ones(n_levels, np.float32)
+    for k in range(1, n_levels):
+        s[k] = s[k - 1] * np.float32(factor)
+    return s
+
+
+def rotation(axis, degrees):
+    a = np.asarray(axis, np.float64); a = a / np.linalg.norm(a)
+    t = np.radians(degrees)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    return np.eye(3) + np.sin(t) * K + (1 - np.cos(t)) * (K @ K)
+
+
+R_CAM12 = rotation((0, 1, 0), 90.0)          # the second camera looks sideways ...
+T_CAM12 = np.array([0.1, 0.0, 0.0])          # ... from the end of a 10 cm lever arm:  X_cam1 = R_CAM12 * X_cam2 + T_CAM12
+
+
+class KF:
+    """One keyframe as the stage reads it.  Scalars are np.float32, arrays float32 / int32."""
+
+    def __init__(self, Rcw, tcw, n_cam1, fx=FX, fy=FY, cx=CX, cy=CY, mbf=MBF, scale=None):
+        Rcw, tcw = np.asarray(Rcw, np.float64), np.asarray(tcw, np.float64)
+        R21 = R_CAM12.T
+        Rcw2, tcw2 = R21 @ Rcw, R21 @ (tcw - T_CAM12)
+        self.Tcw = np.zeros((2, 3, 4), np.float32)
+        self.Tcw[0, :, :3], self.Tcw[0, :, 3] = Rcw, tcw
+        self.Tcw[1, :, :3], self.Tcw[1, :, 3] = Rcw2, tcw2
+        self.centre = np.stack([-Rcw.T @ tcw, -Rcw2.T @ tcw2]).astype(np.float32)
+        self.Twc = np.zeros((3, 4), np.float32)
+        self.Twc[:, :3], self.Twc[:, 3] = Rcw.T, -Rcw.T @ tcw
+        self.Rcam12, self.tcam12 = R_CAM12.astype(np.float32), T_CAM12.astype(np.float32)
+        self.fx, self.fy, self.cx, self.cy, self.mbf = f32(fx), f32(fy), f32(cx), f32(cy), f32(mbf)
+        self.invfx, self.invfy = f32(1.0) / self.fx, f32(1.0) / self.fy
+        self.mb = self.mbf / self.fx
+        self.scale_factors = scale_factors() if scale is None else np.asarray(scale, np.float32)
+        self.level_sigma2 = (self.scale_factors * self.scale_factors).astype(np.float32)
+        self.n_cam1 = int(n_cam1)
+        self.set_features(*[np.zeros(0)] * 7)
+
+    def set_features(self, x, y, xd, yd, octave, uright, depth, cam_of=None):
+        self.x, self.y, self.xd, self.yd = [np.ascontiguousarray(a, np.float32) for a in (x, y, xd, yd)]
+        self.octave = np.ascontiguousarray(octave, np.int32)
+        self.uright, self.depth = np.ascontiguousarray(uright, np.float32), np.ascontiguousarray(depth, np.float32)
+        self.n = len(self.x)
+        self.cam_of = (np.arange(self.n) >= self.n_cam1).astype(np.int32) if cam_of is None else np.ascontiguousarray(cam_of, np.int32)
+        self.cam_of_given = cam_of is not None
+        import multi_orb_slam_amd as m
+        self.cos_stereo = m.cos_stereo(self.mb, self.depth)     # the library's helper: host libm, the same bits for every caller
+        return self
+
+    def native(self, **override):
+        import multi_orb_slam_amd as m
+        a = dict(x=self.x, y=self.y, xd=self.xd, yd=self.yd, octave=self.octave, uright=self.uright, depth=self.depth,
+                 cos_stereo=self.cos_stereo, cam_of=self.cam_of if self.cam_of_given else None)
+        a.update(override)
+        return m.TriKeyframe(self.Tcw, self.centre, self.Twc, self.Rcam12, self.tcam12, self.fx, self.fy, self.cx, self.cy, self.invfx,
+                             self.invfy, self.mbf, self.scale_factors, self.level_sigma2, self.n_cam1, n=self.n, **a)
+
+
+class World:
+    def __init__(self, kf1, kf2, pairs, cam_enabled=(1, 1)):
+        self.kf1, self.kf2 = kf1, kf2
+        self.pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        self.cam_enabled = np.array(cam_enabled, np.uint8)
+        self.ratio_factor = f32(1.5) * kf1.scale_factors[1]          # 1.5f * mfScaleFactor
+
+    def model(self, pairs=None):
+        return tm.triangulate(self.kf1, self.kf2, self.cam_enabled, self.pairs if pairs is None else pairs, self.ratio_factor)
+
+    def host(self, pairs=None):
+        import multi_orb_slam_amd as m
+        return m.triangulate_pairs_host(self.kf1.native(), self.kf2.native(), self.cam_enabled, self.pairs if pairs is None else pairs,
+                                        self.ratio_factor)
+
+    def device(self, search, pairs=None):
+        return search.triangulate_pairs(self.kf1.native(), self.kf2.native(), self.cam_enabled, self.pairs if pairs is None else pairs,
+                                        self.ratio_factor)
+
+
+def _project(kf, cam, Xw):
+    Xc = Xw @ kf.Tcw[cam, :, :3].astype(np.float64).T + kf.Tcw[cam, :, 3].astype(np.float64)
+    z = Xc[:, 2]
+    safe = np.where(np.abs(z) < 1e-6, 1e-6, z)
+    return FX * Xc[:, 0] / safe + CX, FY * Xc[:, 1] / safe + CY, z
+
+
+def make_world(name, n_pairs=N_PAIRS):
+    """n_pairs points seen by the same camera of two keyframes, one feature per point in each keyframe (camera-1 features first, as the
+    reference numbers them; keyframe 2 holds its features in another order)."""
+    t2, deg, seed = WORLDS[name]
+    rng = np.random.default_rng(seed)
+    n2 = int(round(0.35 * n_pairs)); n1 = n_pairs - n2                        # 35 % camera-2 pairs
+    kf1 = KF(rotation((0.3, 1.0, 0.2), 1.5), (0.02, -0.01, 0.03), n1)
+    R2 = rotation((0.2, 1.0, -0.3), deg) @ rotation((0.3, 1.0, 0.2), 1.5)
+    kf2 = KF(R2, -R2 @ (np.asarray(t2) + kf1.centre[0].astype(np.float64)), n1)
+    cam = (np.arange(n_pairs) >= n1).astype(np.int64)
+    s = scale_factors().astype(np.float64)
+    # the point: a pixel and a log-uniform depth in the pair's camera of keyframe 1
+    u = rng.uniform(20, 620, n_pairs); v = rng.uniform(20, 460, n_pairs)
+    z = np.exp(rng.uniform(np.log(0.4), np.log(15.0), n_pairs))
+    Xc = np.stack([(u - CX) / FX * z, (v - CY) / FY * z, z], 1)
+    Xw = np.zeros((n_pairs, 3))
+    for c in (0, 1):
+        R, t = kf1.Tcw[c, :, :3].astype(np.float64), kf1.Tcw[c, :, 3].astype(np.float64)
+        Xw[cam == c] = (Xc[cam == c] - t) @ R
+    u2 = np.zeros(n_pairs); v2 = np.zeros(n_pairs); z2 = np.zeros(n_pairs)
+    for c in (0, 1):
+        a, b, d = _project(kf2, c, Xw[cam == c])
+        u2[cam == c], v2[cam == c], z2[cam == c] = a, b, d
+    # octaves: consistent with the two distances, 6 % unrelated
+    oct1 = rng.integers(0, N_LEVELS, n_pairs)
+    d1 = np.linalg.norm(Xw - kf1.centre[cam].astype(np.float64), axis=1); d2 = np.linalg.norm(Xw - kf2.centre[cam].astype(np.float64), axis=1)
+    oct2 = np.clip(oct1 + np.round(np.log(d1 / d2) / np.log(1.2)).astype(np.int64), 0, N_LEVELS - 1)
+    unrelated = rng.random(n_pairs) < 0.06
+    oct2[unrelated] = rng.integers(0, N_LEVELS, int(unrelated.sum()))
+    # pixel noise 0.4 * scale of the octave; 10 % of the points eight times that in keyframe 2
+    x1 = u + rng.normal(0, 0.4, n_pairs) * s[oct1]; y1 = v + rng.normal(0, 0.4, n_pairs) * s[oct1]
+    wild = np.where(rng.random(n_pairs) < 0.10, 8.0, 1.0)
+    x2 = u2 + rng.normal(0, 0.4, n_pairs) * s[oct2] * wild; y2 = v2 + rng.normal(0, 0.4, n_pairs) * s[oct2] * wild
+    # measured depth with 1 % noise; 30 % of the features without one, independently on either side (and none behind a camera)
+    dep1 = z * (1 + rng.normal(0, 0.01, n_pairs)); dep2 = z2 * (1 + rng.normal(0, 0.01, n_pairs))
+    no1 = rng.random(n_pairs) < 0.30; no2 = (rng.random(n_pairs) < 0.30) | (z2 <= 0.05)
+    ur1 = np.where(no1, -1.0, x1 - MBF / np.where(no1, 1.0, dep1)); dep1 = np.where(no1, -1.0, dep1)
+    ur2 = np.where(no2, -1.0, x2 - MBF / np.where(no2, 1.0, dep2)); dep2 = np.where(no2, -1.0, dep2)
+    # a far stereo point can have a right coordinate left of the image: the reference keeps such a feature only with uright >= 0
+    neg1 = ~no1 & (ur1 < 0); ur1[neg1] = -1.0; dep1[neg1] = -1.0
+    neg2 = ~no2 & (ur2 < 0); ur2[neg2] = -1.0; dep2[neg2] = -1.0
+
+    def distorted(x, y):                                                      # mvKeys_total: the keypoint before undistortion
+        r2 = ((x - CX) / FX) ** 2 + ((y - CY) / FY) ** 2
+        return x + (x - CX) * 0.01 * r2, y + (y - CY) * 0.01 * r2
+    xd1, yd1 = distorted(x1, y1); xd2, yd2 = distorted(x2, y2)
+    kf1.set_features(x1, y1, xd1, yd1, oct1, ur1, dep1)
+    # keyframe 2 in another order, camera by camera
+    order = np.concatenate([rng.permutation(n1), n1 + rng.permutation(n2)])   # feature j of keyframe 2 is point order[j]
+    where = np.empty(n_pairs, np.int64); where[order] = np.arange(n_pairs)
+    kf2.set_features(x2[order], y2[order], xd2[order], yd2[order], oct2[order], ur2[order], dep2[order])
+    pairs = np.stack([np.arange(n_pairs), where], 1)
+    pairs = pairs[rng.permutation(n_pairs)]                                    # the search's pairs come in no special order here
+    return World(kf1, kf2, pairs)
+
+
+@functools.lru_cache(maxsize=None)
+def world_and_model(name):
+    """A generated world and the model's records of it (computed once per process: a few seconds each)."""
+    w = make_world(name)
+    return w, w.model()
+
+
+def check_conditions(records):
+    """The condition on the union of the worlds (asserted), returned as the text the tests print."""
+    oc = np.bincount(np.concatenate([r["outcome"] for r in records]), minlength=11)
+    pa = np.bincount(np.concatenate([r["path"] for r in records]), minlength=4)
+    lines = ["outcomes over %d pairs: " % int(oc.sum()) + ", ".join("%s %d" % (tm.OUTCOME_NAMES[k], oc[k]) for k in range(1, 11)),
+             "paths: " + ", ".join("%s %d" % (tm.PATH_NAMES[k], pa[k]) for k in range(4))]
+    for r in records:
+        o = np.bincount(r["outcome"], minlength=11); p = np.bincount(r["path"], minlength=4)
+        lines.append("  world of %d: " % len(r) + " ".join("%d" % v for v in o[1:]) + " | " + " ".join("%d" % v for v in p))
+    text = "\n".join(lines)
+    for k in (tm.ACCEPTED, tm.LOW_PARALLAX, tm.Z1, tm.Z2, tm.REPROJ1, tm.REPROJ2, tm.SCALE):       # w == 0, zero distance and camera
+        assert oc[k] >= 5, (tm.OUTCOME_NAMES[k], text)                                             # off come from hand-built pairs
+    for k in (tm.PATH_SVD, tm.PATH_UNPROJECT1, tm.PATH_UNPROJECT2):
+        assert pa[k] >= 100, (tm.PATH_NAMES[k], text)
+    return text
+
+
+# ---- hand-built pairs ---------------------------------------------------------------------------------------------------------
+def exact_world(stereo1=True, stereo2=False, baseline=1.0 / 32):
+    """Power-of-two intrinsics (f = 512, mbf = 32, so mb = 1/16 m), axis-aligned poses, keyframe 2 `baseline` metres to the right, and
+    the point (1, 2, 4): pixel (448, 496) in keyframe 1, (448 - 128*baseline, 496) in keyframe 2, disparity 32/4 = 8 in both.  Every
+    quantity of the pair is exact in float.  With baseline = 1/32 the rays are closer to parallel than the stereo pair's, so a stereo
+    feature is unprojected; with 1/4 the linear triangulation runs."""
+    kw = dict(fx=512.0, fy=512.0, cx=320.0, cy=240.0, mbf=32.0)
+    kf1, kf2 = KF(np.eye(3), (0, 0, 0), 1, **kw), KF(np.eye(3), (-baseline, 0, 0), 1, **kw)
+    u2 = 448.0 - 128.0 * baseline
+    kf1.set_features([448.0], [496.0], [448.0], [496.0], [0], [440.0 if stereo1 else -1.0], [4.0 if stereo1 else -1.0])
+    kf2.set_features([u2], [496.0], [u2], [496.0], [0], [u2 - 8.0 if stereo2 else -1.0], [4.0 if stereo2 else -1.0])
+    return World(kf1, kf2, [[0, 0]])
+
+
+def w_zero_world():
+    """An A whose null vector has w = 0.  A camera-2 pair with both features at the principal point (xn = (0, 0, 1)) and a second-camera
+    [R|t] whose rotation is a quarter turn about y in BOTH keyframes: column 0 of A, xn*R20 - R00 and yn*R20 - R10, is zero in all four
+    rows, the Jacobi sweeps never touch the matching row of Vt, which stays (1, 0, 0, 0), and with three non-zero singular values the sort
+    puts it last.  The first cameras are 20 degrees apart, so the rays (which use the FIRST camera's rotations) show parallax and the
+    linear triangulation is entered."""
+    kf1 = KF(np.eye(3), (0, 0, 0), 0)
+    kf2 = KF(rotation((0, 1, 0), 20.0), (0, 0, 0), 0)
+    quarter = np.array([[0, 0, 1], [0, 1, 0], [-1, 0, 0]], np.float32)
+    for kf, t in ((kf1, (0.5, 0.25, 1.0)), (kf2, (-0.75, 1.5, 2.0))):
+        kf.Tcw[1, :, :3] = quarter; kf.Tcw[1, :, 3] = t
+        kf.set_features([CX], [CY], [CX], [CY], [0], [-1.0], [-1.0])
+    return World(kf1, kf2, [[0, 0]])
+
+
+def zero_distance_worlds():
+    """The accepted exact pair with the centre of keyframe 1 (then of keyframe 2) moved onto the point: the [R|t] matrices, which decide
+    depth and reprojection, stay where they were."""
+    out = []
+    for which in (0, 1):
+        w = exact_world()
+        (w.kf1, w.kf2)[which].centre[0] = (1.0, 2.0, 4.0)
+        out.append(w)
+    return out
+
+
+def hand_built():
+    """name -> (world, expected outcome, expected path)"""
+    z1, z2 = zero_distance_worlds()
+    return {"w == 0": (w_zero_world(), tm.W_ZERO, tm.PATH_SVD),
+            "zero distance 1": (z1, tm.ZERO_DIST, tm.PATH_UNPROJECT1),
+            "zero distance 2": (z2, tm.ZERO_DIST, tm.PATH_UNPROJECT1)}
