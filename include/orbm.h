@@ -361,6 +361,73 @@ int orbm_refresh_points(orbm_matcher* m, const orbm_refresh_in* in, orbm_refresh
 /* The same routine entirely on the host, no device needed: the fallback above and the cross-check of the kernels. */
 int orbm_refresh_points_host(const orbm_refresh_in* in, orbm_refresh_out* out);
 
+/* -- pose optimisation: motion-only Levenberg-Marquardt ----------------------------------------------------------
+ * Optimizer::PoseOptimization(Frame*) (reference src/Optimizer.cc:352-618, camera 1 only) and PoseOptimization(Frame*, bool bAllCams)
+ * (:620-898, every camera through Tcim) from the edge list on: one 6-dof vertex, one unary edge per feature with a map point
+ * (EdgeSE3ProjectXYZOnlyPose / EdgeStereoSE3ProjectXYZOnlyPose, mono or stereo by uright < 0; their _multi forms in the all-cameras
+ * mode), four rounds of at most ten Levenberg iterations each restarting from the start pose, a re-classification of every edge
+ * after each round ((float)chi2 > 5.991f / 7.815f), the Huber kernel in the first three rounds.  g2o, Eigen and the C library's sin /
+ * cos / pow are restated, not linked; what that leaves UNPINNED is listed in DESIGN.md section 2.
+ * Two evaluation orders of ONE host routine:
+ *   ORBM_POSE_ORDER_INDEX    every sum over edges sequential in ascending edge position, sin / cos / pow(., 3) of the C library: the
+ *                            restatement of the reference.
+ *   ORBM_POSE_ORDER_DEVICE   the sums in the kernel's fixed tree (256 lanes: lane l owns edges l, l + 256, ... in ascending order, then an
+ *                            xor butterfly 1, 2, ..., 32 inside each wave, then the four waves in wave order); sine and cosine from a fixed
+ *                            sequence of + - * / in double, the cube by multiplication.  What the device computes, bit for bit. */
+enum { ORBM_POSE_CAM0 = 0, ORBM_POSE_ALL_CAMS = 1 };
+enum { ORBM_POSE_ORDER_INDEX = 0, ORBM_POSE_ORDER_DEVICE = 1 };
+enum { ORBM_POSE_CAP = 8192,      /* edges of one problem the device takes; a longer one runs on the host inside the same call */
+       ORBM_POSE_MAX_BATCH = 64, ORBM_POSE_ROUNDS = 4 };
+
+typedef struct orbm_pose_problem {
+    float Tcw[16];                 /* pFrame->mTcw, row-major 4x4: the start pose of every round                      */
+    float fx, fy, cx, cy, bf;      /* pFrame->fx, fy, cx, cy, mbf                                                      */
+    float Rcam12[9], tcam12[3];    /* pFrame->mRcam12 (row-major), mtcam12: read in the all-cameras mode only          */
+    float inv_level_sigma2[ORBM_MAX_LEVELS];   /* pFrame->mvInvLevelSigma2                                             */
+    int32_t n_levels;              /* 1 .. ORBM_MAX_LEVELS: every edge's octave lies below it                          */
+    int32_t mode;                  /* ORBM_POSE_CAM0 / ORBM_POSE_ALL_CAMS                                              */
+    int32_t n_cam0;                /* pFrame->N: in the all-cameras mode feature g belongs to camera 2 when g >= n_cam0 */
+} orbm_pose_problem;               /* 272 bytes */
+
+typedef struct orbm_pose_round {   /* one optimizer.optimize(10) */
+    int32_t iterations, trials;    /* Levenberg iterations run, linear solves (trials) run over all of them            */
+    double chi2, lambda;           /* the robust chi2 and the damping the round ended with (0 when nothing was active) */
+} orbm_pose_round;
+
+typedef struct orbm_pose_result {
+    float Tcw[16];                 /* Converter::toCvMat of the final estimate: what SetPose receives (the start pose, bit for bit, when n_initial < 3) */
+    double q[4], t[3];             /* the estimate it was rounded from: quaternion x y z w, translation                */
+    int32_t n_initial, n_bad;      /* nInitialCorrespondences, nBad of the last round run                              */
+    int32_t n_inliers;             /* the reference's return value: n_initial - n_bad, 0 when n_initial < 3            */
+    int32_t rounds;                /* rounds run: 0 (n_initial < 3), 1 (n_initial < 10) or 4                           */
+    orbm_pose_round round[ORBM_POSE_ROUNDS];
+} orbm_pose_result;                /* 232 bytes, no padding */
+
+/* B problems (1 .. ORBM_POSE_MAX_BATCH) in one call, one workgroup per problem, resident from the first residual to the last flag.
+ * The edges arrive as host arrays, CSR per problem: problem b owns edges first[b] .. first[b+1]-1 in ascending feature index.
+ *   feat[e]    feature index i of the edge (decides the camera in the all-cameras mode)
+ *   pos[3e..]  pMP->GetWorldPos()
+ *   obs[3e..]  mvKeysUn[_total][i].pt.x, .pt.y, mvuRight[_total][i]   (uright < 0: a monocular edge)
+ *   octave[e]  mvKeysUn[_total][i].octave
+ * outlier_out[e] = mvbOutlier of the edge's feature; results[b] as above.  A NaN result is written as the NaN x86 makes from an
+ * invalid operation (sign bit set) by the device and the host routine alike; what a NaN or infinite INPUT gives is not specified bit
+ * for bit.  A problem beyond ORBM_POSE_CAP edges runs through the host routine in the device order inside the same call
+ * (orbm_debug_last_pose, include/orb_debug.h). */
+int orbm_pose_optimize(orbm_matcher* m, const orbm_pose_problem* problems, int B, const int32_t* first, const int32_t* feat,
+                       const float* pos, const float* obs, const int32_t* octave, uint8_t* outlier_out, orbm_pose_result* results);
+/* The same routine entirely on the host, no device needed, in either order. */
+int orbm_pose_optimize_host(const orbm_pose_problem* problems, int B, const int32_t* first, const int32_t* feat, const float* pos,
+                            const float* obs, const int32_t* octave, int order, uint8_t* outlier_out, orbm_pose_result* results);
+/* One problem whose observations and positions are already in HBM: x, y, uright and octave of feature g are read from the resident
+ * frame `cur` (the arrays the searches compare against), the position from row point_of_feature[g] of the table `pts`
+ * (point_of_feature: n_total entries on the host, a row or a negative value = no point; the shape orbm_search_local_points returns in
+ * match_of_feature).  Edges = the features with a point in ascending g (g < n_cam0 only in ORBM_POSE_CAM0).  One 4-byte word per
+ * edge goes up; outlier_out has n_total entries, 0 for a feature without an edge.  Same bytes as orbm_pose_optimize on the same data. */
+int orbm_pose_optimize_resident(orbm_matcher* m, const orbm_pose_problem* problem, const orbm_frame* cur, const orbm_points* pts,
+                                const int32_t* point_of_feature, uint8_t* outlier_out, orbm_pose_result* result);
+/* (test hook) The sine / cosine sequence of ORBM_POSE_ORDER_DEVICE on the host. */
+void orbm_pose_sincos(double x, double* s, double* c);
+
 #ifdef __cplusplus
 }
 #endif

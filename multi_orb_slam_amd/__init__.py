@@ -9,5 +9,7 @@ from ._lib import lib, build, LIB_PATH, OrbError, KP_DTYPE, QUERY_DTYPE, POINT_D
 from .extractor import Extractor, ExtractorParams, tables  # noqa: F401
 from .matcher import Matcher, FrameData, LocalPoints, View, descriptor_distance, three_maxima  # noqa: F401
 from .matcher import frustum_host, level_thresholds, RefreshBatch, refresh_points_host  # noqa: F401
+from .matcher import PoseProblem, pose_optimize_host, pose_sincos  # noqa: F401
+from ._lib import POSE_PROBLEM_DTYPE, POSE_RESULT_DTYPE, POSE_CAM0, POSE_ALL_CAMS, POSE_ORDER_INDEX, POSE_ORDER_DEVICE, POSE_CAP  # noqa: F401
 from .vocabulary import Vocabulary, BowSearch, Side as BowSide, FeatureVector, score_l1, KeyFrameDatabase  # noqa: F401
 from .vocabulary import TriKeyframe, TRI_OUT_DTYPE, cos_stereo, triangulate_pairs_host  # noqa: F401

@@ -25,6 +25,14 @@ REFRESH_DTYPE = np.dtype([("desc", "u1", (32,)), ("normal", "<f4", (3,)), ("min_
                           ("best_obs", "<i4"), ("best_median", "<i4")])   # orbm_refresh_out
 assert REFRESH_DTYPE.itemsize == 60
 REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH, REFRESH_CAP = 1, 2, 256
+POSE_PROBLEM_DTYPE = np.dtype([("Tcw", "<f4", (16,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("bf", "<f4"),
+                               ("Rcam12", "<f4", (9,)), ("tcam12", "<f4", (3,)), ("inv_level_sigma2", "<f4", (32,)),
+                               ("n_levels", "<i4"), ("mode", "<i4"), ("n_cam0", "<i4")])   # orbm_pose_problem
+POSE_ROUND_DTYPE = np.dtype([("iterations", "<i4"), ("trials", "<i4"), ("chi2", "<f8"), ("lambda", "<f8")])
+POSE_RESULT_DTYPE = np.dtype([("Tcw", "<f4", (16,)), ("q", "<f8", (4,)), ("t", "<f8", (3,)), ("n_initial", "<i4"), ("n_bad", "<i4"),
+                              ("n_inliers", "<i4"), ("rounds", "<i4"), ("round", POSE_ROUND_DTYPE, (4,))])   # orbm_pose_result
+assert POSE_PROBLEM_DTYPE.itemsize == 272 and POSE_RESULT_DTYPE.itemsize == 232
+POSE_CAM0, POSE_ALL_CAMS, POSE_ORDER_INDEX, POSE_ORDER_DEVICE, POSE_CAP, POSE_MAX_BATCH = 0, 1, 0, 1, 8192, 64
 
 ORB_OK, ORB_E_ARG, ORB_E_HIP, ORB_E_CAPACITY, ORB_E_NO_DEVICE, ORB_E_TIMEOUT = 0, -1, -2, -3, -4, -5
 
@@ -249,6 +257,11 @@ def lib():
     L.orbm_refresh_points.argtypes = [vp, vp, vp]
     L.orbm_refresh_points_host.argtypes = [vp, vp]
     L.orbm_debug_last_refresh.argtypes = [vp, vp]
+    L.orbm_pose_optimize.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_pose_optimize_host.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp]
+    L.orbm_pose_optimize_resident.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_debug_last_pose.argtypes = [vp, vp]
+    L.orbm_pose_sincos.argtypes = [C.c_double, vp, vp]; L.orbm_pose_sincos.restype = None
     f64 = C.c_double
     L.orbv_create.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp]
     L.orbv_load_text.argtypes = [C.c_char_p, i32, vp]

@@ -235,6 +235,12 @@ void orbm_points_destroy(orbm_points* p) {
 
 int orbm_points_count(const orbm_points* p) { return p ? p->count : ORB_E_ARG; }
 
+int morb::points_view(const orbm_points* p, const orbm_matcher* m, const orbm_point** d_rows, const orbm_point** h_rows, int* count) {
+    MORB_ARG(p && m && p->owner == m);
+    *d_rows = p->d.p; *h_rows = p->h.data(); *count = p->count;
+    return ORB_OK;
+}
+
 int orbm_points_write(orbm_matcher* m, orbm_points* p, int first, int n, const orbm_point* src) {
     MORB_ARG(m && p && p->owner == m && first >= 0 && n >= 0 && (n == 0 || src));
     if ((long long)first + n > p->capacity) {

@@ -122,7 +122,7 @@ void orbm_destroy(orbm_matcher* m) {
     m->d_i0.release(); m->d_i1.release(); m->d_i2.release(); m->d_choice.release(); m->d_claim.release(); m->d_qmeta.release(); m->d_win2.release();
     m->d_match.release(); m->d_status.release(); m->d_gclaim.release(); m->d_rsync.release(); m->d_mergecnt.release(); m->d_u16.release(); m->d_x0.release(); m->d_x1.release(); m->d_x2.release();
     m->h_i0.release(); m->h_i1.release(); m->h_i2.release(); m->h_match.release(); m->h_u16.release(); m->h_ring.release();
-    m->stage_f.release(); m->stage_q.release(); m->stage_r.release(); m->h_refresh.release();
+    m->stage_f.release(); m->stage_q.release(); m->stage_r.release(); m->h_refresh.release(); m->stage_p.release(); m->h_pose.release();
     if (m->ev_stage_f) (void)hipEventDestroy(m->ev_stage_f);
     for (FrameBufs* b : m->pool) { b->release(); delete b; }
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
@@ -134,6 +134,12 @@ void* orbm_stream(const orbm_matcher* m) { return m ? (void*)m->stream : nullptr
 int orbm_debug_last_resolve(const orbm_matcher* m, int* out4) {
     MORB_ARG(m && out4);
     for (int k = 0; k < 4; ++k) out4[k] = m->last_status[k];
+    return ORB_OK;
+}
+
+int orbm_debug_last_pose(const orbm_matcher* m, int* out2) {
+    MORB_ARG(m != nullptr && out2 != nullptr);
+    out2[0] = m->last_pose[0]; out2[1] = m->last_pose[1];
     return ORB_OK;
 }
 

@@ -1,6 +1,6 @@
 // matcher_internal.h -- types and internal entry points shared by the translation units of the matcher / front end
 // (hamming.hip: all-pairs kernels; frame.hip: frame assembly; search.hip: projection search + resolve; matcher.hip: handle
-// + host helpers; exchange.hip: RCCL / loopback transport; frontend.hip: orbf_*; mappoint.hip: map-point refresh).  Not part of the C ABI.
+// + host helpers; exchange.hip: RCCL / loopback transport; frontend.hip: orbf_*; mappoint.hip: map-point refresh; pose.hip: pose optimisation).  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <condition_variable>
@@ -107,6 +107,11 @@ struct orbm_matcher {
     PinnedBuf<orbm_refresh_out> h_refresh;
     std::vector<int32_t> refresh_list;
     int last_refresh[5] = {0, 0, 0, 0, 0};
+    // orbm_pose_optimize (pose.hip): the packed problems and edges of a call (host-written, read in place by the kernel), the records
+    // and flags the kernel writes (mapped pinned) and where the problems of the last call went
+    morb::StageBuf stage_p;
+    PinnedBuf<uint8_t> h_pose;
+    int last_pose[2] = {0, 0};
 };
 namespace morb { hipStream_t side_stream(orbm_matcher* m); }   // (lazily created; NULL after a reported failure)
 
@@ -217,6 +222,9 @@ int frame_from_device_impl(orbm_matcher* m, const orbm_cam_features* cams, int n
                            float max_x, float max_y, const int* d_counts, orbm_frame** out, bool sink_filled = false);
 void frame_set_counts(orbm_frame* F, const int* counts);
 int phases_frame_build(unsigned long long* out64);
+// ---- frustum.hip
+// the device rows and the host mirror of a point table (orbm_pose_optimize_resident reads positions by row)
+int points_view(const orbm_points* p, const orbm_matcher* m, const orbm_point** d_rows, const orbm_point** h_rows, int* count);
 // ---- search.hip
 int search_raise_lds_limits();  // per device, from orbm_create
 int search_enqueue(orbm_matcher* m, SearchJob& J, bool queries_already_on_device = false);

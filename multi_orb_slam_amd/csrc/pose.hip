@@ -1,0 +1,885 @@
+// pose.hip -- motion-only pose optimisation on the device (include/orbm.h, "pose optimisation"): Optimizer::PoseOptimization(Frame*)
+// (reference src/Optimizer.cc:352-618) and PoseOptimization(Frame*, bool bAllCams) (:620-898) from the edge list on, with the parts of
+// g2o they run restated (Thirdparty/g2o/g2o/: types/types_six_dof_expmap.{h,cpp}, types/se3quat.h, types/se3_ops.hpp,
+// core/base_unary_edge.hpp, core/base_edge.h, core/robust_kernel_impl.cpp, core/optimization_algorithm_levenberg.cpp,
+// core/sparse_optimizer.cpp, solvers/linear_solver_dense.h) and the Eigen operators those call.
+//   pose_eigen_*     the Eigen operators, restated from Eigen's published sources and UNPINNED (Eigen is not linked and g2o was never
+//                    compiled against this code: DESIGN.md section 2): each is ONE function that a later pin changes.
+//   pose_edge        one edge: error, chi2 and the Jacobian of its type, ONE statement sequence for the kernel and the host routine.
+//   pose_step        the controller: everything between two passes over the edges (Levenberg bookkeeping, the 6x6 solve, the exp map,
+//                    the round and classification logic) as a resumable state machine over a PoseCtl record.  The host routine calls it
+//                    between its passes, lane 0 of the workgroup calls it on the record in LDS: the same statements.
+//   k_pose_optimize  one workgroup of 256 lanes per problem, resident for the whole call.  Per pass: every lane evaluates its edges
+//                    (lane l owns l, l + 256, ...; the first eight of them stay in registers, a longer tail streams from the staged
+//                    edge arrays), sums 21 + 6 + 1 + 1 doubles over them in ascending order, an xor butterfly (1, 2, 4, 8, 16, 32) sums
+//                    across the wave, lane 0 of each wave leaves its sums in LDS, and lane 0 of the workgroup adds the four waves in wave
+//                    order and runs pose_step.  Two barriers per pass, no atomics, no order that depends on arrival.
+// No libm function runs in the kernel: + - * / sqrt in double (the correctly rounded sequences), conversions.
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/orbm.h"
+#include "../../include/orb_debug.h"
+#include "orb_common.h"
+#include "matcher_internal.h"
+
+namespace {
+
+constexpr int POSE_T = 256;          // lanes of the workgroup = leaves of the summation tree
+constexpr int POSE_REG_SLOTS = 8;    // edges per lane whose constants stay in registers
+constexpr int POSE_NSUM = 29;        // H upper triangle (21, row-major i <= j), b (6), robust chi2, outlier count
+enum { POSE_CMD_FULL = 0, POSE_CMD_CHI = 1, POSE_CMD_CLASSIFY = 2, POSE_CMD_DONE = 3 };
+
+struct PoseSE3 { double q[4], t[3]; };   // g2o::SE3Quat: quaternion in Eigen's coefficient order x y z w, translation
+struct PoseCam {                         // per problem: the members of the edges that do not depend on the edge
+    double fx, fy, cx, cy, bf;
+    PoseSE3 Tc[2];                       // Tcim[cam] (:659-666); read in the all-cameras mode only
+    double Rc[2][9];                     // Tcim_quat.to_homogeneous_matrix().block(0,0,3,3)
+    double delta[2], dsqr[2];            // RobustKernelHuber::_delta (double) and dsqr (a FLOAT member) of a mono / stereo edge
+    int multi, n_cam0;
+};
+struct PoseEdge { float X[3], obs[3], inv_sigma2; int meta; };   // meta: bit 0 camera, bit 1 stereo, bit 2 slot in use
+
+// ---- the Eigen boundary: UNPINNED --------------------------------------------------------------------------------
+// Quaternion<double>(Matrix3d) (Geometry/Quaternion.h, quaternionbase_assign_impl<Other,3,3>)
+__host__ __device__ inline void pose_eigen_quat_from_matrix(const double* m, double* q) {
+    double t = m[0] + m[4] + m[8];
+    if (t > 0) {
+        t = sqrt(t + 1.0);
+        q[3] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (m[7] - m[5]) * t;
+        q[1] = (m[2] - m[6]) * t;
+        q[2] = (m[3] - m[1]) * t;
+    } else if (!(m[4] > m[0]) && !(m[8] > m[0])) {        // i = 0, j = 1, k = 2
+        t = sqrt(m[0] - m[4] - m[8] + 1.0);
+        q[0] = 0.5 * t; t = 0.5 / t;
+        q[3] = (m[7] - m[5]) * t; q[1] = (m[3] + m[1]) * t; q[2] = (m[6] + m[2]) * t;
+    } else if (m[4] > m[0] && !(m[8] > m[4])) {           // i = 1, j = 2, k = 0
+        t = sqrt(m[4] - m[8] - m[0] + 1.0);
+        q[1] = 0.5 * t; t = 0.5 / t;
+        q[3] = (m[2] - m[6]) * t; q[2] = (m[7] + m[5]) * t; q[0] = (m[1] + m[3]) * t;
+    } else {                                              // i = 2, j = 0, k = 1
+        t = sqrt(m[8] - m[0] - m[4] + 1.0);
+        q[2] = 0.5 * t; t = 0.5 / t;
+        q[3] = (m[3] - m[1]) * t; q[0] = (m[2] + m[6]) * t; q[1] = (m[5] + m[7]) * t;
+    }
+}
+// QuaternionBase::normalize: coeffs /= sqrt(squaredNorm), the squares summed in coefficient order
+__host__ __device__ inline void pose_eigen_quat_normalize(double* q) {
+    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    q[0] = q[0] / n; q[1] = q[1] / n; q[2] = q[2] / n; q[3] = q[3] / n;
+}
+// QuaternionBase::_transformVector: uv = vec x v; uv += uv; v + w*uv + vec x uv
+__host__ __device__ inline void pose_eigen_quat_rotate(const double* q, const double* v, double* out) {
+    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
+    uv[0] = uv[0] + uv[0]; uv[1] = uv[1] + uv[1]; uv[2] = uv[2] + uv[2];
+    const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
+    out[0] = v[0] + q[3] * uv[0] + c[0];
+    out[1] = v[1] + q[3] * uv[1] + c[1];
+    out[2] = v[2] + q[3] * uv[2] + c[2];
+}
+// quat_product<Architecture::Generic>
+__host__ __device__ inline void pose_eigen_quat_mul(const double* a, const double* b, double* r) {
+    const double w = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+    const double x = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+    const double y = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
+    const double z = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+    r[0] = x; r[1] = y; r[2] = z; r[3] = w;
+}
+// QuaternionBase::toRotationMatrix
+__host__ __device__ inline void pose_eigen_quat_to_matrix(const double* q, double* m) {
+    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
+    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
+    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
+    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
+    m[0] = 1 - (tyy + tzz); m[1] = txy - twz; m[2] = txz + twy;
+    m[3] = txy + twz; m[4] = 1 - (txx + tzz); m[5] = tyz - twx;
+    m[6] = txz - twy; m[7] = tyz + twx; m[8] = 1 - (txx + tyy);
+}
+// LDLT<MatrixXd>::compute (ldlt_inplace<Lower>::unblocked: the pivot is the FIRST largest |diagonal| of the remaining block) followed
+// by isPositive() and solve() (P, L, D with the 1/highest() tolerance, L^T, P^T); every inner product sequential in ascending index.
+// A: 6x6 row-major, destroyed (only its lower triangle is read).  Returns isPositive(); x is written only then, as g2o does.
+__host__ __device__ inline bool pose_eigen_ldlt_solve(double* A, const double* b, double* x, double* temp, int* transp) {
+    int sign = 0;   // 0 ZeroSign, 1 PositiveSemiDef, -1 NegativeSemiDef, 2 Indefinite
+    bool done = false;
+    for (int k = 0; k < 6 && !done; ++k) {
+        int idx = k;
+        double big = fabs(A[7 * k]);
+        for (int i = k + 1; i < 6; ++i) { const double v = fabs(A[7 * i]); if (v > big) { big = v; idx = i; } }
+        transp[k] = idx;
+        if (k != idx) {
+            for (int j = 0; j < k; ++j) { const double t = A[6 * k + j]; A[6 * k + j] = A[6 * idx + j]; A[6 * idx + j] = t; }
+            for (int i = idx + 1; i < 6; ++i) { const double t = A[6 * i + k]; A[6 * i + k] = A[6 * i + idx]; A[6 * i + idx] = t; }
+            { const double t = A[7 * k]; A[7 * k] = A[7 * idx]; A[7 * idx] = t; }
+            for (int i = k + 1; i < idx; ++i) { const double t = A[6 * i + k]; A[6 * i + k] = A[6 * idx + i]; A[6 * idx + i] = t; }
+        }
+        if (k > 0) {
+            for (int j = 0; j < k; ++j) temp[j] = A[7 * j] * A[6 * k + j];
+            double s = 0;
+            for (int j = 0; j < k; ++j) s += A[6 * k + j] * temp[j];
+            A[7 * k] -= s;
+            for (int i = k + 1; i < 6; ++i) {
+                double r = 0;
+                for (int j = 0; j < k; ++j) r += A[6 * i + j] * temp[j];
+                A[6 * i + k] -= r;
+            }
+        }
+        const double akk = A[7 * k];
+        const bool valid = fabs(akk) > 0;
+        if (k == 0 && !valid) {
+            for (int j = 0; j < 6; ++j) transp[j] = j;
+            done = true;
+        } else {
+            if (valid) for (int i = k + 1; i < 6; ++i) A[6 * i + k] = A[6 * i + k] / akk;
+            if (sign == 1) { if (akk < 0) sign = 2; }
+            else if (sign == -1) { if (akk > 0) sign = 2; }
+            else if (sign == 0) { if (akk > 0) sign = 1; else if (akk < 0) sign = -1; }
+        }
+    }
+    if (!(sign == 1 || sign == 0)) return false;
+    for (int i = 0; i < 6; ++i) x[i] = b[i];
+    for (int k = 0; k < 6; ++k) { const double t = x[k]; x[k] = x[transp[k]]; x[transp[k]] = t; }
+    for (int i = 1; i < 6; ++i) { double s = 0; for (int j = 0; j < i; ++j) s += A[6 * i + j] * x[j]; x[i] -= s; }
+    const double tol = 1.0 / DBL_MAX;
+    for (int i = 0; i < 6; ++i) x[i] = fabs(A[7 * i]) > tol ? x[i] / A[7 * i] : 0.0;
+    for (int i = 4; i >= 0; --i) { double s = 0; for (int j = i + 1; j < 6; ++j) s += A[6 * j + i] * x[j]; x[i] -= s; }
+    for (int k = 5; k >= 0; --k) { const double t = x[k]; x[k] = x[transp[k]]; x[transp[k]] = t; }
+    return true;
+}
+
+// ---- sine and cosine of ORBM_POSE_ORDER_DEVICE: one sequence of + - * / in double (the det_sincos precedent of the extractor) --------
+// k = x * 2/pi rounded to the nearest integer by adding and subtracting 1.5 * 2^52, a two-part pi/2, Taylor polynomials to z^8 on
+// [-pi/4, pi/4].  Within 2 ulp of the C library on [-100, 100] (tests/test_pose_model.py).
+__host__ __device__ inline void pose_sincos(double x, double* sn, double* cs) {
+    const double TWO_OVER_PI = 6.36619772367581382433e-01;
+    const double PIO2_HI = 1.57079632673412561417e+00, PIO2_LO = 6.07710050650619224932e-11;
+    const double MAGIC = 6755399441055744.0;
+    const double kf = (x * TWO_OVER_PI + MAGIC) - MAGIC;
+    const double r = (x - kf * PIO2_HI) - kf * PIO2_LO;
+    const double z = r * r;
+    double ps = 1.0 / 355687428096000.0;
+    ps = ps * z + (-1.0 / 1307674368000.0);
+    ps = ps * z + (1.0 / 6227020800.0);
+    ps = ps * z + (-1.0 / 39916800);
+    ps = ps * z + (1.0 / 362880);
+    ps = ps * z + (-1.0 / 5040);
+    ps = ps * z + (1.0 / 120);
+    ps = ps * z + (-1.0 / 6);
+    const double s = r + r * (z * ps);
+    double pc = 1.0 / 20922789888000.0;
+    pc = pc * z + (-1.0 / 87178291200.0);
+    pc = pc * z + (1.0 / 479001600);
+    pc = pc * z + (-1.0 / 3628800);
+    pc = pc * z + (1.0 / 40320);
+    pc = pc * z + (-1.0 / 720);
+    pc = pc * z + (1.0 / 24);
+    pc = pc * z + (-1.0 / 2);
+    const double c = 1.0 + z * pc;
+    const int q = (int)((long long)kf & 3);
+    *cs = (q == 0) ? c : (q == 1) ? -s : (q == 2) ? -c : s;
+    *sn = (q == 0) ? s : (q == 1) ? c : (q == 2) ? -s : -c;
+}
+
+// ---- SE(3) (types/se3quat.h) ------------------------------------------------------------------------------------------------------------
+__host__ __device__ inline void pose_normalize_rotation(PoseSE3& T) {   // SE3Quat::normalizeRotation
+    if (T.q[3] < 0) { T.q[0] *= -1; T.q[1] *= -1; T.q[2] *= -1; T.q[3] *= -1; }
+    pose_eigen_quat_normalize(T.q);
+}
+__host__ __device__ inline void pose_map(const PoseSE3& T, const double* v, double* out) {   // SE3Quat::map: _r*xyz + _t
+    double r[3];
+    pose_eigen_quat_rotate(T.q, v, r);
+    out[0] = r[0] + T.t[0]; out[1] = r[1] + T.t[1]; out[2] = r[2] + T.t[2];
+}
+// SE3Quat(R, t): Quaterniond(R), normalizeRotation
+__host__ __device__ inline void pose_from_matrix(const double* R, const double* t, PoseSE3& T) {
+    pose_eigen_quat_from_matrix(R, T.q);
+    T.t[0] = t[0]; T.t[1] = t[1]; T.t[2] = t[2];
+    pose_normalize_rotation(T);
+}
+// Converter::toSE3Quat: float 4x4 -> Matrix3d, Vector3d -> SE3Quat(R, t)
+__host__ __device__ inline void pose_from_cv(const float* M, PoseSE3& T) {
+    double R[9], t[3];
+    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) R[3 * r + c] = (double)M[4 * r + c]; t[r] = (double)M[4 * r + 3]; }
+    pose_from_matrix(R, t, T);
+}
+// SE3Quat::operator*: t = t1 + r1*t2, r = r1*r2, normalizeRotation
+__host__ __device__ inline void pose_mul(const PoseSE3& a, const PoseSE3& b, PoseSE3& out) {
+    double r[3], q[4];
+    pose_eigen_quat_rotate(a.q, b.t, r);
+    pose_eigen_quat_mul(a.q, b.q, q);
+    out.t[0] = a.t[0] + r[0]; out.t[1] = a.t[1] + r[1]; out.t[2] = a.t[2] + r[2];
+    out.q[0] = q[0]; out.q[1] = q[1]; out.q[2] = q[2]; out.q[3] = q[3];
+    pose_normalize_rotation(out);
+}
+// SE3Quat::exp (:223-257).  order: where sin, cos and pow(theta, 3) come from.
+__host__ __device__ inline void pose_exp(const double* update, int order, PoseSE3& T) {
+    const double o0 = update[0], o1 = update[1], o2 = update[2];
+    const double theta = sqrt(o0 * o0 + o1 * o1 + o2 * o2);
+    const double O[9] = {0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0};   // skew(omega)
+    double O2[9], R[9], V[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) O2[3 * i + j] = O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j] + O[3 * i + 2] * O[6 + j];
+    if (theta < 0.00001) {
+        for (int i = 0; i < 9; ++i) { R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + O[i]) + O2[i]; V[i] = R[i]; }
+    } else {
+        double sn, cs, th3;
+#ifndef __HIP_DEVICE_COMPILE__
+        if (order == ORBM_POSE_ORDER_INDEX) { sn = sin(theta); cs = cos(theta); th3 = pow(theta, 3); } else
+#endif
+        { pose_sincos(theta, &sn, &cs); th3 = theta * theta * theta; }
+        const double a = sn / theta, c = (1 - cs) / (theta * theta), d = (theta - sn) / th3;
+        for (int i = 0; i < 9; ++i) {
+            const double I = i % 4 == 0 ? 1.0 : 0.0;
+            R[i] = (I + a * O[i]) + c * O2[i];
+            V[i] = (I + c * O[i]) + d * O2[i];
+        }
+    }
+    double t[3];
+    for (int i = 0; i < 3; ++i) t[i] = V[3 * i] * update[3] + V[3 * i + 1] * update[4] + V[3 * i + 2] * update[5];
+    pose_from_matrix(R, t, T);   // SE3Quat(Quaterniond(R), V*upsilon)
+}
+
+// ---- one edge ---------------------------------------------------------------------------------------------------------------------------
+// computeError and chi2 of the edge's type; with want_jacobian also linearizeOplus (J: D rows of 6).  Returns chi2 = e . (Omega e) with
+// Omega = Identity * (double)invSigma2.
+__host__ __device__ inline double pose_edge(const PoseCam& C, const PoseSE3& T, const PoseEdge& E, double* e, bool want_jacobian, double (*J)[6]) {
+    const int cam = E.meta & 1;
+    const bool stereo = (E.meta & 2) != 0;
+    const double Xw[3] = {(double)E.X[0], (double)E.X[1], (double)E.X[2]};
+    double p[3], pc[3];
+    pose_map(T, Xw, p);                                   // v1->estimate().map(Xw)
+    if (C.multi) pose_map(C.Tc[cam], p, pc);              // Tcim_quat.map(...), also where it is the identity
+    else { pc[0] = p[0]; pc[1] = p[1]; pc[2] = p[2]; }
+    if (!stereo) {
+        const double proj0 = pc[0] / pc[2], proj1 = pc[1] / pc[2];            // project2d
+        e[0] = (double)E.obs[0] - (proj0 * C.fx + C.cx);
+        e[1] = (double)E.obs[1] - (proj1 * C.fy + C.cy);
+        e[2] = 0.0;
+    } else {
+        const float invz = (float)(1.0 / pc[2]);                               // `const float invz = 1.0f/trans_xyz[2]`
+        const double r0 = pc[0] * (double)invz * C.fx + C.cx;
+        const double r1 = pc[1] * (double)invz * C.fy + C.cy;
+        const double r2 = r0 - C.bf * (double)invz;
+        e[0] = (double)E.obs[0] - r0; e[1] = (double)E.obs[1] - r1; e[2] = (double)E.obs[2] - r2;
+    }
+    const double w = (double)E.inv_sigma2;
+    double chi2 = e[0] * (w * e[0]) + e[1] * (w * e[1]);
+    if (stereo) chi2 = chi2 + e[2] * (w * e[2]);
+    if (!want_jacobian) return chi2;
+    if (!C.multi) {                                       // the closed expressions of the plain edges (:495-517, :883-912)
+        const double x = p[0], y = p[1], invz = 1.0 / p[2], invz_2 = invz * invz;
+        J[0][0] = x * y * invz_2 * C.fx;
+        J[0][1] = -(1 + (x * x * invz_2)) * C.fx;
+        J[0][2] = y * invz * C.fx;
+        J[0][3] = -invz * C.fx;
+        J[0][4] = 0;
+        J[0][5] = x * invz_2 * C.fx;
+        J[1][0] = (1 + y * y * invz_2) * C.fy;
+        J[1][1] = -x * y * invz_2 * C.fy;
+        J[1][2] = -x * invz * C.fy;
+        J[1][3] = 0;
+        J[1][4] = -invz * C.fy;
+        J[1][5] = y * invz_2 * C.fy;
+        if (stereo) {
+            J[2][0] = J[0][0] - C.bf * y * invz_2;
+            J[2][1] = J[0][1] + C.bf * x * invz_2;
+            J[2][2] = J[0][2];
+            J[2][3] = J[0][3];
+            J[2][4] = 0;
+            J[2][5] = J[0][5] - C.bf * invz_2;
+        }
+    } else {                                              // the _multi edges multiply by Rcim, the identity included (:627-696, :952-1036)
+        const double* r = C.Rc[cam];
+        const double x = p[0], y = p[1], z = p[2];
+        const double xc = pc[0], yc = pc[1], zc = pc[2], zc_2 = zc * zc;
+        const double a1 = C.bf / zc_2;
+        double t1[3][3], t2[3][3];
+        t1[0][0] = -C.fx / zc; t1[0][1] = 0; t1[0][2] = C.fx * xc / zc_2;
+        t1[1][0] = 0; t1[1][1] = -C.fy / zc; t1[1][2] = C.fy * yc / zc_2;
+        t1[2][0] = t1[0][0]; t1[2][1] = 0; t1[2][2] = t1[0][2] - a1;
+        t2[0][0] = t1[0][0] * r[0] + t1[0][2] * r[6];
+        t2[0][1] = t1[0][0] * r[1] + t1[0][2] * r[7];
+        t2[0][2] = t1[0][0] * r[2] + t1[0][2] * r[8];
+        t2[1][0] = t1[1][1] * r[3] + t1[1][2] * r[6];
+        t2[1][1] = t1[1][1] * r[4] + t1[1][2] * r[7];
+        t2[1][2] = t1[1][1] * r[5] + t1[1][2] * r[8];
+        t2[2][0] = t2[0][0] - a1 * r[6];
+        t2[2][1] = t2[0][1] - a1 * r[7];
+        t2[2][2] = t2[0][2] - a1 * r[8];
+        const int D = stereo ? 3 : 2;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (k >= D) continue;
+            J[k][0] = -t2[k][1] * z + t2[k][2] * y;
+            J[k][1] = t2[k][0] * z - t2[k][2] * x;
+            J[k][2] = -t2[k][0] * y + t2[k][1] * x;
+            J[k][3] = t2[k][0];
+            J[k][4] = t2[k][1];
+            J[k][5] = t2[k][2];
+        }
+    }
+    return chi2;
+}
+
+// RobustKernelHuber::robustify as far as rho[0] and rho[1] go (core/robust_kernel_impl.cpp:78-91); dsqr is the kernel's float member
+__host__ __device__ inline void pose_huber(double e, double delta, double dsqr, double* rho0, double* rho1) {
+    if (e <= dsqr) { *rho0 = e; *rho1 = 1.; }
+    else { const double sqrte = sqrt(e); *rho0 = 2 * sqrte * delta - dsqr; *rho1 = delta / sqrte; }
+}
+
+// One ACTIVE edge's share of a pass (computeActiveErrors + activeRobustChi2, with `system` also linearizeOplus + constructQuadraticForm,
+// core/base_unary_edge.hpp:44-72): acc[27] += rho[0]; b -= rho[1] * J^T (Omega e); H += J^T (rho[1] Omega) J.  The edge's own 6-vector
+// and 6x6 are formed first (rows of J in order) and then added, as the edge adds its products to the vertex.  UNPINNED: Eigen's
+// evaluation order inside the two products.
+__host__ __device__ inline void pose_accumulate(const PoseCam& C, const PoseSE3& T, const PoseEdge& E, bool system, bool robust, double* acc) {
+    double e[3], J[3][6];
+    const bool stereo = (E.meta & 2) != 0;
+    const double chi2 = pose_edge(C, T, E, e, system, J);
+    double rho0 = chi2, rho1 = 1.;
+    if (robust) pose_huber(chi2, C.delta[stereo ? 1 : 0], C.dsqr[stereo ? 1 : 0], &rho0, &rho1);
+    acc[27] += rho0;
+    if (!system) return;
+    const double w = (double)E.inv_sigma2, rw = rho1 * w;
+    const double we[3] = {w * e[0], w * e[1], w * e[2]};
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = i; j < 6; ++j, ++k) {
+            double h = (J[0][i] * rw) * J[0][j] + (J[1][i] * rw) * J[1][j];
+            if (stereo) h = h + (J[2][i] * rw) * J[2][j];
+            acc[k] += h;
+        }
+        double g = J[0][i] * we[0] + J[1][i] * we[1];
+        if (stereo) g = g + J[2][i] * we[2];
+        acc[21 + i] -= rho1 * g;
+    }
+}
+
+// the classification of one edge after a round (:541-597): an outlier's error is recomputed at the estimate, an inlier keeps the error
+// of the last computeActiveErrors (the pose of the last pass, which is the REJECTED trial when the round ended on one)
+__host__ __device__ inline bool pose_classify(const PoseCam& C, const PoseSE3& est, const PoseSE3& last, const PoseEdge& E, bool was_outlier) {
+    double e[3], J[3][6];
+    const float chi2 = (float)pose_edge(C, was_outlier ? est : last, E, e, false, J);
+    return (E.meta & 2) ? chi2 > 7.815f : chi2 > 5.991f;
+}
+
+// ---- the controller ---------------------------------------------------------------------------------------------------------------------
+struct PoseCtl {
+    int cmd, order, n, round, iter, qmax, n_bad_steps, robust, n_bad, ok2;
+    PoseSE3 start, est, eval, last;          // eval: the pose of the next pass; last: the pose of the last FULL / CHI pass
+    double H[21], b[6], x[6], lambda, ni, current_chi, ini_chi;
+    double A[36], temp[6]; int transp[6];    // the solver's working storage (indexed at run time: LDS on the device, never registers)
+    orbm_pose_result res;
+};
+
+__host__ __device__ inline double pose_canonical(double x) {
+    if (x == x) return x;
+    const unsigned long long bits = 0xfff8000000000000ull;
+    double d;
+    memcpy(&d, &bits, 8);
+    return d;
+}
+__host__ __device__ inline float pose_canonical_f(float x) {
+    if (x == x) return x;
+    const uint32_t bits = 0xffc00000u;
+    float f;
+    memcpy(&f, &bits, 4);
+    return f;
+}
+
+// Converter::toCvMat(SE3Quat): to_homogeneous_matrix() rounded to float
+__host__ __device__ inline void pose_write_estimate(PoseCtl& S) {
+    double R[9];
+    pose_eigen_quat_to_matrix(S.est.q, R);
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) S.res.Tcw[4 * r + c] = pose_canonical_f((float)R[3 * r + c]);
+        S.res.Tcw[4 * r + 3] = pose_canonical_f((float)S.est.t[r]);
+    }
+    S.res.Tcw[12] = 0.0f; S.res.Tcw[13] = 0.0f; S.res.Tcw[14] = 0.0f; S.res.Tcw[15] = 1.0f;
+    for (int k = 0; k < 4; ++k) S.res.q[k] = pose_canonical(S.est.q[k]);
+    for (int k = 0; k < 3; ++k) S.res.t[k] = pose_canonical(S.est.t[k]);
+}
+
+// one trial of the Levenberg loop up to its pass (:103-121): H + lambda on the diagonal, the dense solve, update(x) = exp(x) * estimate
+__host__ __device__ inline void pose_try(PoseCtl& S) {
+    int k = 0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j, ++k) { S.A[6 * i + j] = S.H[k]; S.A[6 * j + i] = S.H[k]; }
+    for (int i = 0; i < 6; ++i) S.A[7 * i] += S.lambda;
+    S.ok2 = pose_eigen_ldlt_solve(S.A, S.b, S.x, S.temp, S.transp) ? 1 : 0;
+    PoseSE3 d;
+    pose_exp(S.x, S.order, d);
+    pose_mul(d, S.est, S.eval);              // oplusImpl: setEstimate(SE3Quat::exp(update) * estimate())
+    S.cmd = POSE_CMD_CHI;
+}
+__host__ __device__ inline void pose_begin_round(PoseCtl& S) {
+    S.est = S.start;                         // vSE3->setEstimate(Converter::toSE3Quat(pFrame->mTcw))
+    S.iter = 0;
+    // initializeOptimization(0) finds no edge of level 0 when every edge is an outlier: optimize() returns at once
+    if (S.n - S.n_bad <= 0) { S.cmd = POSE_CMD_CLASSIFY; return; }
+    S.eval = S.est; S.cmd = POSE_CMD_FULL;
+}
+__host__ __device__ inline void pose_begin(PoseCtl& S, const float* Tcw, int n, int order) {
+    S.order = order; S.n = n; S.round = 0; S.robust = 1; S.n_bad = 0; S.ok2 = 1;
+    S.lambda = 0; S.ni = 2; S.current_chi = 0; S.ini_chi = 0; S.n_bad_steps = 0; S.qmax = 0;
+    for (int i = 0; i < 6; ++i) S.x[i] = 0;
+    pose_from_cv(Tcw, S.start);
+    S.est = S.start; S.last = S.start; S.eval = S.start;
+    memset(&S.res, 0, sizeof(S.res));
+    S.res.n_initial = n;
+    if (n < 3) {                             // `if(nInitialCorrespondences<3) return 0;`: the pose is not touched
+        for (int i = 0; i < 16; ++i) S.res.Tcw[i] = Tcw[i];
+        for (int k = 0; k < 4; ++k) S.res.q[k] = pose_canonical(S.start.q[k]);
+        for (int k = 0; k < 3; ++k) S.res.t[k] = pose_canonical(S.start.t[k]);
+        S.cmd = POSE_CMD_DONE;
+        return;
+    }
+    pose_begin_round(S);
+}
+// Called after every pass with the pass's sums.
+__host__ __device__ inline void pose_step(PoseCtl& S, const double* sum) {
+    orbm_pose_round& R = S.res.round[S.round];
+    if (S.cmd == POSE_CMD_FULL) {            // solve(), :75-101: the errors, the robust chi2 and the system at the estimate
+        S.last = S.eval;
+        S.current_chi = sum[27]; S.ini_chi = S.current_chi;
+        for (int k = 0; k < 21; ++k) S.H[k] = sum[k];
+        for (int k = 0; k < 6; ++k) S.b[k] = sum[21 + k];
+        if (S.iter == 0) {                   // computeLambdaInit: tau * the largest |diagonal|
+            double max_diagonal = 0.;
+            int d = 0;
+            for (int j = 0; j < 6; ++j) { const double v = fabs(S.H[d]); if (v > max_diagonal) max_diagonal = v; d += 6 - j; }
+            S.lambda = 1e-5 * max_diagonal;
+            S.ni = 2; S.n_bad_steps = 0;
+        }
+        S.qmax = 0;
+        pose_try(S);
+        return;
+    }
+    if (S.cmd == POSE_CMD_CHI) {             // :123-149
+        S.last = S.eval;
+        double temp_chi = sum[27];
+        if (!S.ok2) temp_chi = DBL_MAX;
+        double rho = S.current_chi - temp_chi;
+        double scale = 0.;
+        for (int j = 0; j < 6; ++j) scale += S.x[j] * (S.lambda * S.x[j] + S.b[j]);
+        scale += 1e-3;
+        rho /= scale;
+        if (rho > 0 && fabs(temp_chi) <= DBL_MAX) {
+            const double u = 2 * rho - 1;
+            double cube;
+#ifndef __HIP_DEVICE_COMPILE__
+            if (S.order == ORBM_POSE_ORDER_INDEX) cube = pow(u, 3); else
+#endif
+            cube = u * u * u;
+            double alpha = 1. - cube;
+            alpha = alpha < 2. / 3. ? alpha : 2. / 3.;             // (std::min)(alpha, _goodStepUpperScale)
+            const double scale_factor = 1. / 3. < alpha ? alpha : 1. / 3.;   // (std::max)(_goodStepLowerScale, alpha)
+            S.lambda *= scale_factor;
+            S.ni = 2;
+            S.current_chi = temp_chi;
+            S.est = S.eval;                  // discardTop
+        } else {
+            S.lambda *= S.ni;
+            S.ni *= 2;                       // pop: the estimate stays
+        }
+        S.qmax++;
+        R.trials++;
+        if (rho < 0 && S.qmax < 10) { pose_try(S); return; }
+        // the iteration is over: solve()'s result, then optimize()'s loop (core/sparse_optimizer.cpp:376-414)
+        R.iterations++;
+        bool terminate = S.qmax == 10 || rho == 0;
+        if (!terminate) {
+            if ((S.ini_chi - S.current_chi) * 1e3 < S.ini_chi) S.n_bad_steps++; else S.n_bad_steps = 0;
+            if (S.n_bad_steps >= 3) terminate = true;
+        }
+        S.iter++;
+        if (terminate || S.iter == 10) {
+            R.chi2 = pose_canonical(S.current_chi); R.lambda = pose_canonical(S.lambda);
+            S.cmd = POSE_CMD_CLASSIFY;
+        } else {
+            S.eval = S.est; S.cmd = POSE_CMD_FULL;
+        }
+        return;
+    }
+    // POSE_CMD_CLASSIFY
+    S.n_bad = (int)sum[28];
+    S.res.n_bad = S.n_bad;
+    S.res.rounds = S.round + 1;
+    if (S.round == 2) S.robust = 0;          // `if(it==2) e->setRobustKernel(0)`
+    if (S.n < 10 || S.round == 3) {          // `if(optimizer.edges().size()<10) break;`
+        S.res.n_inliers = S.res.n_initial - S.n_bad;
+        pose_write_estimate(S);
+        S.cmd = POSE_CMD_DONE;
+        return;
+    }
+    S.round++;
+    pose_begin_round(S);
+}
+
+// the constants of a problem (:452-456, :497-501, :653-666, :410-411)
+__host__ __device__ inline void pose_camera(const orbm_pose_problem& P, PoseCam& C) {
+    C.fx = (double)P.fx; C.fy = (double)P.fy; C.cx = (double)P.cx; C.cy = (double)P.cy; C.bf = (double)P.bf;
+    C.multi = P.mode == ORBM_POSE_ALL_CAMS ? 1 : 0; C.n_cam0 = P.n_cam0;
+    // Tcam11 = eye; Tcam21 = [Rcam12.t() | -Rcam12.t() * tcam12] in float: cv::gemm's small path (host/cv_compat.h gemm_small_elem),
+    // products and sums in float from left to right, then the scale by alpha = -1
+    float T11[16], T21[16];
+    for (int i = 0; i < 16; ++i) { T11[i] = i % 5 == 0 ? 1.0f : 0.0f; T21[i] = 0.0f; }
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) T21[4 * r + c] = P.Rcam12[3 * c + r];
+        float t = P.Rcam12[r] * P.tcam12[0] + P.Rcam12[3 + r] * P.tcam12[1];
+        t = t + P.Rcam12[6 + r] * P.tcam12[2];
+        T21[4 * r + 3] = (float)((double)t * -1.0 + 0.0 * 0.0);
+    }
+    T21[15] = 1.0f;
+    pose_from_cv(T11, C.Tc[0]);
+    pose_from_cv(T21, C.Tc[1]);
+    pose_eigen_quat_to_matrix(C.Tc[0].q, C.Rc[0]);
+    pose_eigen_quat_to_matrix(C.Tc[1].q, C.Rc[1]);
+    // `const float deltaMono = sqrt(5.991)`, rk->setDelta(deltaMono): _delta = the float as a double, dsqr = (float)(delta*delta)
+    const float delta_mono = (float)sqrt(5.991), delta_stereo = (float)sqrt(7.815);
+    C.delta[0] = (double)delta_mono; C.delta[1] = (double)delta_stereo;
+    C.dsqr[0] = (double)(float)(C.delta[0] * C.delta[0]); C.dsqr[1] = (double)(float)(C.delta[1] * C.delta[1]);
+}
+
+__host__ __device__ inline int pose_meta(const orbm_pose_problem& P, int feat, float uright) {
+    const int cam = (P.mode == ORBM_POSE_ALL_CAMS && feat >= P.n_cam0) ? 1 : 0;
+    return cam | (uright < 0 ? 0 : 2) | 4;
+}
+
+// ---- the kernel -------------------------------------------------------------------------------------------------------------------------
+struct PoseDev {
+    const orbm_pose_problem* prob;     // per problem
+    const int32_t* first;              // CSR, per problem + 1
+    const int32_t* list;               // the problems this launch works on (blockIdx.x -> problem)
+    // the plain form: the caller's arrays, staged
+    const int32_t* feat; const float* pos; const float* obs; const int32_t* octave;
+    // the resident form (packed != NULL): feature << 16 | table row per edge; the frame's arrays and the point table in HBM
+    const uint32_t* packed; const float* un_x; const float* un_y; const float* uright; const int32_t* f_octave; const orbm_point* rows;
+    uint8_t* flags;                    // per edge, mapped pinned
+    orbm_pose_result* res;             // per problem, mapped pinned
+};
+
+__device__ __forceinline__ PoseEdge pose_load(const PoseDev& A, const orbm_pose_problem& P, int e) {
+    PoseEdge E;
+    int feat, oct;
+    if (A.packed) {
+        const uint32_t w = A.packed[e];
+        feat = (int)(w >> 16);
+        const orbm_point& row = A.rows[w & 0xffffu];
+        E.X[0] = row.pos[0]; E.X[1] = row.pos[1]; E.X[2] = row.pos[2];
+        E.obs[0] = A.un_x[feat]; E.obs[1] = A.un_y[feat]; E.obs[2] = A.uright[feat];
+        oct = A.f_octave[feat];
+    } else {
+        feat = A.feat[e];
+        E.X[0] = A.pos[3 * (size_t)e]; E.X[1] = A.pos[3 * (size_t)e + 1]; E.X[2] = A.pos[3 * (size_t)e + 2];
+        E.obs[0] = A.obs[3 * (size_t)e]; E.obs[1] = A.obs[3 * (size_t)e + 1]; E.obs[2] = A.obs[3 * (size_t)e + 2];
+        oct = A.octave[e];
+    }
+    oct = min(max(oct, 0), ORBM_MAX_LEVELS - 1);   // (validated on the host where the host has the octaves; the table is never indexed beyond its end)
+    E.inv_sigma2 = P.inv_level_sigma2[oct];
+    E.meta = pose_meta(P, feat, E.obs[2]);
+    return E;
+}
+
+__device__ __forceinline__ void pose_pass_edge(const PoseCam& C, const PoseCtl& S, int cmd, const PoseEdge& E, uint8_t* flag, double* acc) {
+    if (cmd == POSE_CMD_CLASSIFY) {
+        const bool out = pose_classify(C, S.est, S.last, E, *flag != 0);
+        *flag = out ? 1 : 0;
+        acc[28] += out ? 1.0 : 0.0;
+    } else if (!*flag) {
+        pose_accumulate(C, S.eval, E, cmd == POSE_CMD_FULL, S.robust != 0, acc);
+    }
+}
+
+__global__ __launch_bounds__(POSE_T) void k_pose_optimize(PoseDev A) {
+    __shared__ PoseCtl S;
+    __shared__ PoseCam C;
+    __shared__ double s_part[POSE_T / 64][POSE_NSUM];
+    __shared__ uint8_t s_flag[ORBM_POSE_CAP];
+    const int tid = threadIdx.x;
+    const int pb = A.list[blockIdx.x];
+    const orbm_pose_problem& P = A.prob[pb];
+    const int e0 = A.first[pb];
+    const int n = min(A.first[pb + 1] - e0, (int)ORBM_POSE_CAP);   // (a longer problem never reaches the device)
+    if (tid == 0) { pose_camera(P, C); pose_begin(S, P.Tcw, n, ORBM_POSE_ORDER_DEVICE); }
+    for (int e = tid; e < n; e += POSE_T) s_flag[e] = 0;
+    PoseEdge reg[POSE_REG_SLOTS];
+#pragma unroll
+    for (int s = 0; s < POSE_REG_SLOTS; ++s) {
+        const int e = tid + s * POSE_T;
+        if (e < n) reg[s] = pose_load(A, P, e0 + e);
+        else { reg[s].X[0] = reg[s].X[1] = reg[s].X[2] = 0.0f; reg[s].obs[0] = reg[s].obs[1] = reg[s].obs[2] = 0.0f; reg[s].inv_sigma2 = 0.0f; reg[s].meta = 0; }
+    }
+    for (;;) {
+        __syncthreads();                                   // the controller's record is visible
+        const int cmd = S.cmd;
+        if (cmd == POSE_CMD_DONE) break;
+        double acc[POSE_NSUM];
+#pragma unroll
+        for (int k = 0; k < POSE_NSUM; ++k) acc[k] = 0.0;
+        // this lane's edges in ascending order: ONE copy of the edge code; a slot's constants are selected out of the registers
+        for (int s = 0, e = tid; e < n; ++s, e += POSE_T) {
+            PoseEdge E;
+            if (s < POSE_REG_SLOTS) {
+                E = reg[0];
+#pragma unroll
+                for (int k = 1; k < POSE_REG_SLOTS; ++k) if (s == k) E = reg[k];
+            } else {
+                E = pose_load(A, P, e0 + e);
+            }
+            pose_pass_edge(C, S, cmd, E, &s_flag[e], acc);
+        }
+        // the wave's sums: xor butterfly, offsets 1, 2, 4, 8, 16, 32 (every lane ends with the same bits: a + b == b + a)
+#pragma unroll
+        for (int k = 0; k < POSE_NSUM; ++k) {
+            if (cmd == POSE_CMD_CHI && k < 27) continue;   // (zeros: nothing was added to them in this pass)
+            double v = acc[k];
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) v = v + __shfl_xor(v, off, 64);
+            acc[k] = v;
+        }
+        if ((tid & 63) == 0) {
+#pragma unroll
+            for (int k = 0; k < POSE_NSUM; ++k) s_part[tid >> 6][k] = acc[k];
+        }
+        __syncthreads();                                   // the four waves' sums are visible, every lane is done with the record
+        if (tid == 0) {
+            double sum[POSE_NSUM];
+#pragma unroll
+            for (int k = 0; k < POSE_NSUM; ++k) sum[k] = ((s_part[0][k] + s_part[1][k]) + s_part[2][k]) + s_part[3][k];   // wave order
+            pose_step(S, sum);
+        }
+    }
+    for (int e = tid; e < n; e += POSE_T) A.flags[e0 + e] = s_flag[e];
+    if (tid == 0) A.res[pb] = S.res;
+}
+
+// ---- host routine -----------------------------------------------------------------------------------------------------------------------
+struct PoseEdges { const int32_t* feat; const float* pos; const float* obs; const int32_t* octave; };
+
+PoseEdge host_edge(const orbm_pose_problem& P, const PoseEdges& G, int e) {
+    PoseEdge E;
+    for (int k = 0; k < 3; ++k) { E.X[k] = G.pos[3 * (size_t)e + k]; E.obs[k] = G.obs[3 * (size_t)e + k]; }
+    E.inv_sigma2 = P.inv_level_sigma2[G.octave[e]];
+    E.meta = pose_meta(P, G.feat[e], E.obs[2]);
+    return E;
+}
+
+// one problem; edges e0 .. e0 + n - 1 of G, flags[0 .. n-1]
+void pose_problem_host(const orbm_pose_problem& P, const PoseEdges& G, int e0, int n, int order, uint8_t* flags, orbm_pose_result& res) {
+    PoseCam C;
+    PoseCtl S;
+    pose_camera(P, C);
+    pose_begin(S, P.Tcw, n, order);
+    for (int e = 0; e < n; ++e) flags[e] = 0;
+    std::vector<PoseEdge> E((size_t)n);
+    for (int e = 0; e < n; ++e) E[e] = host_edge(P, G, e0 + e);
+    std::vector<double> part;
+    if (order == ORBM_POSE_ORDER_DEVICE) part.resize((size_t)POSE_T * POSE_NSUM);
+    while (S.cmd != POSE_CMD_DONE) {
+        double sum[POSE_NSUM];
+        const int cmd = S.cmd;
+        auto pass_edge = [&](int e, double* acc) {
+            if (cmd == POSE_CMD_CLASSIFY) {
+                const bool out = pose_classify(C, S.est, S.last, E[e], flags[e] != 0);
+                flags[e] = out ? 1 : 0;
+                acc[28] += out ? 1.0 : 0.0;
+            } else if (!flags[e]) {
+                pose_accumulate(C, S.eval, E[e], cmd == POSE_CMD_FULL, S.robust != 0, acc);
+            }
+        };
+        if (order == ORBM_POSE_ORDER_INDEX) {
+            for (int k = 0; k < POSE_NSUM; ++k) sum[k] = 0.0;
+            for (int e = 0; e < n; ++e) pass_edge(e, sum);
+        } else {                                           // the kernel's tree: lanes, butterfly inside each wave, waves in order
+            std::fill(part.begin(), part.end(), 0.0);
+            for (int l = 0; l < POSE_T && l < n; ++l)
+                for (int e = l; e < n; e += POSE_T) pass_edge(e, &part[(size_t)l * POSE_NSUM]);
+            for (int off = 1; off < 64; off <<= 1)
+                for (int l = 0; l < POSE_T; ++l)
+                    if (!(l & off) && !(l & (off - 1)))
+                        for (int k = 0; k < POSE_NSUM; ++k) part[(size_t)l * POSE_NSUM + k] = part[(size_t)l * POSE_NSUM + k] + part[(size_t)(l | off) * POSE_NSUM + k];
+            for (int k = 0; k < POSE_NSUM; ++k)
+                sum[k] = ((part[k] + part[(size_t)64 * POSE_NSUM + k]) + part[(size_t)128 * POSE_NSUM + k]) + part[(size_t)192 * POSE_NSUM + k];
+        }
+        pose_step(S, sum);
+    }
+    res = S.res;
+}
+
+int validate(const orbm_pose_problem* problems, int B, const int32_t* first, const int32_t* feat, const float* pos, const float* obs,
+             const int32_t* octave, const uint8_t* outlier_out, const orbm_pose_result* results) {
+    MORB_ARG(problems && first && results);
+    if (B < 1 || B > ORBM_POSE_MAX_BATCH) { morb::set_error("B = %d is outside 1..%d", B, (int)ORBM_POSE_MAX_BATCH); return ORB_E_ARG; }
+    MORB_ARG(first[0] == 0);
+    for (int b = 0; b < B; ++b) {
+        if (first[b + 1] < first[b]) { morb::set_error("first[] decreases at problem %d", b); return ORB_E_ARG; }
+        const orbm_pose_problem& P = problems[b];
+        if (P.mode != ORBM_POSE_CAM0 && P.mode != ORBM_POSE_ALL_CAMS) { morb::set_error("problem %d: mode = %d", b, P.mode); return ORB_E_ARG; }
+        if (P.n_levels < 1 || P.n_levels > ORBM_MAX_LEVELS) { morb::set_error("problem %d: n_levels = %d is outside 1..%d", b, P.n_levels, (int)ORBM_MAX_LEVELS); return ORB_E_ARG; }
+    }
+    const int ne = first[B];
+    if (ne > 0 && !(feat && pos && obs && octave && outlier_out)) { morb::set_error("an edge array is NULL"); return ORB_E_ARG; }
+    for (int b = 0; b < B; ++b)
+        for (int e = first[b]; e < first[b + 1]; ++e) {
+            if (octave[e] < 0 || octave[e] >= problems[b].n_levels) { morb::set_error("edge %d: octave %d is outside the %d levels of problem %d", e, octave[e], problems[b].n_levels, b); return ORB_E_ARG; }
+            if (feat[e] < 0) { morb::set_error("edge %d: feature index %d", e, feat[e]); return ORB_E_ARG; }
+        }
+    return ORB_OK;
+}
+
+inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// Stages the problems, the CSR, the work list and the form's own edge arrays (plain: feat, pos, obs, octave; resident, marked by
+// A.packed != NULL: the packed words); launches; leaves records and flags in m->h_pose.  flags_off: where the flags start there.
+int launch(orbm_matcher* m, const orbm_pose_problem* problems, int B, const int32_t* first, const std::vector<int32_t>& list, PoseDev A,
+           const void* const* edge_src, const size_t* edge_len, int n_arrays, size_t* flags_off) {
+    const int ne = first[B];
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = align16(off + bytes); return o; };
+    const size_t o_prob = take((size_t)B * sizeof(orbm_pose_problem)), o_first = take((size_t)(B + 1) * 4), o_list = take(list.size() * 4);
+    size_t o_edge[4];
+    for (int k = 0; k < n_arrays; ++k) o_edge[k] = take(edge_len[k]);
+    const size_t res_bytes = align16((size_t)B * sizeof(orbm_pose_result));
+    int rc;
+    if ((rc = m->stage_p.reserve(off)) || (rc = m->h_pose.reserve(res_bytes + (size_t)std::max(ne, 1)))) return rc;
+    uint8_t* hp = m->stage_p.p;
+    memcpy(hp + o_prob, problems, (size_t)B * sizeof(orbm_pose_problem));
+    memcpy(hp + o_first, first, (size_t)(B + 1) * 4);
+    memcpy(hp + o_list, list.data(), list.size() * 4);
+    for (int k = 0; k < n_arrays; ++k) if (edge_len[k]) memcpy(hp + o_edge[k], edge_src[k], edge_len[k]);
+    m->stage_p.publish();
+    const uint8_t* dp = m->stage_p.dp;
+    A.prob = (const orbm_pose_problem*)(dp + o_prob); A.first = (const int32_t*)(dp + o_first); A.list = (const int32_t*)(dp + o_list);
+    A.res = (orbm_pose_result*)m->h_pose.dp; A.flags = m->h_pose.dp + res_bytes;
+    if (A.packed) A.packed = (const uint32_t*)(dp + o_edge[0]);
+    else { A.feat = (const int32_t*)(dp + o_edge[0]); A.pos = (const float*)(dp + o_edge[1]); A.obs = (const float*)(dp + o_edge[2]); A.octave = (const int32_t*)(dp + o_edge[3]); }
+    *flags_off = res_bytes;
+    hipLaunchKernelGGL(k_pose_optimize, dim3((unsigned)list.size()), dim3(POSE_T), 0, m->stream, A);
+    MORB_HIP(hipGetLastError());
+    return ORB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void orbm_pose_sincos(double x, double* s, double* c) { pose_sincos(x, s, c); }
+
+int orbm_pose_optimize_host(const orbm_pose_problem* problems, int B, const int32_t* first, const int32_t* feat, const float* pos,
+                            const float* obs, const int32_t* octave, int order, uint8_t* outlier_out, orbm_pose_result* results) {
+    int rc = validate(problems, B, first, feat, pos, obs, octave, outlier_out, results);
+    if (rc) return rc;
+    if (order != ORBM_POSE_ORDER_INDEX && order != ORBM_POSE_ORDER_DEVICE) { morb::set_error("order = %d", order); return ORB_E_ARG; }
+    const PoseEdges G = {feat, pos, obs, octave};
+    for (int b = 0; b < B; ++b) pose_problem_host(problems[b], G, first[b], first[b + 1] - first[b], order, outlier_out + first[b], results[b]);
+    return ORB_OK;
+}
+
+int orbm_pose_optimize(orbm_matcher* m, const orbm_pose_problem* problems, int B, const int32_t* first, const int32_t* feat,
+                       const float* pos, const float* obs, const int32_t* octave, uint8_t* outlier_out, orbm_pose_result* results) {
+    MORB_ARG(m != nullptr);
+    int rc = validate(problems, B, first, feat, pos, obs, octave, outlier_out, results);
+    if (rc) return rc;
+    const int ne = first[B];
+    std::vector<int32_t> list;
+    for (int b = 0; b < B; ++b) if (first[b + 1] - first[b] <= ORBM_POSE_CAP) list.push_back(b);
+    size_t flags_off = 0;
+    if (!list.empty()) {
+        MORB_HIP(hipSetDevice(m->device));
+        PoseDev A;
+        memset(&A, 0, sizeof(A));
+        const void* src[4] = {feat, pos, obs, octave};
+        const size_t len[4] = {(size_t)ne * 4, (size_t)ne * 12, (size_t)ne * 12, (size_t)ne * 4};
+        if ((rc = launch(m, problems, B, first, list, A, src, len, 4, &flags_off))) return rc;
+    }
+    // while the kernel runs: the problems the device does not take
+    const PoseEdges G = {feat, pos, obs, octave};
+    for (int b = 0; b < B; ++b)
+        if (first[b + 1] - first[b] > ORBM_POSE_CAP)
+            pose_problem_host(problems[b], G, first[b], first[b + 1] - first[b], ORBM_POSE_ORDER_DEVICE, outlier_out + first[b], results[b]);
+    if (!list.empty()) {
+        MORB_HIP(hipStreamSynchronize(m->stream));
+        const orbm_pose_result* R = (const orbm_pose_result*)m->h_pose.p;
+        for (int b : list) {
+            results[b] = R[b];
+            memcpy(outlier_out + first[b], m->h_pose.p + flags_off + first[b], (size_t)(first[b + 1] - first[b]));
+        }
+    }
+    m->last_pose[0] = (int)list.size(); m->last_pose[1] = B - (int)list.size();
+    return ORB_OK;
+}
+
+int orbm_pose_optimize_resident(orbm_matcher* m, const orbm_pose_problem* problem, const orbm_frame* cur, const orbm_points* pts,
+                                const int32_t* point_of_feature, uint8_t* outlier_out, orbm_pose_result* result) {
+    MORB_ARG(m != nullptr && problem != nullptr && cur != nullptr && pts != nullptr && result != nullptr);
+    MORB_ARG(cur->owner == m && cur->b != nullptr);
+    if (cur->counts_on_device) { morb::set_error("the frame's feature count is not on the host yet (orbf_step_end)"); return ORB_E_ARG; }
+    if (problem->mode != ORBM_POSE_CAM0 && problem->mode != ORBM_POSE_ALL_CAMS) { morb::set_error("mode = %d", problem->mode); return ORB_E_ARG; }
+    if (problem->n_levels < 1 || problem->n_levels > ORBM_MAX_LEVELS) { morb::set_error("n_levels = %d is outside 1..%d", problem->n_levels, (int)ORBM_MAX_LEVELS); return ORB_E_ARG; }
+    const int N = cur->n_total;
+    MORB_ARG(N == 0 || (point_of_feature && outlier_out));
+    if (N > 65536) { morb::set_error("%d features: the resident form packs the feature index into 16 bits", N); return ORB_E_CAPACITY; }
+    const orbm_point* d_rows = nullptr; const orbm_point* h_rows = nullptr;
+    int count = 0, rc;
+    if ((rc = morb::points_view(pts, m, &d_rows, &h_rows, &count))) return rc;
+    const int limit = problem->mode == ORBM_POSE_CAM0 ? std::min(N, std::max(problem->n_cam0, 0)) : N;
+    std::vector<uint32_t> packed;
+    std::vector<int32_t> feat;
+    for (int g = 0; g < limit; ++g) {
+        const int row = point_of_feature[g];
+        if (row < 0) continue;
+        if (row >= count) { morb::set_error("point_of_feature[%d] = %d is beyond the %d rows written", g, row, count); return ORB_E_ARG; }
+        packed.push_back((uint32_t)g << 16 | (uint32_t)row);
+        feat.push_back(g);
+    }
+    const int n = (int)feat.size();
+    for (int g = 0; g < N; ++g) outlier_out[g] = 0;
+    MORB_HIP(hipSetDevice(m->device));
+    const int32_t first[2] = {0, n};
+    if (n > ORBM_POSE_CAP) {
+        // the host routine on the frame's arrays brought back (rare: more edges than the device takes)
+        std::vector<float> x((size_t)N), y((size_t)N), ur((size_t)N), pos((size_t)n * 3), obs((size_t)n * 3);
+        std::vector<int32_t> oct((size_t)N), eoct((size_t)n);
+        MORB_HIP(hipMemcpyAsync(x.data(), cur->b->d_x.p, (size_t)N * 4, hipMemcpyDeviceToHost, m->stream));
+        MORB_HIP(hipMemcpyAsync(y.data(), cur->b->d_y.p, (size_t)N * 4, hipMemcpyDeviceToHost, m->stream));
+        MORB_HIP(hipMemcpyAsync(ur.data(), cur->b->d_ur.p, (size_t)N * 4, hipMemcpyDeviceToHost, m->stream));
+        MORB_HIP(hipMemcpyAsync(oct.data(), cur->b->d_oct.p, (size_t)N * 4, hipMemcpyDeviceToHost, m->stream));
+        MORB_HIP(hipStreamSynchronize(m->stream));
+        for (int e = 0; e < n; ++e) {
+            const int g = feat[e];
+            const orbm_point& row = h_rows[packed[e] & 0xffffu];
+            for (int k = 0; k < 3; ++k) pos[3 * (size_t)e + k] = row.pos[k];
+            obs[3 * (size_t)e] = x[g]; obs[3 * (size_t)e + 1] = y[g]; obs[3 * (size_t)e + 2] = ur[g];
+            eoct[e] = std::min(std::max(oct[g], 0), ORBM_MAX_LEVELS - 1);
+        }
+        std::vector<uint8_t> flags((size_t)n);
+        const PoseEdges G = {feat.data(), pos.data(), obs.data(), eoct.data()};
+        pose_problem_host(*problem, G, 0, n, ORBM_POSE_ORDER_DEVICE, flags.data(), *result);
+        for (int e = 0; e < n; ++e) outlier_out[feat[e]] = flags[e];
+        m->last_pose[0] = 0; m->last_pose[1] = 1;
+        return ORB_OK;
+    }
+    PoseDev A;
+    memset(&A, 0, sizeof(A));
+    static const uint32_t none = 0;
+    A.packed = &none;   // (marks the resident form; launch() replaces it by the staged words)
+    A.un_x = cur->b->d_x.p; A.un_y = cur->b->d_y.p; A.uright = cur->b->d_ur.p; A.f_octave = cur->b->d_oct.p; A.rows = d_rows;
+    const std::vector<int32_t> list(1, 0);
+    const void* src[1] = {packed.data()};
+    const size_t len[1] = {(size_t)n * 4};
+    size_t flags_off = 0;
+    if ((rc = launch(m, problem, 1, first, list, A, src, len, 1, &flags_off))) return rc;
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    *result = *(const orbm_pose_result*)m->h_pose.p;
+    for (int e = 0; e < n; ++e) outlier_out[feat[e]] = m->h_pose.p[flags_off + e];
+    m->last_pose[0] = 1; m->last_pose[1] = 0;
+    return ORB_OK;
+}
+
+}  // extern "C"

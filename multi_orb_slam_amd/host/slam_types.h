@@ -103,6 +103,9 @@ public:
     DBoW2::FeatureVector mFeatVec_cam1;
     std::vector<cv::KeyPoint> mvKeys;   // camera 1, distorted
     float mfLogScaleFactor = 0; int mnScaleLevels = 0;
+    // members host/Optimizer.cc reads (include/Frame.h:226-227, :243)
+    std::vector<float> mvInvLevelSigma2;
+    cv::Mat mRcam12, mtcam12;                 // 3x3, 3x1 CV_32F
 
     // pose members (include/Frame.h:82-99, src/Frame.cc:420-499)
     void SetPose(cv::Mat Tcw) { mTcw = Tcw.clone(); UpdatePoseMatrices(); }

@@ -3,6 +3,7 @@ import ctypes as C
 import numpy as np
 from . import _lib
 from ._lib import KP_DTYPE, QUERY_DTYPE, POINT_DTYPE, TRACK_DTYPE, REFRESH_DTYPE, CamFeatures, FrameDesc, check, ptr
+from ._lib import POSE_PROBLEM_DTYPE, POSE_RESULT_DTYPE, POSE_CAM0, POSE_ALL_CAMS, POSE_ORDER_INDEX, POSE_ORDER_DEVICE  # noqa: F401
 
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30  # reference src/ORBmatcher.cc:37-39
 
@@ -84,6 +85,60 @@ def refresh_points_host(batch):
     out = np.zeros(max(batch.n_points, 1), REFRESH_DTYPE)
     check(_lib.lib().orbm_refresh_points_host(C.byref(batch.c), ptr(out)))
     return out[:batch.n_points]
+
+
+class PoseProblem:
+    """One Optimizer::PoseOptimization call from its edge list on (orbm_pose_problem + its edges): Tcw = pFrame->mTcw (float 4x4);
+    fx fy cx cy bf; inv_level_sigma2 = mvInvLevelSigma2; mode POSE_CAM0 / POSE_ALL_CAMS with n_cam0 = pFrame->N and Rcam12 / tcam12;
+    the edges in ascending feature index: feat n, pos n x 3 (the map points), obs n x 3 (x, y, uright; uright < 0 = monocular), octave n."""
+
+    def __init__(self, Tcw, fx, fy, cx, cy, bf, inv_level_sigma2, feat, pos, obs, octave, mode=POSE_CAM0, n_cam0=0, Rcam12=None,
+                 tcam12=None):
+        rec = np.zeros(1, POSE_PROBLEM_DTYPE)
+        rec["Tcw"][0] = np.asarray(Tcw, np.float32).reshape(16)
+        for k, v in (("fx", fx), ("fy", fy), ("cx", cx), ("cy", cy), ("bf", bf)):
+            rec[k] = np.float32(v)
+        rec["Rcam12"][0] = np.eye(3, dtype=np.float32).reshape(9) if Rcam12 is None else np.asarray(Rcam12, np.float32).reshape(9)
+        rec["tcam12"][0] = 0 if tcam12 is None else np.asarray(tcam12, np.float32).reshape(3)
+        sig = np.asarray(inv_level_sigma2, np.float32)
+        rec["inv_level_sigma2"][0, :len(sig)] = sig
+        rec["n_levels"] = len(sig); rec["mode"] = int(mode); rec["n_cam0"] = int(n_cam0)
+        self.rec = rec
+        self.feat = np.ascontiguousarray(feat, np.int32)
+        self.pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        self.obs = np.ascontiguousarray(obs, np.float32).reshape(-1, 3)
+        self.octave = np.ascontiguousarray(octave, np.int32)
+        self.n = len(self.feat)
+        assert len(self.pos) == len(self.obs) == len(self.octave) == self.n
+
+
+def _pose_pack(problems):
+    recs = np.concatenate([p.rec for p in problems])
+    first = np.zeros(len(problems) + 1, np.int32)
+    first[1:] = np.cumsum([p.n for p in problems])
+    cat = lambda name, dt, shape: np.ascontiguousarray(np.concatenate([getattr(p, name) for p in problems]).reshape(shape), dt)
+    return recs, first, cat("feat", np.int32, (-1,)), cat("pos", np.float32, (-1, 3)), cat("obs", np.float32, (-1, 3)), cat("octave", np.int32, (-1,))
+
+
+def _pose_unpack(problems, first, flags, res):
+    return [(res[b].copy(), flags[first[b]:first[b + 1]].copy()) for b in range(len(problems))]
+
+
+def pose_optimize_host(problems, order=POSE_ORDER_INDEX):
+    """orbm_pose_optimize_host: the batch entirely on the host (no device needed), sums in index order (the restatement of the
+    reference) or in the kernel's order -> [(POSE_RESULT_DTYPE record, outlier flag per edge)] per problem."""
+    recs, first, feat, pos, obs, octave = _pose_pack(problems)
+    flags = np.zeros(max(int(first[-1]), 1), np.uint8); res = np.zeros(len(problems), POSE_RESULT_DTYPE)
+    check(_lib.lib().orbm_pose_optimize_host(ptr(recs), len(problems), ptr(first), ptr(feat), ptr(pos), ptr(obs), ptr(octave), int(order),
+                                             ptr(flags), ptr(res)))
+    return _pose_unpack(problems, first, flags, res)
+
+
+def pose_sincos(x):
+    """The sine / cosine sequence of POSE_ORDER_DEVICE (orbm_pose_sincos) -> (sin, cos)."""
+    s = C.c_double(); c = C.c_double()
+    _lib.lib().orbm_pose_sincos(float(x), C.byref(s), C.byref(c))
+    return s.value, c.value
 
 
 class LocalPoints:
@@ -427,6 +482,32 @@ class Matcher:
         out = np.zeros(max(batch.n_points, 1), REFRESH_DTYPE)
         check(_lib.lib().orbm_refresh_points(self._h, C.byref(batch.c), ptr(out)))
         return out[:batch.n_points]
+
+    def PoseOptimization(self, problems):
+        """Optimizer::PoseOptimization (reference src/Optimizer.cc:352-898) for a batch of PoseProblem in one device call, one workgroup
+        per problem (orbm_pose_optimize) -> [(POSE_RESULT_DTYPE record, outlier flag per edge)] per problem."""
+        recs, first, feat, pos, obs, octave = _pose_pack(problems)
+        flags = np.zeros(max(int(first[-1]), 1), np.uint8); res = np.zeros(len(problems), POSE_RESULT_DTYPE)
+        check(_lib.lib().orbm_pose_optimize(self._h, ptr(recs), len(problems), ptr(first), ptr(feat), ptr(pos), ptr(obs), ptr(octave),
+                                            ptr(flags), ptr(res)))
+        return _pose_unpack(problems, first, flags, res)
+
+    def PoseOptimizationResident(self, problem, frame, points, point_of_feature):
+        """The same for one problem whose observations are the resident frame's and whose positions are rows of a LocalPoints table
+        (orbm_pose_optimize_resident); the edges of `problem` itself are not read.  point_of_feature[g] = a table row or -1
+        -> (POSE_RESULT_DTYPE record, outlier flag per FEATURE)."""
+        pof = np.ascontiguousarray(point_of_feature, np.int32)
+        assert len(pof) >= frame.data.n_total
+        flags = np.zeros(max(frame.data.n_total, 1), np.uint8); res = np.zeros(1, POSE_RESULT_DTYPE)
+        check(_lib.lib().orbm_pose_optimize_resident(self._h, ptr(problem.rec), frame._h, points._h, ptr(pof), ptr(flags), ptr(res)))
+        return res[0].copy(), flags[:frame.data.n_total]
+
+    def last_pose(self):
+        """Problems of the last PoseOptimization[Resident] by path: (device, host routine because of more than POSE_CAP edges)
+        (orbm_debug_last_pose)."""
+        out = (C.c_int * 2)()
+        check(_lib.lib().orbm_debug_last_pose(self._h, out))
+        return tuple(out)
 
     def last_refresh(self):
         """Points of the last RefreshPoints by path: (16-lane groups, one wavefront, one workgroup, host routine because of more than
