@@ -428,6 +428,76 @@ int orbm_pose_optimize_resident(orbm_matcher* m, const orbm_pose_problem* proble
 /* (test hook) The sine / cosine sequence of ORBM_POSE_ORDER_DEVICE on the host. */
 void orbm_pose_sincos(double x, double* s, double* c);
 
+/* -- Sim3Solver: every RANSAC hypothesis of a loop in one call --------------------------------------------------------
+ * Sim3Solver (reference src/Sim3Solver.cc) between SearchByBoW and SearchBySim3 of LoopClosing::ComputeSim3: per hypothesis the
+ * three-point Horn alignment (ComputeCentroid, ComputeSim3 steps 1-8, both branches of mbFixScale) and CheckInliers (Project in both
+ * directions with the second-camera branch, FromCameraToImage, the two threshold tests).  No iteration depends on another, so all
+ * hypotheses of all candidates are evaluated at once and orbm_sim3_walk recovers the reference's sequential `iterate` from the counts.
+ * RANSAC's randomness is an INPUT: the triples arrive drawn.  The OpenCV operators on the path (reduce, gemm, eigen, norm, Rodrigues,
+ * dot, pow, the scaled forms) are restated one function each and UNPINNED.
+ * Two orders of ONE routine, differing in three calls only:
+ *   ORBM_SIM3_MATH_LIBM     atan2, sin, cos of the C library: the restatement of the reference.
+ *   ORBM_SIM3_MATH_DEVICE   atan2 from + - * / sqrt in double (orbm_sim3_atan2), sine / cosine of orbm_pose_sincos.  What the device
+ *                           computes, bit for bit.  No floating-point value crosses lanes: there is no summation order to choose. */
+enum { ORBM_SIM3_MATH_LIBM = 0, ORBM_SIM3_MATH_DEVICE = 1 };
+enum { ORBM_SIM3_CAP = 8192,      /* correspondences of one problem the device takes; a longer one runs on the host inside the same call */
+       ORBM_SIM3_MAX_ITS = 1024,  /* hypotheses of one problem (the reference draws at most 300)                                          */
+       ORBM_SIM3_MAX_BATCH = 64 };
+
+typedef struct orbm_sim3_problem {
+    float fx1, fy1, cx1, cy1;      /* mK1 = pKF1->mK                                                                   */
+    float fx2, fy2, cx2, cy2;      /* mK2 = pKF2->mK                                                                   */
+    float Rcam21[9], tcam21[3];    /* mRcam21 = Rcam12.t(), mtcam21 = -mRcam21 * tcam12 (row-major), as the constructor forms them */
+    int32_t fix_scale;             /* mbFixScale                                                                       */
+} orbm_sim3_problem;               /* 84 bytes */
+
+typedef struct orbm_sim3_hyp {     /* one iteration of `iterate` */
+    float R12[9], t12[3], s12;     /* mR12i (row-major), mt12i, ms12i                                                  */
+    float T12[16], T21[16];        /* mT12i, mT21i (row-major 4x4)                                                     */
+    int32_t n_inliers;             /* mnInliersi                                                                       */
+} orbm_sim3_hyp;                   /* 184 bytes, no padding */
+
+/* B problems (1 .. ORBM_SIM3_MAX_BATCH), one enqueue, one synchronisation.  Correspondences are CSR per problem: problem b owns
+ * first[b] .. first[b+1]-1, in the order of the constructor's push_backs:
+ *   x3dc1[3i..], x3dc2[3i..]   mvX3Dc1[i], mvX3Dc2[i] (camera-frame points of keyframe 1 and 2)
+ *   cam1[i], cam2[i]           camIdx1[i], camIdx2[i] (1 = the second camera of the rig)
+ *   max_err1[i], max_err2[i]   mvnMaxError1[i], mvnMaxError2[i] as the comparison reads them: 9.210 * sigma2 through the reference's
+ *                              std::vector<size_t> (truncated), converted to float
+ * mvP1im1 / mvP2im2 are computed inside.  Hypotheses are CSR per problem too: problem b owns its_first[b] .. its_first[b+1]-1 (at most
+ * ORBM_SIM3_MAX_ITS), hypothesis g draws the correspondences triples[3g..3g+2] (positions inside the problem, 0 .. N_b-1).
+ * hyp_out[g] is the record of hypothesis g.  mask_out holds one bit per correspondence (bit i & 63 of word i >> 6 = mvbInliersi[i]),
+ * W_b = (N_b + 63) / 64 words per hypothesis, hypothesis-major inside a problem, the problems one after another: hypothesis h of
+ * problem b starts at word sum over b' < b of H_b' * W_b', plus h * W_b.
+ * A degenerate triple (coincident or collinear points) gives non-finite values: every comparison with them is false, the count is 0
+ * and the mask empty.  A NaN is written as the NaN x86 makes from an invalid operation; what a non-finite INPUT gives is unspecified.
+ * A problem beyond ORBM_SIM3_CAP correspondences runs through the host routine in DEVICE order inside the same call
+ * (orbm_debug_last_sim3, include/orb_debug.h). */
+int orbm_sim3_ransac(orbm_matcher* m, const orbm_sim3_problem* problems, int B, const int32_t* first, const float* x3dc1,
+                     const float* x3dc2, const int32_t* cam1, const int32_t* cam2, const float* max_err1, const float* max_err2,
+                     const int32_t* its_first, const int32_t* triples, orbm_sim3_hyp* hyp_out, uint64_t* mask_out);
+/* The same routine entirely on the host, no device needed, in either order. */
+int orbm_sim3_ransac_host(const orbm_sim3_problem* problems, int B, const int32_t* first, const float* x3dc1, const float* x3dc2,
+                          const int32_t* cam1, const int32_t* cam2, const float* max_err1, const float* max_err2,
+                          const int32_t* its_first, const int32_t* triples, int order, orbm_sim3_hyp* hyp_out, uint64_t* mask_out);
+
+/* The reference's `iterate` loop over precomputed counts (host only; the class, the Python wrapper and the tests share it).
+ * counts[0 .. H-1]: n_inliers of the solver's hypotheses in drawing order, H = mRansacMaxIts; N = correspondences. */
+typedef struct orbm_sim3_walk_state {
+    int32_t iterations;            /* mnIterations after the call                                                      */
+    int32_t best_inliers;          /* mnBestInliers; start a solver with 0                                             */
+    int32_t best_index;            /* the hypothesis mBestT12 / mBestRotation / ... were taken from; start with -1     */
+    int32_t no_more;               /* bNoMore of the call                                                              */
+} orbm_sim3_walk_state;
+/* iterate(n_iterations, ...) starting at mnIterations = start_iteration: `mnInliersi >= mnBestInliers` (greater OR EQUAL) makes a
+ * hypothesis the best, `mnInliersi > mRansacMinInliers` (strictly greater) then ends the call.  Returns the hypothesis whose T12
+ * `iterate` returns, or -1 for the empty cv::Mat; N < min_inliers returns -1 at once with no_more set. */
+int orbm_sim3_walk(const int32_t* counts, int H, int N, int min_inliers, int start_iteration, int n_iterations, orbm_sim3_walk_state* state);
+/* SetRansacParameters' arithmetic as the reference's statement resolves it: float epsilon, pow, log and ceil of the C library, the
+ * conversion to int as x86 performs it (INT_MIN for a NaN or a value out of range), max(1, min(., max_its)). */
+int orbm_sim3_iterations(double probability, int min_inliers, int max_its, int N);
+/* (test hook) The atan2 sequence of ORBM_SIM3_MATH_DEVICE on the host: y >= 0, x in [-1, 1]. */
+double orbm_sim3_atan2(double y, double x);
+
 #ifdef __cplusplus
 }
 #endif

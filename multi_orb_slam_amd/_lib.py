@@ -33,6 +33,13 @@ POSE_RESULT_DTYPE = np.dtype([("Tcw", "<f4", (16,)), ("q", "<f8", (4,)), ("t", "
                               ("n_inliers", "<i4"), ("rounds", "<i4"), ("round", POSE_ROUND_DTYPE, (4,))])   # orbm_pose_result
 assert POSE_PROBLEM_DTYPE.itemsize == 272 and POSE_RESULT_DTYPE.itemsize == 232
 POSE_CAM0, POSE_ALL_CAMS, POSE_ORDER_INDEX, POSE_ORDER_DEVICE, POSE_CAP, POSE_MAX_BATCH = 0, 1, 0, 1, 8192, 64
+SIM3_PROBLEM_DTYPE = np.dtype([("fx1", "<f4"), ("fy1", "<f4"), ("cx1", "<f4"), ("cy1", "<f4"), ("fx2", "<f4"), ("fy2", "<f4"), ("cx2", "<f4"),
+                               ("cy2", "<f4"), ("Rcam21", "<f4", (9,)), ("tcam21", "<f4", (3,)), ("fix_scale", "<i4")])   # orbm_sim3_problem
+SIM3_HYP_DTYPE = np.dtype([("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "<f4"), ("T12", "<f4", (16,)), ("T21", "<f4", (16,)),
+                           ("n_inliers", "<i4")])   # orbm_sim3_hyp
+SIM3_WALK_DTYPE = np.dtype([("iterations", "<i4"), ("best_inliers", "<i4"), ("best_index", "<i4"), ("no_more", "<i4")])   # orbm_sim3_walk_state
+assert SIM3_PROBLEM_DTYPE.itemsize == 84 and SIM3_HYP_DTYPE.itemsize == 184 and SIM3_WALK_DTYPE.itemsize == 16
+SIM3_MATH_LIBM, SIM3_MATH_DEVICE, SIM3_CAP, SIM3_MAX_ITS, SIM3_MAX_BATCH = 0, 1, 8192, 1024, 64
 
 ORB_OK, ORB_E_ARG, ORB_E_HIP, ORB_E_CAPACITY, ORB_E_NO_DEVICE, ORB_E_TIMEOUT = 0, -1, -2, -3, -4, -5
 
@@ -262,6 +269,12 @@ def lib():
     L.orbm_pose_optimize_resident.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.orbm_debug_last_pose.argtypes = [vp, vp]
     L.orbm_pose_sincos.argtypes = [C.c_double, vp, vp]; L.orbm_pose_sincos.restype = None
+    L.orbm_sim3_ransac.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_sim3_ransac_host.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
+    L.orbm_sim3_walk.argtypes = [vp, i32, i32, i32, i32, i32, vp]
+    L.orbm_sim3_iterations.argtypes = [C.c_double, i32, i32, i32]
+    L.orbm_sim3_atan2.argtypes = [C.c_double, C.c_double]; L.orbm_sim3_atan2.restype = C.c_double
+    L.orbm_debug_last_sim3.argtypes = [vp, vp]
     f64 = C.c_double
     L.orbv_create.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp]
     L.orbv_load_text.argtypes = [C.c_char_p, i32, vp]

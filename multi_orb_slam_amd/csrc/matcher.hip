@@ -123,6 +123,7 @@ void orbm_destroy(orbm_matcher* m) {
     m->d_match.release(); m->d_status.release(); m->d_gclaim.release(); m->d_rsync.release(); m->d_mergecnt.release(); m->d_u16.release(); m->d_x0.release(); m->d_x1.release(); m->d_x2.release();
     m->h_i0.release(); m->h_i1.release(); m->h_i2.release(); m->h_match.release(); m->h_u16.release(); m->h_ring.release();
     m->stage_f.release(); m->stage_q.release(); m->stage_r.release(); m->h_refresh.release(); m->stage_p.release(); m->h_pose.release();
+    m->stage_s.release(); m->d_sim3.release(); m->h_sim3.release();
     if (m->ev_stage_f) (void)hipEventDestroy(m->ev_stage_f);
     for (FrameBufs* b : m->pool) { b->release(); delete b; }
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
@@ -140,6 +141,12 @@ int orbm_debug_last_resolve(const orbm_matcher* m, int* out4) {
 int orbm_debug_last_pose(const orbm_matcher* m, int* out2) {
     MORB_ARG(m != nullptr && out2 != nullptr);
     out2[0] = m->last_pose[0]; out2[1] = m->last_pose[1];
+    return ORB_OK;
+}
+
+int orbm_debug_last_sim3(const orbm_matcher* m, int* out2) {
+    MORB_ARG(m != nullptr && out2 != nullptr);
+    out2[0] = m->last_sim3[0]; out2[1] = m->last_sim3[1];
     return ORB_OK;
 }
 

@@ -1,6 +1,6 @@
 // matcher_internal.h -- types and internal entry points shared by the translation units of the matcher / front end
 // (hamming.hip: all-pairs kernels; frame.hip: frame assembly; search.hip: projection search + resolve; matcher.hip: handle
-// + host helpers; exchange.hip: RCCL / loopback transport; frontend.hip: orbf_*; mappoint.hip: map-point refresh; pose.hip: pose optimisation).  Not part of the C ABI.
+// + host helpers; exchange.hip: RCCL / loopback transport; frontend.hip: orbf_*; mappoint.hip: map-point refresh; pose.hip: pose optimisation; sim3.hip: Sim3 RANSAC).  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <condition_variable>
@@ -112,6 +112,13 @@ struct orbm_matcher {
     morb::StageBuf stage_p;
     PinnedBuf<uint8_t> h_pose;
     int last_pose[2] = {0, 0};
+    // orbm_sim3_ransac (sim3.hip): the packed problems, correspondences (structure of arrays) and triples of a call (host-written, read
+    // in place by the kernels), the hypothesis records in HBM between the two kernels, the records and mask words the kernels write
+    // (mapped pinned) and where the problems of the last call went
+    morb::StageBuf stage_s;
+    DevBuf<uint8_t> d_sim3;
+    PinnedBuf<uint8_t> h_sim3;
+    int last_sim3[2] = {0, 0};
 };
 namespace morb { hipStream_t side_stream(orbm_matcher* m); }   // (lazily created; NULL after a reported failure)
 

@@ -4,6 +4,7 @@ import numpy as np
 from . import _lib
 from ._lib import KP_DTYPE, QUERY_DTYPE, POINT_DTYPE, TRACK_DTYPE, REFRESH_DTYPE, CamFeatures, FrameDesc, check, ptr
 from ._lib import POSE_PROBLEM_DTYPE, POSE_RESULT_DTYPE, POSE_CAM0, POSE_ALL_CAMS, POSE_ORDER_INDEX, POSE_ORDER_DEVICE  # noqa: F401
+from ._lib import SIM3_PROBLEM_DTYPE, SIM3_HYP_DTYPE, SIM3_WALK_DTYPE, SIM3_MATH_LIBM, SIM3_MATH_DEVICE  # noqa: F401
 
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30  # reference src/ORBmatcher.cc:37-39
 
@@ -139,6 +140,94 @@ def pose_sincos(x):
     s = C.c_double(); c = C.c_double()
     _lib.lib().orbm_pose_sincos(float(x), C.byref(s), C.byref(c))
     return s.value, c.value
+
+
+class Sim3Problem:
+    """One Sim3Solver from its constructor's vectors on (orbm_sim3_problem + its correspondences + its drawn triples): K1, K2 =
+    (fx, fy, cx, cy) of mK1, mK2; x3dc1, x3dc2 n x 3 (mvX3Dc1, mvX3Dc2); cam1, cam2 n (camIdx1, camIdx2); max_err1, max_err2 n
+    (mvnMaxError1/2 as floats); triples H x 3 positions 0 .. n-1; either Rcam21 / tcam21 or calib = the constructor's CalibMatrix
+    (rows 0-2: Rcam12, row 3: tcam12), from which they are derived as the constructor does."""
+
+    def __init__(self, K1, K2, x3dc1, x3dc2, cam1, cam2, max_err1, max_err2, triples, fix_scale=False, Rcam21=None, tcam21=None, calib=None):
+        rec = np.zeros(1, SIM3_PROBLEM_DTYPE)
+        for k, v in zip(("fx1", "fy1", "cx1", "cy1"), K1):
+            rec[k] = np.float32(v)
+        for k, v in zip(("fx2", "fy2", "cx2", "cy2"), K2):
+            rec[k] = np.float32(v)
+        if calib is not None:
+            Rcam21, tcam21 = sim3_second_camera(calib)
+        rec["Rcam21"][0] = np.eye(3, dtype=np.float32).reshape(9) if Rcam21 is None else np.asarray(Rcam21, np.float32).reshape(9)
+        rec["tcam21"][0] = 0 if tcam21 is None else np.asarray(tcam21, np.float32).reshape(3)
+        rec["fix_scale"] = 1 if fix_scale else 0
+        self.rec = rec
+        self.x3dc1 = np.ascontiguousarray(x3dc1, np.float32).reshape(-1, 3)
+        self.x3dc2 = np.ascontiguousarray(x3dc2, np.float32).reshape(-1, 3)
+        self.cam1 = np.ascontiguousarray(cam1, np.int32); self.cam2 = np.ascontiguousarray(cam2, np.int32)
+        self.max_err1 = np.ascontiguousarray(max_err1, np.float32); self.max_err2 = np.ascontiguousarray(max_err2, np.float32)
+        self.triples = np.ascontiguousarray(triples, np.int32).reshape(-1, 3)
+        self.n = len(self.x3dc1); self.h = len(self.triples); self.w = (self.n + 63) // 64
+        assert len(self.x3dc2) == len(self.cam1) == len(self.cam2) == len(self.max_err1) == len(self.max_err2) == self.n
+
+
+def sim3_second_camera(calib):
+    """mRcam21 = Rcam12.t(), mtcam21 = -mRcam21 * tcam12 of the constructor (reference src/Sim3Solver.cc:61-70): the transpose, then
+    cv::gemm's small path with alpha = -1 -> (Rcam21 3 x 3, tcam21 3), float32."""
+    calib = np.asarray(calib, np.float32)
+    R21 = np.ascontiguousarray(calib[:3, :3].T)
+    t12 = calib[3, :3]
+    t = R21[:, 0] * t12[0] + R21[:, 1] * t12[1]
+    t = t + R21[:, 2] * t12[2]
+    return R21, (t.astype(np.float64) * -1.0 + 0.0 * 0.0).astype(np.float32)
+
+
+def _sim3_pack(problems):
+    recs = np.concatenate([p.rec for p in problems])
+    first = np.zeros(len(problems) + 1, np.int32); its_first = np.zeros(len(problems) + 1, np.int32)
+    first[1:] = np.cumsum([p.n for p in problems]); its_first[1:] = np.cumsum([p.h for p in problems])
+    cat = lambda name, dt, shape: np.ascontiguousarray(np.concatenate([getattr(p, name) for p in problems]).reshape(shape), dt)
+    words = int(sum(p.h * p.w for p in problems))
+    hyp = np.zeros(max(int(its_first[-1]), 1), SIM3_HYP_DTYPE); masks = np.zeros(max(words, 1), np.uint64)
+    args = (ptr(recs), len(problems), ptr(first), ptr(cat("x3dc1", np.float32, (-1, 3))), ptr(cat("x3dc2", np.float32, (-1, 3))),
+            ptr(cat("cam1", np.int32, (-1,))), ptr(cat("cam2", np.int32, (-1,))), ptr(cat("max_err1", np.float32, (-1,))),
+            ptr(cat("max_err2", np.float32, (-1,))), ptr(its_first), ptr(cat("triples", np.int32, (-1, 3))))
+    return args, its_first, hyp, masks
+
+
+def _sim3_unpack(problems, its_first, hyp, masks):
+    out, w0 = [], 0
+    for b, p in enumerate(problems):
+        out.append((hyp[its_first[b]:its_first[b + 1]].copy(), masks[w0:w0 + p.h * p.w].reshape(p.h, p.w).copy()))
+        w0 += p.h * p.w
+    return out
+
+
+def sim3_ransac_host(problems, order=SIM3_MATH_LIBM):
+    """orbm_sim3_ransac_host: every hypothesis of every problem on the host (no device needed), atan2 / sin / cos of the C library
+    (the restatement of the reference) or the device's sequences -> [(SIM3_HYP_DTYPE records H, mask words H x W uint64)] per problem."""
+    args, its_first, hyp, masks = _sim3_pack(problems)
+    check(_lib.lib().orbm_sim3_ransac_host(*args, int(order), ptr(hyp), ptr(masks)))
+    return _sim3_unpack(problems, its_first, hyp, masks)
+
+
+def sim3_walk(counts, N, min_inliers, start_iteration, n_iterations, state=None):
+    """orbm_sim3_walk: Sim3Solver::iterate(n_iterations, ...) over the precomputed inlier counts of the solver's hypotheses, starting at
+    mnIterations = start_iteration with state = (best_inliers, best_index) (None: a fresh solver)
+    -> (hypothesis returned or -1, no_more, iterations, best_inliers, best_index)."""
+    counts = np.ascontiguousarray(counts, np.int32)
+    st = np.zeros(1, SIM3_WALK_DTYPE)
+    st["best_inliers"], st["best_index"] = (0, -1) if state is None else state
+    found = _lib.lib().orbm_sim3_walk(ptr(counts), len(counts), int(N), int(min_inliers), int(start_iteration), int(n_iterations), ptr(st))
+    return int(found), bool(st["no_more"][0]), int(st["iterations"][0]), int(st["best_inliers"][0]), int(st["best_index"][0])
+
+
+def sim3_iterations(probability, min_inliers, max_its, N):
+    """orbm_sim3_iterations: mRansacMaxIts after SetRansacParameters(probability, min_inliers, max_its) with N correspondences."""
+    return int(_lib.lib().orbm_sim3_iterations(float(probability), int(min_inliers), int(max_its), int(N)))
+
+
+def sim3_atan2(y, x):
+    """The atan2 sequence of SIM3_MATH_DEVICE (orbm_sim3_atan2): y >= 0, x in [-1, 1]."""
+    return float(_lib.lib().orbm_sim3_atan2(float(y), float(x)))
 
 
 class LocalPoints:
@@ -501,6 +590,20 @@ class Matcher:
         flags = np.zeros(max(frame.data.n_total, 1), np.uint8); res = np.zeros(1, POSE_RESULT_DTYPE)
         check(_lib.lib().orbm_pose_optimize_resident(self._h, ptr(problem.rec), frame._h, points._h, ptr(pof), ptr(flags), ptr(res)))
         return res[0].copy(), flags[:frame.data.n_total]
+
+    def Sim3Ransac(self, problems):
+        """Every RANSAC hypothesis of a batch of Sim3Solvers in one call, two kernels back to back, one synchronisation
+        (orbm_sim3_ransac) -> [(SIM3_HYP_DTYPE records H, mask words H x W uint64)] per problem."""
+        args, its_first, hyp, masks = _sim3_pack(problems)
+        check(_lib.lib().orbm_sim3_ransac(self._h, *args, ptr(hyp), ptr(masks)))
+        return _sim3_unpack(problems, its_first, hyp, masks)
+
+    def last_sim3(self):
+        """Problems of the last Sim3Ransac by path: (device, host routine because of more than SIM3_CAP correspondences)
+        (orbm_debug_last_sim3)."""
+        out = (C.c_int * 2)()
+        check(_lib.lib().orbm_debug_last_sim3(self._h, out))
+        return tuple(out)
 
     def last_pose(self):
         """Problems of the last PoseOptimization[Resident] by path: (device, host routine because of more than POSE_CAP edges)
