@@ -21,6 +21,8 @@
 #include "../../include/orbv.h"
 #include "orb_common.h"
 #include "bow_internal.h"
+#include "hamming_dev.h"
+#include "stage_pack.h"
 
 using morb::DevBuf;
 using morb::PinnedBuf;
@@ -34,11 +36,6 @@ namespace {
 constexpr int HISTO = 30;        // ORBmatcher::HISTO_LENGTH, src/ORBmatcher.cc:39
 constexpr int JOIN_MAX_NODE = 32768;  // candidates of one node (one LDS byte each)
 constexpr int JOIN_LDS_BYTES = 65536; // dynamic LDS of one join workgroup: claimed bytes + staged descriptors
-
-__device__ __forceinline__ int ham256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) +
-           __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 __global__ __launch_bounds__(256) void k_bow_transform(const uint4* __restrict__ vdesc, const int* __restrict__ first_child,
                                                        const uint32_t* __restrict__ orig, const uint32_t* __restrict__ word,
@@ -380,8 +377,6 @@ __global__ __launch_bounds__(256) void k_bow_finish(JoinWork W, int n_out, int c
     if (d_final) d_final[i] = mt;
 }
 
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 }  // namespace
 
 struct orbv_vocabulary {
@@ -641,13 +636,11 @@ void orbv_workspace_destroy(orbv_workspace* w) {
 
 namespace {
 
-struct Packer {   // lays the arrays of both sides out in one pinned block, mirrored by one device block
-    size_t off = 0;
+struct Packer : morb::BlockLayout {   // lays the arrays of both sides out in one pinned block, mirrored by one device block
     uint8_t* h = nullptr; uint8_t* d = nullptr;
-    size_t reserve_bytes(size_t bytes) { const size_t o = off; off = up16(off + bytes); return o; }
     template <typename T> const T* put(const T* src, size_t count) {
         if (!src) return nullptr;
-        const size_t o = reserve_bytes(count * sizeof(T));
+        const size_t o = take(count * sizeof(T));
         if (h) memcpy(h + o, src, count * sizeof(T));
         return (const T*)(d + o);
     }
@@ -703,12 +696,12 @@ int enqueue_join(orbv_workspace* w, const SideDev& A, const SideDev& B, int max_
     const int n_out = mode == 0 ? B.n : A.n;
     if (max_nc > JOIN_MAX_NODE) { morb::set_error("a vocabulary node holds %d features (limit %d)", max_nc, JOIN_MAX_NODE); return ORB_E_CAPACITY; }
     int rc;
-    const size_t work_bytes = up16((size_t)n_out * 4) + up16((HISTO + 1) * 4) + up16((size_t)n_out);
+    const size_t work_bytes = morb::align16((size_t)n_out * 4) + morb::align16((HISTO + 1) * 4) + morb::align16((size_t)n_out);
     if ((rc = w->d_work.reserve(work_bytes)) || (rc = w->h_match.reserve((size_t)n_out + 4))) return rc;
     JoinWork W;
     W.match = (int32_t*)w->d_work.p;
-    W.hist = (int*)(w->d_work.p + up16((size_t)n_out * 4));
-    W.bin_of = w->d_work.p + up16((size_t)n_out * 4) + up16((HISTO + 1) * 4);
+    W.hist = (int*)(w->d_work.p + morb::align16((size_t)n_out * 4));
+    W.bin_of = w->d_work.p + morb::align16((size_t)n_out * 4) + morb::align16((HISTO + 1) * 4);
     hipStream_t st = w->stream;
     k_bow_init<<<(std::max(n_out, HISTO + 1) + 255) / 256, 256, 0, st>>>(W, n_out);
     const int claimed_bytes = (max_nc + 63) & ~63;
@@ -804,7 +797,7 @@ int prepare_join_resident(orbv_workspace* w, const orbv_keyframe* a, const uint8
     MORB_HIP(hipSetDevice(w->device));
     SideDev A = a->D, B = b->D;
     if (flags_a || flags_b) {       // per-call MapPoint state: two small arrays through the pinned stage
-        const size_t na = flags_a ? up16((size_t)A.n) : 0, nb = flags_b ? up16((size_t)B.n) : 0;
+        const size_t na = flags_a ? morb::align16((size_t)A.n) : 0, nb = flags_b ? morb::align16((size_t)B.n) : 0;
         if ((rc = w->h_stage.reserve(na + nb)) || (rc = w->d_stage.reserve(na + nb))) return rc;
         if (flags_a) { memcpy(w->h_stage.p, flags_a, (size_t)A.n); A.flags = w->d_stage.p; }
         if (flags_b) { memcpy(w->h_stage.p + na, flags_b, (size_t)B.n); B.flags = w->d_stage.p + na; }
@@ -898,14 +891,13 @@ int orbv_keyframe_from_device(orbv_workspace* w, const orbv_vocabulary* v, const
     orbv_keyframe* k = new orbv_keyframe();
     k->device = w->device; k->tri = tri;
     // block: desc | angle | flags | node_id | node_start | items | word | node | bin | [x | y | octave | cam_of] | counts | bin_to_node | meta
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = up16(off + bytes); return o; };
+    morb::BlockLayout L;
     const size_t nn = (size_t)std::max(n, 1);
-    const size_t o_desc = take(nn * 32), o_ang = take(nn * 4), o_fl = take(nn), o_nid = take((size_t)nbins * 4), o_ns = take((size_t)(nbins + 1) * 4),
-                 o_it = take(nn * 4), o_w = take(nn * 4), o_nd = take(nn * 4), o_bin = take(nn * 4);
-    const size_t o_x = tri ? take(nn * 4) : 0, o_y = tri ? take(nn * 4) : 0, o_oc = tri ? take(nn * 4) : 0;
-    const size_t o_cam = take(nn * 4), o_cnt = take((size_t)nbins * 4), o_b2n = take((size_t)nbins * 4), o_meta = take(16);
-    int rc = k->block.reserve(off);
+    const size_t o_desc = L.take(nn * 32), o_ang = L.take(nn * 4), o_fl = L.take(nn), o_nid = L.take((size_t)nbins * 4), o_ns = L.take((size_t)(nbins + 1) * 4),
+                 o_it = L.take(nn * 4), o_w = L.take(nn * 4), o_nd = L.take(nn * 4), o_bin = L.take(nn * 4);
+    const size_t o_x = tri ? L.take(nn * 4) : 0, o_y = tri ? L.take(nn * 4) : 0, o_oc = tri ? L.take(nn * 4) : 0;
+    const size_t o_cam = L.take(nn * 4), o_cnt = L.take((size_t)nbins * 4), o_b2n = L.take((size_t)nbins * 4), o_meta = L.take(16);
+    int rc = k->block.reserve(L.off);
     if (rc) { delete k; return rc; }
     uint8_t* B = k->block.p;
     hipStream_t st = w->stream;

@@ -17,6 +17,7 @@
 #include "../../include/orbm.h"
 #include "orb_common.h"
 #include "matcher_internal.h"
+#include "cv_dev.h"
 
 using namespace morb;
 
@@ -36,18 +37,13 @@ struct FrustumOut { float u, v, ur, view_cos, radius; int level; };
 
 // Frame::isInFrustum + PredictScale + the window radius of SearchByProjection, operation for operation in the reference's
 // number formats (this library is built without contraction and without fast-math):
-//   Pc = mRcw*P + mtcw     one cv::gemm call on its small path: products and sums in float, left to right, then
-//                          (float)(t*1.0 + c*1.0) in double (host/cv_compat.h gemm_small_elem)
-//   cv::norm, Mat::dot     squares / products summed in double from 0.0, in index order
+//   Pc = mRcw*P + mtcw     one cv::gemm call on its small path, alpha = beta = 1 (cv_dev.h cv_gemm3)
+//   cv::norm, Mat::dot     squares / products summed in double from 0.0, in index order (cv_norm3, cv_dot3)
 // Returns false where the reference returns false, and for a non-finite projection.
 __host__ __device__ inline bool frustum_eval(const FrustumView& V, const float* P, const float* Pn, float min_dist, float max_dist,
                                              FrustumOut& o) {
     float Pc[3];
-    for (int k = 0; k < 3; ++k) {
-        float t = V.Rcw[3 * k] * P[0] + V.Rcw[3 * k + 1] * P[1];
-        t = t + V.Rcw[3 * k + 2] * P[2];
-        Pc[k] = (float)((double)t * 1.0 + (double)V.tcw[k] * 1.0);
-    }
+    for (int k = 0; k < 3; ++k) Pc[k] = cv_gemm3(V.Rcw + 3 * k, 1, P, 1.0, V.tcw[k], 1.0);
     if (Pc[2] < 0.0f) return false;
     const float invz = 1.0f / Pc[2];
     const float u = V.fx * Pc[0] * invz + V.cx;
@@ -59,13 +55,9 @@ __host__ __device__ inline bool frustum_eval(const FrustumView& V, const float* 
     const float minDistance = 0.8f * min_dist;
     float PO[3];
     for (int k = 0; k < 3; ++k) PO[k] = P[k] - V.Ow[k];
-    double s = 0;
-    for (int k = 0; k < 3; ++k) s += (double)PO[k] * (double)PO[k];
-    const float dist = (float)sqrt(s);
+    const float dist = (float)cv_norm3(PO);
     if (dist < minDistance || dist > maxDistance) return false;
-    double d = 0;
-    for (int k = 0; k < 3; ++k) d += (double)PO[k] * (double)Pn[k];
-    const float viewCos = (float)(d / (double)dist);
+    const float viewCos = (float)(cv_dot3(PO, Pn) / (double)dist);
     if (viewCos < V.cos_limit) return false;
     const float ratio = max_dist / dist;
     int level = 0;

@@ -1,0 +1,186 @@
+// g2o_dev.h -- the Eigen / g2o boundary: the parts of Eigen and g2o that the reference's optimisers run and this library restates, ONE
+// definition each, for the kernels and the host routines (pose.hip today).  Restated from the published sources (Eigen's Geometry and
+// Cholesky modules; Thirdparty/g2o/g2o/types/se3quat.h, core/robust_kernel_impl.cpp) and UNPINNED: Eigen is not linked and g2o was never
+// compiled against this code, so each is ONE function that a later pin changes.  The library is built without
+// contraction and without fast-math, and the tests compare bytes: nothing inside these bodies is to be reordered.
+#pragma once
+#include <cfloat>
+#include <cmath>
+#include <hip/hip_runtime.h>
+#include "../../include/orbm.h"
+#include "sincos_dev.h"
+
+struct SE3Quat { double q[4], t[3]; };   // g2o::SE3Quat: quaternion in Eigen's coefficient order x y z w, translation
+
+// ---- Eigen ----------------------------------------------------------------------------------------------------------------------------
+// Quaternion<double>(Matrix3d) (Geometry/Quaternion.h, quaternionbase_assign_impl<Other,3,3>)
+__host__ __device__ inline void eigen_quat_from_matrix(const double* m, double* q) {
+    double t = m[0] + m[4] + m[8];
+    if (t > 0) {
+        t = sqrt(t + 1.0);
+        q[3] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (m[7] - m[5]) * t;
+        q[1] = (m[2] - m[6]) * t;
+        q[2] = (m[3] - m[1]) * t;
+    } else if (!(m[4] > m[0]) && !(m[8] > m[0])) {        // i = 0, j = 1, k = 2
+        t = sqrt(m[0] - m[4] - m[8] + 1.0);
+        q[0] = 0.5 * t; t = 0.5 / t;
+        q[3] = (m[7] - m[5]) * t; q[1] = (m[3] + m[1]) * t; q[2] = (m[6] + m[2]) * t;
+    } else if (m[4] > m[0] && !(m[8] > m[4])) {           // i = 1, j = 2, k = 0
+        t = sqrt(m[4] - m[8] - m[0] + 1.0);
+        q[1] = 0.5 * t; t = 0.5 / t;
+        q[3] = (m[2] - m[6]) * t; q[2] = (m[7] + m[5]) * t; q[0] = (m[1] + m[3]) * t;
+    } else {                                              // i = 2, j = 0, k = 1
+        t = sqrt(m[8] - m[0] - m[4] + 1.0);
+        q[2] = 0.5 * t; t = 0.5 / t;
+        q[3] = (m[3] - m[1]) * t; q[0] = (m[2] + m[6]) * t; q[1] = (m[5] + m[7]) * t;
+    }
+}
+// QuaternionBase::normalize: coeffs /= sqrt(squaredNorm), the squares summed in coefficient order
+__host__ __device__ inline void eigen_quat_normalize(double* q) {
+    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    q[0] = q[0] / n; q[1] = q[1] / n; q[2] = q[2] / n; q[3] = q[3] / n;
+}
+// QuaternionBase::_transformVector: uv = vec x v; uv += uv; v + w*uv + vec x uv
+__host__ __device__ inline void eigen_quat_rotate(const double* q, const double* v, double* out) {
+    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
+    uv[0] = uv[0] + uv[0]; uv[1] = uv[1] + uv[1]; uv[2] = uv[2] + uv[2];
+    const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
+    out[0] = v[0] + q[3] * uv[0] + c[0];
+    out[1] = v[1] + q[3] * uv[1] + c[1];
+    out[2] = v[2] + q[3] * uv[2] + c[2];
+}
+// quat_product<Architecture::Generic>
+__host__ __device__ inline void eigen_quat_mul(const double* a, const double* b, double* r) {
+    const double w = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+    const double x = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+    const double y = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
+    const double z = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+    r[0] = x; r[1] = y; r[2] = z; r[3] = w;
+}
+// QuaternionBase::toRotationMatrix
+__host__ __device__ inline void eigen_quat_to_matrix(const double* q, double* m) {
+    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
+    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
+    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
+    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
+    m[0] = 1 - (tyy + tzz); m[1] = txy - twz; m[2] = txz + twy;
+    m[3] = txy + twz; m[4] = 1 - (txx + tzz); m[5] = tyz - twx;
+    m[6] = txz - twy; m[7] = tyz + twx; m[8] = 1 - (txx + tyy);
+}
+// LDLT<MatrixXd>::compute (ldlt_inplace<Lower>::unblocked: the pivot is the FIRST largest |diagonal| of the remaining block) followed
+// by isPositive() and solve() (P, L, D with the 1/highest() tolerance, L^T, P^T); every inner product sequential in ascending index.
+// A: 6x6 row-major, destroyed (only its lower triangle is read).  Returns isPositive(); x is written only then, as g2o does.
+__host__ __device__ inline bool eigen_ldlt_solve(double* A, const double* b, double* x, double* temp, int* transp) {
+    int sign = 0;   // 0 ZeroSign, 1 PositiveSemiDef, -1 NegativeSemiDef, 2 Indefinite
+    bool done = false;
+    for (int k = 0; k < 6 && !done; ++k) {
+        int idx = k;
+        double big = fabs(A[7 * k]);
+        for (int i = k + 1; i < 6; ++i) { const double v = fabs(A[7 * i]); if (v > big) { big = v; idx = i; } }
+        transp[k] = idx;
+        if (k != idx) {
+            for (int j = 0; j < k; ++j) { const double t = A[6 * k + j]; A[6 * k + j] = A[6 * idx + j]; A[6 * idx + j] = t; }
+            for (int i = idx + 1; i < 6; ++i) { const double t = A[6 * i + k]; A[6 * i + k] = A[6 * i + idx]; A[6 * i + idx] = t; }
+            { const double t = A[7 * k]; A[7 * k] = A[7 * idx]; A[7 * idx] = t; }
+            for (int i = k + 1; i < idx; ++i) { const double t = A[6 * i + k]; A[6 * i + k] = A[6 * idx + i]; A[6 * idx + i] = t; }
+        }
+        if (k > 0) {
+            for (int j = 0; j < k; ++j) temp[j] = A[7 * j] * A[6 * k + j];
+            double s = 0;
+            for (int j = 0; j < k; ++j) s += A[6 * k + j] * temp[j];
+            A[7 * k] -= s;
+            for (int i = k + 1; i < 6; ++i) {
+                double r = 0;
+                for (int j = 0; j < k; ++j) r += A[6 * i + j] * temp[j];
+                A[6 * i + k] -= r;
+            }
+        }
+        const double akk = A[7 * k];
+        const bool valid = fabs(akk) > 0;
+        if (k == 0 && !valid) {
+            for (int j = 0; j < 6; ++j) transp[j] = j;
+            done = true;
+        } else {
+            if (valid) for (int i = k + 1; i < 6; ++i) A[6 * i + k] = A[6 * i + k] / akk;
+            if (sign == 1) { if (akk < 0) sign = 2; }
+            else if (sign == -1) { if (akk > 0) sign = 2; }
+            else if (sign == 0) { if (akk > 0) sign = 1; else if (akk < 0) sign = -1; }
+        }
+    }
+    if (!(sign == 1 || sign == 0)) return false;
+    for (int i = 0; i < 6; ++i) x[i] = b[i];
+    for (int k = 0; k < 6; ++k) { const double t = x[k]; x[k] = x[transp[k]]; x[transp[k]] = t; }
+    for (int i = 1; i < 6; ++i) { double s = 0; for (int j = 0; j < i; ++j) s += A[6 * i + j] * x[j]; x[i] -= s; }
+    const double tol = 1.0 / DBL_MAX;
+    for (int i = 0; i < 6; ++i) x[i] = fabs(A[7 * i]) > tol ? x[i] / A[7 * i] : 0.0;
+    for (int i = 4; i >= 0; --i) { double s = 0; for (int j = i + 1; j < 6; ++j) s += A[6 * j + i] * x[j]; x[i] -= s; }
+    for (int k = 5; k >= 0; --k) { const double t = x[k]; x[k] = x[transp[k]]; x[transp[k]] = t; }
+    return true;
+}
+
+// ---- SE(3) (types/se3quat.h) ------------------------------------------------------------------------------------------------------------
+__host__ __device__ inline void se3_normalize_rotation(SE3Quat& T) {   // SE3Quat::normalizeRotation
+    if (T.q[3] < 0) { T.q[0] *= -1; T.q[1] *= -1; T.q[2] *= -1; T.q[3] *= -1; }
+    eigen_quat_normalize(T.q);
+}
+__host__ __device__ inline void se3_map(const SE3Quat& T, const double* v, double* out) {   // SE3Quat::map: _r*xyz + _t
+    double r[3];
+    eigen_quat_rotate(T.q, v, r);
+    out[0] = r[0] + T.t[0]; out[1] = r[1] + T.t[1]; out[2] = r[2] + T.t[2];
+}
+// SE3Quat(R, t): Quaterniond(R), normalizeRotation
+__host__ __device__ inline void se3_from_matrix(const double* R, const double* t, SE3Quat& T) {
+    eigen_quat_from_matrix(R, T.q);
+    T.t[0] = t[0]; T.t[1] = t[1]; T.t[2] = t[2];
+    se3_normalize_rotation(T);
+}
+// Converter::toSE3Quat: float 4x4 -> Matrix3d, Vector3d -> SE3Quat(R, t)
+__host__ __device__ inline void se3_from_cv(const float* M, SE3Quat& T) {
+    double R[9], t[3];
+    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) R[3 * r + c] = (double)M[4 * r + c]; t[r] = (double)M[4 * r + 3]; }
+    se3_from_matrix(R, t, T);
+}
+// SE3Quat::operator*: t = t1 + r1*t2, r = r1*r2, normalizeRotation
+__host__ __device__ inline void se3_mul(const SE3Quat& a, const SE3Quat& b, SE3Quat& out) {
+    double r[3], q[4];
+    eigen_quat_rotate(a.q, b.t, r);
+    eigen_quat_mul(a.q, b.q, q);
+    out.t[0] = a.t[0] + r[0]; out.t[1] = a.t[1] + r[1]; out.t[2] = a.t[2] + r[2];
+    out.q[0] = q[0]; out.q[1] = q[1]; out.q[2] = q[2]; out.q[3] = q[3];
+    se3_normalize_rotation(out);
+}
+// SE3Quat::exp (:223-257).  order: where sin, cos and pow(theta, 3) come from.
+__host__ __device__ inline void se3_exp(const double* update, int order, SE3Quat& T) {
+    const double o0 = update[0], o1 = update[1], o2 = update[2];
+    const double theta = sqrt(o0 * o0 + o1 * o1 + o2 * o2);
+    const double O[9] = {0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0};   // skew(omega)
+    double O2[9], R[9], V[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) O2[3 * i + j] = O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j] + O[3 * i + 2] * O[6 + j];
+    if (theta < 0.00001) {
+        for (int i = 0; i < 9; ++i) { R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + O[i]) + O2[i]; V[i] = R[i]; }
+    } else {
+        double sn, cs, th3;
+#ifndef __HIP_DEVICE_COMPILE__
+        if (order == ORBM_POSE_ORDER_INDEX) { sn = sin(theta); cs = cos(theta); th3 = pow(theta, 3); } else
+#endif
+        { pose_sincos(theta, &sn, &cs); th3 = theta * theta * theta; }
+        const double a = sn / theta, c = (1 - cs) / (theta * theta), d = (theta - sn) / th3;
+        for (int i = 0; i < 9; ++i) {
+            const double I = i % 4 == 0 ? 1.0 : 0.0;
+            R[i] = (I + a * O[i]) + c * O2[i];
+            V[i] = (I + c * O[i]) + d * O2[i];
+        }
+    }
+    double t[3];
+    for (int i = 0; i < 3; ++i) t[i] = V[3 * i] * update[3] + V[3 * i + 1] * update[4] + V[3 * i + 2] * update[5];
+    se3_from_matrix(R, t, T);   // SE3Quat(Quaterniond(R), V*upsilon)
+}
+
+// RobustKernelHuber::robustify as far as rho[0] and rho[1] go (core/robust_kernel_impl.cpp:78-91); dsqr is the kernel's float member
+__host__ __device__ inline void g2o_huber(double e, double delta, double dsqr, double* rho0, double* rho1) {
+    if (e <= dsqr) { *rho0 = e; *rho1 = 1.; }
+    else { const double sqrte = sqrt(e); *rho0 = 2 * sqrte * delta - dsqr; *rho1 = delta / sqrte; }
+}

@@ -17,6 +17,7 @@
 #include <vector>
 #include "../../include/orbv.h"
 #include "orb_common.h"
+#include "stage_pack.h"
 
 using morb::DevBuf;
 using morb::PinnedBuf;
@@ -106,8 +107,6 @@ __global__ __launch_bounds__(DB_BLOCK) void k_db_compact(const uint32_t* __restr
     for (uint32_t i = threadIdx.x; i < mv.z; i += DB_BLOCK) { d_id[mv.y + i] = s_id[mv.x + i]; d_val[mv.y + i] = s_val[mv.x + i]; }
 }
 
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 struct Entry { uint64_t key, seq; uint32_t off, len; };
 
 }  // namespace
@@ -195,8 +194,9 @@ int compact(orbv_database* db) {
 int run_query(orbv_database* db, const uint2* d_table, int E, int Q, const uint32_t* const* id, const double* const* val, const int* n) {
     size_t total = 0; int nmax = 0;
     for (int q = 0; q < Q; ++q) { total += (size_t)n[q]; nmax = std::max(nmax, n[q]); }
-    const size_t o_off = 0, o_val = up16((size_t)(Q + 1) * sizeof(int)), o_id = o_val + up16(total * sizeof(double));
-    const size_t q_bytes = o_id + up16(total * sizeof(uint32_t));
+    morb::BlockLayout L;
+    const size_t o_off = L.take((size_t)(Q + 1) * sizeof(int)), o_val = L.take(total * sizeof(double)), o_id = L.take(total * sizeof(uint32_t));
+    const size_t q_bytes = L.off;
     int rc = db->h_q.reserve(q_bytes); if (rc != ORB_OK) return rc;
     rc = db->d_q.reserve(q_bytes); if (rc != ORB_OK) return rc;
     int* h_off = (int*)(db->h_q.p + o_off);

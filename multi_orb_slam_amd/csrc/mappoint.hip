@@ -18,6 +18,9 @@
 #include "../../include/orbm.h"
 #include "orb_common.h"
 #include "matcher_internal.h"
+#include "cv_dev.h"
+#include "hamming_dev.h"
+#include "stage_pack.h"
 
 using namespace morb;
 
@@ -31,9 +34,7 @@ namespace {
 __host__ __device__ inline void refresh_term(const float* pos, const float* centre, float* t) {
     float d[3];
     for (int k = 0; k < 3; ++k) d[k] = pos[k] - centre[k];
-    double s = 0;
-    for (int k = 0; k < 3; ++k) s += (double)d[k] * (double)d[k];
-    const double nrm = sqrt(s);
+    const double nrm = cv_norm3(d);
     const float be = (float)(1.0 / nrm);
     for (int k = 0; k < 3; ++k) t[k] = d[k] * be;
 }
@@ -42,29 +43,18 @@ __host__ __device__ inline void refresh_term(const float* pos, const float* cent
 __host__ __device__ inline void refresh_accumulate(float* normal, const float* t) {
     for (int k = 0; k < 3; ++k) normal[k] = normal[k] * 1.0f + t[k] + 0.0f;
 }
-// A NaN leaves as the NaN x86 makes from an invalid operation (sign bit set); the GCN ALUs make 0x7fc00000 from the same operation.
-__host__ __device__ inline float refresh_canonical(float x) {
-    if (x == x) return x;
-    const uint32_t bits = 0xffc00000u;
-    float f;
-    memcpy(&f, &bits, 4);
-    return f;
-}
-// mNormalVector = normal/n: convertTo with scale (float)(1.0/n), `x*scale + 0.0f`; n == 1 is cv::add(M, Scalar(0)), `x + 0.0f`
-// (cv_compat.h ew_scale).  const float dist = cv::norm(Pos - pRefKF->GetCameraCenter()); mfMaxDistance = dist*levelScaleFactor;
+// mNormalVector = normal/n: a scaled matrix with weight 1.0/n (cv_dev.h cv_scale); a NaN leaves as x86's (x86_nan).  const float dist = cv::norm(Pos - pRefKF->GetCameraCenter()); mfMaxDistance = dist*levelScaleFactor;
 // mfMinDistance = mfMaxDistance/mvScaleFactors[nLevels-1]   (src/MapPoint.cc:517-527)
 __host__ __device__ inline void refresh_finish(const float* sum, int n, const float* pos, const float* ref_centre, float level_scale,
                                                float top_scale, orbm_refresh_out& o) {
-    const float inv = (float)(1.0 / (double)n);
-    for (int k = 0; k < 3; ++k) o.normal[k] = refresh_canonical(n == 1 ? sum[k] + 0.0f : sum[k] * inv + 0.0f);
+    const double inv = 1.0 / (double)n;
+    for (int k = 0; k < 3; ++k) o.normal[k] = x86_nan(cv_scale(sum[k], inv));
     float d[3];
     for (int k = 0; k < 3; ++k) d[k] = pos[k] - ref_centre[k];
-    double s = 0;
-    for (int k = 0; k < 3; ++k) s += (double)d[k] * (double)d[k];
-    const float dist = (float)sqrt(s);
+    const float dist = (float)cv_norm3(d);
     const float max_dist = dist * level_scale;
-    o.max_dist = refresh_canonical(max_dist);
-    o.min_dist = refresh_canonical(max_dist / top_scale);
+    o.max_dist = x86_nan(max_dist);
+    o.min_dist = x86_nan(max_dist / top_scale);
 }
 
 struct RefreshDev {   // the packed inputs of a call as the kernels see them, and one class's worklist
@@ -75,11 +65,6 @@ struct RefreshDev {   // the packed inputs of a call as the kernels see them, an
     int n_levels;
     float scale[ORBM_MAX_LEVELS];
 };
-
-__device__ __forceinline__ int hamming256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 // No thread leaves early: the barriers and the lane exchanges below are reached by all 256.  A slot without a point, a lane without
 // an observation and a job that was not asked for carry n = 0 / zeros through the same statements.
@@ -131,7 +116,7 @@ __global__ __launch_bounds__(256) void k_refresh(RefreshDev A) {
         if (ROWS) {
             uint16_t* row = s_row + slot * RSTRIDE + l;
             for (int j = 0; j < n; ++j)
-                row[j * G] = alive_at(j) ? (uint16_t)hamming256(d0, d1, s_desc[2 * (base + j)], s_desc[2 * (base + j) + 1]) : (uint16_t)0xffff;
+                row[j * G] = alive_at(j) ? (uint16_t)ham256(d0, d1, s_desc[2 * (base + j)], s_desc[2 * (base + j) + 1]) : (uint16_t)0xffff;
         }
         int lo = 0, hi = 256;                          // the median is the smallest v with more than `rank` distances <= v
         while (lo < hi) {
@@ -142,7 +127,7 @@ __global__ __launch_bounds__(256) void k_refresh(RefreshDev A) {
                 for (int j = 0; j < n; ++j) c += ((int)row[j * G] <= mid) ? 1 : 0;   // (a dead column holds 0xffff)
             } else {
                 for (int j = 0; j < n; ++j)
-                    c += (alive_at(j) && hamming256(d0, d1, s_desc[2 * (base + j)], s_desc[2 * (base + j) + 1]) <= mid) ? 1 : 0;
+                    c += (alive_at(j) && ham256(d0, d1, s_desc[2 * (base + j)], s_desc[2 * (base + j) + 1]) <= mid) ? 1 : 0;
             }
             if (c > rank) hi = mid; else lo = mid + 1;
         }
@@ -252,8 +237,6 @@ int validate(const orbm_refresh_in* in, const orbm_refresh_out* out) {
     return ORB_OK;
 }
 
-inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 }  // namespace
 
 int orbm_refresh_points_host(const orbm_refresh_in* in, orbm_refresh_out* out) {
@@ -287,35 +270,26 @@ int orbm_refresh_points(orbm_matcher* m, const orbm_refresh_in* in, orbm_refresh
     if (n_dev > 0) {
         MORB_HIP(hipSetDevice(m->device));
         // one packed block: every array 16-byte aligned, written once by the host, read in place by the kernels
-        size_t off = 0;
-        auto take = [&](size_t bytes) { const size_t o = off; off = align16(off + bytes); return o; };
-        const size_t o_first = take((size_t)(P + 1) * 4), o_desc = take((size_t)NO * 32), o_centre = take((size_t)NO * 12),
-                     o_alive = take((size_t)NO), o_pos = take((size_t)P * 12), o_ref = take((size_t)P * 12), o_level = take((size_t)P * 4),
-                     o_what = take((size_t)P), o_list = take((size_t)n_dev * 4);
-        if ((rc = m->stage_r.reserve(off)) || (rc = m->h_refresh.reserve((size_t)n_dev))) return rc;
-        uint8_t* hp = m->stage_r.p;
-        memcpy(hp + o_first, in->first, (size_t)(P + 1) * 4);
-        memcpy(hp + o_desc, in->obs_desc, (size_t)NO * 32);
-        memcpy(hp + o_centre, in->obs_centre, (size_t)NO * 12);
-        memcpy(hp + o_alive, in->obs_alive, (size_t)NO);
-        // (the four per-point arrays of the normal / depth job may be absent when no point asks for it: zeros then, never read)
-        if (in->pos) memcpy(hp + o_pos, in->pos, (size_t)P * 12); else memset(hp + o_pos, 0, (size_t)P * 12);
-        if (in->ref_centre) memcpy(hp + o_ref, in->ref_centre, (size_t)P * 12); else memset(hp + o_ref, 0, (size_t)P * 12);
-        if (in->ref_level) memcpy(hp + o_level, in->ref_level, (size_t)P * 4); else memset(hp + o_level, 0, (size_t)P * 4);
-        memcpy(hp + o_what, in->what, (size_t)P);
-        memcpy(hp + o_list, list.data(), (size_t)n_dev * 4);
-        m->stage_r.publish();
-        const uint8_t* dp = m->stage_r.dp;
+        morb::StagePack pk;
+        const int i_first = pk.add(in->first, (size_t)(P + 1) * 4), i_desc = pk.add(in->obs_desc, (size_t)NO * 32),
+                  i_centre = pk.add(in->obs_centre, (size_t)NO * 12), i_alive = pk.add(in->obs_alive, (size_t)NO),
+                  // (the per-point arrays of the normal / depth job may be absent when no point asks for it: zeros then, never read)
+                  i_pos = pk.add_or_zeros(in->pos, (size_t)P * 12), i_ref = pk.add_or_zeros(in->ref_centre, (size_t)P * 12),
+                  i_level = pk.add_or_zeros(in->ref_level, (size_t)P * 4),
+                  i_what = pk.add(in->what, (size_t)P), i_list = pk.add(list.data(), (size_t)n_dev * 4);
+        const morb::StagePack::Block blk = pk.open(m->refresh.stage, &rc);
+        if (rc || (rc = m->refresh.out.reserve((size_t)n_dev))) return rc;
+        blk.publish();
         RefreshDev A;
-        A.first = (const int*)(dp + o_first); A.desc = (const uint4*)(dp + o_desc); A.centre = (const float*)(dp + o_centre);
-        A.alive = dp + o_alive; A.pos = (const float*)(dp + o_pos); A.ref_centre = (const float*)(dp + o_ref);
-        A.ref_level = (const int*)(dp + o_level); A.what = dp + o_what;
+        A.first = blk.dev<int>(i_first); A.desc = blk.dev<uint4>(i_desc); A.centre = blk.dev<float>(i_centre);
+        A.alive = blk.dev<uint8_t>(i_alive); A.pos = blk.dev<float>(i_pos); A.ref_centre = blk.dev<float>(i_ref);
+        A.ref_level = blk.dev<int>(i_level); A.what = blk.dev<uint8_t>(i_what);
         const bool levels = in->scale_factors && in->n_levels >= 1 && in->n_levels <= ORBM_MAX_LEVELS;
         A.n_levels = levels ? in->n_levels : 1;
         for (int k = 0; k < ORBM_MAX_LEVELS; ++k) A.scale[k] = levels && k < in->n_levels ? in->scale_factors[k] : 0.0f;
         for (int c = 0; c < 3; ++c) {
             if (!cnt[c]) continue;
-            A.list = (const int*)(dp + o_list) + start[c]; A.count = cnt[c]; A.out = m->h_refresh.dp + start[c];
+            A.list = blk.dev<int>(i_list) + start[c]; A.count = cnt[c]; A.out = m->refresh.out.dp + start[c];
             if (c == 0) hipLaunchKernelGGL(k_refresh<16>, dim3((cnt[c] + 15) / 16), dim3(256), 0, m->stream, A);
             else if (c == 1) hipLaunchKernelGGL(k_refresh<64>, dim3((cnt[c] + 3) / 4), dim3(256), 0, m->stream, A);
             else hipLaunchKernelGGL(k_refresh<256>, dim3(cnt[c]), dim3(256), 0, m->stream, A);
@@ -331,7 +305,7 @@ int orbm_refresh_points(orbm_matcher* m, const orbm_refresh_in* in, orbm_refresh
     }
     if (n_dev > 0) {
         MORB_HIP(hipStreamSynchronize(m->stream));
-        const orbm_refresh_out* R = m->h_refresh.p;
+        const orbm_refresh_out* R = m->refresh.out.p;
         for (int w = 0; w < n_dev; ++w) out[list[w]] = R[w];
     }
     for (int k = 0; k < 5; ++k) m->last_refresh[k] = cnt[k];

@@ -122,8 +122,7 @@ void orbm_destroy(orbm_matcher* m) {
     m->d_i0.release(); m->d_i1.release(); m->d_i2.release(); m->d_choice.release(); m->d_claim.release(); m->d_qmeta.release(); m->d_win2.release();
     m->d_match.release(); m->d_status.release(); m->d_gclaim.release(); m->d_rsync.release(); m->d_mergecnt.release(); m->d_u16.release(); m->d_x0.release(); m->d_x1.release(); m->d_x2.release();
     m->h_i0.release(); m->h_i1.release(); m->h_i2.release(); m->h_match.release(); m->h_u16.release(); m->h_ring.release();
-    m->stage_f.release(); m->stage_q.release(); m->stage_r.release(); m->h_refresh.release(); m->stage_p.release(); m->h_pose.release();
-    m->stage_s.release(); m->d_sim3.release(); m->h_sim3.release();
+    m->stage_f.release(); m->stage_q.release(); m->refresh.release(); m->pose.release(); m->sim3.release();
     if (m->ev_stage_f) (void)hipEventDestroy(m->ev_stage_f);
     for (FrameBufs* b : m->pool) { b->release(); delete b; }
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);

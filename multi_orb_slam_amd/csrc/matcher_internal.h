@@ -1,6 +1,8 @@
 // matcher_internal.h -- types and internal entry points shared by the translation units of the matcher / front end
 // (hamming.hip: all-pairs kernels; frame.hip: frame assembly; search.hip: projection search + resolve; matcher.hip: handle
-// + host helpers; exchange.hip: RCCL / loopback transport; frontend.hip: orbf_*; mappoint.hip: map-point refresh; pose.hip: pose optimisation; sim3.hip: Sim3 RANSAC).  Not part of the C ABI.
+// + host helpers; exchange.hip: RCCL / loopback transport; frontend.hip: orbf_*; mappoint.hip: map-point refresh; pose.hip: pose
+// optimisation; sim3.hip: Sim3 RANSAC).  Not part of the C ABI.  Next to it: cv_dev.h / g2o_dev.h (the restated OpenCV and Eigen / g2o
+// operations those ports share), sincos_dev.h, hamming_dev.h, stage_pack.h (the staged input block of a batched call).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <condition_variable>
@@ -49,6 +51,16 @@ struct FrameBufs {  // device storage of one frame; recycled through the matcher
         d_cell_start.release(); d_items.release(); d_cell_of.release(); d_cursor.release(); d_cam_start.release(); d_ntotal.release();
         d_desc.release(); d_kps.release(); d_cams.release();
     }
+};
+
+// The buffers of one batched port (orbm_refresh_points, orbm_pose_optimize, orbm_sim3_ransac): one set per port, so that the calls
+// of different ports do not reallocate each other's.
+template <typename Out>
+struct PortBufs {
+    morb::StageBuf stage;      // the packed inputs of a call: host-written (stage_pack.h), read in place by the kernels
+    PinnedBuf<Out> out;        // what the kernels write: mapped pinned
+    DevBuf<uint8_t> scratch;   // HBM that one kernel of the call leaves for the next: Sim3 alone has two kernels and uses it, the others leave it empty
+    void release() { stage.release(); out.release(); scratch.release(); }
 };
 
 struct orbm_matcher {
@@ -101,23 +113,18 @@ struct orbm_matcher {
     bool foreign_work = false;     // something other than a step's own search was put on the stream (orbf_step_end then waits for all of it)
     DevBuf<int32_t> d_mergecnt;    // running count of the merging workgroups that rode in resolve launches (MergeJob)
     bool merge_ready = false; unsigned merge_target = 0;
-    // orbm_refresh_points (mappoint.hip): the packed inputs of a call (host-written, read in place by the kernels), the records the
-    // kernels write (mapped pinned, dense in worklist order) and where the points of the last call went
-    morb::StageBuf stage_r;
-    PinnedBuf<orbm_refresh_out> h_refresh;
+    // orbm_refresh_points (mappoint.hip): the packed inputs of a call, the records the kernels write (dense in worklist order) and
+    // where the points of the last call went
+    PortBufs<orbm_refresh_out> refresh;
     std::vector<int32_t> refresh_list;
     int last_refresh[5] = {0, 0, 0, 0, 0};
-    // orbm_pose_optimize (pose.hip): the packed problems and edges of a call (host-written, read in place by the kernel), the records
-    // and flags the kernel writes (mapped pinned) and where the problems of the last call went
-    morb::StageBuf stage_p;
-    PinnedBuf<uint8_t> h_pose;
+    // orbm_pose_optimize (pose.hip): the packed problems and edges of a call, the records and flags the kernel writes and where the
+    // problems of the last call went
+    PortBufs<uint8_t> pose;
     int last_pose[2] = {0, 0};
-    // orbm_sim3_ransac (sim3.hip): the packed problems, correspondences (structure of arrays) and triples of a call (host-written, read
-    // in place by the kernels), the hypothesis records in HBM between the two kernels, the records and mask words the kernels write
-    // (mapped pinned) and where the problems of the last call went
-    morb::StageBuf stage_s;
-    DevBuf<uint8_t> d_sim3;
-    PinnedBuf<uint8_t> h_sim3;
+    // orbm_sim3_ransac (sim3.hip): the packed problems, correspondences (structure of arrays) and triples of a call, the hypothesis
+    // records between the two kernels (scratch), the records and mask words the kernels write and where the problems of the last call went
+    PortBufs<uint8_t> sim3;
     int last_sim3[2] = {0, 0};
 };
 namespace morb { hipStream_t side_stream(orbm_matcher* m); }   // (lazily created; NULL after a reported failure)

@@ -3,8 +3,7 @@
 // g2o they run restated (Thirdparty/g2o/g2o/: types/types_six_dof_expmap.{h,cpp}, types/se3quat.h, types/se3_ops.hpp,
 // core/base_unary_edge.hpp, core/base_edge.h, core/robust_kernel_impl.cpp, core/optimization_algorithm_levenberg.cpp,
 // core/sparse_optimizer.cpp, solvers/linear_solver_dense.h) and the Eigen operators those call.
-//   pose_eigen_*     the Eigen operators, restated from Eigen's published sources and UNPINNED (Eigen is not linked and g2o was never
-//                    compiled against this code: DESIGN.md section 2): each is ONE function that a later pin changes.
+//   eigen_*, se3_*, g2o_huber   the Eigen operators, g2o::SE3Quat and the Huber kernel: g2o_dev.h (UNPINNED).
 //   pose_edge        one edge: error, chi2 and the Jacobian of its type, ONE statement sequence for the kernel and the host routine.
 //   pose_step        the controller: everything between two passes over the edges (Levenberg bookkeeping, the 6x6 solve, the exp map,
 //                    the round and classification logic) as a resumable state machine over a PoseCtl record.  The host routine calls it
@@ -25,7 +24,9 @@
 #include "../../include/orb_debug.h"
 #include "orb_common.h"
 #include "matcher_internal.h"
-#include "sincos_dev.h"
+#include "cv_dev.h"
+#include "g2o_dev.h"
+#include "stage_pack.h"
 
 namespace {
 
@@ -34,195 +35,25 @@ constexpr int POSE_REG_SLOTS = 8;    // edges per lane whose constants stay in r
 constexpr int POSE_NSUM = 29;        // H upper triangle (21, row-major i <= j), b (6), robust chi2, outlier count
 enum { POSE_CMD_FULL = 0, POSE_CMD_CHI = 1, POSE_CMD_CLASSIFY = 2, POSE_CMD_DONE = 3 };
 
-struct PoseSE3 { double q[4], t[3]; };   // g2o::SE3Quat: quaternion in Eigen's coefficient order x y z w, translation
 struct PoseCam {                         // per problem: the members of the edges that do not depend on the edge
     double fx, fy, cx, cy, bf;
-    PoseSE3 Tc[2];                       // Tcim[cam] (:659-666); read in the all-cameras mode only
+    SE3Quat Tc[2];                       // Tcim[cam] (:659-666); read in the all-cameras mode only
     double Rc[2][9];                     // Tcim_quat.to_homogeneous_matrix().block(0,0,3,3)
     double delta[2], dsqr[2];            // RobustKernelHuber::_delta (double) and dsqr (a FLOAT member) of a mono / stereo edge
     int multi, n_cam0;
 };
 struct PoseEdge { float X[3], obs[3], inv_sigma2; int meta; };   // meta: bit 0 camera, bit 1 stereo, bit 2 slot in use
 
-// ---- the Eigen boundary: UNPINNED --------------------------------------------------------------------------------
-// Quaternion<double>(Matrix3d) (Geometry/Quaternion.h, quaternionbase_assign_impl<Other,3,3>)
-__host__ __device__ inline void pose_eigen_quat_from_matrix(const double* m, double* q) {
-    double t = m[0] + m[4] + m[8];
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (m[7] - m[5]) * t;
-        q[1] = (m[2] - m[6]) * t;
-        q[2] = (m[3] - m[1]) * t;
-    } else if (!(m[4] > m[0]) && !(m[8] > m[0])) {        // i = 0, j = 1, k = 2
-        t = sqrt(m[0] - m[4] - m[8] + 1.0);
-        q[0] = 0.5 * t; t = 0.5 / t;
-        q[3] = (m[7] - m[5]) * t; q[1] = (m[3] + m[1]) * t; q[2] = (m[6] + m[2]) * t;
-    } else if (m[4] > m[0] && !(m[8] > m[4])) {           // i = 1, j = 2, k = 0
-        t = sqrt(m[4] - m[8] - m[0] + 1.0);
-        q[1] = 0.5 * t; t = 0.5 / t;
-        q[3] = (m[2] - m[6]) * t; q[2] = (m[7] + m[5]) * t; q[0] = (m[1] + m[3]) * t;
-    } else {                                              // i = 2, j = 0, k = 1
-        t = sqrt(m[8] - m[0] - m[4] + 1.0);
-        q[2] = 0.5 * t; t = 0.5 / t;
-        q[3] = (m[3] - m[1]) * t; q[0] = (m[2] + m[6]) * t; q[1] = (m[5] + m[7]) * t;
-    }
-}
-// QuaternionBase::normalize: coeffs /= sqrt(squaredNorm), the squares summed in coefficient order
-__host__ __device__ inline void pose_eigen_quat_normalize(double* q) {
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    q[0] = q[0] / n; q[1] = q[1] / n; q[2] = q[2] / n; q[3] = q[3] / n;
-}
-// QuaternionBase::_transformVector: uv = vec x v; uv += uv; v + w*uv + vec x uv
-__host__ __device__ inline void pose_eigen_quat_rotate(const double* q, const double* v, double* out) {
-    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] = uv[0] + uv[0]; uv[1] = uv[1] + uv[1]; uv[2] = uv[2] + uv[2];
-    const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
-    out[0] = v[0] + q[3] * uv[0] + c[0];
-    out[1] = v[1] + q[3] * uv[1] + c[1];
-    out[2] = v[2] + q[3] * uv[2] + c[2];
-}
-// quat_product<Architecture::Generic>
-__host__ __device__ inline void pose_eigen_quat_mul(const double* a, const double* b, double* r) {
-    const double w = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    const double x = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    const double y = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    const double z = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-    r[0] = x; r[1] = y; r[2] = z; r[3] = w;
-}
-// QuaternionBase::toRotationMatrix
-__host__ __device__ inline void pose_eigen_quat_to_matrix(const double* q, double* m) {
-    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    m[0] = 1 - (tyy + tzz); m[1] = txy - twz; m[2] = txz + twy;
-    m[3] = txy + twz; m[4] = 1 - (txx + tzz); m[5] = tyz - twx;
-    m[6] = txz - twy; m[7] = tyz + twx; m[8] = 1 - (txx + tyy);
-}
-// LDLT<MatrixXd>::compute (ldlt_inplace<Lower>::unblocked: the pivot is the FIRST largest |diagonal| of the remaining block) followed
-// by isPositive() and solve() (P, L, D with the 1/highest() tolerance, L^T, P^T); every inner product sequential in ascending index.
-// A: 6x6 row-major, destroyed (only its lower triangle is read).  Returns isPositive(); x is written only then, as g2o does.
-__host__ __device__ inline bool pose_eigen_ldlt_solve(double* A, const double* b, double* x, double* temp, int* transp) {
-    int sign = 0;   // 0 ZeroSign, 1 PositiveSemiDef, -1 NegativeSemiDef, 2 Indefinite
-    bool done = false;
-    for (int k = 0; k < 6 && !done; ++k) {
-        int idx = k;
-        double big = fabs(A[7 * k]);
-        for (int i = k + 1; i < 6; ++i) { const double v = fabs(A[7 * i]); if (v > big) { big = v; idx = i; } }
-        transp[k] = idx;
-        if (k != idx) {
-            for (int j = 0; j < k; ++j) { const double t = A[6 * k + j]; A[6 * k + j] = A[6 * idx + j]; A[6 * idx + j] = t; }
-            for (int i = idx + 1; i < 6; ++i) { const double t = A[6 * i + k]; A[6 * i + k] = A[6 * i + idx]; A[6 * i + idx] = t; }
-            { const double t = A[7 * k]; A[7 * k] = A[7 * idx]; A[7 * idx] = t; }
-            for (int i = k + 1; i < idx; ++i) { const double t = A[6 * i + k]; A[6 * i + k] = A[6 * idx + i]; A[6 * idx + i] = t; }
-        }
-        if (k > 0) {
-            for (int j = 0; j < k; ++j) temp[j] = A[7 * j] * A[6 * k + j];
-            double s = 0;
-            for (int j = 0; j < k; ++j) s += A[6 * k + j] * temp[j];
-            A[7 * k] -= s;
-            for (int i = k + 1; i < 6; ++i) {
-                double r = 0;
-                for (int j = 0; j < k; ++j) r += A[6 * i + j] * temp[j];
-                A[6 * i + k] -= r;
-            }
-        }
-        const double akk = A[7 * k];
-        const bool valid = fabs(akk) > 0;
-        if (k == 0 && !valid) {
-            for (int j = 0; j < 6; ++j) transp[j] = j;
-            done = true;
-        } else {
-            if (valid) for (int i = k + 1; i < 6; ++i) A[6 * i + k] = A[6 * i + k] / akk;
-            if (sign == 1) { if (akk < 0) sign = 2; }
-            else if (sign == -1) { if (akk > 0) sign = 2; }
-            else if (sign == 0) { if (akk > 0) sign = 1; else if (akk < 0) sign = -1; }
-        }
-    }
-    if (!(sign == 1 || sign == 0)) return false;
-    for (int i = 0; i < 6; ++i) x[i] = b[i];
-    for (int k = 0; k < 6; ++k) { const double t = x[k]; x[k] = x[transp[k]]; x[transp[k]] = t; }
-    for (int i = 1; i < 6; ++i) { double s = 0; for (int j = 0; j < i; ++j) s += A[6 * i + j] * x[j]; x[i] -= s; }
-    const double tol = 1.0 / DBL_MAX;
-    for (int i = 0; i < 6; ++i) x[i] = fabs(A[7 * i]) > tol ? x[i] / A[7 * i] : 0.0;
-    for (int i = 4; i >= 0; --i) { double s = 0; for (int j = i + 1; j < 6; ++j) s += A[6 * j + i] * x[j]; x[i] -= s; }
-    for (int k = 5; k >= 0; --k) { const double t = x[k]; x[k] = x[transp[k]]; x[transp[k]] = t; }
-    return true;
-}
-
-// ---- sine and cosine of ORBM_POSE_ORDER_DEVICE: pose_sincos, shared with sim3.hip (sincos_dev.h) ----------------------------------
-
-// ---- SE(3) (types/se3quat.h) ------------------------------------------------------------------------------------------------------------
-__host__ __device__ inline void pose_normalize_rotation(PoseSE3& T) {   // SE3Quat::normalizeRotation
-    if (T.q[3] < 0) { T.q[0] *= -1; T.q[1] *= -1; T.q[2] *= -1; T.q[3] *= -1; }
-    pose_eigen_quat_normalize(T.q);
-}
-__host__ __device__ inline void pose_map(const PoseSE3& T, const double* v, double* out) {   // SE3Quat::map: _r*xyz + _t
-    double r[3];
-    pose_eigen_quat_rotate(T.q, v, r);
-    out[0] = r[0] + T.t[0]; out[1] = r[1] + T.t[1]; out[2] = r[2] + T.t[2];
-}
-// SE3Quat(R, t): Quaterniond(R), normalizeRotation
-__host__ __device__ inline void pose_from_matrix(const double* R, const double* t, PoseSE3& T) {
-    pose_eigen_quat_from_matrix(R, T.q);
-    T.t[0] = t[0]; T.t[1] = t[1]; T.t[2] = t[2];
-    pose_normalize_rotation(T);
-}
-// Converter::toSE3Quat: float 4x4 -> Matrix3d, Vector3d -> SE3Quat(R, t)
-__host__ __device__ inline void pose_from_cv(const float* M, PoseSE3& T) {
-    double R[9], t[3];
-    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) R[3 * r + c] = (double)M[4 * r + c]; t[r] = (double)M[4 * r + 3]; }
-    pose_from_matrix(R, t, T);
-}
-// SE3Quat::operator*: t = t1 + r1*t2, r = r1*r2, normalizeRotation
-__host__ __device__ inline void pose_mul(const PoseSE3& a, const PoseSE3& b, PoseSE3& out) {
-    double r[3], q[4];
-    pose_eigen_quat_rotate(a.q, b.t, r);
-    pose_eigen_quat_mul(a.q, b.q, q);
-    out.t[0] = a.t[0] + r[0]; out.t[1] = a.t[1] + r[1]; out.t[2] = a.t[2] + r[2];
-    out.q[0] = q[0]; out.q[1] = q[1]; out.q[2] = q[2]; out.q[3] = q[3];
-    pose_normalize_rotation(out);
-}
-// SE3Quat::exp (:223-257).  order: where sin, cos and pow(theta, 3) come from.
-__host__ __device__ inline void pose_exp(const double* update, int order, PoseSE3& T) {
-    const double o0 = update[0], o1 = update[1], o2 = update[2];
-    const double theta = sqrt(o0 * o0 + o1 * o1 + o2 * o2);
-    const double O[9] = {0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0};   // skew(omega)
-    double O2[9], R[9], V[9];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) O2[3 * i + j] = O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j] + O[3 * i + 2] * O[6 + j];
-    if (theta < 0.00001) {
-        for (int i = 0; i < 9; ++i) { R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + O[i]) + O2[i]; V[i] = R[i]; }
-    } else {
-        double sn, cs, th3;
-#ifndef __HIP_DEVICE_COMPILE__
-        if (order == ORBM_POSE_ORDER_INDEX) { sn = sin(theta); cs = cos(theta); th3 = pow(theta, 3); } else
-#endif
-        { pose_sincos(theta, &sn, &cs); th3 = theta * theta * theta; }
-        const double a = sn / theta, c = (1 - cs) / (theta * theta), d = (theta - sn) / th3;
-        for (int i = 0; i < 9; ++i) {
-            const double I = i % 4 == 0 ? 1.0 : 0.0;
-            R[i] = (I + a * O[i]) + c * O2[i];
-            V[i] = (I + c * O[i]) + d * O2[i];
-        }
-    }
-    double t[3];
-    for (int i = 0; i < 3; ++i) t[i] = V[3 * i] * update[3] + V[3 * i + 1] * update[4] + V[3 * i + 2] * update[5];
-    pose_from_matrix(R, t, T);   // SE3Quat(Quaterniond(R), V*upsilon)
-}
-
 // ---- one edge ---------------------------------------------------------------------------------------------------------------------------
 // computeError and chi2 of the edge's type; with want_jacobian also linearizeOplus (J: D rows of 6).  Returns chi2 = e . (Omega e) with
 // Omega = Identity * (double)invSigma2.
-__host__ __device__ inline double pose_edge(const PoseCam& C, const PoseSE3& T, const PoseEdge& E, double* e, bool want_jacobian, double (*J)[6]) {
+__host__ __device__ inline double pose_edge(const PoseCam& C, const SE3Quat& T, const PoseEdge& E, double* e, bool want_jacobian, double (*J)[6]) {
     const int cam = E.meta & 1;
     const bool stereo = (E.meta & 2) != 0;
     const double Xw[3] = {(double)E.X[0], (double)E.X[1], (double)E.X[2]};
     double p[3], pc[3];
-    pose_map(T, Xw, p);                                   // v1->estimate().map(Xw)
-    if (C.multi) pose_map(C.Tc[cam], p, pc);              // Tcim_quat.map(...), also where it is the identity
+    se3_map(T, Xw, p);                                   // v1->estimate().map(Xw)
+    if (C.multi) se3_map(C.Tc[cam], p, pc);              // Tcim_quat.map(...), also where it is the identity
     else { pc[0] = p[0]; pc[1] = p[1]; pc[2] = p[2]; }
     if (!stereo) {
         const double proj0 = pc[0] / pc[2], proj1 = pc[1] / pc[2];            // project2d
@@ -295,22 +126,16 @@ __host__ __device__ inline double pose_edge(const PoseCam& C, const PoseSE3& T, 
     return chi2;
 }
 
-// RobustKernelHuber::robustify as far as rho[0] and rho[1] go (core/robust_kernel_impl.cpp:78-91); dsqr is the kernel's float member
-__host__ __device__ inline void pose_huber(double e, double delta, double dsqr, double* rho0, double* rho1) {
-    if (e <= dsqr) { *rho0 = e; *rho1 = 1.; }
-    else { const double sqrte = sqrt(e); *rho0 = 2 * sqrte * delta - dsqr; *rho1 = delta / sqrte; }
-}
-
 // One ACTIVE edge's share of a pass (computeActiveErrors + activeRobustChi2, with `system` also linearizeOplus + constructQuadraticForm,
 // core/base_unary_edge.hpp:44-72): acc[27] += rho[0]; b -= rho[1] * J^T (Omega e); H += J^T (rho[1] Omega) J.  The edge's own 6-vector
 // and 6x6 are formed first (rows of J in order) and then added, as the edge adds its products to the vertex.  UNPINNED: Eigen's
 // evaluation order inside the two products.
-__host__ __device__ inline void pose_accumulate(const PoseCam& C, const PoseSE3& T, const PoseEdge& E, bool system, bool robust, double* acc) {
+__host__ __device__ inline void pose_accumulate(const PoseCam& C, const SE3Quat& T, const PoseEdge& E, bool system, bool robust, double* acc) {
     double e[3], J[3][6];
     const bool stereo = (E.meta & 2) != 0;
     const double chi2 = pose_edge(C, T, E, e, system, J);
     double rho0 = chi2, rho1 = 1.;
-    if (robust) pose_huber(chi2, C.delta[stereo ? 1 : 0], C.dsqr[stereo ? 1 : 0], &rho0, &rho1);
+    if (robust) g2o_huber(chi2, C.delta[stereo ? 1 : 0], C.dsqr[stereo ? 1 : 0], &rho0, &rho1);
     acc[27] += rho0;
     if (!system) return;
     const double w = (double)E.inv_sigma2, rw = rho1 * w;
@@ -332,7 +157,7 @@ __host__ __device__ inline void pose_accumulate(const PoseCam& C, const PoseSE3&
 
 // the classification of one edge after a round (:541-597): an outlier's error is recomputed at the estimate, an inlier keeps the error
 // of the last computeActiveErrors (the pose of the last pass, which is the REJECTED trial when the round ended on one)
-__host__ __device__ inline bool pose_classify(const PoseCam& C, const PoseSE3& est, const PoseSE3& last, const PoseEdge& E, bool was_outlier) {
+__host__ __device__ inline bool pose_classify(const PoseCam& C, const SE3Quat& est, const SE3Quat& last, const PoseEdge& E, bool was_outlier) {
     double e[3], J[3][6];
     const float chi2 = (float)pose_edge(C, was_outlier ? est : last, E, e, false, J);
     return (E.meta & 2) ? chi2 > 7.815f : chi2 > 5.991f;
@@ -341,38 +166,23 @@ __host__ __device__ inline bool pose_classify(const PoseCam& C, const PoseSE3& e
 // ---- the controller ---------------------------------------------------------------------------------------------------------------------
 struct PoseCtl {
     int cmd, order, n, round, iter, qmax, n_bad_steps, robust, n_bad, ok2;
-    PoseSE3 start, est, eval, last;          // eval: the pose of the next pass; last: the pose of the last FULL / CHI pass
+    SE3Quat start, est, eval, last;          // eval: the pose of the next pass; last: the pose of the last FULL / CHI pass
     double H[21], b[6], x[6], lambda, ni, current_chi, ini_chi;
     double A[36], temp[6]; int transp[6];    // the solver's working storage (indexed at run time: LDS on the device, never registers)
     orbm_pose_result res;
 };
 
-__host__ __device__ inline double pose_canonical(double x) {
-    if (x == x) return x;
-    const unsigned long long bits = 0xfff8000000000000ull;
-    double d;
-    memcpy(&d, &bits, 8);
-    return d;
-}
-__host__ __device__ inline float pose_canonical_f(float x) {
-    if (x == x) return x;
-    const uint32_t bits = 0xffc00000u;
-    float f;
-    memcpy(&f, &bits, 4);
-    return f;
-}
-
 // Converter::toCvMat(SE3Quat): to_homogeneous_matrix() rounded to float
 __host__ __device__ inline void pose_write_estimate(PoseCtl& S) {
     double R[9];
-    pose_eigen_quat_to_matrix(S.est.q, R);
+    eigen_quat_to_matrix(S.est.q, R);
     for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) S.res.Tcw[4 * r + c] = pose_canonical_f((float)R[3 * r + c]);
-        S.res.Tcw[4 * r + 3] = pose_canonical_f((float)S.est.t[r]);
+        for (int c = 0; c < 3; ++c) S.res.Tcw[4 * r + c] = x86_nan((float)R[3 * r + c]);
+        S.res.Tcw[4 * r + 3] = x86_nan((float)S.est.t[r]);
     }
     S.res.Tcw[12] = 0.0f; S.res.Tcw[13] = 0.0f; S.res.Tcw[14] = 0.0f; S.res.Tcw[15] = 1.0f;
-    for (int k = 0; k < 4; ++k) S.res.q[k] = pose_canonical(S.est.q[k]);
-    for (int k = 0; k < 3; ++k) S.res.t[k] = pose_canonical(S.est.t[k]);
+    for (int k = 0; k < 4; ++k) S.res.q[k] = x86_nan(S.est.q[k]);
+    for (int k = 0; k < 3; ++k) S.res.t[k] = x86_nan(S.est.t[k]);
 }
 
 // one trial of the Levenberg loop up to its pass (:103-121): H + lambda on the diagonal, the dense solve, update(x) = exp(x) * estimate
@@ -381,10 +191,10 @@ __host__ __device__ inline void pose_try(PoseCtl& S) {
     for (int i = 0; i < 6; ++i)
         for (int j = i; j < 6; ++j, ++k) { S.A[6 * i + j] = S.H[k]; S.A[6 * j + i] = S.H[k]; }
     for (int i = 0; i < 6; ++i) S.A[7 * i] += S.lambda;
-    S.ok2 = pose_eigen_ldlt_solve(S.A, S.b, S.x, S.temp, S.transp) ? 1 : 0;
-    PoseSE3 d;
-    pose_exp(S.x, S.order, d);
-    pose_mul(d, S.est, S.eval);              // oplusImpl: setEstimate(SE3Quat::exp(update) * estimate())
+    S.ok2 = eigen_ldlt_solve(S.A, S.b, S.x, S.temp, S.transp) ? 1 : 0;
+    SE3Quat d;
+    se3_exp(S.x, S.order, d);
+    se3_mul(d, S.est, S.eval);              // oplusImpl: setEstimate(SE3Quat::exp(update) * estimate())
     S.cmd = POSE_CMD_CHI;
 }
 __host__ __device__ inline void pose_begin_round(PoseCtl& S) {
@@ -398,14 +208,14 @@ __host__ __device__ inline void pose_begin(PoseCtl& S, const float* Tcw, int n, 
     S.order = order; S.n = n; S.round = 0; S.robust = 1; S.n_bad = 0; S.ok2 = 1;
     S.lambda = 0; S.ni = 2; S.current_chi = 0; S.ini_chi = 0; S.n_bad_steps = 0; S.qmax = 0;
     for (int i = 0; i < 6; ++i) S.x[i] = 0;
-    pose_from_cv(Tcw, S.start);
+    se3_from_cv(Tcw, S.start);
     S.est = S.start; S.last = S.start; S.eval = S.start;
     memset(&S.res, 0, sizeof(S.res));
     S.res.n_initial = n;
     if (n < 3) {                             // `if(nInitialCorrespondences<3) return 0;`: the pose is not touched
         for (int i = 0; i < 16; ++i) S.res.Tcw[i] = Tcw[i];
-        for (int k = 0; k < 4; ++k) S.res.q[k] = pose_canonical(S.start.q[k]);
-        for (int k = 0; k < 3; ++k) S.res.t[k] = pose_canonical(S.start.t[k]);
+        for (int k = 0; k < 4; ++k) S.res.q[k] = x86_nan(S.start.q[k]);
+        for (int k = 0; k < 3; ++k) S.res.t[k] = x86_nan(S.start.t[k]);
         S.cmd = POSE_CMD_DONE;
         return;
     }
@@ -469,7 +279,7 @@ __host__ __device__ inline void pose_step(PoseCtl& S, const double* sum) {
         }
         S.iter++;
         if (terminate || S.iter == 10) {
-            R.chi2 = pose_canonical(S.current_chi); R.lambda = pose_canonical(S.lambda);
+            R.chi2 = x86_nan(S.current_chi); R.lambda = x86_nan(S.lambda);
             S.cmd = POSE_CMD_CLASSIFY;
         } else {
             S.eval = S.est; S.cmd = POSE_CMD_FULL;
@@ -495,21 +305,19 @@ __host__ __device__ inline void pose_step(PoseCtl& S, const double* sum) {
 __host__ __device__ inline void pose_camera(const orbm_pose_problem& P, PoseCam& C) {
     C.fx = (double)P.fx; C.fy = (double)P.fy; C.cx = (double)P.cx; C.cy = (double)P.cy; C.bf = (double)P.bf;
     C.multi = P.mode == ORBM_POSE_ALL_CAMS ? 1 : 0; C.n_cam0 = P.n_cam0;
-    // Tcam11 = eye; Tcam21 = [Rcam12.t() | -Rcam12.t() * tcam12] in float: cv::gemm's small path (host/cv_compat.h gemm_small_elem),
-    // products and sums in float from left to right, then the scale by alpha = -1
+    // Tcam11 = eye; Tcam21 = [Rcam12.t() | -Rcam12.t() * tcam12] in float: cv::gemm's small path (cv_dev.h cv_gemm3) over a column of
+    // Rcam12, alpha = -1, no C
     float T11[16], T21[16];
     for (int i = 0; i < 16; ++i) { T11[i] = i % 5 == 0 ? 1.0f : 0.0f; T21[i] = 0.0f; }
     for (int r = 0; r < 3; ++r) {
         for (int c = 0; c < 3; ++c) T21[4 * r + c] = P.Rcam12[3 * c + r];
-        float t = P.Rcam12[r] * P.tcam12[0] + P.Rcam12[3 + r] * P.tcam12[1];
-        t = t + P.Rcam12[6 + r] * P.tcam12[2];
-        T21[4 * r + 3] = (float)((double)t * -1.0 + 0.0 * 0.0);
+        T21[4 * r + 3] = cv_gemm3(P.Rcam12 + r, 3, P.tcam12, -1.0, 0.0f, 0.0);
     }
     T21[15] = 1.0f;
-    pose_from_cv(T11, C.Tc[0]);
-    pose_from_cv(T21, C.Tc[1]);
-    pose_eigen_quat_to_matrix(C.Tc[0].q, C.Rc[0]);
-    pose_eigen_quat_to_matrix(C.Tc[1].q, C.Rc[1]);
+    se3_from_cv(T11, C.Tc[0]);
+    se3_from_cv(T21, C.Tc[1]);
+    eigen_quat_to_matrix(C.Tc[0].q, C.Rc[0]);
+    eigen_quat_to_matrix(C.Tc[1].q, C.Rc[1]);
     // `const float deltaMono = sqrt(5.991)`, rk->setDelta(deltaMono): _delta = the float as a double, dsqr = (float)(delta*delta)
     const float delta_mono = (float)sqrt(5.991), delta_stereo = (float)sqrt(7.815);
     C.delta[0] = (double)delta_mono; C.delta[1] = (double)delta_stereo;
@@ -703,32 +511,25 @@ int validate(const orbm_pose_problem* problems, int B, const int32_t* first, con
     return ORB_OK;
 }
 
-inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 // Stages the problems, the CSR, the work list and the form's own edge arrays (plain: feat, pos, obs, octave; resident, marked by
-// A.packed != NULL: the packed words); launches; leaves records and flags in m->h_pose.  flags_off: where the flags start there.
+// A.packed != NULL: the packed words); launches; leaves records and flags in m->pose.out.  flags_off: where the flags start there.
 int launch(orbm_matcher* m, const orbm_pose_problem* problems, int B, const int32_t* first, const std::vector<int32_t>& list, PoseDev A,
            const void* const* edge_src, const size_t* edge_len, int n_arrays, size_t* flags_off) {
     const int ne = first[B];
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = align16(off + bytes); return o; };
-    const size_t o_prob = take((size_t)B * sizeof(orbm_pose_problem)), o_first = take((size_t)(B + 1) * 4), o_list = take(list.size() * 4);
-    size_t o_edge[4];
-    for (int k = 0; k < n_arrays; ++k) o_edge[k] = take(edge_len[k]);
-    const size_t res_bytes = align16((size_t)B * sizeof(orbm_pose_result));
+    morb::StagePack pk;
+    const int i_prob = pk.add(problems, (size_t)B * sizeof(orbm_pose_problem)), i_first = pk.add(first, (size_t)(B + 1) * 4),
+              i_list = pk.add(list.data(), list.size() * 4);
+    int i_edge[4];
+    for (int k = 0; k < n_arrays; ++k) i_edge[k] = pk.add(edge_src[k], edge_len[k]);
+    const size_t res_bytes = morb::align16((size_t)B * sizeof(orbm_pose_result));
     int rc;
-    if ((rc = m->stage_p.reserve(off)) || (rc = m->h_pose.reserve(res_bytes + (size_t)std::max(ne, 1)))) return rc;
-    uint8_t* hp = m->stage_p.p;
-    memcpy(hp + o_prob, problems, (size_t)B * sizeof(orbm_pose_problem));
-    memcpy(hp + o_first, first, (size_t)(B + 1) * 4);
-    memcpy(hp + o_list, list.data(), list.size() * 4);
-    for (int k = 0; k < n_arrays; ++k) if (edge_len[k]) memcpy(hp + o_edge[k], edge_src[k], edge_len[k]);
-    m->stage_p.publish();
-    const uint8_t* dp = m->stage_p.dp;
-    A.prob = (const orbm_pose_problem*)(dp + o_prob); A.first = (const int32_t*)(dp + o_first); A.list = (const int32_t*)(dp + o_list);
-    A.res = (orbm_pose_result*)m->h_pose.dp; A.flags = m->h_pose.dp + res_bytes;
-    if (A.packed) A.packed = (const uint32_t*)(dp + o_edge[0]);
-    else { A.feat = (const int32_t*)(dp + o_edge[0]); A.pos = (const float*)(dp + o_edge[1]); A.obs = (const float*)(dp + o_edge[2]); A.octave = (const int32_t*)(dp + o_edge[3]); }
+    const morb::StagePack::Block blk = pk.open(m->pose.stage, &rc);
+    if (rc || (rc = m->pose.out.reserve(res_bytes + (size_t)std::max(ne, 1)))) return rc;
+    blk.publish();
+    A.prob = blk.dev<orbm_pose_problem>(i_prob); A.first = blk.dev<int32_t>(i_first); A.list = blk.dev<int32_t>(i_list);
+    A.res = (orbm_pose_result*)m->pose.out.dp; A.flags = m->pose.out.dp + res_bytes;
+    if (A.packed) A.packed = blk.dev<uint32_t>(i_edge[0]);
+    else { A.feat = blk.dev<int32_t>(i_edge[0]); A.pos = blk.dev<float>(i_edge[1]); A.obs = blk.dev<float>(i_edge[2]); A.octave = blk.dev<int32_t>(i_edge[3]); }
     *flags_off = res_bytes;
     hipLaunchKernelGGL(k_pose_optimize, dim3((unsigned)list.size()), dim3(POSE_T), 0, m->stream, A);
     MORB_HIP(hipGetLastError());
@@ -775,10 +576,10 @@ int orbm_pose_optimize(orbm_matcher* m, const orbm_pose_problem* problems, int B
             pose_problem_host(problems[b], G, first[b], first[b + 1] - first[b], ORBM_POSE_ORDER_DEVICE, outlier_out + first[b], results[b]);
     if (!list.empty()) {
         MORB_HIP(hipStreamSynchronize(m->stream));
-        const orbm_pose_result* R = (const orbm_pose_result*)m->h_pose.p;
+        const orbm_pose_result* R = (const orbm_pose_result*)m->pose.out.p;
         for (int b : list) {
             results[b] = R[b];
-            memcpy(outlier_out + first[b], m->h_pose.p + flags_off + first[b], (size_t)(first[b + 1] - first[b]));
+            memcpy(outlier_out + first[b], m->pose.out.p + flags_off + first[b], (size_t)(first[b + 1] - first[b]));
         }
     }
     m->last_pose[0] = (int)list.size(); m->last_pose[1] = B - (int)list.size();
@@ -846,8 +647,8 @@ int orbm_pose_optimize_resident(orbm_matcher* m, const orbm_pose_problem* proble
     size_t flags_off = 0;
     if ((rc = launch(m, problem, 1, first, list, A, src, len, 1, &flags_off))) return rc;
     MORB_HIP(hipStreamSynchronize(m->stream));
-    *result = *(const orbm_pose_result*)m->h_pose.p;
-    for (int e = 0; e < n; ++e) outlier_out[feat[e]] = m->h_pose.p[flags_off + e];
+    *result = *(const orbm_pose_result*)m->pose.out.p;
+    for (int e = 0; e < n; ++e) outlier_out[feat[e]] = m->pose.out.p[flags_off + e];
     m->last_pose[0] = 1; m->last_pose[1] = 0;
     return ORB_OK;
 }

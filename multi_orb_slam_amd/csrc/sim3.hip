@@ -1,8 +1,9 @@
 // sim3.hip -- every RANSAC hypothesis of a loop's Sim3Solvers in one call (include/orbm.h, "Sim3Solver"): Sim3Solver::ComputeCentroid,
 // ComputeSim3 (steps 1-8), Project, FromCameraToImage and CheckInliers (reference src/Sim3Solver.cc:271-522) restated, with the OpenCV
 // operators they call.
-//   sim3_cv_*        the OpenCV operators, restated from OpenCV's published sources (2.4.x / 3.2) and UNPINNED (OpenCV is not in the build:
-//                    DESIGN.md section 2): each is ONE function that a later pin changes.
+//   sim3_cv_*        the OpenCV operators only Sim3Solver calls (cv::eigen, cv::Rodrigues), restated from OpenCV's published sources
+//                    (2.4.x / 3.2) and UNPINNED (OpenCV is not in the build: DESIGN.md section 2): each is ONE function that a later
+//                    pin changes.  The operators other routines call as well (gemm, dot, norm, scaled matrices) are cv_dev.h's.
 //   sim3_atan2       the atan2 of ORBM_SIM3_MATH_DEVICE: + - * / sqrt in double.  Sine and cosine of that order: pose_sincos (sincos_dev.h).
 //   sim3_horn        one hypothesis: three point pairs -> mR12i, mt12i, ms12i, mT12i, mT21i.  ONE statement sequence for the kernel and
 //                    the host routine; the 4x4 Jacobi addresses its matrices with compile-time indices only (nothing goes to scratch).
@@ -26,50 +27,14 @@
 #include "orb_common.h"
 #include "matcher_internal.h"
 #include "sincos_dev.h"
+#include "cv_dev.h"
+#include "stage_pack.h"
 
 namespace {
 
 constexpr int SIM3_T = 64;   // lanes of a workgroup of either kernel = one wave
 
-// ---- the OpenCV boundary: UNPINNED -------------------------------------------------------------------------------
-// cv::reduce(P, C, 1, CV_REDUCE_SUM) of a 3x3 CV_32F into CV_32F: one row, summed in float in column order
-__host__ __device__ inline float sim3_cv_reduce_row(float a, float b, float c) { return (a + b) + c; }
-// a scaled matrix evaluated on its own (host/cv_compat.h ew_scale): cv::add(M, 0) for a weight of 1, cv::subtract(0, M) for -1, else
-// convertTo, whose float kernel computes src * (float)alpha + 0.0f.  `C / P.cols` is this with alpha = 1. / 3, `2*ang*vec/norm(vec)` with
-// alpha = (2 * ang) * (1. / norm), `ms12i * mR12i` with alpha = (double)ms12i.
-__host__ __device__ inline float sim3_cv_scale(float x, double alpha) {
-    const float al = (float)alpha;
-    return alpha == 1 ? x + 0.0f : alpha == -1 ? 0.0f - x : x * al + 0.0f;
-}
-// s * M.t() (MatOp_T: the transpose, then convertTo when the weight is not 1): one element of the transposed matrix
-__host__ __device__ inline float sim3_cv_scale_t(float x, double alpha) { return alpha != 1 ? x * (float)alpha + 0.0f : x; }
-// cv::gemm's small path for an inner length of 3 (host/cv_compat.h gemm_small_elem): products and sums in float from left to right,
-// then d = (float)(t * alpha + c * beta) in double.  R*x + t, R*P, O1 - s*R*O2 and -sRinv*t all arrive here.
-__host__ __device__ inline float sim3_cv_gemm3(float a0, float a1, float a2, float b0, float b1, float b2, double alpha, float c, double beta) {
-    float t = a0 * b0 + a1 * b1;
-    t = t + a2 * b2;
-    return (float)((double)t * alpha + (double)c * beta);
-}
-// cv::gemm's general path for Pr2 * Pr1.t() (GEMM_2_T, inner length 3): the products summed in double from 0.0 in one running sum (the
-// four-way unrolled loop does not run below a length of 4), (s0 + s1 + s2 + s3) * alpha with the idle sums 0, one rounding to float
-__host__ __device__ inline float sim3_cv_gemm3_bt(const float* a, const float* b) {
-    double s0 = 0;
-    for (int k = 0; k < 3; ++k) s0 += (double)a[k] * (double)b[k];
-    return (float)((((s0 + 0.0) + 0.0) + 0.0) * 1.0);
-}
-// cv::norm(NORM_L2) of three floats: squares summed in double, sqrt in double
-__host__ __device__ inline double sim3_cv_norm3(const float* a) {
-    double s = 0;
-    for (int k = 0; k < 3; ++k) s += (double)a[k] * (double)a[k];
-    return sqrt(s);
-}
-// hypot of lapack.cpp (the template JacobiImpl_ calls), in float
-__host__ __device__ inline float sim3_cv_hypot(float a, float b) {
-    a = fabsf(a); b = fabsf(b);
-    if (a > b) { b = b / a; return a * (float)sqrt((double)(1 + b * b)); }
-    if (b > 0) { a = a / b; return b * (float)sqrt((double)(1 + a * a)); }
-    return 0.0f;
-}
+// ---- the OpenCV boundary, Sim3Solver's own part: UNPINNED -----------------------------------------------------------
 __host__ __device__ __forceinline__ void sim3_rot(float& v0, float& v1, float c, float s) {
     const float a0 = v0, b0 = v1;
     v0 = a0 * c - b0 * s;
@@ -80,8 +45,8 @@ template <int K, int L>
 __host__ __device__ __forceinline__ void sim3_jacobi_rotate(float (&A)[4][4], float (&V)[4][4], float (&e)[4]) {
     const float p = A[K][L];
     const float y = (e[L] - e[K]) * 0.5f;
-    float t = fabsf(y) + sim3_cv_hypot(p, y);
-    float s = sim3_cv_hypot(p, t);
+    float t = fabsf(y) + cv_hypot_lapack(p, y);
+    float s = cv_hypot_lapack(p, t);
     const float c = t / s;
     s = p / s; t = (p / t) * p;
     if (y < 0) { s = -s; t = -t; }
@@ -193,14 +158,6 @@ __host__ __device__ inline void sim3_cv_rodrigues(const float* vec, int math, fl
     for (int k = 0; k < 9; ++k) R[k] = (float)((c * (k % 4 == 0 ? 1.0 : 0.0) + c1 * rrt[k]) + s * r_x[k]);
 }
 
-__host__ __device__ inline float sim3_canonical(float x) {   // the NaN x86 makes from an invalid operation, whatever made this one
-    if (x == x) return x;
-    const uint32_t bits = 0xffc00000u;
-    float f;
-    memcpy(&f, &bits, 4);
-    return f;
-}
-
 // ---- one hypothesis: ComputeCentroid + ComputeSim3 (:275-407) ---------------------------------------------------------------------------
 // P1, P2: P3Dc1i, P3Dc2i as [row x y z][column = point of the triple]
 __host__ __device__ inline void sim3_horn(const float (&P1)[3][3], const float (&P2)[3][3], bool fix_scale, int math, orbm_sim3_hyp& o) {
@@ -208,8 +165,8 @@ __host__ __device__ inline void sim3_horn(const float (&P1)[3][3], const float (
     float Pr1[3][3], Pr2[3][3], O1[3], O2[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-        O1[r] = sim3_cv_scale(sim3_cv_reduce_row(P1[r][0], P1[r][1], P1[r][2]), 1. / 3);
-        O2[r] = sim3_cv_scale(sim3_cv_reduce_row(P2[r][0], P2[r][1], P2[r][2]), 1. / 3);
+        O1[r] = cv_scale(cv_reduce_row(P1[r][0], P1[r][1], P1[r][2]), 1. / 3);
+        O2[r] = cv_scale(cv_reduce_row(P2[r][0], P2[r][1], P2[r][2]), 1. / 3);
 #pragma unroll
         for (int i = 0; i < 3; ++i) { Pr1[r][i] = P1[r][i] - O1[r]; Pr2[r][i] = P2[r][i] - O2[r]; }
     }
@@ -218,7 +175,7 @@ __host__ __device__ inline void sim3_horn(const float (&P1)[3][3], const float (
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) M[i][j] = sim3_cv_gemm3_bt(Pr2[i], Pr1[j]);
+        for (int j = 0; j < 3; ++j) M[i][j] = cv_gemm3_bt(Pr2[i], Pr1[j]);
     // Step 3: N -- the sums are float expressions assigned to doubles and stored as floats again
     float N[4][4];
     N[0][0] = (M[0][0] + M[1][1]) + M[2][2];
@@ -236,7 +193,7 @@ __host__ __device__ inline void sim3_horn(const float (&P1)[3][3], const float (
     float q[4];
     sim3_cv_eigen_row0(N, q);
     float vec[3] = {q[1], q[2], q[3]};
-    const double nrm = sim3_cv_norm3(vec);
+    const double nrm = cv_norm3(vec);
     double ang;
 #ifndef __HIP_DEVICE_COMPILE__
     if (math == ORBM_SIM3_MATH_LIBM) ang = atan2(nrm, (double)q[0]); else
@@ -244,7 +201,7 @@ __host__ __device__ inline void sim3_horn(const float (&P1)[3][3], const float (
     ang = sim3_atan2(nrm, (double)q[0]);
     const double w = (2 * ang) * (1. / nrm);             // `2*ang*vec/norm(vec)`: one scaled matrix with the weights multiplied
 #pragma unroll
-    for (int k = 0; k < 3; ++k) vec[k] = sim3_cv_scale(vec[k], w);
+    for (int k = 0; k < 3; ++k) vec[k] = cv_scale(vec[k], w);
     float R[9];
     sim3_cv_rodrigues(vec, math, R);
     // Step 5: P3 = mR12i * Pr2
@@ -252,7 +209,7 @@ __host__ __device__ inline void sim3_horn(const float (&P1)[3][3], const float (
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) P3[i][j] = sim3_cv_gemm3(R[3 * i], R[3 * i + 1], R[3 * i + 2], Pr2[0][j], Pr2[1][j], Pr2[2][j], 1.0, 0.0f, 0.0);
+        for (int j = 0; j < 3; ++j) P3[i][j] = cv_gemm3(R[3 * i], R[3 * i + 1], R[3 * i + 2], Pr2[0][j], Pr2[1][j], Pr2[2][j], 1.0, 0.0f, 0.0);
     // Step 6: scale -- Mat::dot and the den loop accumulate in double in element order, cv::pow(., 2) squares in float
     float ms = 1.0f;
     if (!fix_scale) {
@@ -271,7 +228,7 @@ __host__ __device__ inline void sim3_horn(const float (&P1)[3][3], const float (
     const double s = (double)ms;
     float t[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) t[i] = sim3_cv_gemm3(R[3 * i], R[3 * i + 1], R[3 * i + 2], O2[0], O2[1], O2[2], -s, O1[i], 1.0);
+    for (int i = 0; i < 3; ++i) t[i] = cv_gemm3(R[3 * i], R[3 * i + 1], R[3 * i + 2], O2[0], O2[1], O2[2], -s, O1[i], 1.0);
     // Step 8: mT12i = [ms12i*mR12i | mt12i], mT21i = [sRinv | -sRinv*mt12i] with sRinv = (1.0/ms12i)*mR12i.t()
     const double is = 1.0 / s;
     float sRinv[3][3];
@@ -279,19 +236,19 @@ __host__ __device__ inline void sim3_horn(const float (&P1)[3][3], const float (
     for (int i = 0; i < 3; ++i) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            o.T12[4 * i + j] = sim3_canonical(sim3_cv_scale(R[3 * i + j], s));
-            sRinv[i][j] = sim3_cv_scale_t(R[3 * j + i], is);
-            o.T21[4 * i + j] = sim3_canonical(sRinv[i][j]);
-            o.R12[3 * i + j] = sim3_canonical(R[3 * i + j]);
+            o.T12[4 * i + j] = x86_nan(cv_scale(R[3 * i + j], s));
+            sRinv[i][j] = cv_scale_t(R[3 * j + i], is);
+            o.T21[4 * i + j] = x86_nan(sRinv[i][j]);
+            o.R12[3 * i + j] = x86_nan(R[3 * i + j]);
         }
-        o.T12[4 * i + 3] = sim3_canonical(t[i]);
-        o.t12[i] = sim3_canonical(t[i]);
+        o.T12[4 * i + 3] = x86_nan(t[i]);
+        o.t12[i] = x86_nan(t[i]);
     }
 #pragma unroll
-    for (int i = 0; i < 3; ++i) o.T21[4 * i + 3] = sim3_canonical(sim3_cv_gemm3(sRinv[i][0], sRinv[i][1], sRinv[i][2], t[0], t[1], t[2], -1.0, 0.0f, 0.0));
+    for (int i = 0; i < 3; ++i) o.T21[4 * i + 3] = x86_nan(cv_gemm3(sRinv[i][0], sRinv[i][1], sRinv[i][2], t[0], t[1], t[2], -1.0, 0.0f, 0.0));
     o.T12[12] = 0.0f; o.T12[13] = 0.0f; o.T12[14] = 0.0f; o.T12[15] = 1.0f;
     o.T21[12] = 0.0f; o.T21[13] = 0.0f; o.T21[14] = 0.0f; o.T21[15] = 1.0f;
-    o.s12 = sim3_canonical(ms);
+    o.s12 = x86_nan(ms);
     o.n_inliers = 0;
 }
 
@@ -305,13 +262,13 @@ __host__ __device__ inline void sim3_to_image(float X, float Y, float Z, float f
 // Project (:459-487): Rcw*P + tcw out of the rows of T, the second camera's Rcam21*P + tcam21 for camIdxs[i] == 1, the pinhole
 __host__ __device__ inline void sim3_project(const float* T, const orbm_sim3_problem& P, bool second, float X, float Y, float Z, float fx, float fy,
                                              float cx, float cy, float* u, float* v) {
-    float p0 = sim3_cv_gemm3(T[0], T[1], T[2], X, Y, Z, 1.0, T[3], 1.0);
-    float p1 = sim3_cv_gemm3(T[4], T[5], T[6], X, Y, Z, 1.0, T[7], 1.0);
-    float p2 = sim3_cv_gemm3(T[8], T[9], T[10], X, Y, Z, 1.0, T[11], 1.0);
+    float p0 = cv_gemm3(T[0], T[1], T[2], X, Y, Z, 1.0, T[3], 1.0);
+    float p1 = cv_gemm3(T[4], T[5], T[6], X, Y, Z, 1.0, T[7], 1.0);
+    float p2 = cv_gemm3(T[8], T[9], T[10], X, Y, Z, 1.0, T[11], 1.0);
     if (second) {
-        const float c0 = sim3_cv_gemm3(P.Rcam21[0], P.Rcam21[1], P.Rcam21[2], p0, p1, p2, 1.0, P.tcam21[0], 1.0);
-        const float c1 = sim3_cv_gemm3(P.Rcam21[3], P.Rcam21[4], P.Rcam21[5], p0, p1, p2, 1.0, P.tcam21[1], 1.0);
-        const float c2 = sim3_cv_gemm3(P.Rcam21[6], P.Rcam21[7], P.Rcam21[8], p0, p1, p2, 1.0, P.tcam21[2], 1.0);
+        const float c0 = cv_gemm3(P.Rcam21[0], P.Rcam21[1], P.Rcam21[2], p0, p1, p2, 1.0, P.tcam21[0], 1.0);
+        const float c1 = cv_gemm3(P.Rcam21[3], P.Rcam21[4], P.Rcam21[5], p0, p1, p2, 1.0, P.tcam21[1], 1.0);
+        const float c2 = cv_gemm3(P.Rcam21[6], P.Rcam21[7], P.Rcam21[8], p0, p1, p2, 1.0, P.tcam21[2], 1.0);
         p0 = c0; p1 = c1; p2 = c2;
     }
     sim3_to_image(p0, p1, p2, fx, fy, cx, cy, u, v);
@@ -460,8 +417,6 @@ int validate(const Sim3In& I, int B, const orbm_sim3_hyp* hyp_out, const uint64_
     return ORB_OK;
 }
 
-inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 }  // namespace
 
 extern "C" {
@@ -500,43 +455,37 @@ int orbm_sim3_ransac(orbm_matcher* m, const orbm_sim3_problem* problems, int B, 
     size_t o_rec = 0, o_mask = 0;
     if (hyp_dev > 0) {
         MORB_HIP(hipSetDevice(m->device));
-        size_t off = 0;
-        auto take = [&](size_t bytes) { const size_t o = off; off = align16(off + bytes); return o; };
-        const size_t o_prob = take((size_t)B * sizeof(orbm_sim3_problem)), o_first = take((size_t)(B + 1) * 4), o_its = take((size_t)(B + 1) * 4),
-                     o_mf = take((size_t)(B + 1) * 4), o_hp = take((size_t)HT * 4), o_tri = take((size_t)HT * 12);
-        size_t o_arr[9];
-        for (int k = 0; k < 9; ++k) o_arr[k] = take((size_t)N * 4);
-        o_mask = align16((size_t)HT * sizeof(orbm_sim3_hyp));
+        morb::StagePack pk;
+        const int i_prob = pk.add(problems, (size_t)B * sizeof(orbm_sim3_problem)), i_first = pk.add(first, (size_t)(B + 1) * 4),
+                  i_its = pk.add(its_first, (size_t)(B + 1) * 4), i_mf = pk.add(mask_first.data(), (size_t)(B + 1) * 4),
+                  i_hp = pk.add(hyp_prob.data(), (size_t)HT * 4), i_tri = pk.add(triples, (size_t)HT * 12);
+        int i_soa[8];                                      // x1 y1 z1 x2 y2 z2 e1 e2, transposed below
+        for (int k = 0; k < 8; ++k) i_soa[k] = pk.add_in_place((size_t)N * 4);
+        const int i_cams = pk.add_in_place((size_t)N * 4);
+        o_mask = morb::align16((size_t)HT * sizeof(orbm_sim3_hyp));
         const size_t out_bytes = o_mask + (size_t)mask_first[B] * 8 + 16;
-        if ((rc = m->stage_s.reserve(off)) || (rc = m->d_sim3.reserve((size_t)HT * sizeof(orbm_sim3_hyp))) || (rc = m->h_sim3.reserve(out_bytes))) return rc;
-        uint8_t* hp = m->stage_s.p;
-        memcpy(hp + o_prob, problems, (size_t)B * sizeof(orbm_sim3_problem));
-        memcpy(hp + o_first, first, (size_t)(B + 1) * 4);
-        memcpy(hp + o_its, its_first, (size_t)(B + 1) * 4);
-        memcpy(hp + o_mf, mask_first.data(), (size_t)(B + 1) * 4);
-        memcpy(hp + o_hp, hyp_prob.data(), (size_t)HT * 4);
-        memcpy(hp + o_tri, triples, (size_t)HT * 12);
+        const morb::StagePack::Block blk = pk.open(m->sim3.stage, &rc);
+        if (rc || (rc = m->sim3.scratch.reserve((size_t)HT * sizeof(orbm_sim3_hyp))) || (rc = m->sim3.out.reserve(out_bytes))) return rc;
         float* soa[8];
-        for (int k = 0; k < 8; ++k) soa[k] = (float*)(hp + o_arr[k]);
-        int32_t* cams = (int32_t*)(hp + o_arr[8]);
+        for (int k = 0; k < 8; ++k) soa[k] = blk.host<float>(i_soa[k]);
+        int32_t* cams = blk.host<int32_t>(i_cams);
         for (int k = 0; k < N; ++k) {                      // array of structures -> structure of arrays, once per call
             soa[0][k] = x3dc1[3 * (size_t)k]; soa[1][k] = x3dc1[3 * (size_t)k + 1]; soa[2][k] = x3dc1[3 * (size_t)k + 2];
             soa[3][k] = x3dc2[3 * (size_t)k]; soa[4][k] = x3dc2[3 * (size_t)k + 1]; soa[5][k] = x3dc2[3 * (size_t)k + 2];
             soa[6][k] = max_err1[k]; soa[7][k] = max_err2[k];
             cams[k] = sim3_cams(I, k);
         }
-        m->stage_s.publish();
-        const uint8_t* dp = m->stage_s.dp;
+        blk.publish();
         Sim3Dev A;
-        A.prob = (const orbm_sim3_problem*)(dp + o_prob); A.first = (const int32_t*)(dp + o_first); A.its_first = (const int32_t*)(dp + o_its);
-        A.mask_first = (const int32_t*)(dp + o_mf); A.hyp_prob = (const int32_t*)(dp + o_hp); A.triples = (const int32_t*)(dp + o_tri);
-        A.x1 = (const float*)(dp + o_arr[0]); A.y1 = (const float*)(dp + o_arr[1]); A.z1 = (const float*)(dp + o_arr[2]);
-        A.x2 = (const float*)(dp + o_arr[3]); A.y2 = (const float*)(dp + o_arr[4]); A.z2 = (const float*)(dp + o_arr[5]);
-        A.e1 = (const float*)(dp + o_arr[6]); A.e2 = (const float*)(dp + o_arr[7]); A.cams = (const int32_t*)(dp + o_arr[8]);
+        A.prob = blk.dev<orbm_sim3_problem>(i_prob); A.first = blk.dev<int32_t>(i_first); A.its_first = blk.dev<int32_t>(i_its);
+        A.mask_first = blk.dev<int32_t>(i_mf); A.hyp_prob = blk.dev<int32_t>(i_hp); A.triples = blk.dev<int32_t>(i_tri);
+        A.x1 = blk.dev<float>(i_soa[0]); A.y1 = blk.dev<float>(i_soa[1]); A.z1 = blk.dev<float>(i_soa[2]);
+        A.x2 = blk.dev<float>(i_soa[3]); A.y2 = blk.dev<float>(i_soa[4]); A.z2 = blk.dev<float>(i_soa[5]);
+        A.e1 = blk.dev<float>(i_soa[6]); A.e2 = blk.dev<float>(i_soa[7]); A.cams = blk.dev<int32_t>(i_cams);
         A.n_hyp = HT;
-        A.rec_dev = (orbm_sim3_hyp*)m->d_sim3.p;
-        A.rec_out = (orbm_sim3_hyp*)(m->h_sim3.dp + o_rec);
-        A.mask_out = (uint64_t*)(m->h_sim3.dp + o_mask);
+        A.rec_dev = (orbm_sim3_hyp*)m->sim3.scratch.p;
+        A.rec_out = (orbm_sim3_hyp*)(m->sim3.out.dp + o_rec);
+        A.mask_out = (uint64_t*)(m->sim3.out.dp + o_mask);
         hipLaunchKernelGGL(k_sim3_hyp, dim3((unsigned)((HT + SIM3_T - 1) / SIM3_T)), dim3(SIM3_T), 0, m->stream, A);
         hipLaunchKernelGGL(k_sim3_inliers, dim3((unsigned)HT), dim3(SIM3_T), 0, m->stream, A);
         MORB_HIP(hipGetLastError());
@@ -546,8 +495,8 @@ int orbm_sim3_ransac(orbm_matcher* m, const orbm_sim3_problem* problems, int B, 
         if (first[b + 1] - first[b] > ORBM_SIM3_CAP) sim3_problem_host(I, b, ORBM_SIM3_MATH_DEVICE, hyp_out + its_first[b], mask_out + mask_first[b]);
     if (hyp_dev > 0) {
         MORB_HIP(hipStreamSynchronize(m->stream));
-        const orbm_sim3_hyp* R = (const orbm_sim3_hyp*)(m->h_sim3.p + o_rec);
-        const uint64_t* Wd = (const uint64_t*)(m->h_sim3.p + o_mask);
+        const orbm_sim3_hyp* R = (const orbm_sim3_hyp*)(m->sim3.out.p + o_rec);
+        const uint64_t* Wd = (const uint64_t*)(m->sim3.out.p + o_mask);
         for (int b = 0; b < B; ++b) {
             if (first[b + 1] - first[b] > ORBM_SIM3_CAP) continue;
             const int H = its_first[b + 1] - its_first[b];

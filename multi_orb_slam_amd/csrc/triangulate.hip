@@ -3,7 +3,8 @@
 // (src/KeyFrame.cc:985-1012), from the pair of feature indices to the verdict and the point, up to `new MapPoint`.
 //   tri_*            the arithmetic, ONE statement sequence for the kernel and for the host routine (orbv_triangulate_pairs_host), statement
 //                    by statement in the number formats the reference's statements have under OpenCV 2.4.x / 3.2 (the rules of
-//                    host/cv_compat.h: gemm_small_f32 for 3x3 * 3x1, Mat::dot and cv::norm in double, MatExpr folding).
+//                    host/cv_compat.h: gemm_small_f32 for 3x3 * 3x1, Mat::dot and cv::norm in double, MatExpr folding).  The OpenCV
+//                    operations that other routines call as well are cv_dev.h's; the SVD and the row expression are this file's.
 //   k_triangulate    one lane per pair, no LDS, no exchange between lanes: pairs are independent.  The 4x4, its working copy, Vt and the
 //                    four double row norms of the Jacobi sweeps stay in registers (every index below is a compile-time constant after
 //                    unrolling; the row swaps of the sort are selects).  A few hundred flops per pair on at most a few thousand lanes:
@@ -19,6 +20,8 @@
 #include "../../include/orbv.h"
 #include "orb_common.h"
 #include "bow_internal.h"
+#include "cv_dev.h"
+#include "stage_pack.h"
 
 using morb::MAX_LEVELS;
 
@@ -33,30 +36,7 @@ struct TriKf {   // one keyframe's constants.  The kernel reads the pair of them
 };
 struct TriFeat { float x, y, xd, yd, uright, depth, cos_stereo; int octave, cam, idx; };   // one feature of a pair
 
-// ---- the OpenCV boundary ------------------------------------------------------------------------------------------------------------
-// cv::gemm, the small path (flags == 0, len == 3, a 3x1 destination: cv_compat.h gemm_small_elem): products and sums in float, left
-// to right, then (float)(t*alpha + c*beta) in double.  a: a row of the left matrix with element stride sa.
-__host__ __device__ inline float tri_gemm3(const float* a, int sa, const float* b, double alpha, float c, double beta) {
-    float t = a[0] * b[0] + a[sa] * b[1];
-    t = t + a[2 * sa] * b[2];
-    return (float)((double)t * alpha + (double)c * beta);
-}
-// cv::Mat::dot of a 1x3 row with a 1x3 row: products summed in double, in order
-__host__ __device__ inline double tri_dot3(const float* a, const float* b) {
-    double s = 0;
-    for (int k = 0; k < 3; ++k) s += (double)a[k] * (double)b[k];
-    return s;
-}
-// cv::norm(NORM_L2) of three floats: squares summed in double, sqrt in double
-__host__ __device__ inline double tri_norm3(const float* a) {
-    double s = 0;
-    for (int k = 0; k < 3; ++k) s += (double)a[k] * (double)a[k];
-    return sqrt(s);
-}
-// UNPINNED against OpenCV.  JacobiSVDImpl_ calls hypot(p, beta) of the C library; no libm function runs in the
-// kernel, so kernel, host routine and model all take this sequence in its place.  A later pin changes this one definition.
-__host__ __device__ inline double tri_hypot(double a, double b) { return sqrt(a * a + b * b); }
-
+// ---- the OpenCV boundary: what only CreateNewMapPoints calls (the rest: cv_dev.h) ------------------------------------------------------
 // cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) of a 4x4 CV_32F, as far as vt goes.  UNPINNED against OpenCV: restated from
 // JacobiSVDImpl_<float> (modules/core/src/lapack.cpp, 2.4.x / 3.2) as called by _SVDcompute for m == n == 4:
 //   * the working copy is the TRANSPOSE of A (row i of At = column i of A; Vt starts as the identity);
@@ -64,7 +44,7 @@ __host__ __device__ inline double tri_hypot(double a, double b) { return sqrt(a 
 //   * a pair is skipped when |p| <= eps*sqrt(a*b) with eps = FLT_EPSILON*2 (a float, promoted); minval = FLT_MIN enters only the
 //     completion below and is therefore not used here;
 //   * at most max(m, 30) = 30 sweeps over the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), ended by a sweep that rotates nothing;
-//   * c and s are computed in double from p*2, beta = a - b and gamma = hypot(p, beta) (tri_hypot here) and ROUNDED TO FLOAT, the
+//   * c and s are computed in double from p*2, beta = a - b and gamma = hypot(p, beta) (cv_hypot_libm here) and ROUNDED TO FLOAT, the
 //     second of them from the rounded first; the rotation of the rows of At and of Vt is in float, t0 = c*x + s*y, t1 = -s*x + c*y
 //     (the SSE form of the Vt rotation, y*c - x*s, has the same bits); the new W[i], W[j] are double sums of the rotated elements;
 //   * the singular values are sqrt of freshly summed row norms; the sort is a selection sort, descending, strict `W[j] < W[k]`, that
@@ -101,7 +81,7 @@ __host__ __device__ inline void tri_svd_null(const float A[4][4], float* null4) 
                 for (int k = 0; k < 4; ++k) p += (double)At[i][k] * At[j][k];
                 if (fabs(p) <= eps * sqrt(a * b)) continue;
                 p *= 2;
-                const double beta = a - b, gamma = tri_hypot(p, beta);
+                const double beta = a - b, gamma = cv_hypot_libm(p, beta);
                 float c, s;
                 if (beta < 0) {
                     const double delta = (gamma - beta) * 0.5;
@@ -166,12 +146,6 @@ __host__ __device__ inline void tri_row(float s, const float* T, int q, float* r
 #pragma unroll
     for (int k = 0; k < 4; ++k) row[k] = alpha == 1 ? T[8 + k] - T[4 * q + k] : T[8 + k] * al + T[4 * q + k] * be + 0.0f;
 }
-// x3D.rowRange(0,3)/w: a scaled matrix with weight 1./w (double), evaluated by cv_compat.h ew_scale: cv::add(M, 0) for a weight of
-// exactly 1, cv::subtract(0, M) for -1, otherwise convertTo with scale (float)(1./w): `x*scale + 0.0f`.  UNPINNED against OpenCV.
-__host__ __device__ inline float tri_over_w(float x, double alpha) {
-    return alpha == 1 ? x + 0.0f : alpha == -1 ? 0.0f - x : x * (float)alpha + 0.0f;
-}
-
 // KeyFrame::UnprojectStereo(i) (src/KeyFrame.cc:985-1012) for z > 0 (validated by the callers): the DISTORTED keypoint, the camera by
 // i >= N of the feature's own keyframe, camera 2 through mRcam12*x3Dc + mtcam12; every product-plus-vector is one small-path gemm with
 // beta = 1.
@@ -183,27 +157,18 @@ __host__ __device__ inline void tri_unproject(const TriKf& K, const TriFeat& f, 
     float c[3] = {x, y, z};
     if (!(f.idx < K.n_cam1)) {
         float t[3];
-        for (int r = 0; r < 3; ++r) t[r] = tri_gemm3(K.Rcam12 + 3 * r, 1, c, 1.0, K.tcam12[r], 1.0);
+        for (int r = 0; r < 3; ++r) t[r] = cv_gemm3(K.Rcam12 + 3 * r, 1, c, 1.0, K.tcam12[r], 1.0);
         for (int r = 0; r < 3; ++r) c[r] = t[r];
     }
-    for (int r = 0; r < 3; ++r) x3D[r] = tri_gemm3(K.Twc + 4 * r, 1, c, 1.0, K.Twc[4 * r + 3], 1.0);
-}
-
-// A NaN leaves as the NaN x86 makes from an invalid operation (sign bit set); the GCN ALUs make 0x7fc00000 from the same operation.
-__host__ __device__ inline float tri_canonical(float x) {
-    if (x == x) return x;
-    const uint32_t bits = 0xffc00000u;
-    float f;
-    memcpy(&f, &bits, 4);
-    return f;
+    for (int r = 0; r < 3; ++r) x3D[r] = cv_gemm3(K.Twc + 4 * r, 1, c, 1.0, K.Twc[4 * r + 3], 1.0);
 }
 
 // the reprojection test of one keyframe (:549-591 / :596-634): T = the pair camera's [R|t] of that keyframe, K its intrinsics, mbf the
 // CURRENT keyframe's in both tests (:583, :626).  true = rejected.
 __host__ __device__ inline bool tri_reproject_fails(const float* T, const TriKf& K, float mbf, const TriFeat& f, const float* x3D, float z) {
     const float sigmaSquare = K.sigma2[f.octave];
-    const float x = (float)(tri_dot3(T, x3D) + T[3]);
-    const float y = (float)(tri_dot3(T + 4, x3D) + T[7]);
+    const float x = (float)(cv_dot3(T, x3D) + T[3]);
+    const float y = (float)(cv_dot3(T + 4, x3D) + T[7]);
     const float invz = (float)(1.0 / z);
     if (!(f.uright >= 0)) {
         const float u = K.fx * x * invz + K.cx;
@@ -233,10 +198,10 @@ __host__ __device__ inline void tri_pair(const TriKf& K1, const TriKf& K2, const
     // ray = Rwc*xn with Rwc = Rcw.t() evaluated: the CAMERA-1 rotations, also for a camera-2 pair (:428-429)
     float ray1[3], ray2[3];
     for (int r = 0; r < 3; ++r) {
-        ray1[r] = tri_gemm3(&K1.Tcw[0][r], 4, xn1, 1.0, 0.0f, 0.0);
-        ray2[r] = tri_gemm3(&K2.Tcw[0][r], 4, xn2, 1.0, 0.0f, 0.0);
+        ray1[r] = cv_gemm3(&K1.Tcw[0][r], 4, xn1, 1.0, 0.0f, 0.0);
+        ray2[r] = cv_gemm3(&K2.Tcw[0][r], 4, xn2, 1.0, 0.0f, 0.0);
     }
-    const float cosParallaxRays = (float)(tri_dot3(ray1, ray2) / (tri_norm3(ray1) * tri_norm3(ray2)));
+    const float cosParallaxRays = (float)(cv_dot3(ray1, ray2) / (cv_norm3(ray1) * cv_norm3(ray2)));
     float cosParallaxStereo = cosParallaxRays + 1;
     float cosParallaxStereo1 = cosParallaxStereo;
     float cosParallaxStereo2 = cosParallaxStereo;
@@ -256,11 +221,11 @@ __host__ __device__ inline void tri_pair(const TriKf& K1, const TriKf& K2, const
         tri_svd_null(A, nv);
         o.path = ORBV_TRI_PATH_SVD;
         if (nv[3] == 0) {
-            for (int k = 0; k < 3; ++k) o.x3D[k] = tri_canonical(nv[k]);
+            for (int k = 0; k < 3; ++k) o.x3D[k] = x86_nan(nv[k]);
             o.outcome = ORBV_TRI_W_ZERO; return;
         }
         const double alpha = 1. / (double)nv[3];
-        for (int k = 0; k < 3; ++k) x3D[k] = tri_over_w(nv[k], alpha);
+        for (int k = 0; k < 3; ++k) x3D[k] = cv_scale(nv[k], alpha);
     } else if (bStereo1 && cosParallaxStereo1 < cosParallaxStereo2) {
         tri_unproject(K1, f1, x3D);
         o.path = ORBV_TRI_PATH_UNPROJECT1;
@@ -270,19 +235,19 @@ __host__ __device__ inline void tri_pair(const TriKf& K1, const TriKf& K2, const
     } else {
         o.outcome = ORBV_TRI_LOW_PARALLAX; return;
     }
-    for (int k = 0; k < 3; ++k) o.x3D[k] = tri_canonical(x3D[k]);
+    for (int k = 0; k < 3; ++k) o.x3D[k] = x86_nan(x3D[k]);
 
-    const float z1 = (float)(tri_dot3(T1 + 8, x3D) + T1[11]);
+    const float z1 = (float)(cv_dot3(T1 + 8, x3D) + T1[11]);
     if (z1 <= 0) { o.outcome = ORBV_TRI_Z1; return; }
-    const float z2 = (float)(tri_dot3(T2 + 8, x3D) + T2[11]);
+    const float z2 = (float)(cv_dot3(T2 + 8, x3D) + T2[11]);
     if (z2 <= 0) { o.outcome = ORBV_TRI_Z2; return; }
     if (tri_reproject_fails(T1, K1, K1.mbf, f1, x3D, z1)) { o.outcome = ORBV_TRI_REPROJ1; return; }
     if (tri_reproject_fails(T2, K2, K1.mbf, f2, x3D, z2)) { o.outcome = ORBV_TRI_REPROJ2; return; }
 
     float normal1[3], normal2[3];
     for (int k = 0; k < 3; ++k) { normal1[k] = x3D[k] - K1.centre[camIdx1][k]; normal2[k] = x3D[k] - K2.centre[camIdx1][k]; }
-    const float dist1 = (float)tri_norm3(normal1);
-    const float dist2 = (float)tri_norm3(normal2);
+    const float dist1 = (float)cv_norm3(normal1);
+    const float dist2 = (float)cv_norm3(normal2);
     if (dist1 == 0 || dist2 == 0) { o.outcome = ORBV_TRI_ZERO_DIST; return; }
     const float ratioDist = dist2 / dist1;
     const float ratioOctave = K1.scale[f1.octave] / K2.scale[f2.octave];
@@ -387,7 +352,6 @@ int stage_constants(orbv_workspace* w, const orbv_tri_keyframe* kf1, const orbv_
     return ORB_OK;
 }
 inline unsigned cam_bits_of(const uint8_t* cam_enabled) { return (cam_enabled[0] ? 1u : 0u) | (cam_enabled[1] ? 2u : 0u); }
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
 
@@ -421,32 +385,31 @@ int orbv_triangulate_pairs(orbv_workspace* w, const orbv_tri_keyframe* kf1, cons
     if (rc) return rc;
     if (n_pairs == 0) return ORB_OK;
     MORB_HIP(hipSetDevice(w->device));
-    // one packed block through the pinned stage: nine arrays per keyframe, then the pairs
+    // one packed block through the pinned stage: nine arrays per keyframe (a keyframe without features keeps its slots), then the pairs
     const orbv_tri_keyframe* kf[2] = {kf1, kf2};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = up16(off + bytes); return o; };
-    size_t o_arr[2][9];
-    for (int s = 0; s < 2; ++s) for (int a = 0; a < 9; ++a) o_arr[s][a] = take((size_t)std::max(kf[s]->n, 1) * 4);
-    const size_t o_pairs = take((size_t)n_pairs * 8);
-    if ((rc = w->h_stage.reserve(off)) || (rc = w->d_stage.reserve(off)) || (rc = w->h_tri.reserve((size_t)n_pairs * sizeof(orbv_tri_out)))) return rc;
-    uint8_t* hp = w->h_stage.p; const uint8_t* dp = w->d_stage.p;
+    morb::StagePack pk;
+    int id[2][9];
+    for (int s = 0; s < 2; ++s) {
+        const orbv_tri_keyframe* k = kf[s]; const size_t slot = (size_t)std::max(k->n, 1) * 4;
+        const void* src[8] = {k->x, k->y, k->xd, k->yd, k->uright, k->depth, k->cos_stereo, k->octave};
+        for (int a = 0; a < 8; ++a) id[s][a] = k->n > 0 ? pk.add(src[a], slot) : pk.add_in_place(slot);
+        id[s][8] = pk.add_in_place(slot);   // the camera of every feature, written below
+    }
+    const int i_pairs = pk.add(pairs, (size_t)n_pairs * 8);
+    const morb::StagePack::Block blk = pk.open(w->h_stage, w->d_stage, &rc);
+    if (rc || (rc = w->h_tri.reserve((size_t)n_pairs * sizeof(orbv_tri_out)))) return rc;
     TriArrays F[2];
     for (int s = 0; s < 2; ++s) {
-        const orbv_tri_keyframe* k = kf[s];
-        const void* src[8] = {k->x, k->y, k->xd, k->yd, k->uright, k->depth, k->cos_stereo, k->octave};
-        for (int a = 0; a < 8; ++a) if (k->n > 0) memcpy(hp + o_arr[s][a], src[a], (size_t)k->n * 4);
-        int32_t* cam = (int32_t*)(hp + o_arr[s][8]);
-        for (int i = 0; i < k->n; ++i) cam[i] = cam_of(k, i);
-        F[s].n = k->n;
-        F[s].x = (const float*)(dp + o_arr[s][0]); F[s].y = (const float*)(dp + o_arr[s][1]); F[s].xd = (const float*)(dp + o_arr[s][2]);
-        F[s].yd = (const float*)(dp + o_arr[s][3]); F[s].uright = (const float*)(dp + o_arr[s][4]); F[s].depth = (const float*)(dp + o_arr[s][5]);
-        F[s].cos_stereo = (const float*)(dp + o_arr[s][6]); F[s].octave = (const int32_t*)(dp + o_arr[s][7]); F[s].cam_of = (const int32_t*)(dp + o_arr[s][8]);
+        const int* a = id[s];
+        for (int i = 0; i < kf[s]->n; ++i) blk.host<int32_t>(a[8])[i] = cam_of(kf[s], i);
+        F[s].n = kf[s]->n; F[s].x = blk.dev<float>(a[0]); F[s].y = blk.dev<float>(a[1]); F[s].xd = blk.dev<float>(a[2]); F[s].yd = blk.dev<float>(a[3]);
+        F[s].uright = blk.dev<float>(a[4]); F[s].depth = blk.dev<float>(a[5]); F[s].cos_stereo = blk.dev<float>(a[6]);
+        F[s].octave = blk.dev<int32_t>(a[7]); F[s].cam_of = blk.dev<int32_t>(a[8]);
     }
-    memcpy(hp + o_pairs, pairs, (size_t)n_pairs * 8);
     const TriKf* d_K = nullptr;
     if ((rc = stage_constants(w, kf1, kf2, &d_K))) return rc;
-    MORB_HIP(hipMemcpyAsync(w->d_stage.p, hp, off, hipMemcpyHostToDevice, w->stream));
-    hipLaunchKernelGGL(k_triangulate, dim3((n_pairs + 63) / 64), dim3(64), 0, w->stream, d_K, F[0], F[1], (const int32_t*)(dp + o_pairs),
+    MORB_HIP(hipMemcpyAsync(w->d_stage.p, w->h_stage.p, pk.bytes(), hipMemcpyHostToDevice, w->stream));
+    hipLaunchKernelGGL(k_triangulate, dim3((n_pairs + 63) / 64), dim3(64), 0, w->stream, d_K, F[0], F[1], blk.dev<int32_t>(i_pairs),
                        (const int32_t*)nullptr, n_pairs, cam_bits_of(cam_enabled), ratio_factor, (orbv_tri_out*)w->h_tri.dp);
     MORB_HIP(hipGetLastError());
     MORB_HIP(hipStreamSynchronize(w->stream));
@@ -463,7 +426,7 @@ int orbv_keyframe_set_geometry(orbv_workspace* w, orbv_keyframe* k, const float*
     for (int i = 0; i < n; ++i)
         if (uright[i] >= 0 && !(depth[i] > 0)) { morb::set_error("feature %d is stereo (uright >= 0) with depth %g", i, (double)depth[i]); return ORB_E_ARG; }
     MORB_HIP(hipSetDevice(w->device));
-    const size_t stride = up16((size_t)std::max(n, 1) * 4);
+    const size_t stride = morb::align16((size_t)std::max(n, 1) * 4);
     int rc = k->geometry.reserve(5 * stride);
     if (rc) return rc;
     std::vector<uint8_t> host(5 * stride, 0);

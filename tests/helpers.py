@@ -1,10 +1,13 @@
-"""Shared builders for matcher test inputs (used by CPU oracle tests and GPU parity tests)."""
+"""Shared builders for matcher test inputs (used by CPU oracle tests and GPU parity tests) and the two helpers of the header-compile
+tests.  The package is imported inside the builders that need it: the header-compile tests need a compiler and nothing else."""
+import os
+import subprocess
+
 import numpy as np
-from multi_orb_slam_amd import synth
-from multi_orb_slam_amd._lib import QUERY_DTYPE
 
 
 def rand_u32(n, seed):
+    from multi_orb_slam_amd import synth
     return synth.hash32(np.arange(n, dtype=np.uint64) + np.uint64((seed * 0x9E3779B1) & 0xFFFFFFFF))
 
 
@@ -14,6 +17,7 @@ def rand_unit(n, seed):
 
 def make_frame_arrays(n_per_cam, width, height, seed=1, nlevels=8, frac_coords=True, with_right=True):
     """Random 'current frame': keypoints spread over the image (some outside the bounds, some on cell edges)."""
+    from multi_orb_slam_amd import synth
     xs, ys, octs, angs, urs, cams, locs, descs = [], [], [], [], [], [], [], []
     for c, n in enumerate(n_per_cam):
         x = rand_unit(n, seed + 11 * c) * (width + 20) - 10
@@ -35,6 +39,8 @@ def make_frame_arrays(n_per_cam, width, height, seed=1, nlevels=8, frac_coords=T
 
 def make_queries(fr, nq, seed=5, th=15.0, scale_factor=1.2, nlevels=8, dup_prob=0.5, blocks=1):
     """Projected 'last frame' points: half are perturbed copies of frame features (so real matches exist)."""
+    from multi_orb_slam_amd import synth
+    from multi_orb_slam_amd._lib import QUERY_DTYPE
     n = len(fr["un_x"])
     q = np.zeros(nq, QUERY_DTYPE)
     pick = (rand_u32(nq, seed) % max(n, 1)).astype(np.int64)
@@ -95,7 +101,8 @@ def make_two_window_queries(fr, nq, seed=5, th=10.0, scale_factor=1.2, nlevels=8
     """Loop points of the two-camera loop search: every point looks at a feature of camera `c0` and (most of them) also at a
     feature of the other camera -- either of the two windows may be missing -- with a descriptor close to one of the two
     targets, so that the winner comes from either camera and contested features exist.  -> (queries, second windows)."""
-    from multi_orb_slam_amd._lib import WINDOW_DTYPE
+    from multi_orb_slam_amd import synth
+    from multi_orb_slam_amd._lib import QUERY_DTYPE, WINDOW_DTYPE
     n = len(fr["un_x"]); cam_of = np.asarray(fr["cam_of"])
     idx_by_cam = [np.flatnonzero(cam_of == c) for c in (0, 1)]
     q = np.zeros(nq, QUERY_DTYPE); w2 = np.zeros(nq, WINDOW_DTYPE)
@@ -118,3 +125,46 @@ def make_two_window_queries(fr, nq, seed=5, th=10.0, scale_factor=1.2, nlevels=8
     q["desc"] = synth.perturbed_queries(all_desc[tgt], seed + 4, 0.04)
     q["desc"][::3] = all_desc[tgt][::3]
     return q, w2
+
+
+# ---- the header-compile tests (test_*_headers.py): a drop-in source against the reference's own headers, used in place --------------
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOST = os.path.join(ROOT, "multi_orb_slam_amd", "host")
+REF = "/root/reference"
+BASE_REPLACED = ("ORBextractor.h", "ORBmatcher.h", "ORBVocabulary.h")
+BASE_ADDED = ("cv_compat.h", "slam_types.h")
+
+
+def reference_tree(tmp_path, replaced=BASE_REPLACED, added=BASE_ADDED, mappoint_patch=None):
+    """The include directory of an integration: symbolic links to the reference's headers where they lie, ours (host/) for those in
+    `replaced`, ours in `added` beside them.  mappoint_patch = (anchor, text): MapPoint.h is written into the directory with `text`
+    behind the one occurrence of `anchor` (nothing of the reference is kept in the repository).  -> the directory."""
+    inc = tmp_path / "include"
+    inc.mkdir()
+    for name in os.listdir(os.path.join(REF, "include")):
+        os.symlink(os.path.join(REF, "include", name), inc / name)
+    for name in replaced:
+        os.unlink(inc / name)
+        os.symlink(os.path.join(HOST, name), inc / name)
+    for name in added:
+        os.symlink(os.path.join(HOST, name), inc / name)
+    if mappoint_patch:
+        anchor, extra = mappoint_patch
+        text = open(os.path.join(REF, "include", "MapPoint.h")).read()
+        assert text.count(anchor) == 1
+        os.unlink(inc / "MapPoint.h")
+        (inc / "MapPoint.h").write_text(text.replace(anchor, anchor + extra))
+    return str(inc)
+
+
+def syntax_only(src, includes):
+    """g++ -fsyntax-only -DMORB_USE_REFERENCE_TYPES over `src` (a path, or a file name in host/); includes: a list of directories, or
+    the directory of reference_tree, which stands for [it, the OpenCV shim, the reference's root, include/].  -> (rc, error lines)."""
+    if isinstance(includes, str):
+        includes = [includes, os.path.join(HOST, "cv_shim"), REF, os.path.join(ROOT, "include")]
+    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-ffp-contract=off", "-DMORB_USE_REFERENCE_TYPES"]
+    for inc in includes:
+        cmd += ["-I", inc]
+    cmd.append(src if os.path.isabs(src) else os.path.join(HOST, src))
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    return p.returncode, [ln for ln in p.stderr.splitlines() if "error" in ln]

@@ -182,3 +182,31 @@ def test_cpp_class_fills_the_map_points_with_the_models_bytes(tmp_path, n_points
     assert (what & 2) == 0 or (~keep_nd).sum() > 0.8 * b.n_points
     for k in exp.dtype.names:
         assert got[k].tobytes() == exp[k].tobytes(), k
+
+
+def test_the_staged_block_grows_and_is_reused_on_a_fresh_matcher():
+    """A handle of its own, so that the staged block is reallocated inside the test: one point with one observation and the descriptor
+    job alone, its per-point arrays of the normal / depth job ABSENT (NULL); then 300 points over the three size classes; then the
+    first again.  Every call byte for byte the host routine, the two small calls each other."""
+    import multi_orb_slam_amd as m
+    b, _ = mw.make_world(300, 21)
+    counts = b.first[1:] - b.first[:-1]
+    one = b.subset([int(np.flatnonzero(counts >= 1)[0])])
+    small = mw.Batch([0, 1], one.obs_desc[:1], one.obs_centre[:1], [1], one.pos, one.ref_centre, one.ref_level, [1], one.scale_factors).native()
+    small.c.pos = None; small.c.ref_centre = None; small.c.ref_level = None
+    large = b.native()
+    paths = expected_paths(b)
+    assert min(paths[:3]) >= 1                                           # <= 16, <= 64 and > 64 observations are all there
+    mt = m.Matcher(0.8, True)
+    try:
+        want_small = m.refresh_points_host(small)
+        first = mt.RefreshPoints(small)
+        assert mt.last_refresh() == (1, 0, 0, 0, 0)
+        assert first.tobytes() == want_small.tobytes() and first["best_obs"][0] == 0
+        got = mt.RefreshPoints(large)
+        assert mt.last_refresh() == paths
+        assert got.tobytes() == m.refresh_points_host(large).tobytes() == mm.refresh(b)[0].tobytes()
+        again = mt.RefreshPoints(small)
+        assert again.tobytes() == want_small.tobytes() == first.tobytes()
+    finally:
+        mt.close()

@@ -133,3 +133,20 @@ def test_resident_form_equals_the_plain_form(matcher, mode):
         rrec, rflags = matcher.PoseOptimizationResident(prob, F, pts, np.full(N, -1, np.int32))
         assert rrec["n_inliers"] == 0 and rrec["rounds"] == 0 and rrec["Tcw"].tobytes() == Tcw.tobytes() and not rflags.any()
     F.close()
+
+
+def test_the_staged_block_grows_and_is_reused_on_a_fresh_matcher():
+    """A handle of its own, so that the staged block is reallocated inside the test: 1 problem of 2 edges, then 8 problems of 400
+    edges, then the first again.  Every call byte for byte the host routine in device order, the two small calls each other."""
+    import multi_orb_slam_amd as m
+    mt = m.Matcher(0.8, True)
+    try:
+        small, large = [sized(2)], [sized(400, seed=50 + 3 * i) for i in range(8)]
+        first = device_and_host(mt, small)
+        assert mt.last_pose() == (1, 0)
+        device_and_host(mt, large)
+        assert mt.last_pose() == (8, 0)
+        again = device_and_host(mt, small)
+        same(first[0], again[0], "the small call before and after the large one")
+    finally:
+        mt.close()

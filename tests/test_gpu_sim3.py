@@ -103,3 +103,21 @@ def test_a_call_after_an_unrelated_search_on_the_same_matcher(matcher):
         assert nmatches > 100
         device_and_host(matcher, ["n1000_free_1.0_wrong30", "n40_free_0.7_wrong30"])
     F.close()
+
+
+def test_the_staged_block_grows_and_is_reused_on_a_fresh_matcher():
+    """A handle of its own, so that the staged block is reallocated inside the test: (n, h) = (3, 1), then (1000, 300) next to a
+    problem without a hypothesis, then (3, 1) again.  Every call byte for byte the host routine in device order, the two small calls
+    each other."""
+    import multi_orb_slam_amd as m
+    mt = m.Matcher(0.8, True)
+    try:
+        small, large = [sized(3, 1)], [sized(1000, 300), sized(200, 0)]
+        first = device_and_host(mt, small)
+        assert mt.last_sim3() == (1, 0)
+        got = device_and_host(mt, large)
+        assert mt.last_sim3() == (2, 0) and [len(r) for r, _ in got] == [300, 0]
+        again = device_and_host(mt, small)
+        same(first[0], again[0], "the small call before and after the large one")
+    finally:
+        mt.close()

@@ -165,3 +165,22 @@ def test_set_geometry_refuses_a_stereo_feature_without_depth(search):
         KA.set_geometry(kf1.uright, depth, kf1.cos_stereo, kf1.xd, kf1.yd)
     assert "feature %d" % i in str(e.value)
     KA.close()
+
+
+def test_the_staged_block_grows_and_is_reused_on_a_fresh_workspace():
+    """A workspace of its own, so that the staged block is reallocated inside the test: the one pair of a hand-built world (keyframes of
+    one feature), then 2000 pairs of a generated world (keyframes of thousands), then the one pair again.  Every call byte for byte the
+    host routine, the two small calls each other."""
+    small = tw.exact_world(False, False, 0.25)
+    large, _ = tw.world_and_model("25cm")
+    pairs = large.pairs[:2000]
+    S = m.BowSearch()
+    try:
+        first = small.device(S)
+        assert len(first) == 1 and first.tobytes() == small.host().tobytes()
+        got = large.device(S, pairs)
+        assert len(got) == 2000 and got.tobytes() == large.host(pairs).tobytes()
+        again = small.device(S)
+        assert again.tobytes() == small.host().tobytes() == first.tobytes()
+    finally:
+        S.close()

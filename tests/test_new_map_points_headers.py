@@ -4,33 +4,16 @@ the reference's.  Everything the drop-in reads of a KeyFrame is public there (th
 mtcam12, the keypoint vectors, the index map, the level tables): no member is added.  The tree is made of symbolic links into the
 reference checkout (nothing of the reference is kept here).  Skipped where the reference checkout is absent."""
 import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "multi_orb_slam_amd", "host")
+from helpers import BASE_ADDED, reference_tree, syntax_only
+
 REF = "/root/reference"
 needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "include")), reason="reference checkout not present")
 
 
-def _tree(tmp_path):
-    inc = tmp_path / "include"
-    inc.mkdir()
-    for name in os.listdir(os.path.join(REF, "include")):
-        os.symlink(os.path.join(REF, "include", name), inc / name)
-    for name in ("ORBextractor.h", "ORBmatcher.h", "ORBVocabulary.h"):
-        os.unlink(inc / name)
-        os.symlink(os.path.join(HOST, name), inc / name)
-    for name in ("cv_compat.h", "slam_types.h", "NewMapPoints.h"):
-        os.symlink(os.path.join(HOST, name), inc / name)
-    return str(inc)
-
-
 @needs_ref
 def test_new_map_points_compiles_against_the_reference_headers(tmp_path):
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-ffp-contract=off", "-DMORB_USE_REFERENCE_TYPES", "-I", _tree(tmp_path), "-I", os.path.join(HOST, "cv_shim"),
-           "-I", REF, "-I", os.path.join(ROOT, "include"), os.path.join(HOST, "NewMapPoints.cc")]
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    errors = [ln for ln in p.stderr.splitlines() if "error" in ln]
-    assert p.returncode == 0 and not errors, "\n".join(errors[:20])
+    rc, errors = syntax_only("NewMapPoints.cc", reference_tree(tmp_path, added=BASE_ADDED + ("NewMapPoints.h",)))
+    assert rc == 0 and not errors, "\n".join(errors[:20])

@@ -13,9 +13,10 @@ lacks, is stood in for by host/cv_compat.h through the include shim host/cv_shim
 The compile checks are skipped where the reference checkout is absent (the GPU box); the container types of the stand-ins are
 checked everywhere."""
 import os
-import subprocess
 
 import pytest
+
+from helpers import reference_tree, syntax_only
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "multi_orb_slam_amd", "host")
@@ -26,43 +27,20 @@ HAVE_REF = os.path.isdir(os.path.join(REF, "include"))
 needs_ref = pytest.mark.skipif(not HAVE_REF, reason="reference checkout not present")
 
 
-def _syntax_only(src, includes):
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-ffp-contract=off", "-DMORB_USE_REFERENCE_TYPES"]
-    for inc in includes:
-        cmd += ["-I", inc]
-    cmd.append(src)
-    p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    errors = [ln for ln in p.stderr.splitlines() if "error" in ln]
-    return p.returncode, errors
-
-
 @needs_ref
 @pytest.mark.parametrize("src", OURS)
 def test_host_sources_compile_against_the_reference_headers_in_place(src):
-    rc, errors = _syntax_only(os.path.join(HOST, src),
+    rc, errors = syntax_only(os.path.join(HOST, src),
                               [HOST, os.path.join(HOST, "cv_shim"), os.path.join(REF, "include"), REF, os.path.join(ROOT, "include")])
     assert rc == 0 and not errors, "\n".join(errors[:20])
-
-
-def _replaced_tree(tmp_path):
-    inc = tmp_path / "include"
-    inc.mkdir()
-    for name in os.listdir(os.path.join(REF, "include")):
-        os.symlink(os.path.join(REF, "include", name), inc / name)
-    for name in ("ORBextractor.h", "ORBmatcher.h", "ORBVocabulary.h"):       # ours take the place of the reference's
-        os.unlink(inc / name)
-        os.symlink(os.path.join(HOST, name), inc / name)
-    for name in ("cv_compat.h", "slam_types.h"):
-        os.symlink(os.path.join(HOST, name), inc / name)
-    return str(inc)
 
 
 @needs_ref
 @pytest.mark.parametrize("src", OURS + ["ref:src/KeyFrameDatabase.cc", "ref:src/MapPoint.cc", "ref:src/Map.cc"])
 def test_replaced_headers_serve_our_sources_and_the_reference_consumers(tmp_path, src):
-    inc = _replaced_tree(tmp_path)
+    inc = reference_tree(tmp_path)       # ours take the place of the reference's three
     path = os.path.join(REF, src[4:]) if src.startswith("ref:") else os.path.join(HOST, src)
-    rc, errors = _syntax_only(path, [inc, os.path.join(HOST, "cv_shim"), REF, os.path.join(ROOT, "include")])
+    rc, errors = syntax_only(path, [inc, os.path.join(HOST, "cv_shim"), REF, os.path.join(ROOT, "include")])
     assert rc == 0 and not errors, "\n".join(errors[:20])
 
 
