@@ -35,6 +35,21 @@ int orbx_debug_pyramid_plan(int tile_w, int tile_h, int split);
 /* ---- matcher ------------------------------------------------------------------------------------------------------------- */
 /* {status, nmatches, sweeps, longest candidate list} of the last device-side resolve (inspection only) */
 int orbm_debug_last_resolve(const orbm_matcher* m, int* out4);
+/* {which resolve produced the result of the last search, capacity retries it took} (inspection only; host-side bookkeeping of
+ * search_enqueue, no kernel knows it).  A test written for one form asserts this, so that a moved threshold fails it instead of
+ * quietly running another kernel.  The form is the one that delivered the result: the host routine after a device resolve that did
+ * not converge, the form of the last launch after a capacity retry. */
+#define ORBM_FORM_NONE 0           /* nothing to resolve (no queries or no features) */
+#define ORBM_FORM_HOST 1           /* host_resolve: MORB_HOST_RESOLVE=1, more queries than the device takes, or the fallback */
+#define ORBM_FORM_MONO2_ANG 2      /* k_resolve_mono<2, true>: up to 2048 queries, rotation angles in LDS */
+#define ORBM_FORM_MONO2 3          /* k_resolve_mono<2, false>: the angles stay in HBM */
+#define ORBM_FORM_MONO4_WORKLIST 4 /* k_resolve_mono<4, .>, worklist rounds (more than 2048 queries) */
+#define ORBM_FORM_MONO4_WAVES 5    /* k_resolve_mono<4, .>, per-wave passes (MORB_RESOLVE_MONO=1) */
+#define ORBM_FORM_JACOBI_LDSQ 6    /* k_resolve<., true>: Jacobi sweeps, per-query state in LDS */
+#define ORBM_FORM_JACOBI 7         /* k_resolve<., false>: per-query state in HBM */
+#define ORBM_FORM_CAMS 8           /* k_resolve_cams: one workgroup per camera */
+#define ORBM_FORM_SWEEPS 9         /* k_rs_sweep + k_rs_owner [+ k_rs_reject] + k_rs_write: one launch per sweep, tables in HBM */
+int orbm_debug_last_resolve_form(const orbm_matcher* m, int* out2);
 /* Where the points of the last orbm_refresh_points went: {16-lane groups, one wavefront, one workgroup, host routine because the
  * point has more than ORBM_REFRESH_CAP observations, no work (no observations or no job)} (inspection only) */
 int orbm_debug_last_refresh(const orbm_matcher* m, int* out5);

@@ -238,6 +238,7 @@ def lib():
     L.orbf_extractor.argtypes = [vp]; L.orbf_extractor.restype = vp
     L.orbf_matcher.argtypes = [vp]; L.orbf_matcher.restype = vp
     L.orbm_debug_last_resolve.argtypes = [vp, vp]
+    L.orbm_debug_last_resolve_form.argtypes = [vp, vp]
     L.orbm_queries_from_motion.argtypes = [vp, vp, vp, vp, i32, f32, f32, f32, vp, f32, vp, vp, vp]
     L.orbm_count_ratio_accepted.argtypes = [vp, vp, i32, i32, f32]
     L.orbm_set_calibration.argtypes = [vp, vp]

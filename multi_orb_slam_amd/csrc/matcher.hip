@@ -137,6 +137,12 @@ int orbm_debug_last_resolve(const orbm_matcher* m, int* out4) {
     return ORB_OK;
 }
 
+int orbm_debug_last_resolve_form(const orbm_matcher* m, int* out2) {
+    MORB_ARG(m && out2);
+    out2[0] = m->last_form[0]; out2[1] = m->last_form[1];
+    return ORB_OK;
+}
+
 int orbm_debug_last_pose(const orbm_matcher* m, int* out2) {
     MORB_ARG(m != nullptr && out2 != nullptr);
     out2[0] = m->last_pose[0]; out2[1] = m->last_pose[1];

@@ -106,6 +106,7 @@ struct orbm_matcher {
     orb_calibration calib = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // orbm_set_calibration: undistortion applied by device-built frames (k1 == 0: off)
     int frame_min_rows = 0;  // the next device-built frame gets at least this many descriptor rows (fixed export block size)
     int last_status[4] = {0, 0, 0, 0};  // {status, nmatches, sweeps, longest list} of the last device resolve
+    int last_form[2] = {0, 0};          // {ORBM_FORM_* that produced the last search's result, capacity retries it took} (search_finish)
     std::vector<int> rs_cam_count;     // scratch of search_enqueue: queries per camera (per-camera resolve)
     int rs_sweeps_hint = 24;           // sweeps the multi-workgroup resolve enqueues next time (what the last one needed + 4)
     bool host_resolve = false;     // MORB_HOST_RESOLVE=1: always use the host resolve (testing / fallback path)
@@ -184,6 +185,7 @@ struct SearchJob {
     int q_cam_max = 0;                  // upper bound of the queries any one camera has (0 = not known; counted from `q` when that is final)
     const int* q_cam_start = nullptr;   // host, n_cams + 1 entries: the queries are camera-contiguous, camera c's are [q_cam_start[c], q_cam_start[c + 1])
     void (*q_fill)(void*) = nullptr; void* q_fill_ctx = nullptr;   // ... which call this first when `q` has not been written yet
+    int form = 0;                       // ORBM_FORM_* of the resolve search_enqueue launched (include/orb_debug.h)
 };
 
 // Work of an isolated orbf_step that rides in the projection kernel's launch instead of on a stream of its own (a fork onto a

@@ -1661,7 +1661,9 @@ static int host_resolve(orbm_matcher* m, const orbm_frame* cur, const orbm_query
 int morb::search_enqueue(orbm_matcher* m, SearchJob& J, bool queries_already_on_device) {
     const int n = J.cur->n_total;
     J.device_path = false; J.pollable = false; J.multi = false;
+    J.form = ORBM_FORM_NONE;
     if (J.nq == 0 || n == 0) return ORB_OK;
+    J.form = ORBM_FORM_HOST;   // (until a launch below says otherwise: host bookkeeping for orbm_debug_last_resolve_form, no kernel reads it)
     // two claim tables (one int per feature each) + the candidate counts (u16 per query, padded); tables that do not fit LDS go
     // to an HBM workspace (GCL variant of the kernel)
     const size_t lds = (size_t)2 * n * sizeof(int) + (size_t)((J.nq + 1) / 2) * sizeof(int);
@@ -1752,7 +1754,7 @@ int morb::search_enqueue(orbm_matcher* m, SearchJob& J, bool queries_already_on_
         // fallback and the next one gets the full 24 again.
         if (cams_fit) {   // one launch, one workgroup per camera (k_resolve_cams): meeting, rejection and the tagged result words inside
             if ((rc = launch_cams(MergeJob{nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr}, 0))) return rc;
-            J.device_path = true;
+            J.device_path = true; J.form = ORBM_FORM_CAMS;
             J.pollable = J.seq != 0;
             return ORB_OK;
         }
@@ -1782,7 +1784,7 @@ int morb::search_enqueue(orbm_matcher* m, SearchJob& J, bool queries_already_on_
         hipLaunchKernelGGL(k_rs_write, dim3(nb_f), dim3(256), 0, m->stream, n, cur->dev().n_total_dev, cap, (const int*)m->d_match.p,
                            (const int*)state, m->h_match.dp + 4, m->h_match.dp);
         MORB_HIP(hipGetLastError());
-        J.device_path = true;
+        J.device_path = true; J.form = ORBM_FORM_SWEEPS;
         return ORB_OK;
     }
     // claim table + (when it fits) the per-query sweep state
@@ -1818,6 +1820,7 @@ int morb::search_enqueue(orbm_matcher* m, SearchJob& J, bool queries_already_on_
         }
         if ((rc = launch_cams(MJ, merge_blocks))) return rc;
         MJ.S = 0;   // (carried)
+        J.form = ORBM_FORM_CAMS;
     } else if (will_mono) {
         const bool ang = mono_lds(true) <= 150 * 1024;
         const size_t ml = mono_lds(ang);
@@ -1836,9 +1839,10 @@ int morb::search_enqueue(orbm_matcher* m, SearchJob& J, bool queries_already_on_
         if (nq <= 2048) { if (ang) MORB_MONO_LAUNCH(2, true); else MORB_MONO_LAUNCH(2, false); }
         else { if (ang) MORB_MONO_LAUNCH(4, true); else MORB_MONO_LAUNCH(4, false); }
         MJ.S = 0;   // (carried)
+        J.form = nq <= 2048 ? (ang ? ORBM_FORM_MONO2_ANG : ORBM_FORM_MONO2) : (mono_worklist ? ORBM_FORM_MONO4_WORKLIST : ORBM_FORM_MONO4_WAVES);
 #undef MORB_MONO_LAUNCH
-    } else if (ldsq) { if (J.points) MORB_RESOLVE_LAUNCH(true, true); else MORB_RESOLVE_LAUNCH(false, true); }
-    else { if (J.points) MORB_RESOLVE_LAUNCH(true, false); else MORB_RESOLVE_LAUNCH(false, false); }
+    } else if (ldsq) { if (J.points) MORB_RESOLVE_LAUNCH(true, true); else MORB_RESOLVE_LAUNCH(false, true); J.form = ORBM_FORM_JACOBI_LDSQ; }
+    else { if (J.points) MORB_RESOLVE_LAUNCH(true, false); else MORB_RESOLVE_LAUNCH(false, false); J.form = ORBM_FORM_JACOBI; }
 #undef MORB_RESOLVE_LAUNCH
     MORB_HIP(hipGetLastError());  // status + matches are written by the kernel into the mapped pinned buffer
     J.device_path = true;
@@ -1850,6 +1854,7 @@ int morb::search_enqueue(orbm_matcher* m, SearchJob& J, bool queries_already_on_
 int morb::search_finish(orbm_matcher* m, SearchJob& J, int32_t* match_of_feature, int* nmatches) {
     const int n = J.cur->n_total;
     *nmatches = 0;
+    m->last_form[0] = J.device_path ? J.form : (J.nq == 0 || n == 0 ? ORBM_FORM_NONE : ORBM_FORM_HOST); m->last_form[1] = 0;
     if (J.nq == 0 || n == 0) { for (int g = 0; g < n; g++) match_of_feature[g] = -1; return ORB_OK; }
     if (!J.device_path) {
         m->last_status[0] = -1; m->last_status[1] = 0; m->last_status[2] = 0; m->last_status[3] = 0;  // (host path)
@@ -1888,12 +1893,14 @@ int morb::search_finish(orbm_matcher* m, SearchJob& J, int32_t* match_of_feature
             J.cap = (m->last_status[3] + 63) & ~63;
             int rc = search_enqueue(m, J, /*queries_already_on_device=*/true);
             if (rc) return rc;
+            m->last_form[0] = J.form; m->last_form[1]++;   // (the retry may take another form: `cap` enters no form's limit today)
             MORB_HIP(hipStreamSynchronize(m->stream));
             synced = true;
             continue;
         }
         // not converged within the sweep limit: exact host fallback
         need_q();
+        m->last_form[0] = ORBM_FORM_HOST;
         return host_resolve(m, J.cur, J.q, J.nq, J.occupied, J.points, J.nnratio, J.th_high, J.check_ori, J.cap, match_of_feature, nmatches, J.win2_dev);
     }
     if (J.seq) {

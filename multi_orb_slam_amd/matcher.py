@@ -7,6 +7,9 @@ from ._lib import POSE_PROBLEM_DTYPE, POSE_RESULT_DTYPE, POSE_CAM0, POSE_ALL_CAM
 from ._lib import SIM3_PROBLEM_DTYPE, SIM3_HYP_DTYPE, SIM3_WALK_DTYPE, SIM3_MATH_LIBM, SIM3_MATH_DEVICE  # noqa: F401
 
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30  # reference src/ORBmatcher.cc:37-39
+# which resolve delivered a search's result (ORBM_FORM_*, include/orb_debug.h; Matcher.last_resolve_form)
+(FORM_NONE, FORM_HOST, FORM_MONO2_ANG, FORM_MONO2, FORM_MONO4_WORKLIST, FORM_MONO4_WAVES, FORM_JACOBI_LDSQ, FORM_JACOBI, FORM_CAMS,
+ FORM_SWEEPS) = range(10)
 
 
 def descriptor_distance(a, b):
@@ -450,6 +453,12 @@ class Matcher:
         """(status, matches, sweeps, longest candidate list) of the last device resolve (orbm_debug_last_resolve)."""
         out = (C.c_int * 4)()
         check(_lib.lib().orbm_debug_last_resolve(self._h, out))
+        return tuple(out)
+
+    def last_resolve_form(self):
+        """(form, capacity retries) of the last search: which resolve delivered its result, one of FORM_* (orbm_debug_last_resolve_form)."""
+        out = (C.c_int * 2)()
+        check(_lib.lib().orbm_debug_last_resolve_form(self._h, out))
         return tuple(out)
 
     def cross_top2_gathered(self, gathered_ptr, world, block_bytes, cap_rows, cams_per_rank, rank):

@@ -51,3 +51,13 @@ def test_product_never_imports_the_oracle():
             if f.endswith((".py", ".h", ".hip", ".cpp", ".cc")) or f == "Makefile":
                 txt = open(os.path.join(dirpath, f), errors="replace").read()
                 assert "oracle/" not in txt and "import oracle" not in txt and "liborb_oracle" not in txt, f
+
+
+def test_resolve_form_codes_of_the_binding_are_those_of_the_header():
+    """matcher.FORM_* (what Matcher.last_resolve_form() is read with) against ORBM_FORM_* of include/orb_debug.h: every code, by name."""
+    from multi_orb_slam_amd import matcher
+    src = open(os.path.join(ROOT, "include", "orb_debug.h")).read()
+    header = {name: int(val) for name, val in re.findall(r"#define ORBM_FORM_([A-Z0-9_]+)\s+(\d+)", src)}
+    binding = {k[len("FORM_"):]: v for k, v in vars(matcher).items() if k.startswith("FORM_")}
+    assert len(header) == 10 and len(set(header.values())) == 10
+    assert binding == header
