@@ -1,5 +1,6 @@
 """Host-side mirror of the hot part of ORB_SLAM2::ORBmatcher over the C ABI (include/orbm.h)."""
 import ctypes as C
+import weakref
 import numpy as np
 from . import _lib
 from ._lib import KP_DTYPE, QUERY_DTYPE, POINT_DTYPE, TRACK_DTYPE, REFRESH_DTYPE, CamFeatures, FrameDesc, check, ptr
@@ -326,6 +327,11 @@ class Frame:
             self.data = data
             self._h = C.c_void_p()
             check(_lib.lib().orbm_frame_create(matcher._h, C.byref(data.c), C.byref(self._h)))
+        # orbm_frame_destroy hands the buffers back to the matcher's pool: the frame must go before its matcher does, also when the
+        # last reference to it dies late (a failed test's traceback keeps it alive beyond the fixture that closes the matcher)
+        children = getattr(matcher, "_frames", None)
+        if children is not None:
+            children.add(self)
 
     def download(self, kps=True, desc=True, uright=True, depth=True):
         """Host copies of the merged arrays of a device-built frame (global, cam-major order)."""
@@ -361,10 +367,16 @@ class Matcher:
     def __init__(self, nnratio=0.6, check_orientation=True, device=0):
         self.nnratio = float(nnratio); self.check_orientation = bool(check_orientation)
         self._h = C.c_void_p()
+        self._frames = weakref.WeakSet()
         check(_lib.lib().orbm_create(device, C.byref(self._h)))
 
     def close(self):
         if getattr(self, "_h", None):
+            try:
+                for f in list(getattr(self, "_frames", ())):      # frames first: their destroy reads the matcher
+                    f.close()
+            except Exception:  # interpreter teardown
+                pass
             try:
                 _lib.lib().orbm_destroy(self._h)
             except Exception:  # interpreter teardown

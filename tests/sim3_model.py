@@ -235,13 +235,18 @@ def horn(P1, P2, fix_scale, order):
 
 
 # ---- the inlier phase, all hypotheses of a problem at once ------------------------------------------------------------------------------
-def to_image(X, Y, Z, fx, fy, cx, cy):
+RULES = ("inlier_le", "float_sum", "fma_to_image")      # the deliberately WRONG rules of evaluate(..., rules=)
+
+
+def to_image(X, Y, Z, fx, fy, cx, cy, rules=()):
     invz = F(1) / Z
     x, y = X * invz, Y * invz
+    if "fma_to_image" in rules:      # fx*x + cx rounded once: the product of two floats is exact in double, the sum rounds to double and
+        return (np.asarray(fx, D) * x + D(cx)).astype(F), (np.asarray(fy, D) * y + D(cy)).astype(F)       # then to float
     return fx * x + cx, fy * y + cy
 
 
-def project(T, W, second, X, Y, Z, fx, fy, cx, cy):
+def project(T, W, second, X, Y, Z, fx, fy, cx, cy, rules=()):
     """T: (H, 16) float32 as columns of shape (H, 1); X, Y, Z: (1, N)."""
     col = lambda k: T[:, k:k + 1]
     p0 = cv_gemm3(col(0), col(1), col(2), X, Y, Z, 1.0, col(3), 1.0)
@@ -252,26 +257,32 @@ def project(T, W, second, X, Y, Z, fx, fy, cx, cy):
     c1 = cv_gemm3(R[3], R[4], R[5], p0, p1, p2, 1.0, t[1], 1.0)
     c2 = cv_gemm3(R[6], R[7], R[8], p0, p1, p2, 1.0, t[2], 1.0)
     p0, p1, p2 = np.where(second, c0, p0), np.where(second, c1, p1), np.where(second, c2, p2)
-    return to_image(p0, p1, p2, fx, fy, cx, cy)
+    return to_image(p0, p1, p2, fx, fy, cx, cy, rules)
 
 
-def check_inliers(W, T12, T21):
+def check_inliers(W, T12, T21, rules=()):
     """-> (inlier (H, N) bool, err1, err2 (H, N) float32)."""
     with np.errstate(all="ignore"):
         X1 = np.asarray(W["x3dc1"], F).reshape(-1, 3); X2 = np.asarray(W["x3dc2"], F).reshape(-1, 3)
         row = lambda a: np.ascontiguousarray(a, F).reshape(1, -1)
         x1, y1, z1, x2, y2, z2 = row(X1[:, 0]), row(X1[:, 1]), row(X1[:, 2]), row(X2[:, 0]), row(X2[:, 1]), row(X2[:, 2])
         fx1, fy1, cx1, cy1 = (F(v) for v in W["K1"]); fx2, fy2, cx2, cy2 = (F(v) for v in W["K2"])
-        u1, v1 = to_image(x1, y1, z1, fx1, fy1, cx1, cy1)
-        u2, v2 = to_image(x2, y2, z2, fx2, fy2, cx2, cy2)
+        u1, v1 = to_image(x1, y1, z1, fx1, fy1, cx1, cy1, rules)
+        u2, v2 = to_image(x2, y2, z2, fx2, fy2, cx2, cy2, rules)
         s1 = (np.asarray(W["cam1"]) == 1).reshape(1, -1); s2 = (np.asarray(W["cam2"]) == 1).reshape(1, -1)
-        pu, pv = project(T12, W, s2, x2, y2, z2, fx1, fy1, cx1, cy1)
+        pu, pv = project(T12, W, s2, x2, y2, z2, fx1, fy1, cx1, cy1, rules)
         d10, d11 = u1 - pu, v1 - pv
-        pu, pv = project(T21, W, s1, x1, y1, z1, fx2, fy2, cx2, cy2)
+        pu, pv = project(T21, W, s1, x1, y1, z1, fx2, fy2, cx2, cy2, rules)
         d20, d21 = pu - u2, pv - v2
-        err1 = (d10.astype(D) * d10.astype(D) + d11.astype(D) * d11.astype(D)).astype(F)
-        err2 = (d20.astype(D) * d20.astype(D) + d21.astype(D) * d21.astype(D)).astype(F)
-        inl = (err1 < row(W["max_err1"])) & (err2 < row(W["max_err2"]))
+        if "float_sum" in rules:
+            err1, err2 = d10 * d10 + d11 * d11, d20 * d20 + d21 * d21
+        else:
+            err1 = (d10.astype(D) * d10.astype(D) + d11.astype(D) * d11.astype(D)).astype(F)
+            err2 = (d20.astype(D) * d20.astype(D) + d21.astype(D) * d21.astype(D)).astype(F)
+        if "inlier_le" in rules:
+            inl = (err1 <= row(W["max_err1"])) & (err2 <= row(W["max_err2"]))
+        else:
+            inl = (err1 < row(W["max_err1"])) & (err2 < row(W["max_err2"]))
     return inl, err1, err2
 
 
@@ -290,9 +301,12 @@ def pack_masks(inl):
     return np.packbits(bits.reshape(H, Wd, 8, 8), axis=-1, bitorder="little").reshape(H, Wd, 8).copy().view("<u8").reshape(H, Wd)
 
 
-def evaluate(W, order):
+def evaluate(W, order, rules=()):
     """A world (dict: K1, K2, Rcam21, tcam21, fix_scale, x3dc1, x3dc2, cam1, cam2, max_err1, max_err2, triples) -> (records HYP_DTYPE H,
-    mask words (H, W) uint64, err1, err2 (H, N) float32)."""
+    mask words (H, W) uint64, err1, err2 (H, N) float32).  rules: names of deliberately WRONG rules of the inlier phase (RULES: "<=" for
+    "<", the sum of squares in float, a fused multiply-add in FromCameraToImage / Project's last step), which the boundary worlds must
+    catch (tests/test_geometry_boundary_worlds.py)."""
+    assert all(r in RULES for r in rules), rules
     X1 = np.asarray(W["x3dc1"], F).reshape(-1, 3); X2 = np.asarray(W["x3dc2"], F).reshape(-1, 3)
     tri = np.asarray(W["triples"], np.int64).reshape(-1, 3)
     H = len(tri)
@@ -303,7 +317,7 @@ def evaluate(W, order):
     for k in ("R12", "t12", "s12", "T12", "T21"):
         rec[k] = canonical(rec[k])
     Wm = dict(W, Rcam21=np.asarray(W["Rcam21"], F).reshape(9), tcam21=np.asarray(W["tcam21"], F).reshape(3))
-    inl, e1, e2 = check_inliers(Wm, rec["T12"], rec["T21"])
+    inl, e1, e2 = check_inliers(Wm, rec["T12"], rec["T21"], rules)
     if H:
         rec["n_inliers"] = inl.sum(axis=1)
     return rec, pack_masks(inl), e1, e2

@@ -71,7 +71,7 @@ def sized(n, seed=50, two_cams=True):
 
 def test_edge_counts_around_the_wave_and_the_capacity(matcher):
     import multi_orb_slam_amd as m
-    counts = [0, 1, 63, 64, 65, m.POSE_CAP, m.POSE_CAP + 1]
+    counts = [0, 1, 9, 10, 11, 63, 64, 65, m.POSE_CAP, m.POSE_CAP + 1]        # (9, 10, 11: `n < 10` ends the call after one round)
     probs = [sized(n) for n in counts]
     got = device_and_host(matcher, probs)
     assert matcher.last_pose() == (len(counts) - 1, 1)             # one problem beyond the device capacity: the host routine took it
@@ -81,6 +81,20 @@ def test_edge_counts_around_the_wave_and_the_capacity(matcher):
         assert matcher.last_pose() == (1, 0)
     device_and_host(matcher, [probs[-1]])
     assert matcher.last_pose() == (0, 1)
+
+
+@pytest.mark.parametrize("kind", ["mono", "stereo", "mixed"])
+def test_nine_ten_and_eleven_edges(matcher, kind):
+    """The counts either side of `if (S.n < 10 || S.round == 3)`: 9 edges end after the first round, 10 and 11 run all four."""
+    import multi_orb_slam_amd as m
+    counts = [9, 10, 11]
+    probs = [pw.to_problem(m, pw.generate(seed=70 + n, n=n, kind=kind, outliers=0.1, start=(0.02, 1.0))) for n in counts]
+    got = device_and_host(matcher, probs)
+    assert matcher.last_pose() == (3, 0)
+    assert [(int(r["n_initial"]), int(r["rounds"])) for r, _ in got] == [(9, 1), (10, 4), (11, 4)]
+    for p in probs:
+        device_and_host(matcher, [p])
+        assert matcher.last_pose() == (1, 0)
 
 
 def test_the_call_made_twice_gives_identical_bytes(matcher):

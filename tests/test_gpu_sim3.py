@@ -105,6 +105,20 @@ def test_a_call_after_an_unrelated_search_on_the_same_matcher(matcher):
     F.close()
 
 
+def test_a_matcher_closes_its_frames_before_itself():
+    """orbm_frame_destroy hands the frame's buffers back to its matcher: a frame that is still open when the matcher closes (the
+    test above failing before its F.close(), the frame kept alive by the traceback) must be closed by the matcher, not after it."""
+    import multi_orb_slam_amd as m
+    import frustum_worlds as fw
+    w = fw.make_world(2000, [1000, 500], 640, 480, 2, 3.0)
+    mt = m.Matcher(0.8, True)
+    F = mt.frame(m.FrameData(**w["fr"]))
+    assert F._h
+    mt.close()
+    assert F._h is None and mt._h is None
+    F.close()
+
+
 def test_the_staged_block_grows_and_is_reused_on_a_fresh_matcher():
     """A handle of its own, so that the staged block is reallocated inside the test: (n, h) = (3, 1), then (1000, 300) next to a
     problem without a hypothesis, then (3, 1) again.  Every call byte for byte the host routine in device order, the two small calls

@@ -168,7 +168,9 @@ def system_matrix(kf1, kf2, idx1, idx2):
     return xn1, xn2, A
 
 
-def reprojection_rejects(kf, idx, R, t, x3D, z, mbf_current):
+def reprojection_rejects(kf, idx, R, t, x3D, z, mbf_current, rules=(), trace=None, which=1):
+    exceeds = (lambda a, b: a >= b) if "reproj_ge" in rules else (lambda a, b: a > b)
+    stereo_gate = f64(7.815) if "stereo_7.815" in rules else f64(7.8)
     sigma_square = f32(kf.level_sigma2[int(kf.octave[idx])])
     x = f32(row_dot(R[0], x3D) + f64(t[0]))
     y = f32(row_dot(R[1], x3D) + f64(t[1]))
@@ -178,16 +180,29 @@ def reprojection_rejects(kf, idx, R, t, x3D, z, mbf_current):
         u = kf.fx * x * invz + kf.cx
         v = kf.fy * y * invz + kf.cy
         ex, ey = u - kx, v - ky
-        return bool(f64(ex * ex + ey * ey) > f64(5.991) * f64(sigma_square))
+        if trace is not None:
+            trace["err%d" % which], trace["gate%d" % which] = f64(ex * ex + ey * ey), f64(5.991) * f64(sigma_square)
+        return bool(exceeds(f64(ex * ex + ey * ey), f64(5.991) * f64(sigma_square)))
     u = kf.fx * x * invz + kf.cx
     u_r = u - mbf_current * invz
     v = kf.fy * y * invz + kf.cy
     ex, ey, er = u - kx, v - ky, u_r - ur
-    return bool(f64(ex * ex + ey * ey + er * er) > f64(7.8) * f64(sigma_square))
+    if trace is not None:
+        trace["err%d" % which], trace["gate%d" % which] = f64(ex * ex + ey * ey + er * er), f64(7.8) * f64(sigma_square)
+    return bool(exceeds(f64(ex * ex + ey * ey + er * er), stereo_gate * f64(sigma_square)))
 
 
-def one_pair(kf1, kf2, cam_enabled, idx1, idx2, ratio_factor):
-    """-> (x3D or None, outcome, path)"""
+RULES = ("reproj_ge", "stereo_7.815", "float_0.9998", "depth_lt", "scale_le")
+
+
+def one_pair(kf1, kf2, cam_enabled, idx1, idx2, ratio_factor, rules=(), trace=None):
+    """-> (x3D or None, outcome, path).  `rules`: names of deliberately WRONG rules (RULES; tests/test_geometry_boundary_worlds.py shows
+    that the boundary worlds catch each of them): ">=" for ">" in the reprojection gates, 7.815 for the stage's 7.8, the float
+    constant 0.9998f for the double one, "<" for "<=" on the depth signs, "<=" for "<" in the first scale gate.  `trace`: a dict that
+    receives the intermediates the boundary worlds are built from.  With neither, the function is what it was."""
+    assert all(r in RULES for r in rules), rules
+    tr = trace if trace is not None else {}
+    behind = (lambda z: z < 0) if "depth_lt" in rules else (lambda z: z <= 0)
     stereo1, stereo2 = bool(kf1.uright[idx1] >= 0), bool(kf2.uright[idx2] >= 0)
     cam = int(kf1.cam_of[idx1])
     if not cam_enabled[cam]:
@@ -206,8 +221,10 @@ def one_pair(kf1, kf2, cam_enabled, idx1, idx2, ratio_factor):
     elif stereo2:
         cos_stereo2 = f32(kf2.cos_stereo[idx2])
     cos_stereo = cos_stereo2 if cos_stereo2 < cos_stereo1 else cos_stereo1
+    tr.update(cam=cam, stereo1=stereo1, stereo2=stereo2, cos_rays=cos_rays, cos_stereo1=cos_stereo1, cos_stereo2=cos_stereo2)
+    limit = f64(f32(0.9998)) if "float_0.9998" in rules else f64(0.9998)
 
-    if cos_rays < cos_stereo and cos_rays > 0 and (stereo1 or stereo2 or f64(cos_rays) < f64(0.9998)):
+    if cos_rays < cos_stereo and cos_rays > 0 and (stereo1 or stereo2 or f64(cos_rays) < limit):
         vt3 = jacobi_vt(A)[3]
         path = PATH_SVD
         if vt3[3] == 0:
@@ -222,14 +239,16 @@ def one_pair(kf1, kf2, cam_enabled, idx1, idx2, ratio_factor):
 
     R1, t1 = rows_of(kf1.Tcw[cam]); R2, t2 = rows_of(kf2.Tcw[cam])
     z1 = f32(row_dot(R1[2], x3D) + f64(t1[2]))
-    if z1 <= 0:
+    tr.update(x3D=list(x3D), z1=z1)
+    if behind(z1):
         return x3D, Z1, path
     z2 = f32(row_dot(R2[2], x3D) + f64(t2[2]))
-    if z2 <= 0:
+    tr.update(z2=z2)
+    if behind(z2):
         return x3D, Z2, path
-    if reprojection_rejects(kf1, idx1, R1, t1, x3D, z1, kf1.mbf):
+    if reprojection_rejects(kf1, idx1, R1, t1, x3D, z1, kf1.mbf, rules, tr, 1):
         return x3D, REPROJ1, path
-    if reprojection_rejects(kf2, idx2, R2, t2, x3D, z2, kf1.mbf):
+    if reprojection_rejects(kf2, idx2, R2, t2, x3D, z2, kf1.mbf, rules, tr, 2):
         return x3D, REPROJ2, path
     normal1 = [x3D[k] - f32(kf1.centre[cam][k]) for k in range(3)]
     normal2 = [x3D[k] - f32(kf2.centre[cam][k]) for k in range(3)]
@@ -239,18 +258,24 @@ def one_pair(kf1, kf2, cam_enabled, idx1, idx2, ratio_factor):
     ratio_dist = dist2 / dist1
     ratio_octave = f32(kf1.scale_factors[int(kf1.octave[idx1])]) / f32(kf2.scale_factors[int(kf2.octave[idx2])])
     rf = f32(ratio_factor)
-    if ratio_dist * rf < ratio_octave or ratio_dist > ratio_octave * rf:
+    tr.update(dist1=dist1, dist2=dist2, ratio_dist=ratio_dist, ratio_octave=ratio_octave, low=ratio_dist * rf, high=ratio_octave * rf)
+    too_near = ratio_dist * rf <= ratio_octave if "scale_le" in rules else ratio_dist * rf < ratio_octave
+    if too_near or ratio_dist > ratio_octave * rf:
         return x3D, SCALE, path
     return x3D, ACCEPTED, path
 
 
-def triangulate(kf1, kf2, cam_enabled, pairs, ratio_factor):
-    """Records (RECORD) of the pairs; kf1 / kf2: triangulate_worlds.KF."""
+def triangulate(kf1, kf2, cam_enabled, pairs, ratio_factor, rules=(), traces=None):
+    """Records (RECORD) of the pairs; kf1 / kf2: triangulate_worlds.KF.  rules: see one_pair; traces: a list that receives one dict of
+    intermediates per pair."""
     pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
     rec = np.zeros(len(pairs), RECORD)
     with np.errstate(all="ignore"):
         for p, (i1, i2) in enumerate(pairs):
-            x3D, outcome, path = one_pair(kf1, kf2, cam_enabled, int(i1), int(i2), ratio_factor)
+            tr = {} if traces is not None else None
+            x3D, outcome, path = one_pair(kf1, kf2, cam_enabled, int(i1), int(i2), ratio_factor, rules, tr)
+            if traces is not None:
+                traces.append(tr)
             rec["outcome"][p], rec["path"][p] = outcome, path
             if x3D is not None:
                 rec["x3D"][p] = np.array(x3D, np.float32)

@@ -84,8 +84,8 @@ class World:
         self.cam_enabled = np.array(cam_enabled, np.uint8)
         self.ratio_factor = f32(1.5) * kf1.scale_factors[1]          # 1.5f * mfScaleFactor
 
-    def model(self, pairs=None):
-        return tm.triangulate(self.kf1, self.kf2, self.cam_enabled, self.pairs if pairs is None else pairs, self.ratio_factor)
+    def model(self, pairs=None, rules=(), traces=None):
+        return tm.triangulate(self.kf1, self.kf2, self.cam_enabled, self.pairs if pairs is None else pairs, self.ratio_factor, rules, traces)
 
     def host(self, pairs=None):
         import multi_orb_slam_amd as m
