@@ -59,6 +59,9 @@ int orbm_debug_last_pose(const orbm_matcher* m, int* out2);
 /* Where the problems of the last orbm_sim3_ransac went: {the device, host routine because the problem has more than ORBM_SIM3_CAP
  * correspondences} (inspection only) */
 int orbm_debug_last_sim3(const orbm_matcher* m, int* out2);
+/* Where the problems of the last orbm_sim3_optimize went: {one workgroup on the device, host routine because the problem has more than
+ * ORBM_SIM3OPT_CAP correspondences} (inspection only) */
+int orbm_debug_last_sim3opt(const orbm_matcher* m, int* out2);
 /* Inspection / bench (roofline M3): `iters` launches of the projection kernel alone, as the frame search
  * launches it (window + level + right-coordinate gates, distances, shortlist), timed with HIP events on the handle's
  * stream.  *avg_us = average launch duration, *n_gated = candidates that passed the gates, summed over the queries. */

@@ -498,6 +498,61 @@ int orbm_sim3_iterations(double probability, int min_inliers, int max_its, int N
 /* (test hook) The atan2 sequence of ORBM_SIM3_MATH_DEVICE on the host: y >= 0, x in [-1, 1]. */
 double orbm_sim3_atan2(double y, double x);
 
+/* -- Sim3 refinement: Optimizer::OptimizeSim3_cam1 ----------------------------------------------------------------------
+ * Optimizer::OptimizeSim3_cam1 (reference src/Optimizer.cc:1984-2243) from its correspondence list on: one 7-dof Sim3 vertex, per
+ * correspondence an EdgeSim3ProjectXYZ (the point of keyframe 2 through S12 into camera 1) and an EdgeInverseSim3ProjectXYZ (the point
+ * of keyframe 1 through S12^-1 into camera 2) with fixed point vertices and Huber kernels, optimize(5), the chi-square test that
+ * removes correspondences, optimize(5 or 10) on the survivors, the final test.  Neither edge has an analytic Jacobian: g2o's numeric
+ * linearizeOplus (central differences at 1e-9 through oplus) is restated with them, as are g2o::Sim3 (never normalised), the Huber
+ * kernel, the Levenberg loop, optimize()'s stopping rules and Eigen's LDLT; what that leaves UNPINNED is listed in DESIGN.md section 2.
+ * Two orders of ONE host routine, as for the pose (ORBM_POSE_ORDER_INDEX / ORBM_POSE_ORDER_DEVICE):
+ *   INDEX    sums over correspondences sequential in ascending position (e12 then e21 of each); sin, cos, exp, pow of the C library.
+ *   DEVICE   the kernel's tree (256 lanes, lane l owns l, l + 256, ...; xor butterfly in each wave; the four waves in order),
+ *            orbm_pose_sincos, orbm_sim3opt_exp, the cube by multiplication.  What the device computes, bit for bit. */
+enum { ORBM_SIM3OPT_CAP = 8192,   /* correspondences of one problem the device takes; a longer one runs on the host inside the same call */
+       ORBM_SIM3OPT_MAX_BATCH = 64 };
+
+typedef struct orbm_sim3opt_problem {
+    float K1[4], K2[4];            /* fx, fy, cx, cy of pKF1->mK, pKF2->mK                                              */
+    float inv_level_sigma2_1[ORBM_MAX_LEVELS];   /* pKF1->mvInvLevelSigma2                                              */
+    float inv_level_sigma2_2[ORBM_MAX_LEVELS];   /* pKF2->mvInvLevelSigma2                                              */
+    int32_t n_levels1, n_levels2;  /* 1 .. ORBM_MAX_LEVELS: every octave1 / octave2 lies below it                       */
+    float R[9], t[3], s;           /* the start g2oS12 as g2o::Sim3(Matrix3d, Vector3d, double) receives it (R row-major) */
+    float th2;                     /* th2: the chi-square bound of both tests, deltaHuber = sqrt(th2) in float          */
+    int32_t fix_scale;             /* bFixScale                                                                         */
+} orbm_sim3opt_problem;            /* 356 bytes */
+
+typedef struct orbm_sim3opt_result {
+    double q[4], t[3], s;          /* the vertex's estimate when the call returns (quaternion x y z w, NOT normalised); the start when written == 0 */
+    int32_t n_inliers;             /* the reference's return value: nIn, 0 on the early return                          */
+    int32_t n_correspondences, n_bad, n_more_iterations;   /* nCorrespondences, nBad, nMoreIterations                   */
+    int32_t written;               /* 1: `g2oS12 = vSim3_recov->estimate()` was reached; 0: the early return left g2oS12 alone */
+    int32_t optimisations;         /* optimize() calls that found an active edge: 0, 1 or 2                             */
+    orbm_pose_round round[2];      /* optimize(5) and optimize(nMoreIterations)                                         */
+} orbm_sim3opt_result;             /* 136 bytes, no padding */
+
+/* B problems (1 .. ORBM_SIM3OPT_MAX_BATCH), one workgroup per problem, one enqueue, one synchronisation.  Correspondences are CSR per
+ * problem (problem b owns first[b] .. first[b+1]-1), in the order of the reference's loop over vpMatches1:
+ *   x3dc1[3i..], x3dc2[3i..]   P3D1c = R1w*P3D1w + t1w and P3D2c = R2w*P3D2w + t2w, camera-frame float points
+ *   obs1[2i..], obs2[2i..]     kpUn1.pt, kpUn2.pt
+ *   octave1[i], octave2[i]     kpUn1.octave, kpUn2.octave
+ * flag_out[i]: 0 = kept, 1 = removed by the test after the first optimisation, 2 = failed the final test (vpMatches1 is nulled for
+ * both).  A NaN result leaves as the NaN x86 makes; what a non-finite INPUT gives is unspecified.  A problem beyond ORBM_SIM3OPT_CAP
+ * runs through the host routine in DEVICE order inside the same call (orbm_debug_last_sim3opt, include/orb_debug.h). */
+int orbm_sim3_optimize(orbm_matcher* m, const orbm_sim3opt_problem* problems, int B, const int32_t* first, const float* x3dc1,
+                       const float* x3dc2, const float* obs1, const float* obs2, const int32_t* octave1, const int32_t* octave2,
+                       uint8_t* flag_out, orbm_sim3opt_result* results);
+/* The same routine entirely on the host, no device needed, in either order (ORBM_POSE_ORDER_INDEX / ORBM_POSE_ORDER_DEVICE). */
+int orbm_sim3_optimize_host(const orbm_sim3opt_problem* problems, int B, const int32_t* first, const float* x3dc1, const float* x3dc2,
+                            const float* obs1, const float* obs2, const int32_t* octave1, const int32_t* octave2, int order,
+                            uint8_t* flag_out, orbm_sim3opt_result* results);
+/* (test hook) The exponential of the DEVICE order on the host; exp(0) is exactly 1. */
+double orbm_sim3opt_exp(double x);
+/* (test hooks) g2o::Sim3(Vector7d) in either order -> q[4], t[3], s in out8, returns the branch of fabs(sigma) < eps x theta < eps
+ * (0: both small, 1: sigma small, 2: theta small, 3: neither); the 7x7 LDLT solve of the Levenberg trial (A row-major, destroyed). */
+int orbm_sim3opt_expmap(const double* update7, int order, double* out8);
+int orbm_sim3opt_ldlt7(double* A49, const double* b7, double* x7);
+
 #ifdef __cplusplus
 }
 #endif

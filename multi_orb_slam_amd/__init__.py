@@ -13,5 +13,7 @@ from .matcher import PoseProblem, pose_optimize_host, pose_sincos  # noqa: F401
 from ._lib import POSE_PROBLEM_DTYPE, POSE_RESULT_DTYPE, POSE_CAM0, POSE_ALL_CAMS, POSE_ORDER_INDEX, POSE_ORDER_DEVICE, POSE_CAP  # noqa: F401
 from .matcher import Sim3Problem, sim3_ransac_host, sim3_walk, sim3_iterations, sim3_atan2  # noqa: F401
 from ._lib import SIM3_PROBLEM_DTYPE, SIM3_HYP_DTYPE, SIM3_MATH_LIBM, SIM3_MATH_DEVICE, SIM3_CAP, SIM3_MAX_ITS, SIM3_MAX_BATCH  # noqa: F401
+from .matcher import Sim3OptProblem, sim3_optimize_host, sim3opt_exp, sim3opt_expmap, sim3opt_ldlt7  # noqa: F401
+from ._lib import SIM3OPT_PROBLEM_DTYPE, SIM3OPT_RESULT_DTYPE, SIM3OPT_CAP, SIM3OPT_MAX_BATCH  # noqa: F401
 from .vocabulary import Vocabulary, BowSearch, Side as BowSide, FeatureVector, score_l1, KeyFrameDatabase  # noqa: F401
 from .vocabulary import TriKeyframe, TRI_OUT_DTYPE, cos_stereo, triangulate_pairs_host  # noqa: F401

@@ -40,6 +40,14 @@ SIM3_HYP_DTYPE = np.dtype([("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "
 SIM3_WALK_DTYPE = np.dtype([("iterations", "<i4"), ("best_inliers", "<i4"), ("best_index", "<i4"), ("no_more", "<i4")])   # orbm_sim3_walk_state
 assert SIM3_PROBLEM_DTYPE.itemsize == 84 and SIM3_HYP_DTYPE.itemsize == 184 and SIM3_WALK_DTYPE.itemsize == 16
 SIM3_MATH_LIBM, SIM3_MATH_DEVICE, SIM3_CAP, SIM3_MAX_ITS, SIM3_MAX_BATCH = 0, 1, 8192, 1024, 64
+SIM3OPT_PROBLEM_DTYPE = np.dtype([("K1", "<f4", (4,)), ("K2", "<f4", (4,)), ("inv_level_sigma2_1", "<f4", (32,)),
+                                  ("inv_level_sigma2_2", "<f4", (32,)), ("n_levels1", "<i4"), ("n_levels2", "<i4"), ("R", "<f4", (9,)),
+                                  ("t", "<f4", (3,)), ("s", "<f4"), ("th2", "<f4"), ("fix_scale", "<i4")])   # orbm_sim3opt_problem
+SIM3OPT_RESULT_DTYPE = np.dtype([("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8"), ("n_inliers", "<i4"), ("n_correspondences", "<i4"),
+                                 ("n_bad", "<i4"), ("n_more_iterations", "<i4"), ("written", "<i4"), ("optimisations", "<i4"),
+                                 ("round", POSE_ROUND_DTYPE, (2,))])   # orbm_sim3opt_result
+assert SIM3OPT_PROBLEM_DTYPE.itemsize == 356 and SIM3OPT_RESULT_DTYPE.itemsize == 136
+SIM3OPT_CAP, SIM3OPT_MAX_BATCH = 8192, 64
 
 ORB_OK, ORB_E_ARG, ORB_E_HIP, ORB_E_CAPACITY, ORB_E_NO_DEVICE, ORB_E_TIMEOUT = 0, -1, -2, -3, -4, -5
 
@@ -276,6 +284,12 @@ def lib():
     L.orbm_sim3_iterations.argtypes = [C.c_double, i32, i32, i32]
     L.orbm_sim3_atan2.argtypes = [C.c_double, C.c_double]; L.orbm_sim3_atan2.restype = C.c_double
     L.orbm_debug_last_sim3.argtypes = [vp, vp]
+    L.orbm_sim3_optimize.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_sim3_optimize_host.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
+    L.orbm_sim3opt_exp.argtypes = [C.c_double]; L.orbm_sim3opt_exp.restype = C.c_double
+    L.orbm_sim3opt_expmap.argtypes = [vp, i32, vp]
+    L.orbm_sim3opt_ldlt7.argtypes = [vp, vp, vp]
+    L.orbm_debug_last_sim3opt.argtypes = [vp, vp]
     f64 = C.c_double
     L.orbv_create.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp]
     L.orbv_load_text.argtypes = [C.c_char_p, i32, vp]

@@ -1,5 +1,5 @@
 // g2o_dev.h -- the Eigen / g2o boundary: the parts of Eigen and g2o that the reference's optimisers run and this library restates, ONE
-// definition each, for the kernels and the host routines (pose.hip today).  Restated from the published sources (Eigen's Geometry and
+// definition each, for the kernels and the host routines (pose.hip, sim3opt.hip).  Restated from the published sources (Eigen's Geometry and
 // Cholesky modules; Thirdparty/g2o/g2o/types/se3quat.h, core/robust_kernel_impl.cpp) and UNPINNED: Eigen is not linked and g2o was never
 // compiled against this code, so each is ONE function that a later pin changes.  The library is built without
 // contraction and without fast-math, and the tests compare bytes: nothing inside these bodies is to be reordered.
@@ -71,52 +71,54 @@ __host__ __device__ inline void eigen_quat_to_matrix(const double* q, double* m)
 }
 // LDLT<MatrixXd>::compute (ldlt_inplace<Lower>::unblocked: the pivot is the FIRST largest |diagonal| of the remaining block) followed
 // by isPositive() and solve() (P, L, D with the 1/highest() tolerance, L^T, P^T); every inner product sequential in ascending index.
-// A: 6x6 row-major, destroyed (only its lower triangle is read).  Returns isPositive(); x is written only then, as g2o does.
+// A: NxN row-major (N = 6: the pose vertex, 7: the Sim3 vertex), destroyed (only its lower triangle is read).  Returns isPositive(); x is
+// written only then, as g2o does.
+template <int N = 6>
 __host__ __device__ inline bool eigen_ldlt_solve(double* A, const double* b, double* x, double* temp, int* transp) {
     int sign = 0;   // 0 ZeroSign, 1 PositiveSemiDef, -1 NegativeSemiDef, 2 Indefinite
     bool done = false;
-    for (int k = 0; k < 6 && !done; ++k) {
+    for (int k = 0; k < N && !done; ++k) {
         int idx = k;
-        double big = fabs(A[7 * k]);
-        for (int i = k + 1; i < 6; ++i) { const double v = fabs(A[7 * i]); if (v > big) { big = v; idx = i; } }
+        double big = fabs(A[(N + 1) * k]);
+        for (int i = k + 1; i < N; ++i) { const double v = fabs(A[(N + 1) * i]); if (v > big) { big = v; idx = i; } }
         transp[k] = idx;
         if (k != idx) {
-            for (int j = 0; j < k; ++j) { const double t = A[6 * k + j]; A[6 * k + j] = A[6 * idx + j]; A[6 * idx + j] = t; }
-            for (int i = idx + 1; i < 6; ++i) { const double t = A[6 * i + k]; A[6 * i + k] = A[6 * i + idx]; A[6 * i + idx] = t; }
-            { const double t = A[7 * k]; A[7 * k] = A[7 * idx]; A[7 * idx] = t; }
-            for (int i = k + 1; i < idx; ++i) { const double t = A[6 * i + k]; A[6 * i + k] = A[6 * idx + i]; A[6 * idx + i] = t; }
+            for (int j = 0; j < k; ++j) { const double t = A[N * k + j]; A[N * k + j] = A[N * idx + j]; A[N * idx + j] = t; }
+            for (int i = idx + 1; i < N; ++i) { const double t = A[N * i + k]; A[N * i + k] = A[N * i + idx]; A[N * i + idx] = t; }
+            { const double t = A[(N + 1) * k]; A[(N + 1) * k] = A[(N + 1) * idx]; A[(N + 1) * idx] = t; }
+            for (int i = k + 1; i < idx; ++i) { const double t = A[N * i + k]; A[N * i + k] = A[N * idx + i]; A[N * idx + i] = t; }
         }
         if (k > 0) {
-            for (int j = 0; j < k; ++j) temp[j] = A[7 * j] * A[6 * k + j];
+            for (int j = 0; j < k; ++j) temp[j] = A[(N + 1) * j] * A[N * k + j];
             double s = 0;
-            for (int j = 0; j < k; ++j) s += A[6 * k + j] * temp[j];
-            A[7 * k] -= s;
-            for (int i = k + 1; i < 6; ++i) {
+            for (int j = 0; j < k; ++j) s += A[N * k + j] * temp[j];
+            A[(N + 1) * k] -= s;
+            for (int i = k + 1; i < N; ++i) {
                 double r = 0;
-                for (int j = 0; j < k; ++j) r += A[6 * i + j] * temp[j];
-                A[6 * i + k] -= r;
+                for (int j = 0; j < k; ++j) r += A[N * i + j] * temp[j];
+                A[N * i + k] -= r;
             }
         }
-        const double akk = A[7 * k];
+        const double akk = A[(N + 1) * k];
         const bool valid = fabs(akk) > 0;
         if (k == 0 && !valid) {
-            for (int j = 0; j < 6; ++j) transp[j] = j;
+            for (int j = 0; j < N; ++j) transp[j] = j;
             done = true;
         } else {
-            if (valid) for (int i = k + 1; i < 6; ++i) A[6 * i + k] = A[6 * i + k] / akk;
+            if (valid) for (int i = k + 1; i < N; ++i) A[N * i + k] = A[N * i + k] / akk;
             if (sign == 1) { if (akk < 0) sign = 2; }
             else if (sign == -1) { if (akk > 0) sign = 2; }
             else if (sign == 0) { if (akk > 0) sign = 1; else if (akk < 0) sign = -1; }
         }
     }
     if (!(sign == 1 || sign == 0)) return false;
-    for (int i = 0; i < 6; ++i) x[i] = b[i];
-    for (int k = 0; k < 6; ++k) { const double t = x[k]; x[k] = x[transp[k]]; x[transp[k]] = t; }
-    for (int i = 1; i < 6; ++i) { double s = 0; for (int j = 0; j < i; ++j) s += A[6 * i + j] * x[j]; x[i] -= s; }
+    for (int i = 0; i < N; ++i) x[i] = b[i];
+    for (int k = 0; k < N; ++k) { const double t = x[k]; x[k] = x[transp[k]]; x[transp[k]] = t; }
+    for (int i = 1; i < N; ++i) { double s = 0; for (int j = 0; j < i; ++j) s += A[N * i + j] * x[j]; x[i] -= s; }
     const double tol = 1.0 / DBL_MAX;
-    for (int i = 0; i < 6; ++i) x[i] = fabs(A[7 * i]) > tol ? x[i] / A[7 * i] : 0.0;
-    for (int i = 4; i >= 0; --i) { double s = 0; for (int j = i + 1; j < 6; ++j) s += A[6 * j + i] * x[j]; x[i] -= s; }
-    for (int k = 5; k >= 0; --k) { const double t = x[k]; x[k] = x[transp[k]]; x[transp[k]] = t; }
+    for (int i = 0; i < N; ++i) x[i] = fabs(A[(N + 1) * i]) > tol ? x[i] / A[(N + 1) * i] : 0.0;
+    for (int i = N - 2; i >= 0; --i) { double s = 0; for (int j = i + 1; j < N; ++j) s += A[N * j + i] * x[j]; x[i] -= s; }
+    for (int k = N - 1; k >= 0; --k) { const double t = x[k]; x[k] = x[transp[k]]; x[transp[k]] = t; }
     return true;
 }
 
@@ -183,4 +185,98 @@ __host__ __device__ inline void se3_exp(const double* update, int order, SE3Quat
 __host__ __device__ inline void g2o_huber(double e, double delta, double dsqr, double* rho0, double* rho1) {
     if (e <= dsqr) { *rho0 = e; *rho1 = 1.; }
     else { const double sqrte = sqrt(e); *rho0 = 2 * sqrte * delta - dsqr; *rho1 = delta / sqrte; }
+}
+
+// ---- Sim(3) (types/sim3.h) --------------------------------------------------------------------------------------------------------------
+// g2o::Sim3 NEVER normalises its quaternion: with theta < 1e-5 the rotation of Sim3(update) is I + Omega + Omega^2, which is not
+// orthonormal, Quaterniond(R) of it is not a unit quaternion, operator* multiplies the quaternions as they are and map() rotates with
+// _transformVector, which assumes a unit one.  All of that is followed here; se3_normalize_rotation is not to be called on a Sim3Quat.
+struct Sim3Quat { double q[4], t[3], s; };   // g2o::Sim3: r (x y z w), t, s
+enum { SIM3_EXP_SIGMA0_THETA0 = 0, SIM3_EXP_SIGMA0 = 1, SIM3_EXP_THETA0 = 2, SIM3_EXP_GENERAL = 3 };   // the branches of Sim3(Vector7d)
+
+__host__ __device__ inline void sim3_map(const Sim3Quat& T, const double* v, double* out) {   // Sim3::map: s*(r*xyz) + t
+    double r[3];
+    eigen_quat_rotate(T.q, v, r);
+    out[0] = T.s * r[0] + T.t[0]; out[1] = T.s * r[1] + T.t[1]; out[2] = T.s * r[2] + T.t[2];
+}
+// Sim3(Matrix3d, Vector3d, double): Quaterniond(R) as it comes
+__host__ __device__ inline void sim3_from_matrix(const double* R, const double* t, double s, Sim3Quat& T) {
+    eigen_quat_from_matrix(R, T.q);
+    T.t[0] = t[0]; T.t[1] = t[1]; T.t[2] = t[2];
+    T.s = s;
+}
+// Sim3::inverse: Sim3(r.conjugate(), r.conjugate()*((-1./s)*t), 1./s)
+__host__ __device__ inline void sim3_inverse(const Sim3Quat& T, Sim3Quat& out) {
+    const double c = -1. / T.s;
+    const double v[3] = {c * T.t[0], c * T.t[1], c * T.t[2]};
+    out.q[0] = -T.q[0]; out.q[1] = -T.q[1]; out.q[2] = -T.q[2]; out.q[3] = T.q[3];
+    eigen_quat_rotate(out.q, v, out.t);
+    out.s = 1. / T.s;
+}
+// Sim3::operator*: r = r1*r2, t = s1*(r1*t2) + t1, s = s1*s2 (out is neither a nor b)
+__host__ __device__ inline void sim3_mul(const Sim3Quat& a, const Sim3Quat& b, Sim3Quat& out) {
+    double r[3];
+    eigen_quat_mul(a.q, b.q, out.q);
+    eigen_quat_rotate(a.q, b.t, r);
+    out.t[0] = a.s * r[0] + a.t[0]; out.t[1] = a.s * r[1] + a.t[1]; out.t[2] = a.s * r[2] + a.t[2];
+    out.s = a.s * b.s;
+}
+// Sim3(const Vector7d& update) (:70-142), all four branches of fabs(sigma) < eps x theta < eps.  order: where sin, cos and exp come
+// from (ORBM_POSE_ORDER_INDEX: the C library; otherwise pose_sincos and pose_exp).  Returns the branch taken.
+__host__ __device__ inline int sim3_exp(const double* update, int order, Sim3Quat& T) {
+    const double o0 = update[0], o1 = update[1], o2 = update[2];
+    const double sigma = update[6];
+    const double theta = sqrt(o0 * o0 + o1 * o1 + o2 * o2);
+    const double O[9] = {0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0};   // skew(omega)
+    double O2[9], R[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) O2[3 * i + j] = O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j] + O[3 * i + 2] * O[6 + j];
+    double s, sn = 0., cs = 0.;
+    const double eps = 0.00001;
+#ifndef __HIP_DEVICE_COMPILE__
+    if (order == ORBM_POSE_ORDER_INDEX) { s = exp(sigma); if (!(theta < eps)) { sn = sin(theta); cs = cos(theta); } } else
+#endif
+    { s = pose_exp(sigma); if (!(theta < eps)) pose_sincos(theta, &sn, &cs); }
+    double A, B, C;
+    int branch;
+    if (fabs(sigma) < eps) {
+        C = 1;
+        if (theta < eps) {
+            branch = SIM3_EXP_SIGMA0_THETA0;
+            A = 1. / 2.;
+            B = 1. / 6.;
+            for (int i = 0; i < 9; ++i) R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + O[i]) + O2[i];
+        } else {
+            branch = SIM3_EXP_SIGMA0;
+            const double theta2 = theta * theta;
+            A = (1 - cs) / theta2;
+            B = (theta - sn) / (theta2 * theta);
+            const double a = sn / theta, c = (1 - cs) / (theta * theta);
+            for (int i = 0; i < 9; ++i) R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + a * O[i]) + c * O2[i];
+        }
+    } else {
+        C = (s - 1) / sigma;
+        if (theta < eps) {
+            branch = SIM3_EXP_THETA0;
+            const double sigma2 = sigma * sigma;
+            A = ((sigma - 1) * s + 1) / sigma2;
+            B = ((0.5 * sigma2 - sigma + 1) * s) / (sigma2 * sigma);
+            for (int i = 0; i < 9; ++i) R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + O[i]) + O2[i];
+        } else {
+            branch = SIM3_EXP_GENERAL;
+            const double ra = sn / theta, rc = (1 - cs) / (theta * theta);
+            for (int i = 0; i < 9; ++i) R[i] = ((i % 4 == 0 ? 1.0 : 0.0) + ra * O[i]) + rc * O2[i];
+            const double a = s * sn, b = s * cs;
+            const double theta2 = theta * theta, sigma2 = sigma * sigma;
+            const double c = theta2 + sigma2;
+            A = (a * sigma + (1 - b) * theta) / (theta * c);
+            B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / theta2;
+        }
+    }
+    eigen_quat_from_matrix(R, T.q);                        // r = Quaterniond(R)
+    double W[9];
+    for (int i = 0; i < 9; ++i) W[i] = (A * O[i] + B * O2[i]) + C * (i % 4 == 0 ? 1.0 : 0.0);
+    for (int i = 0; i < 3; ++i) T.t[i] = W[3 * i] * update[3] + W[3 * i + 1] * update[4] + W[3 * i + 2] * update[5];
+    T.s = s;
+    return branch;
 }

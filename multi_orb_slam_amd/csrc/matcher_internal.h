@@ -1,7 +1,7 @@
 // matcher_internal.h -- types and internal entry points shared by the translation units of the matcher / front end
 // (hamming.hip: all-pairs kernels; frame.hip: frame assembly; search.hip: projection search + resolve; matcher.hip: handle
 // + host helpers; exchange.hip: RCCL / loopback transport; frontend.hip: orbf_*; mappoint.hip: map-point refresh; pose.hip: pose
-// optimisation; sim3.hip: Sim3 RANSAC).  Not part of the C ABI.  Next to it: cv_dev.h / g2o_dev.h (the restated OpenCV and Eigen / g2o
+// optimisation; sim3.hip: Sim3 RANSAC; sim3opt.hip: Sim3 refinement).  Not part of the C ABI.  Next to it: cv_dev.h / g2o_dev.h (the restated OpenCV and Eigen / g2o
 // operations those ports share), sincos_dev.h, hamming_dev.h, stage_pack.h (the staged input block of a batched call).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -53,7 +53,7 @@ struct FrameBufs {  // device storage of one frame; recycled through the matcher
     }
 };
 
-// The buffers of one batched port (orbm_refresh_points, orbm_pose_optimize, orbm_sim3_ransac): one set per port, so that the calls
+// The buffers of one batched port (orbm_refresh_points, orbm_pose_optimize, orbm_sim3_ransac, orbm_sim3_optimize): one set per port, so that the calls
 // of different ports do not reallocate each other's.
 template <typename Out>
 struct PortBufs {
@@ -127,6 +127,10 @@ struct orbm_matcher {
     // records between the two kernels (scratch), the records and mask words the kernels write and where the problems of the last call went
     PortBufs<uint8_t> sim3;
     int last_sim3[2] = {0, 0};
+    // orbm_sim3_optimize (sim3opt.hip): the packed problems and correspondences of a call, the records and flags the kernel writes and
+    // where the problems of the last call went
+    PortBufs<uint8_t> sim3opt;
+    int last_sim3opt[2] = {0, 0};
 };
 namespace morb { hipStream_t side_stream(orbm_matcher* m); }   // (lazily created; NULL after a reported failure)
 

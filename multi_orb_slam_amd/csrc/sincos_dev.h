@@ -1,5 +1,6 @@
-// sincos_dev.h -- the double sine / cosine sequence shared by the device orders of pose.hip (ORBM_POSE_ORDER_DEVICE) and sim3.hip
-// (ORBM_SIM3_MATH_DEVICE); orbm_pose_sincos (include/orbm.h) is its test hook.
+// sincos_dev.h -- the double sine / cosine sequence shared by the device orders of pose.hip (ORBM_POSE_ORDER_DEVICE), sim3.hip
+// (ORBM_SIM3_MATH_DEVICE) and sim3opt.hip; orbm_pose_sincos (include/orbm.h) is its test hook.  Next to it the exponential of
+// sim3opt.hip's device order (test hook: orbm_sim3opt_exp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,4 +35,38 @@ __host__ __device__ inline void pose_sincos(double x, double* sn, double* cs) {
     const int q = (int)((long long)kf & 3);
     *cs = (q == 0) ? c : (q == 1) ? -s : (q == 2) ? -c : s;
     *sn = (q == 0) ? s : (q == 1) ? c : (q == 2) ? -s : -c;
+}
+
+// ---- exp of the device order of sim3opt.hip: + - * / and conversions in double -------------------------------------------------------
+// k = x / ln 2 rounded to the nearest integer (the same 1.5 * 2^52 step), a two-part ln 2 whose high part has 21 trailing zero bits (k
+// times it is exact), the Taylor polynomial to r^14 on [-ln2/2, ln2/2] in Horner form, then |k| exact doublings or halvings.  exp(0) is
+// exactly 1.  Beyond the range of a double: infinity above, 0 below; a NaN stays one.
+__host__ __device__ inline double pose_exp(double x) {
+    if (!(x == x)) return x;
+    if (x > 709.782712893384) return 1.79769313486231570815e+308 * 2.0;
+    if (x < -745.2) return 0.0;
+    const double INV_LN2 = 1.44269504088896338700e+00;
+    const double LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10;
+    const double MAGIC = 6755399441055744.0;
+    const double kf = (x * INV_LN2 + MAGIC) - MAGIC;
+    const double r = (x - kf * LN2_HI) - kf * LN2_LO;
+    double p = 1.0 / 87178291200.0;
+    p = p * r + (1.0 / 6227020800.0);
+    p = p * r + (1.0 / 479001600);
+    p = p * r + (1.0 / 39916800);
+    p = p * r + (1.0 / 3628800);
+    p = p * r + (1.0 / 362880);
+    p = p * r + (1.0 / 40320);
+    p = p * r + (1.0 / 5040);
+    p = p * r + (1.0 / 720);
+    p = p * r + (1.0 / 120);
+    p = p * r + (1.0 / 24);
+    p = p * r + (1.0 / 6);
+    p = p * r + (1.0 / 2);
+    double e = 1.0 + (r + (r * r) * p);
+    const int k = (int)kf;
+    const double f = k < 0 ? 0.5 : 2.0;
+    const int m = k < 0 ? -k : k;
+    for (int i = 0; i < m; ++i) e = e * f;
+    return e;
 }

@@ -1,6 +1,6 @@
 // stage_pack.h -- how the batched entry points lay out and stage the arrays of one call: one block, every array 16-byte aligned, in the
 // order the arrays are added.  The one definition of the round-up (align16), of the running layout (BlockLayout: bow.hip's keyframe block,
-// kfdb.hip's query block) and of the staging sequence (StagePack: mappoint.hip, pose.hip, sim3.hip, triangulate.hip).
+// kfdb.hip's query block) and of the staging sequence (StagePack: mappoint.hip, pose.hip, sim3.hip, sim3opt.hip, triangulate.hip).
 #pragma once
 #include <string.h>
 #include "orb_common.h"

@@ -5,14 +5,24 @@
 // below keep its signatures and replace the body: they fill the edge arrays from the frame (mvpMapPoints, mvKeysUn[_total],
 // mvuRight[_total], mvInvLevelSigma2), hand them to orbm_pose_optimize (include/orbm.h: one workgroup carries the problem through all
 // four rounds), write mvbOutlier and call SetPose.  Only this translation unit replaces the reference's: bundle adjustment, the
-// essential graph and Sim3 stay with g2o.  INTEGRATION.md shows the swap.
+// essential graph and OptimizeSim3 (all cameras) stay with g2o.  INTEGRATION.md shows the swap.
+//
+// Optimizer::OptimizeSim3_cam1 (reference include/Optimizer.h:62-63, src/Optimizer.cc:1984-2243), the refinement LoopClosing::ComputeSim3
+// runs between SearchBySim3 and the acceptance of a loop, likewise: the reference's filtering of vpMatches1 statement by statement, the
+// camera-frame points as it computes them, then orbm_sim3_optimize (one workgroup carries the problem through both optimisations and both
+// chi-square tests).  g2o::Sim3 is the reference's own type inside the reference build and host/g2o_compat.h's stand-in here.
 #ifndef OPTIMIZER_H
 #define OPTIMIZER_H
 
 #include <vector>
 #include "ORBmatcher.h"
 
+namespace g2o { struct Sim3; }   // (the reference's Thirdparty/g2o/g2o/types/sim3.h, or host/g2o_compat.h)
+
 namespace ORB_SLAM2 {
+
+class KeyFrame;
+class MapPoint;
 
 class Optimizer {
 public:
@@ -24,11 +34,28 @@ public:
     // PoseOptimization(vpFrames[i][, bAllCams]) would have returned; every frame's mvbOutlier and pose are written the same way.
     // Returns false -- reported as every search of ORBmatcher reports a failure, nothing written -- when the library refuses the call.
     bool static PoseOptimizationBatch(const std::vector<Frame*>& vpFrames, bool bAllCams, std::vector<int>& vnInliers);
+
+    // Returns nIn; nulls vpMatches1[idx] of every correspondence either chi-square test rejected; writes g2oS12 only where the reference
+    // does (not on `return 0` after the first test).  The start reaches the library as the float rotation matrix, translation and scale
+    // g2o::Sim3(Matrix3d, Vector3d, double) was built from in ComputeSim3 (rotation().toRotationMatrix() rounded to float: exact for a
+    // g2oS12 made from float matrices up to the rounding of that round trip).
+    int static OptimizeSim3_cam1(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2,
+                                 const bool bFixScale);
+
+    // This repository's own: the candidates of one loop (ComputeSim3 runs OptimizeSim3_cam1 once per candidate whose RANSAC succeeded and
+    // takes the first with nInliers >= 20) in ONE batched call, at most ORBM_SIM3OPT_MAX_BATCH.  pKF1 is the current keyframe of all;
+    // vnInliers[i], vvpMatches1[i] and vg2oS12[i] end as OptimizeSim3_cam1(pKF1, vpKF2[i], vvpMatches1[i], vg2oS12[i], th2, bFixScale)
+    // leaves them.  Returns false, nothing written, when the library refuses the call.
+    bool static OptimizeSim3Batch(KeyFrame* pKF1, const std::vector<KeyFrame*>& vpKF2, std::vector<std::vector<MapPoint*> >& vvpMatches1,
+                                  std::vector<g2o::Sim3>& vg2oS12, const float th2, const bool bFixScale, std::vector<int>& vnInliers);
 };
 
 // The edge count below which a single call is computed by the library's host routine (the same statements in the kernel's order, no
 // launch).  UNMEASURED placeholder until tools/pose_bench.py has run on a device.
 extern const int POSE_HOST_BELOW;
+// The same for OptimizeSim3_cam1, in correspondences: where tools/sim3opt_bench.py found the two to cross for a single problem
+// (profiles/r14/notes_sim3opt.md; a batched call always takes the device).
+extern const int SIM3OPT_HOST_BELOW;
 
 }  // namespace ORB_SLAM2
 

@@ -6,6 +6,7 @@ from . import _lib
 from ._lib import KP_DTYPE, QUERY_DTYPE, POINT_DTYPE, TRACK_DTYPE, REFRESH_DTYPE, CamFeatures, FrameDesc, check, ptr
 from ._lib import POSE_PROBLEM_DTYPE, POSE_RESULT_DTYPE, POSE_CAM0, POSE_ALL_CAMS, POSE_ORDER_INDEX, POSE_ORDER_DEVICE  # noqa: F401
 from ._lib import SIM3_PROBLEM_DTYPE, SIM3_HYP_DTYPE, SIM3_WALK_DTYPE, SIM3_MATH_LIBM, SIM3_MATH_DEVICE  # noqa: F401
+from ._lib import SIM3OPT_PROBLEM_DTYPE, SIM3OPT_RESULT_DTYPE  # noqa: F401
 
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30  # reference src/ORBmatcher.cc:37-39
 # which resolve delivered a search's result (ORBM_FORM_*, include/orb_debug.h; Matcher.last_resolve_form)
@@ -232,6 +233,74 @@ def sim3_iterations(probability, min_inliers, max_its, N):
 def sim3_atan2(y, x):
     """The atan2 sequence of SIM3_MATH_DEVICE (orbm_sim3_atan2): y >= 0, x in [-1, 1]."""
     return float(_lib.lib().orbm_sim3_atan2(float(y), float(x)))
+
+
+class Sim3OptProblem:
+    """One Optimizer::OptimizeSim3_cam1 call from its correspondence list on (orbm_sim3opt_problem + its correspondences): K1, K2 =
+    (fx, fy, cx, cy) of pKF1->mK, pKF2->mK; inv_level_sigma2_1 / _2 = mvInvLevelSigma2 of the two keyframes; the start g2oS12 as float
+    R 3 x 3, t 3, s; th2; fix_scale; x3dc1, x3dc2 n x 3 (camera-frame points of keyframe 1 and 2), obs1, obs2 n x 2 (kpUn.pt), octave1,
+    octave2 n."""
+
+    def __init__(self, K1, K2, inv_level_sigma2_1, inv_level_sigma2_2, R, t, s, th2, fix_scale, x3dc1, x3dc2, obs1, obs2, octave1, octave2):
+        rec = np.zeros(1, SIM3OPT_PROBLEM_DTYPE)
+        rec["K1"][0] = np.asarray(K1, np.float32); rec["K2"][0] = np.asarray(K2, np.float32)
+        s1 = np.asarray(inv_level_sigma2_1, np.float32); s2 = np.asarray(inv_level_sigma2_2, np.float32)
+        rec["inv_level_sigma2_1"][0, :len(s1)] = s1; rec["inv_level_sigma2_2"][0, :len(s2)] = s2
+        rec["n_levels1"] = len(s1); rec["n_levels2"] = len(s2)
+        rec["R"][0] = np.asarray(R, np.float32).reshape(9); rec["t"][0] = np.asarray(t, np.float32).reshape(3)
+        rec["s"] = np.float32(s); rec["th2"] = np.float32(th2); rec["fix_scale"] = 1 if fix_scale else 0
+        self.rec = rec
+        self.x3dc1 = np.ascontiguousarray(x3dc1, np.float32).reshape(-1, 3)
+        self.x3dc2 = np.ascontiguousarray(x3dc2, np.float32).reshape(-1, 3)
+        self.obs1 = np.ascontiguousarray(obs1, np.float32).reshape(-1, 2)
+        self.obs2 = np.ascontiguousarray(obs2, np.float32).reshape(-1, 2)
+        self.octave1 = np.ascontiguousarray(octave1, np.int32); self.octave2 = np.ascontiguousarray(octave2, np.int32)
+        self.n = len(self.x3dc1)
+        assert len(self.x3dc2) == len(self.obs1) == len(self.obs2) == len(self.octave1) == len(self.octave2) == self.n
+
+
+def _sim3opt_pack(problems):
+    recs = np.concatenate([p.rec for p in problems])
+    first = np.zeros(len(problems) + 1, np.int32)
+    first[1:] = np.cumsum([p.n for p in problems])
+    cat = lambda name, dt, shape: np.ascontiguousarray(np.concatenate([getattr(p, name) for p in problems]).reshape(shape), dt)
+    arrays = (cat("x3dc1", np.float32, (-1, 3)), cat("x3dc2", np.float32, (-1, 3)), cat("obs1", np.float32, (-1, 2)),
+              cat("obs2", np.float32, (-1, 2)), cat("octave1", np.int32, (-1,)), cat("octave2", np.int32, (-1,)))
+    flags = np.zeros(max(int(first[-1]), 1), np.uint8); res = np.zeros(len(problems), SIM3OPT_RESULT_DTYPE)
+    return recs, first, arrays, flags, res
+
+
+def _sim3opt_unpack(problems, first, flags, res):
+    return [(res[b].copy(), flags[first[b]:first[b + 1]].copy()) for b in range(len(problems))]
+
+
+def sim3_optimize_host(problems, order=POSE_ORDER_INDEX):
+    """orbm_sim3_optimize_host: the batch entirely on the host (no device needed), sums in index order with the C library's sin / cos /
+    exp (the restatement of the reference) or in the kernel's order with the device's sequences
+    -> [(SIM3OPT_RESULT_DTYPE record, flag per correspondence: 0 kept, 1 removed after the first optimisation, 2 failed the final test)]."""
+    recs, first, arrays, flags, res = _sim3opt_pack(problems)
+    check(_lib.lib().orbm_sim3_optimize_host(ptr(recs), len(problems), ptr(first), *[ptr(a) for a in arrays], int(order), ptr(flags), ptr(res)))
+    return _sim3opt_unpack(problems, first, flags, res)
+
+
+def sim3opt_exp(x):
+    """The exponential of the device order of the Sim3 refinement (orbm_sim3opt_exp)."""
+    return float(_lib.lib().orbm_sim3opt_exp(float(x)))
+
+
+def sim3opt_expmap(update, order=POSE_ORDER_INDEX):
+    """g2o::Sim3(Vector7d) as the library restates it (orbm_sim3opt_expmap) -> (q 4, t 3, s, branch)."""
+    u = np.ascontiguousarray(update, np.float64); out = np.zeros(8)
+    assert len(u) == 7
+    branch = _lib.lib().orbm_sim3opt_expmap(ptr(u), int(order), ptr(out))
+    return out[:4].copy(), out[4:7].copy(), float(out[7]), int(branch)
+
+
+def sim3opt_ldlt7(A, b):
+    """The 7 x 7 LDLT solve of a Levenberg trial (orbm_sim3opt_ldlt7) -> (isPositive, x)."""
+    A = np.array(A, np.float64).reshape(49); b = np.ascontiguousarray(b, np.float64); x = np.zeros(7)
+    ok = _lib.lib().orbm_sim3opt_ldlt7(ptr(A), ptr(b), ptr(x))
+    return bool(ok), x
 
 
 class LocalPoints:
@@ -618,6 +687,20 @@ class Matcher:
         args, its_first, hyp, masks = _sim3_pack(problems)
         check(_lib.lib().orbm_sim3_ransac(self._h, *args, ptr(hyp), ptr(masks)))
         return _sim3_unpack(problems, its_first, hyp, masks)
+
+    def sim3_optimize(self, problems):
+        """Optimizer::OptimizeSim3_cam1 (reference src/Optimizer.cc:1984-2243) for a batch of Sim3OptProblem in one device call, one
+        workgroup per problem (orbm_sim3_optimize) -> [(SIM3OPT_RESULT_DTYPE record, flag per correspondence)] per problem."""
+        recs, first, arrays, flags, res = _sim3opt_pack(problems)
+        check(_lib.lib().orbm_sim3_optimize(self._h, ptr(recs), len(problems), ptr(first), *[ptr(a) for a in arrays], ptr(flags), ptr(res)))
+        return _sim3opt_unpack(problems, first, flags, res)
+
+    def last_sim3opt(self):
+        """Problems of the last sim3_optimize by path: (device, host routine because of more than SIM3OPT_CAP correspondences)
+        (orbm_debug_last_sim3opt)."""
+        out = (C.c_int * 2)()
+        check(_lib.lib().orbm_debug_last_sim3opt(self._h, out))
+        return tuple(out)
 
     def last_sim3(self):
         """Problems of the last Sim3Ransac by path: (device, host routine because of more than SIM3_CAP correspondences)
