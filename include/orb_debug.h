@@ -6,6 +6,7 @@
 #include "orbx.h"
 #include "orbm.h"
 #include "orbf.h"
+#include "orbv.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -67,6 +68,13 @@ int orbm_debug_last_sim3opt(const orbm_matcher* m, int* out2);
  * stream.  *avg_us = average launch duration, *n_gated = candidates that passed the gates, summed over the queries. */
 int orbm_debug_time_project(orbm_matcher* m, const orbm_frame* f, const orbm_query* q, int nq, int th_high, int iters,
                             float* avg_us, long long* n_gated);
+
+/* ---- BoW-gated searches -------------------------------------------------------------------------------------------------- */
+/* {waves per vocabulary node (1 or 4), largest node of side B, candidates of a node staged in LDS (lds_cand; candidates from there on
+ * are read from HBM), mode (0 SearchByBoW(KF, F), 1 SearchByBoW(KF, KF), 2 SearchForTriangulation)} of the last join enqueued on the
+ * workspace (inspection only; host-side bookkeeping of enqueue_join, no kernel knows it; all zero before the first one).  A test written
+ * for one form of k_bow_join asserts this, so that a moved threshold fails it instead of quietly running another kernel. */
+int orbv_debug_last_join(const orbv_workspace* w, int* out4);
 
 /* ---- front end: probes of the multi-GPU exchange ------------------------------------------------------------------------- */
 /* With on != 0 every step of a handle with an exchange records (HIP events) when its search and when its exchange (all-gather +

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 #include "../../include/orbv.h"
+#include "../../include/orb_debug.h"
 #include "orb_common.h"
 #include "bow_internal.h"
 #include "hamming_dev.h"
@@ -710,6 +711,7 @@ int enqueue_join(orbv_workspace* w, const SideDev& A, const SideDev& B, int max_
     const size_t lds = (size_t)claimed_bytes + (size_t)lds_cand * 40;
     // four waves per node from ~128 candidates per node on (the barriers cost more than they save below that)
     const bool wide = max_nc >= 128;
+    w->last_join[0] = wide ? 4 : 1; w->last_join[1] = max_nc; w->last_join[2] = lds_cand; w->last_join[3] = mode;   // (host bookkeeping, no kernel reads it)
     if (wide) {
         if (mode == 0) k_bow_join<0, 4><<<A.n_nodes, 256, lds, st>>>(A, B, T, th_low, nnratio, check_ori, W, claimed_bytes, lds_cand);
         else if (mode == 1) k_bow_join<1, 4><<<A.n_nodes, 256, lds, st>>>(A, B, T, th_low, nnratio, check_ori, W, claimed_bytes, lds_cand);
@@ -830,6 +832,12 @@ void bow_search_collect(orbv_workspace* w, int n_out, int32_t* match, int* nmatc
 }  // namespace morb
 
 extern "C" {
+
+int orbv_debug_last_join(const orbv_workspace* w, int* out4) {
+    MORB_ARG(w != nullptr && out4 != nullptr);
+    for (int i = 0; i < 4; ++i) out4[i] = w->last_join[i];
+    return ORB_OK;
+}
 
 int orbv_search_by_bow(orbv_workspace* w, const orbv_side* a, const orbv_side* b, int mode, int th_low, float nnratio,
                        int check_orientation, int32_t* match, int* nmatches) {

@@ -43,6 +43,7 @@ struct orbv_workspace {
     morb::PinnedBuf<int32_t> h_match;
     morb::PinnedBuf<uint8_t> h_tri;   // records of the triangulation kernel
     morb::StageBuf tri_const;         // the two keyframes' constants of a triangulation call
+    int last_join[4] = {0, 0, 0, 0};  // {waves per node, largest B node, lds_cand, mode} of the last enqueued join (orbv_debug_last_join)
 };
 
 // One frame / keyframe resident in HBM for any number of searches (descriptors, angles, FeatureVector, and the triangulation

@@ -240,6 +240,12 @@ class BowSearch:
         check(_lib.lib().orbv_search_by_bow(self._h, C.byref(ca), C.byref(cb), mode, th_low, nnratio, int(check_orientation), ptr(match), C.byref(nm)))
         return nm.value, match[:n_out]
 
+    def last_join(self):
+        """(waves per node, largest node of b, candidates staged in LDS, mode) of the last search enqueued here (orbv_debug_last_join)."""
+        out = (C.c_int * 4)()
+        check(_lib.lib().orbv_debug_last_join(self._h, out))
+        return tuple(out)
+
     def keyframe_from_device(self, vocabulary, feats, levelsup=4, triangulation=True):
         """Keyframe built entirely on the device from a front end's resident frame (feats = NativeFrontEnd.export_features())."""
         from ._lib import DeviceSide

@@ -61,3 +61,22 @@ def test_resolve_form_codes_of_the_binding_are_those_of_the_header():
     binding = {k[len("FORM_"):]: v for k, v in vars(matcher).items() if k.startswith("FORM_")}
     assert len(header) == 10 and len(set(header.values())) == 10
     assert binding == header
+
+
+def test_last_join_report_of_the_binding_is_the_one_of_the_header():
+    """BowSearch.last_join() (what the BoW boundary tests assert their form with) against orbv_debug_last_join of include/orb_debug.h: the
+    declaration, its four fields in the order the binding names them, the export and the binding's argument list."""
+    import inspect
+    from multi_orb_slam_amd import _lib, vocabulary
+    src = open(os.path.join(ROOT, "include", "orb_debug.h")).read()
+    decl = re.search(r"/\*((?:(?!\*/).)*)\*/\s*int orbv_debug_last_join\(const orbv_workspace\* w, int\* out4\);", src, re.S)
+    assert decl, "orbv_debug_last_join is not declared as (const orbv_workspace*, int* out4)"
+    fields = re.search(r"\{(.*?)\}", decl.group(1), re.S).group(1)
+    order = [fields.index(k) for k in ("waves per vocabulary node", "largest node of side B", "lds_cand", "mode")]
+    assert order == sorted(order) and fields.count(",") >= 3
+    lib = _lib.lib()
+    assert hasattr(lib, "orbv_debug_last_join") and len(lib.orbv_debug_last_join.argtypes) == 2
+    doc = inspect.getdoc(vocabulary.BowSearch.last_join)
+    assert "orbv_debug_last_join" in doc and [doc.index(k) for k in ("waves per node", "largest node", "staged in LDS", "mode")] == sorted(
+        doc.index(k) for k in ("waves per node", "largest node", "staged in LDS", "mode"))
+    assert "(ctypes.c_int * 4)" in inspect.getsource(vocabulary.BowSearch.last_join).replace("C.c_int", "ctypes.c_int")

@@ -1,14 +1,10 @@
 """Known-answer tests of the oracle's vocabulary transform and BoW-gated searches (oracle/bow_oracle.cpp), plus a
 second, independent restatement in plain Python loops for small random cases.  No GPU, no product code."""
-import math
 import numpy as np
 import oracle
+from bow_model import popcount, py_bin, py_search_by_bow, py_three_maxima, py_triangulation  # noqa: F401
 from helpers import make_bow_pair
 from multi_orb_slam_amd import synth
-
-
-def popcount(a, b):
-    return int(np.unpackbits(np.asarray(a, np.uint8) ^ np.asarray(b, np.uint8)).sum())
 
 
 def tiny_tree():
@@ -69,98 +65,7 @@ def test_l1_score():
     assert oracle.bow_score_l1(a, b) == -s / 2.0
 
 
-# ---- second restatement: plain Python over dict-of-lists feature vectors -------------------------------------------------
-def py_three_maxima(sizes):
-    m1 = m2 = m3 = 0; i1 = i2 = i3 = -1
-    for i, s in enumerate(sizes):
-        if s > m1: m3, i3, m2, i2, m1, i1 = m2, i2, m1, i1, s, i
-        elif s > m2: m3, i3, m2, i2 = m2, i2, s, i
-        elif s > m3: m3, i3 = s, i
-    if np.float32(m2) < np.float32(0.1) * np.float32(m1): i2 = i3 = -1
-    elif np.float32(m3) < np.float32(0.1) * np.float32(m1): i3 = -1
-    return i1, i2, i3
-
-
-def py_bin(a1, a2):
-    rot = np.float32(a1) - np.float32(a2)
-    if rot < 0: rot = np.float32(rot + np.float32(360.0))
-    v = float(np.float32(rot * np.float32(1.0 / 30)))
-    b = int(math.floor(v + 0.5))   # round half away from zero, v >= 0
-    return 0 if b == 30 else b
-
-
-def fv_dict(s):
-    return {int(k): s["items"][s["node_start"][i]:s["node_start"][i + 1]].tolist() for i, k in enumerate(s["node_id"])}
-
-
-def py_search_by_bow(a, b, mode, th_low, nnratio, check_ori):
-    fa, fb = fv_dict(a), fv_dict(b)
-    n_out = len(b["desc"]) if mode == 0 else len(a["desc"])
-    match = [-1] * n_out
-    matched2 = set()
-    hist = [[] for _ in range(30)]
-    nm = 0
-    for node in sorted(set(fa) & set(fb)):
-        for i1 in fa[node]:
-            if not a["flags"][i1] & 1: continue
-            b1, b2, bi = 256, 256, -1
-            for i2 in fb[node]:
-                if mode == 0 and match[i2] >= 0: continue
-                if mode == 1 and (i2 in matched2 or not b["flags"][i2] & 1): continue
-                d = popcount(a["desc"][i1], b["desc"][i2])
-                if d < b1: b2, b1, bi = b1, d, i2
-                elif d < b2: b2 = d
-            ok = b1 <= th_low if mode == 0 else b1 < th_low
-            if ok and np.float32(b1) < np.float32(nnratio) * np.float32(b2):
-                if mode == 0: match[bi] = i1
-                else: match[i1] = bi; matched2.add(bi)
-                if check_ori: hist[py_bin(a["angle"][i1], b["angle"][bi])].append(bi if mode == 0 else i1)
-                nm += 1
-    if check_ori:
-        keep = py_three_maxima([len(h) for h in hist])
-        for i, h in enumerate(hist):
-            if i in keep: continue
-            for j in h: match[j] = -1; nm -= 1
-    return nm, match
-
-
-def py_triangulation(a, b, F12, ex, ey, sf, s2, th_low, check_ori):
-    f32 = np.float32
-    fa, fb = fv_dict(a), fv_dict(b)
-    match = [-1] * len(a["desc"]); hist = [[] for _ in range(30)]; nm = 0
-    for node in sorted(set(fa) & set(fb)):
-        for i1 in fa[node]:
-            if not a["flags"][i1] & 1: continue
-            cam = int(a["cam_of"][i1]); st1 = bool(a["flags"][i1] & 2)
-            best, bi = th_low, -1
-            F = F12[cam]
-            x1, y1 = f32(a["x"][i1]), f32(a["y"][i1])
-            la = f32(f32(f32(x1 * F[0]) + f32(y1 * F[3])) + F[6]); lb = f32(f32(f32(x1 * F[1]) + f32(y1 * F[4])) + F[7])
-            lc = f32(f32(f32(x1 * F[2]) + f32(y1 * F[5])) + F[8])
-            for i2 in fb[node]:
-                if not b["flags"][i2] & 1 or int(b["cam_of"][i2]) != cam: continue
-                d = popcount(a["desc"][i1], b["desc"][i2])
-                if d > th_low or d > best: continue
-                x2, y2, o2 = f32(b["x"][i2]), f32(b["y"][i2]), int(b["octave"][i2])
-                if not st1 and not b["flags"][i2] & 2:
-                    dx, dy = f32(ex[cam] - x2), f32(ey[cam] - y2)
-                    if f32(f32(dx * dx) + f32(dy * dy)) < f32(f32(100) * sf[o2]): continue
-                num = f32(f32(f32(la * x2) + f32(lb * y2)) + lc); den = f32(f32(la * la) + f32(lb * lb))
-                if den == 0: continue
-                dsqr = f32(f32(num * num) / den)
-                if not float(dsqr) < 3.84 * float(s2[o2]): continue
-                best, bi = d, i2
-            if bi >= 0:
-                match[i1] = bi; nm += 1
-                if check_ori: hist[py_bin(a["angle"][i1], b["angle"][bi])].append(i1)
-    if check_ori:
-        keep = py_three_maxima([len(h) for h in hist])
-        for i, h in enumerate(hist):
-            if i in keep: continue
-            for j in h: match[j] = -1; nm -= 1
-    return nm, match
-
-
+# ---- second restatement: tests/bow_model.py (plain NumPy over dict-of-lists feature vectors) ---------------------------------
 def test_search_by_bow_matches_python_restatement():
     voc = synth.vocabulary(6, 3, seed=5)
     V = oracle.Vocabulary(voc)
