@@ -63,6 +63,14 @@ int orbm_debug_last_sim3(const orbm_matcher* m, int* out2);
 /* Where the problems of the last orbm_sim3_optimize went: {one workgroup on the device, host routine because the problem has more than
  * ORBM_SIM3OPT_CAP correspondences} (inspection only) */
 int orbm_debug_last_sim3opt(const orbm_matcher* m, int* out2);
+/* Where the work of the last orbm_pnp_ransac went: {problems on the device, problems through the host routine because they have more
+ * than ORBM_PNP_CAP correspondences, records refined on the device, records refined by the host routine because they lie beyond
+ * ORBM_PNP_MAX_RECORDS of a device problem} (inspection only) */
+int orbm_debug_last_pnp(const orbm_matcher* m, int* out4);
+/* The capacities in bytes of the buffers orbm_pnp_ransac keeps between calls: {the staged inputs, the device block the kernels leave
+ * for one another (records, counts, masks, the inlier sets and per-point arrays of the refinements), the mapped results}: they grow
+ * with the largest call and are reused by every smaller one (inspection only) */
+int orbm_debug_pnp_buffers(const orbm_matcher* m, unsigned long long* out3);
 /* Inspection / bench (roofline M3): `iters` launches of the projection kernel alone, as the frame search
  * launches it (window + level + right-coordinate gates, distances, shortlist), timed with HIP events on the handle's
  * stream.  *avg_us = average launch duration, *n_gated = candidates that passed the gates, summed over the queries. */

@@ -553,6 +553,116 @@ double orbm_sim3opt_exp(double x);
 int orbm_sim3opt_expmap(const double* update7, int order, double* out8);
 int orbm_sim3opt_ldlt7(double* A49, const double* b7, double* x7);
 
+/* -- PnPsolver: every EPnP RANSAC hypothesis of a relocalisation in one call ---------------------------------------------
+ * PnPsolver (reference src/PnPsolver.cc) between SearchByBoW_cam1 and Optimizer::PoseOptimization of Tracking::Relocalization: per
+ * hypothesis the four-point EPnP (compute_pose: choose_control_points, compute_barycentric_coordinates, M^T M, its 12x12 SVD, the three
+ * beta approximations with five Gauss-Newton steps each, estimate_R_and_t, the reprojection error) and CheckInliers; per record --
+ * a hypothesis that `iterate` makes its best -- Refine(): the n-point compute_pose on the record's inlier set and CheckInliers again.
+ * No iteration depends on another, so all hypotheses of all candidates are evaluated at once and orbm_pnp_walk recovers the
+ * reference's sequential `iterate` from the counts and the refined records.  RANSAC's randomness is an INPUT: the quadruples arrive drawn.
+ * The OpenCV operators on the path (cvMulTransposed, cvSVD, cvInvert, cvSolve) are restated one function each and UNPINNED (DESIGN.md
+ * section 2).  Everything below compute_pose is + - * / sqrt fabs in double: there is ONE order, no transcendental function, and every
+ * sum runs in the reference's element order on the device as on the host.
+ * The one stated deviation: qr_solve's result `x` is an uninitialised stack array in the reference's gauss_newton and qr_solve returns
+ * without writing it when a column is all zero.  Here x starts as zeros at the entry of gauss_newton, a singular return leaves it as
+ * it was, and the record carries ORBM_PNP_FLAG_SINGULAR_QR. */
+enum { ORBM_PNP_CAP = 8192,         /* correspondences of one problem the device takes; a longer one runs on the host inside the same call */
+       ORBM_PNP_MAX_ITS = 1024,     /* hypotheses of one problem (the reference draws at most 300 per block)                              */
+       ORBM_PNP_MAX_BATCH = 64,
+       ORBM_PNP_MAX_RECORDS = 16 }; /* refined records of one problem the device takes; later ones are refined on the host inside the same call */
+enum { ORBM_PNP_FLAG_SINGULAR_QR = 1,   /* qr_solve met an all-zero column in some Gauss-Newton step                                        */
+       ORBM_PNP_FLAG_RANDOM_SVD = 2 };  /* some cvSVD completed U with the random-vector branch (a singular value <= DBL_MIN)              */
+
+typedef struct orbm_pnp_problem {
+    double fu, fv, uc, vc;         /* F.fx, F.fy, F.cx, F.cy widened to the solver's double members                     */
+    int32_t min_inliers;           /* mRansacMinInliers after SetRansacParameters (orbm_pnp_parameters)                 */
+    int32_t best_start;            /* mnBestInliers on entry: 0 for a fresh solver                                      */
+} orbm_pnp_problem;                /* 40 bytes */
+
+typedef struct orbm_pnp_hyp {      /* one iteration of `iterate` */
+    double R[9], t[3], rep_error;  /* mRi (row-major), mti, compute_pose's return value                                 */
+    int32_t choice;                /* 1..3: which beta approximation won                                                */
+    int32_t n_inliers;             /* mnInliersi                                                                        */
+    int32_t flags;                 /* ORBM_PNP_FLAG_*                                                                   */
+    int32_t reserved;              /* 0: the fourth int32 that keeps the record free of implicit padding                */
+} orbm_pnp_hyp;                    /* 120 bytes, no padding */
+
+typedef struct orbm_pnp_refined {  /* Refine() on one record */
+    int32_t hyp;                   /* the record's hypothesis (position inside the problem)                             */
+    int32_t n_set;                 /* points of the n-point compute_pose = the record's n_inliers                       */
+    int32_t n_inliers;             /* mnRefinedInliers                                                                  */
+    int32_t flags;                 /* ORBM_PNP_FLAG_*                                                                   */
+    double R[9], t[3];             /* mRi, mti after the n-point compute_pose                                           */
+} orbm_pnp_refined;                /* 112 bytes, no padding */
+
+/* B problems (1 .. ORBM_PNP_MAX_BATCH), one enqueue (four kernels back to back), one synchronisation.  Correspondences are CSR per
+ * problem: problem b owns first[b] .. first[b+1]-1, in the order of the constructor's push_backs:
+ *   p3dw[3i..]    mvP3Dw[i] (world position, floats)
+ *   p2d[2i..]     mvP2D[i] = mvKeysUn[.].pt
+ *   max_err[i]    mvMaxError[i] = mvSigma2[i]*th2 in float
+ * Hypotheses are CSR per problem too: problem b owns its_first[b] .. its_first[b+1]-1 (at most ORBM_PNP_MAX_ITS), hypothesis g draws
+ * the correspondences quads[4g..4g+3] (positions inside the problem, 0 .. N_b-1) in drawing order -- EPnP's sums depend on it.
+ * hyp_out[g] is the record of hypothesis g.  mask_out is laid out as orbm_sim3_ransac's: one bit per correspondence, W_b = (N_b + 63) / 64
+ * words per hypothesis, hypothesis-major inside a problem, the problems one after another.
+ * The problem's RECORDS are the strict prefix maxima of n_inliers above best_start among the hypotheses with n_inliers >= min_inliers,
+ * in order: exactly the hypotheses `iterate` would copy into mvbBestInliers.  n_records_out[b] counts them (all of them).  Record r <
+ * ORBM_PNP_MAX_RECORDS of problem b is refined_out[b*ORBM_PNP_MAX_RECORDS + r], its mask W_b words at refined_mask_out[16 * (sum over
+ * b' < b of W_b') + r*W_b]: Refine() on the record's mask -- the n-point compute_pose, then CheckInliers.  Unused slots are zero.
+ * Records beyond ORBM_PNP_MAX_RECORDS are refined by the host routine inside the same call and APPENDED by the caller's leave:
+ * refined_out is sized by the caller for B*ORBM_PNP_MAX_RECORDS + extra_cap records and refined_mask_out for 16 * (sum of W_b) words +
+ * the extra records' W_b words each; the extra records follow in problem order, then record order, from refined_out[B *
+ * ORBM_PNP_MAX_RECORDS] and from the end of the regular mask block.  More extra records than extra_cap: ORB_E_CAPACITY, nothing of the
+ * extras is written (min(H_b, N_b) - ORBM_PNP_MAX_RECORDS per problem always suffices).
+ * Device memory: the handle keeps, and reuses, a block sized by its largest call -- per device problem 120 B per hypothesis, 8 B per mask
+ * word and, for the inlier sets and per-point arrays of the ORBM_PNP_MAX_RECORDS refinements, 16 x 60 B per correspondence (a record's
+ * set can be the whole problem, and how many records there are is known only on the device): 1 MB per 1 000 correspondences, 500 MB for
+ * the largest call there is (64 problems of 8 192).
+ * A NaN is written as the NaN x86 makes from an invalid operation; what a non-finite INPUT gives is unspecified.  A problem beyond
+ * ORBM_PNP_CAP correspondences runs through the host routine inside the same call (orbm_debug_last_pnp, include/orb_debug.h). */
+int orbm_pnp_ransac(orbm_matcher* m, const orbm_pnp_problem* problems, int B, const int32_t* first, const float* p3dw, const float* p2d,
+                    const float* max_err, const int32_t* its_first, const int32_t* quads, orbm_pnp_hyp* hyp_out, uint64_t* mask_out,
+                    int32_t* n_records_out, orbm_pnp_refined* refined_out, uint64_t* refined_mask_out, int extra_cap);
+/* The same routine entirely on the host, no device needed, the same bytes: there is one order. */
+int orbm_pnp_ransac_host(const orbm_pnp_problem* problems, int B, const int32_t* first, const float* p3dw, const float* p2d,
+                         const float* max_err, const int32_t* its_first, const int32_t* quads, orbm_pnp_hyp* hyp_out, uint64_t* mask_out,
+                         int32_t* n_records_out, orbm_pnp_refined* refined_out, uint64_t* refined_mask_out, int extra_cap);
+
+/* The reference's `iterate` loop over precomputed counts and records (host only; the class, the Python wrapper and the tests share it). */
+typedef struct orbm_pnp_walk_state {
+    int32_t iterations;            /* mnIterations                                                                      */
+    int32_t best_inliers;          /* mnBestInliers; start a solver with 0                                              */
+    int32_t best_hyp;              /* the iteration (counted from the solver's first) mBestTcw was taken from; start with -1 */
+    int32_t best_record;           /* the record of THIS block that holds mvbBestInliers, -1 while the best comes from an earlier block */
+    int32_t best_refined_inliers;  /* mnRefinedInliers of Refine() on the current best: carried from block to block; start with 0 */
+    int32_t no_more;               /* bNoMore of the call                                                               */
+    int32_t current;               /* nCurrentIterations of the call in progress                                        */
+    int32_t exhausted;             /* 1: the loop wants iteration `iterations` and the block ends before it: evaluate a continuation
+                                      block (best_start = best_inliers) and call again with the same state               */
+} orbm_pnp_walk_state;
+enum { ORBM_PNP_WALK_NOTHING = 0,  /* the empty cv::Mat                                                                 */
+       ORBM_PNP_WALK_REFINED = 1,  /* mRefinedTcw: Refine() on the current best succeeded                               */
+       ORBM_PNP_WALK_BEST = 2 };   /* mBestTcw: the exit at mnIterations >= mRansacMaxIts                               */
+/* iterate(n_iterations, ...) on a block of evaluated hypotheses: counts[0 .. H-1] are the n_inliers of the iterations block_start ..
+ * block_start + H - 1, rec_hyp[r] / rec_inliers[r] (r < n_rec) the block's records (position inside the block, refined n_inliers).
+ * Transcribed literally: `while(mnIterations<mRansacMaxIts || nCurrentIterations<nIterations)` with ||; a hypothesis becomes the best
+ * with `>= min_inliers` and strict `> mnBestInliers`; Refine() runs on the CURRENT best at every iteration with `>= min_inliers` and
+ * succeeds on strict `> min_inliers`; `mnIterations >= mRansacMaxIts` at the end sets bNoMore and answers mBestTcw when
+ * `mnBestInliers >= min_inliers`.  A call whose state has exhausted == 1 continues the interrupted call (current is kept), any
+ * other starts one.  N < min_inliers answers NOTHING at once with no_more set. */
+int orbm_pnp_walk(const int32_t* counts, int H, int block_start, const int32_t* rec_hyp, const int32_t* rec_inliers, int n_rec, int N,
+                  int min_inliers, int max_its, int n_iterations, orbm_pnp_walk_state* state);
+/* SetRansacParameters' arithmetic: `int nMinInliers = N*mRansacEpsilon` (a float product, truncated as x86 does: INT_MIN for a NaN or
+ * a value out of range), the two lower clamps, epsilon raised to (float)mRansacMinInliers/N, ceil(log(1-p)/log(1-pow(eps,3))) with the
+ * exponent 3, max(1, min(., max_its)).  out2 = {mRansacMaxIts, mRansacMinInliers}, *epsilon_out = mRansacEpsilon. */
+int orbm_pnp_parameters(double probability, int min_inliers, int max_its, int min_set, float epsilon, int N, int32_t* out2, float* epsilon_out);
+/* (test hooks, host only) cvSVD of an m x n matrix, m >= n, row-major: w n values, ut n x m (U transposed), vt n x n (may be NULL);
+ * returns 1 when the random completion ran.  qr_solve(A nr x nc, b nr) -> x nc (left alone on a singular return), returns 1 when
+ * singular; A and b are destroyed.  compute_pose of n points: pws 3n, us 2n doubles, K = fu fv uc vc -> R 9, t 3, out2 = {choice, flags},
+ * returns the reprojection error. */
+int orbm_pnp_svd(const double* A, int m, int n, double* w, double* ut, double* vt);
+int orbm_pnp_qr_solve(double* A, int nr, int nc, double* b, double* x);
+double orbm_pnp_compute_pose(const double* pws, const double* us, int n, const double* K4, double* R9, double* t3, int32_t* out2);
+
 #ifdef __cplusplus
 }
 #endif

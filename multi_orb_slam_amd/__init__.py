@@ -15,5 +15,8 @@ from .matcher import Sim3Problem, sim3_ransac_host, sim3_walk, sim3_iterations, 
 from ._lib import SIM3_PROBLEM_DTYPE, SIM3_HYP_DTYPE, SIM3_MATH_LIBM, SIM3_MATH_DEVICE, SIM3_CAP, SIM3_MAX_ITS, SIM3_MAX_BATCH  # noqa: F401
 from .matcher import Sim3OptProblem, sim3_optimize_host, sim3opt_exp, sim3opt_expmap, sim3opt_ldlt7  # noqa: F401
 from ._lib import SIM3OPT_PROBLEM_DTYPE, SIM3OPT_RESULT_DTYPE, SIM3OPT_CAP, SIM3OPT_MAX_BATCH  # noqa: F401
+from .matcher import PnPProblem, pnp_ransac_host, pnp_walk, pnp_walk_state, pnp_parameters, pnp_svd, pnp_qr_solve, pnp_compute_pose  # noqa: F401
+from ._lib import PNP_PROBLEM_DTYPE, PNP_HYP_DTYPE, PNP_REFINED_DTYPE, PNP_WALK_DTYPE, PNP_CAP, PNP_MAX_ITS, PNP_MAX_BATCH, PNP_MAX_RECORDS  # noqa: F401
+from ._lib import PNP_FLAG_SINGULAR_QR, PNP_FLAG_RANDOM_SVD, PNP_WALK_NOTHING, PNP_WALK_REFINED, PNP_WALK_BEST  # noqa: F401
 from .vocabulary import Vocabulary, BowSearch, Side as BowSide, FeatureVector, score_l1, KeyFrameDatabase  # noqa: F401
 from .vocabulary import TriKeyframe, TRI_OUT_DTYPE, cos_stereo, triangulate_pairs_host  # noqa: F401

@@ -48,6 +48,16 @@ SIM3OPT_RESULT_DTYPE = np.dtype([("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "
                                  ("round", POSE_ROUND_DTYPE, (2,))])   # orbm_sim3opt_result
 assert SIM3OPT_PROBLEM_DTYPE.itemsize == 356 and SIM3OPT_RESULT_DTYPE.itemsize == 136
 SIM3OPT_CAP, SIM3OPT_MAX_BATCH = 8192, 64
+PNP_PROBLEM_DTYPE = np.dtype([("fu", "<f8"), ("fv", "<f8"), ("uc", "<f8"), ("vc", "<f8"), ("min_inliers", "<i4"), ("best_start", "<i4")])   # orbm_pnp_problem
+PNP_HYP_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("rep_error", "<f8"), ("choice", "<i4"), ("n_inliers", "<i4"), ("flags", "<i4"),
+                          ("reserved", "<i4")])   # orbm_pnp_hyp
+PNP_REFINED_DTYPE = np.dtype([("hyp", "<i4"), ("n_set", "<i4"), ("n_inliers", "<i4"), ("flags", "<i4"), ("R", "<f8", (9,)), ("t", "<f8", (3,))])   # orbm_pnp_refined
+PNP_WALK_DTYPE = np.dtype([("iterations", "<i4"), ("best_inliers", "<i4"), ("best_hyp", "<i4"), ("best_record", "<i4"), ("best_refined_inliers", "<i4"),
+                           ("no_more", "<i4"), ("current", "<i4"), ("exhausted", "<i4")])   # orbm_pnp_walk_state
+assert PNP_PROBLEM_DTYPE.itemsize == 40 and PNP_HYP_DTYPE.itemsize == 120 and PNP_REFINED_DTYPE.itemsize == 112 and PNP_WALK_DTYPE.itemsize == 32
+PNP_CAP, PNP_MAX_ITS, PNP_MAX_BATCH, PNP_MAX_RECORDS = 8192, 1024, 64, 16
+PNP_FLAG_SINGULAR_QR, PNP_FLAG_RANDOM_SVD = 1, 2
+PNP_WALK_NOTHING, PNP_WALK_REFINED, PNP_WALK_BEST = 0, 1, 2
 
 ORB_OK, ORB_E_ARG, ORB_E_HIP, ORB_E_CAPACITY, ORB_E_NO_DEVICE, ORB_E_TIMEOUT = 0, -1, -2, -3, -4, -5
 
@@ -290,6 +300,15 @@ def lib():
     L.orbm_sim3opt_expmap.argtypes = [vp, i32, vp]
     L.orbm_sim3opt_ldlt7.argtypes = [vp, vp, vp]
     L.orbm_debug_last_sim3opt.argtypes = [vp, vp]
+    L.orbm_pnp_ransac.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
+    L.orbm_pnp_ransac_host.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
+    L.orbm_pnp_walk.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]
+    L.orbm_pnp_parameters.argtypes = [C.c_double, i32, i32, i32, C.c_float, i32, vp, vp]
+    L.orbm_pnp_svd.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.orbm_pnp_qr_solve.argtypes = [vp, i32, i32, vp, vp]
+    L.orbm_pnp_compute_pose.argtypes = [vp, vp, i32, vp, vp, vp, vp]; L.orbm_pnp_compute_pose.restype = C.c_double
+    L.orbm_debug_last_pnp.argtypes = [vp, vp]
+    L.orbm_debug_pnp_buffers.argtypes = [vp, vp]
     f64 = C.c_double
     L.orbv_create.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp]
     L.orbv_load_text.argtypes = [C.c_char_p, i32, vp]

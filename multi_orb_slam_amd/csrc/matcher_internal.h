@@ -131,6 +131,11 @@ struct orbm_matcher {
     // where the problems of the last call went
     PortBufs<uint8_t> sim3opt;
     int last_sim3opt[2] = {0, 0};
+    // orbm_pnp_ransac (pnp.hip): the packed problems, correspondences (structure of arrays) and quadruples of a call; scratch holds what
+    // one kernel leaves for the next (hypothesis records, counts, mask words) and the per-point arrays of the n-point poses; the
+    // records and mask words the kernels write and where the work of the last call went
+    PortBufs<uint8_t> pnp;
+    int last_pnp[4] = {0, 0, 0, 0};
 };
 namespace morb { hipStream_t side_stream(orbm_matcher* m); }   // (lazily created; NULL after a reported failure)
 

@@ -5,22 +5,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include "ransac_draw.h"
 #include "slam_types.h"
 
 namespace ORB_SLAM2 {
 
 // UNMEASURED placeholder: see Sim3Solver.h
 const long SIM3_HOST_BELOW = 4096;
-
-namespace {
-
-// DUtils::Random::RandomInt (Thirdparty/DBoW2/DUtils/Random.cpp): the arithmetic on rand()
-int RandomInt(int min, int max) {
-    int d = max - min + 1;
-    return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min;
-}
-
-}  // namespace
 
 // src/Sim3Solver.cc:38-153, statement by statement; the per-correspondence cv::Mat vectors are flat float vectors
 Sim3Solver::Sim3Solver(KeyFrame* pKF1, KeyFrame* pKF2, const std::vector<MapPoint*>& vpMatched12, const cv::Mat CalibMatrix, const bool bFixScale)
@@ -123,15 +114,7 @@ void Sim3Solver::Draw() {
     std::vector<size_t> vAvailableIndices;
     mvTriples.reserve(3 * (size_t)mRansacMaxIts);
     for (int it = 0; it < mRansacMaxIts; ++it) {
-        vAvailableIndices.resize((size_t)N);
-        for (int i = 0; i < N; ++i) vAvailableIndices[i] = i;
-        for (short i = 0; i < 3; ++i) {
-            int randi = RandomInt(0, vAvailableIndices.size() - 1);
-            int idx = vAvailableIndices[randi];
-            mvTriples.push_back(idx);
-            vAvailableIndices[randi] = vAvailableIndices.back();
-            vAvailableIndices.pop_back();
-        }
+        RansacDrawSet(vAvailableIndices, N, 3, mvTriples);
     }
 }
 

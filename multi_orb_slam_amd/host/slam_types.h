@@ -104,7 +104,7 @@ public:
     std::vector<cv::KeyPoint> mvKeys;   // camera 1, distorted
     float mfLogScaleFactor = 0; int mnScaleLevels = 0;
     // members host/Optimizer.cc reads (include/Frame.h:226-227, :243)
-    std::vector<float> mvInvLevelSigma2;
+    std::vector<float> mvInvLevelSigma2, mvLevelSigma2;   // (mvLevelSigma2: include/Frame.h:242, read by host/PnPsolver.cc)
     cv::Mat mRcam12, mtcam12;                 // 3x3, 3x1 CV_32F
 
     // pose members (include/Frame.h:82-99, src/Frame.cc:420-499)

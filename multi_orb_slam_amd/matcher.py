@@ -7,6 +7,7 @@ from ._lib import KP_DTYPE, QUERY_DTYPE, POINT_DTYPE, TRACK_DTYPE, REFRESH_DTYPE
 from ._lib import POSE_PROBLEM_DTYPE, POSE_RESULT_DTYPE, POSE_CAM0, POSE_ALL_CAMS, POSE_ORDER_INDEX, POSE_ORDER_DEVICE  # noqa: F401
 from ._lib import SIM3_PROBLEM_DTYPE, SIM3_HYP_DTYPE, SIM3_WALK_DTYPE, SIM3_MATH_LIBM, SIM3_MATH_DEVICE  # noqa: F401
 from ._lib import SIM3OPT_PROBLEM_DTYPE, SIM3OPT_RESULT_DTYPE  # noqa: F401
+from ._lib import PNP_PROBLEM_DTYPE, PNP_HYP_DTYPE, PNP_REFINED_DTYPE, PNP_WALK_DTYPE, PNP_MAX_RECORDS  # noqa: F401
 
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30  # reference src/ORBmatcher.cc:37-39
 # which resolve delivered a search's result (ORBM_FORM_*, include/orb_debug.h; Matcher.last_resolve_form)
@@ -233,6 +234,129 @@ def sim3_iterations(probability, min_inliers, max_its, N):
 def sim3_atan2(y, x):
     """The atan2 sequence of SIM3_MATH_DEVICE (orbm_sim3_atan2): y >= 0, x in [-1, 1]."""
     return float(_lib.lib().orbm_sim3_atan2(float(y), float(x)))
+
+
+class PnPProblem:
+    """One PnPsolver from its constructor's vectors on (orbm_pnp_problem + its correspondences + its drawn quadruples): K = (fx, fy, cx,
+    cy) of the frame (floats, widened to the solver's doubles); p3dw n x 3 (mvP3Dw), p2d n x 2 (mvP2D), max_err n (mvMaxError);
+    quads H x 4 positions 0 .. n-1 in drawing order; min_inliers = mRansacMinInliers after SetRansacParameters; best_start =
+    mnBestInliers on entry."""
+
+    def __init__(self, K, p3dw, p2d, max_err, quads, min_inliers, best_start=0):
+        rec = np.zeros(1, PNP_PROBLEM_DTYPE)
+        for k, v in zip(("fu", "fv", "uc", "vc"), K):
+            rec[k] = float(np.float32(v))
+        rec["min_inliers"] = int(min_inliers); rec["best_start"] = int(best_start)
+        self.rec = rec
+        self.p3dw = np.ascontiguousarray(p3dw, np.float32).reshape(-1, 3)
+        self.p2d = np.ascontiguousarray(p2d, np.float32).reshape(-1, 2)
+        self.max_err = np.ascontiguousarray(max_err, np.float32).reshape(-1)
+        self.quads = np.ascontiguousarray(quads, np.int32).reshape(-1, 4)
+        self.n = len(self.p3dw); self.h = len(self.quads); self.w = (self.n + 63) // 64
+        assert len(self.p2d) == len(self.max_err) == self.n
+
+
+def _pnp_pack(problems):
+    B = len(problems)
+    recs = np.concatenate([p.rec for p in problems])
+    first = np.zeros(B + 1, np.int32); its_first = np.zeros(B + 1, np.int32)
+    first[1:] = np.cumsum([p.n for p in problems]); its_first[1:] = np.cumsum([p.h for p in problems])
+    cat = lambda name, dt, shape: np.ascontiguousarray(np.concatenate([getattr(p, name) for p in problems]).reshape(shape), dt)
+    words = int(sum(p.h * p.w for p in problems))
+    extra = [max(0, min(p.h, p.n) - PNP_MAX_RECORDS) for p in problems]   # always enough (include/orbm.h)
+    rwords = PNP_MAX_RECORDS * int(sum(p.w for p in problems)) + int(sum(e * p.w for e, p in zip(extra, problems)))
+    hyp = np.zeros(max(int(its_first[-1]), 1), PNP_HYP_DTYPE); masks = np.zeros(max(words, 1), np.uint64)
+    n_rec = np.zeros(B, np.int32)
+    refined = np.zeros(B * PNP_MAX_RECORDS + sum(extra), PNP_REFINED_DTYPE); rmasks = np.zeros(max(rwords, 1), np.uint64)
+    args = (ptr(recs), B, ptr(first), ptr(cat("p3dw", np.float32, (-1, 3))), ptr(cat("p2d", np.float32, (-1, 2))),
+            ptr(cat("max_err", np.float32, (-1,))), ptr(its_first), ptr(cat("quads", np.int32, (-1, 4))), ptr(hyp), ptr(masks), ptr(n_rec),
+            ptr(refined), ptr(rmasks), int(sum(extra)))
+    return args, (its_first, hyp, masks, n_rec, refined, rmasks)
+
+
+def _pnp_unpack(problems, out):
+    """-> per problem (PNP_HYP_DTYPE records H, mask words H x W, PNP_REFINED_DTYPE records R, their mask words R x W), R = all records
+    of the problem: the ORBM_PNP_MAX_RECORDS slots first, the appended ones behind."""
+    its_first, hyp, masks, n_rec, refined, rmasks = out
+    B = len(problems)
+    res, w0 = [], 0
+    xr, xw = B * PNP_MAX_RECORDS, PNP_MAX_RECORDS * int(sum(p.w for p in problems))
+    rw0 = 0
+    for b, p in enumerate(problems):
+        nr = int(n_rec[b]); nd = min(nr, PNP_MAX_RECORDS); ne = nr - nd
+        ref = np.concatenate([refined[b * PNP_MAX_RECORDS:b * PNP_MAX_RECORDS + nd], refined[xr:xr + ne]])
+        rm = np.concatenate([rmasks[rw0:rw0 + nd * p.w], rmasks[xw:xw + ne * p.w]]).reshape(nr, p.w)
+        # the unused slots stay zero
+        assert not refined[b * PNP_MAX_RECORDS + nd:(b + 1) * PNP_MAX_RECORDS].view(np.uint8).any()
+        assert not rmasks[rw0 + nd * p.w:rw0 + PNP_MAX_RECORDS * p.w].any()
+        xr += ne; xw += ne * p.w; rw0 += PNP_MAX_RECORDS * p.w
+        res.append((hyp[its_first[b]:its_first[b + 1]].copy(), masks[w0:w0 + p.h * p.w].reshape(p.h, p.w).copy(), ref.copy(), rm.copy()))
+        w0 += p.h * p.w
+    return res
+
+
+def pnp_ransac_host(problems):
+    """orbm_pnp_ransac_host: every hypothesis and every refined record of every problem on the host (no device needed)
+    -> per problem (hypothesis records, mask words H x W, refined records, their mask words)."""
+    args, out = _pnp_pack(problems)
+    check(_lib.lib().orbm_pnp_ransac_host(*args))
+    return _pnp_unpack(problems, out)
+
+
+def pnp_walk_state():
+    """The state of a fresh solver for pnp_walk."""
+    st = np.zeros(1, PNP_WALK_DTYPE)
+    st["best_hyp"] = -1; st["best_record"] = -1
+    return st
+
+
+def pnp_walk(counts, block_start, rec_hyp, rec_inliers, N, min_inliers, max_its, n_iterations, state):
+    """orbm_pnp_walk: PnPsolver::iterate(n_iterations, ...) over a block of evaluated hypotheses (counts; the iterations block_start ..)
+    and the block's records (position inside the block, refined n_inliers); state: PNP_WALK_DTYPE[1], updated in place
+    -> PNP_WALK_NOTHING / PNP_WALK_REFINED / PNP_WALK_BEST."""
+    counts = np.ascontiguousarray(counts, np.int32)
+    rec_hyp = np.ascontiguousarray(rec_hyp, np.int32); rec_inliers = np.ascontiguousarray(rec_inliers, np.int32)
+    ans = _lib.lib().orbm_pnp_walk(ptr(counts), len(counts), int(block_start), ptr(rec_hyp), ptr(rec_inliers), len(rec_hyp), int(N),
+                                   int(min_inliers), int(max_its), int(n_iterations), ptr(state))
+    assert ans >= 0, "orbm_pnp_walk: bad arguments"
+    return int(ans)
+
+
+def pnp_parameters(N, probability=0.99, min_inliers=8, max_its=300, min_set=4, epsilon=0.4):
+    """orbm_pnp_parameters: SetRansacParameters with N correspondences -> (mRansacMaxIts, mRansacMinInliers, mRansacEpsilon float32)."""
+    out = np.zeros(2, np.int32); eps = np.zeros(1, np.float32)
+    assert _lib.lib().orbm_pnp_parameters(float(probability), int(min_inliers), int(max_its), int(min_set), float(np.float32(epsilon)), int(N),
+                                          ptr(out), ptr(eps)) == 0
+    return int(out[0]), int(out[1]), eps[0]
+
+
+def pnp_svd(A):
+    """cvSVD as the library restates it (orbm_pnp_svd) of an m x n float64 matrix, m >= n -> (w n, ut n x m, vt n x n, random branch)."""
+    A = np.ascontiguousarray(A, np.float64)
+    m_, n = A.shape
+    w = np.zeros(n); ut = np.zeros((n, m_)); vt = np.zeros((n, n))
+    r = _lib.lib().orbm_pnp_svd(ptr(A), m_, n, ptr(w), ptr(ut), ptr(vt))
+    assert r >= 0
+    return w, ut, vt, bool(r)
+
+
+def pnp_qr_solve(A, b, x0=None):
+    """qr_solve (orbm_pnp_qr_solve): A nr x nc, b nr -> (x, singular); x0: what x held on entry (it is left alone on a singular return)."""
+    A = np.array(A, np.float64); b = np.array(b, np.float64)
+    nr, nc = A.shape
+    x = np.zeros(nc) if x0 is None else np.array(x0, np.float64)
+    r = _lib.lib().orbm_pnp_qr_solve(ptr(A), nr, nc, ptr(b), ptr(x))
+    assert r >= 0
+    return x, bool(r)
+
+
+def pnp_compute_pose(pws, us, K):
+    """compute_pose of n points (orbm_pnp_compute_pose): pws n x 3, us n x 2 float64, K = fu fv uc vc -> (R 3 x 3, t 3, error, choice, flags)."""
+    pws = np.ascontiguousarray(pws, np.float64).reshape(-1, 3); us = np.ascontiguousarray(us, np.float64).reshape(-1, 2)
+    K = np.ascontiguousarray(K, np.float64)
+    R = np.zeros(9); t = np.zeros(3); out = np.zeros(2, np.int32)
+    err = _lib.lib().orbm_pnp_compute_pose(ptr(pws), ptr(us), len(pws), ptr(K), ptr(R), ptr(t), ptr(out))
+    return R.reshape(3, 3), t, float(err), int(out[0]), int(out[1])
 
 
 class Sim3OptProblem:
@@ -701,6 +825,28 @@ class Matcher:
         out = (C.c_int * 2)()
         check(_lib.lib().orbm_debug_last_sim3opt(self._h, out))
         return tuple(out)
+
+    def pnp_ransac(self, problems):
+        """Every EPnP RANSAC hypothesis of a batch of PnPProblems and Refine() on every record, one enqueue and one synchronisation
+        (orbm_pnp_ransac) -> per problem (hypothesis records, mask words H x W, refined records, their mask words)."""
+        args, out = _pnp_pack(problems)
+        check(_lib.lib().orbm_pnp_ransac(self._h, *args))
+        return _pnp_unpack(problems, out)
+
+    def last_pnp(self):
+        """Where the work of the last pnp_ransac went: (problems on the device, problems through the host routine because of more than
+        PNP_CAP correspondences, records refined on the device, records beyond PNP_MAX_RECORDS refined by the host routine)
+        (orbm_debug_last_pnp)."""
+        out = (C.c_int * 4)()
+        check(_lib.lib().orbm_debug_last_pnp(self._h, out))
+        return tuple(out)
+
+    def pnp_buffers(self):
+        """Capacities in bytes of the buffers pnp_ransac keeps between calls: (staged inputs, device block, mapped results)
+        (orbm_debug_pnp_buffers)."""
+        out = (C.c_ulonglong * 3)()
+        check(_lib.lib().orbm_debug_pnp_buffers(self._h, out))
+        return tuple(int(v) for v in out)
 
     def last_sim3(self):
         """Problems of the last Sim3Ransac by path: (device, host routine because of more than SIM3_CAP correspondences)
