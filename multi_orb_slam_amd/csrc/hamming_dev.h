@@ -41,3 +41,30 @@ static __device__ __forceinline__ void top2_merge_query(const int* __restrict__ 
     }
     best_idx[qi] = I; best_dist[qi] = B; second_dist[qi] = Sd;
 }
+
+// A merging workgroup of a carrier launch (the resolve's: workgroups from `first_block` on; isolated steps only): the slice merge of
+// the camera-pair top-2 that rode in the projection's launch.  The resolve does not need it, the step does -- one kernel and one
+// kernel boundary less between projection and resolve.  Called by every thread of the workgroup, which then returns.
+static __device__ __forceinline__ void merge_carrier_block(const MergeJob& MJ, int first_block) {
+    const int mq = MJ.d_range ? MJ.d_range[2] : MJ.nq;
+    const int qi = ((int)blockIdx.x - first_block) * blockDim.x + threadIdx.x;
+    if (qi < mq) top2_merge_query(MJ.p_idx, MJ.p_best, MJ.p_second, MJ.S, mq, qi, MJ.o_idx, MJ.o_best, MJ.o_second);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");   // (system scope: the results live in mapped host memory)
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_fetch_add(MJ.done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The carrier's side of it.  Every exit of the resolve publishes tagged result words the host takes as "the launch is over": none of
+// them may be written before the merging workgroups of the same launch have released their results.  Called by all threads of the
+// workgroup (s_flag: one int of its LDS); false when the bounded wait gave up -- the status word then says 3 and the host synchronises
+// the stream before it reads anything.
+static __device__ __forceinline__ bool merge_wait(const MergeJob& MJ, int* s_flag) {
+    if (!(MJ.S > 1 && MJ.done)) return true;
+    if (threadIdx.x == 0) {
+        int spins = 0;
+        while ((int)(__hip_atomic_load(MJ.done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) - MJ.target) < 0 && ++spins < (1 << 22)) __builtin_amdgcn_s_sleep(2);
+        *s_flag = spins < (1 << 22) ? 1 : 0;
+    }
+    __syncthreads();
+    return *s_flag != 0;
+}

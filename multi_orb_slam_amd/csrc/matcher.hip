@@ -16,6 +16,7 @@
 #include "orb_common.h"
 #include "frame_sink.h"
 #include "matcher_internal.h"
+#include "resolve_dev.h"
 
 namespace morb {
 
@@ -261,19 +262,7 @@ int orbm_count_ratio_accepted(const int32_t* best_dist, const int32_t* second_di
     return acc;
 }
 
-void orbm_three_maxima(const int* histo, int L, int* ind) {
-    // Keeps the three fullest bins; an earlier bin wins a tie (strict '>'), 2nd/3rd dropped below 10% of the 1st.
-    int m1 = 0, m2 = 0, m3 = 0, i1 = -1, i2 = -1, i3 = -1;
-    for (int i = 0; i < L; i++) {
-        const int s = histo[i];
-        if (s > m1) { m3 = m2; i3 = i2; m2 = m1; i2 = i1; m1 = s; i1 = i; }
-        else if (s > m2) { m3 = m2; i3 = i2; m2 = s; i2 = i; }
-        else if (s > m3) { m3 = s; i3 = i; }
-    }
-    if ((float)m2 < 0.1f * (float)m1) { i2 = -1; i3 = -1; }
-    else if ((float)m3 < 0.1f * (float)m1) { i3 = -1; }
-    ind[0] = i1; ind[1] = i2; ind[2] = i3;
-}
+void orbm_three_maxima(const int* histo, int L, int* ind) { morb::three_maxima(histo, L, ind); }   // (resolve_dev.h: the resolve kernels' own)
 
 extern "C" int morb_debug_phases_matcher(int which, unsigned long long* out64) {   // (experiments: csrc/Makefile PHASES=1)
     return which == 0 ? morb::phases_resolve(out64) : morb::phases_frame_build(out64);

@@ -2,7 +2,8 @@
 // (hamming.hip: all-pairs kernels; frame.hip: frame assembly; search.hip: projection search + resolve; matcher.hip: handle
 // + host helpers; exchange.hip: RCCL / loopback transport; frontend.hip: orbf_*; mappoint.hip: map-point refresh; pose.hip: pose
 // optimisation; sim3.hip: Sim3 RANSAC; sim3opt.hip: Sim3 refinement).  Not part of the C ABI.  Next to it: cv_dev.h / g2o_dev.h (the restated OpenCV and Eigen / g2o
-// operations those ports share), sincos_dev.h, hamming_dev.h, stage_pack.h (the staged input block of a batched call).
+// operations those ports share), sincos_dev.h, hamming_dev.h, resolve_dev.h (the steps the resolve's forms share and their LDS layouts),
+// stage_pack.h (the staged input block of a batched call).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <condition_variable>

@@ -2,16 +2,18 @@
 //   k_project        M3  one wave per query walks the 64x48 grid cells of its window(s) in the reference's visiting order,
 //                    ballot-compacts the survivors in order, gathers their descriptors and keeps a sorted shortlist.
 //                    reference src/ORBmatcher.cc:3547-3592 + src/Frame.cc:574-629.
-//   k_resolve / k_rs_*   the order-dependent part of SearchByProjection (first-come claims, rotation histogram,
-//                    ComputeThreeMaxima) as a fixed-point iteration ON THE DEVICE; host_resolve replays the loop on the host
-//                    as the exact fallback (sweep limit, MORB_HOST_RESOLVE=1).
+//   the resolve      the order-dependent part of SearchByProjection (first-come claims, rotation histogram,
+//                    ComputeThreeMaxima) as a fixed-point iteration ON THE DEVICE, in five forms (search_enqueue chooses):
+//                      k_resolve<POINTS, LDSQ>   Jacobi sweeps in one workgroup (top-2 with ratio test; MORB_RESOLVE_MONO=0)
+//                      k_resolve_mono<RQ, ANG>   the monotone iteration in one workgroup, per-wave passes or worklist rounds
+//                                                (the frame search's default whenever its state fits LDS)
+//                      k_resolve_cams            the monotone iteration, one workgroup per camera (frames beyond one workgroup's LDS)
+//                      k_rs_*                    Jacobi sweeps over the whole chip, one launch per sweep (tables in HBM)
+//                    and host_resolve, which replays the loop on the host as the exact fallback (sweep limit,
+//                    MORB_HOST_RESOLVE=1).  The steps the forms share are written once in resolve_dev.h.
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdlib>
-#include <mutex>
 #include <type_traits>
 #include <vector>
 
@@ -22,6 +24,7 @@
 #include "matcher_internal.h"
 #include "hamming_dev.h"
 #include "project_dev.h"
+#include "resolve_dev.h"
 
 using namespace morb;
 
@@ -47,6 +50,11 @@ __global__ __launch_bounds__(256) void k_project(ProjectArgs A) {
 constexpr int RESOLVE_MAX_Q = 65535;
 MORB_PHASE_DECL(g_ph_res);
 MORB_PHASE_DECL(g_ph_chg);   // (instrumented build) queries whose choice changed, per sweep, accumulated over launches
+#ifdef MORB_PHASE_CLOCKS
+#define MORB_CHG_SLOT(it) ((it) < 15 ? (unsigned long long*)&g_ph_chg[it] : nullptr)   // (mono_pass's counters of round `it`)
+#else
+#define MORB_CHG_SLOT(it) nullptr
+#endif
 
 // RESOLVE_K (above): sorted shortlist per query built by k_project; a full rescan happens only when all of it is taken
 
@@ -77,15 +85,16 @@ __global__ __launch_bounds__(1024) void k_resolve(FrameDev F, const int2* __rest
     // shortlist written by k_project: keys (dist << 16 | visiting position) and feature indices, sorted, occupied excluded
     const int* tk_key = topk;                             // [k*nq + i]
     const int* tk_g = topk + RESOLVE_K * nq;      // [k*nq + i]
-    // LDS after the two claim tables: candidate counts u16[nq] (padded to 4 bytes); with LDSQ also
+    // LDS after the two claim tables (JacobiLds): candidate counts u16[nq]; with LDSQ also
     //   choice[nq] | shortlist (distance << 16 | feature, 0xffff = none) [K][nq] | query angle [nq] | feature angle [F.n_total] | flags [nq] (u8)
-    int* s_claim2 = s_claim + F.n_total;
-    unsigned short* l_cnt = reinterpret_cast<unsigned short*>(s_claim + 2 * F.n_total);   // candidate count of every query
-    int* l_choice = s_claim + 2 * F.n_total + (nq + 1) / 2;
-    int* l_gd = l_choice + nq;
-    float* l_ang = reinterpret_cast<float*>(l_gd + RESOLVE_K * nq);
-    float* l_fang = l_ang + nq;
-    unsigned char* l_fl = reinterpret_cast<unsigned char*>(l_fang + F.n_total);  // bit0 blocks, bit1 list > K, bits 2.. rotation bin + 1
+    const JacobiLds L(F.n_total, nq);
+    int* s_claim2 = lds_at<int>(s_claim, L.claim2());
+    unsigned short* l_cnt = lds_at<unsigned short>(s_claim, L.cnt());   // candidate count of every query
+    int* l_choice = lds_at<int>(s_claim, L.choice());
+    int* l_gd = lds_at<int>(s_claim, L.gd());
+    float* l_ang = lds_at<float>(s_claim, L.ang());
+    float* l_fang = lds_at<float>(s_claim, L.fang());
+    unsigned char* l_fl = lds_at<unsigned char>(s_claim, L.fl());  // bit0 blocks, bit1 list > K, bits 2.. rotation bin + 1
     if (tid == 0) { s_red = 0; s_nres2[0] = 0; s_nres2[1] = 0; }
     for (int g = tid; g < F.n_total; g += T) {  // capacity-sized: rows past the real count are never referenced
         s_claim[g] = 0x7fffffff; s_claim2[g] = 0x7fffffff;
@@ -303,34 +312,14 @@ __global__ __launch_bounds__(1024) void k_resolve(FrameDev F, const int2* __rest
                 const int src = __ffsll((long long)todo) - 1;
                 todo &= todo - 1;
                 const int qi = __builtin_amdgcn_readlane(i, src);
-                const int full = l_cnt[qi];
-                int k1 = 0x7fffffff, k2 = 0x7fffffff, g1 = -1;
-                for (int k0 = 0; k0 < full; k0 += 64) {
-                    const int k = k0 + lane;
-                    int key = 0x7fffffff, g = -1;
-                    if (k < full) {
-                        g = cand_idx[k * nq + qi];
-                        const int d = cand_dist[k * nq + qi];
-                        bool avail = !(occupied && occupied[g]);
-                        if ((unsigned)(rd[g] - tag) < (unsigned)qi) avail = false;
-                        if (avail) key = (d << 16) | k;
-                    }
-                    const int m1 = (int)wave_min_u32((unsigned)key);   // keys are non-negative: unsigned order == signed order
-                    int m2 = 0x7fffffff;
-                    if (POINTS) m2 = (int)wave_min_u32((unsigned)(key == m1 ? 0x7fffffff : key));
-                    // merge the round's (m1 <= m2) into the running (k1 <= k2); the winner's feature comes along by readlane
-                    if (m1 < k1) {
-                        k2 = min(k1, m2); k1 = m1;
-                        g1 = __builtin_amdgcn_readlane(g, __ffsll((long long)__ballot(key == m1)) - 1);   // positions are unique
-                    }
-                    else k2 = min(k2, m1);
-                }
+                const Rescan r = rescan_wave<POINTS>(qi, l_cnt[qi], nq, cand_idx, cand_dist, occupied, lane,
+                                                     [&](int g, int q) { return (unsigned)(rd[g] - tag) < (unsigned)q; });
                 int best = 256, best2 = 256, lvl = -1, lvl2 = -1, bidx = -1;   // (wave-uniform from here on)
-                if (k1 != 0x7fffffff) {
-                    best = k1 >> 16; bidx = g1;
+                if (r.k1 != 0x7fffffff) {
+                    best = r.k1 >> 16; bidx = r.g1;
                     if (POINTS) lvl = F.octave[bidx];
                 }
-                if (POINTS && k2 != 0x7fffffff) { best2 = k2 >> 16; lvl2 = F.octave[cand_idx[(k2 & 0xffff) * nq + qi]]; }
+                if (POINTS && r.k2 != 0x7fffffff) { best2 = r.k2 >> 16; lvl2 = F.octave[cand_idx[(r.k2 & 0xffff) * nq + qi]]; }
                 int rnc = -1;
                 if (best <= th_high && bidx >= 0) {
                     rnc = bidx;
@@ -373,7 +362,8 @@ __global__ __launch_bounds__(1024) void k_resolve(FrameDev F, const int2* __rest
     if (tid == 0) s_red = 0;
     __syncthreads();
     MORB_PHASE(g_ph_res, 52);
-    const float factor = 1.0f / ORBM_HISTO_LENGTH;
+    // (the rotation bin of a match: kept in the query's flags when those live in LDS, otherwise worked out again for the rejection)
+    auto bin_of = [&](int i, int c) { return LDSQ ? rotation_bin(l_ang[i], l_fang[c]) : rotation_bin(__int_as_float(qmeta[i].y), f_angle[c]); };
     int acc = 0;
     for (int i = tid; i < nq; i += T) {
         const int c = LDSQ ? l_choice[i] : choice[i];
@@ -381,22 +371,9 @@ __global__ __launch_bounds__(1024) void k_resolve(FrameDev F, const int2* __rest
         ++acc;
         atomicMax(&s_claim[c], i);
         if (!POINTS && check_ori) {
-            float rot = LDSQ ? l_ang[i] - l_fang[c] : __int_as_float(qmeta[i].y) - f_angle[c];
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == ORBM_HISTO_LENGTH) bin = 0;
-            const bool inr = bin >= 0 && bin < ORBM_HISTO_LENGTH;
-            if (LDSQ) l_fl[i] = (unsigned char)((l_fl[i] & 3) | ((inr ? bin + 1 : 0) << 2));
-            // most matches of a frame share a rotation bin: up to three bins of the wave (those of its first lanes) are
-            // counted with one atomic each, whatever is left (scattered bins: few lanes per address) goes in directly
-            unsigned long long todo = __ballot(inr);
-            for (int rounds = 0; todo && rounds < 3; ++rounds) {
-                const int b0 = __builtin_amdgcn_readlane(bin, __ffsll((long long)todo) - 1);
-                const unsigned long long same = __ballot(inr && bin == b0);
-                if (inr && bin == b0 && lane == __ffsll((long long)same) - 1) atomicAdd(&s_hist[b0], __popcll(same));
-                todo &= ~same;
-            }
-            if (inr && ((todo >> lane) & 1)) atomicAdd(&s_hist[bin], 1);
+            const int bin = bin_of(i, c);
+            if (LDSQ) l_fl[i] = (unsigned char)((l_fl[i] & 3) | ((bin + 1) << 2));
+            hist_add_wave(s_hist, bin >= 0, bin, lane);
         }
     }
     acc = __builtin_amdgcn_readlane(wave_incl_scan(acc), 63);   // wave sum on the DPP path
@@ -405,24 +382,9 @@ __global__ __launch_bounds__(1024) void k_resolve(FrameDev F, const int2* __rest
     MORB_PHASE(g_ph_res, 53);
     if (!POINTS && check_ori) {
         if (tid < 64) {
-            // ComputeThreeMaxima (reference src/ORBmatcher.cc:3948-3989).  Its scan with strict '>' keeps the three fullest
-            // non-empty bins, the earlier bin first among equals: bin b's place is the number of bins that beat it
-            // (fuller, or as full and earlier) -- 30 readlanes on one wave instead of 30 dependent LDS reads on one thread.
-            const int sv = tid < ORBM_HISTO_LENGTH ? s_hist[tid] : 0;
-            int rank = 0;
-#pragma unroll
-            for (int j = 0; j < ORBM_HISTO_LENGTH; ++j) {
-                const int sj = __builtin_amdgcn_readlane(sv, j);
-                rank += (sj > sv || (sj == sv && j < tid)) ? 1 : 0;
-            }
-            const bool in = tid < ORBM_HISTO_LENGTH && sv > 0;
-            const unsigned long long r1 = __ballot(in && rank == 0), r2 = __ballot(in && rank == 1), r3 = __ballot(in && rank == 2);
-            int i1 = r1 ? __ffsll((long long)r1) - 1 : -1, i2 = r2 ? __ffsll((long long)r2) - 1 : -1, i3 = r3 ? __ffsll((long long)r3) - 1 : -1;
-            const int m1 = i1 >= 0 ? __builtin_amdgcn_readlane(sv, i1) : 0, m2 = i2 >= 0 ? __builtin_amdgcn_readlane(sv, i2) : 0,
-                      m3 = i3 >= 0 ? __builtin_amdgcn_readlane(sv, i3) : 0;
-            if ((float)m2 < 0.1f * (float)m1) { i2 = -1; i3 = -1; }
-            else if ((float)m3 < 0.1f * (float)m1) { i3 = -1; }
-            if (tid == 0) { s_keep[0] = i1; s_keep[1] = i2; s_keep[2] = i3; }
+            int keep[3];
+            three_maxima_wave(tid < ORBM_HISTO_LENGTH ? s_hist[tid] : 0, lane, keep);
+            if (tid == 0) { s_keep[0] = keep[0]; s_keep[1] = keep[1]; s_keep[2] = keep[2]; }
         }
         __syncthreads();
         MORB_PHASE(g_ph_res, 54);
@@ -430,16 +392,8 @@ __global__ __launch_bounds__(1024) void k_resolve(FrameDev F, const int2* __rest
         for (int i = tid; i < nq; i += T) {
             const int c = LDSQ ? l_choice[i] : choice[i];
             if (c < 0) continue;
-            int bin;
-            if (LDSQ) {
-                bin = (int)(l_fl[i] >> 2) - 1;  // -1: outside the histogram, never rejected
-            } else {
-                float rot = __int_as_float(qmeta[i].y) - f_angle[c];
-                if (rot < 0.0) rot += 360.0f;
-                bin = (int)roundf(rot * factor);
-                if (bin == ORBM_HISTO_LENGTH) bin = 0;
-            }
-            if (bin >= 0 && bin < ORBM_HISTO_LENGTH && bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) {
+            const int bin = LDSQ ? (int)(l_fl[i] >> 2) - 1 : bin_of(i, c);  // -1: outside the histogram, never rejected
+            if (bin >= 0 && bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) {
                 s_claim[c] = -2;  // every writer stores -2; owners were settled before the barrier
                 ++rej;
             }
@@ -449,12 +403,8 @@ __global__ __launch_bounds__(1024) void k_resolve(FrameDev F, const int2* __rest
         __syncthreads();
     }
     MORB_PHASE(g_ph_res, 60);
-    for (int g = tid; g < NT; g += T) match_of_feature[g] = tagb ? (tagb | (s_claim[g] + 2)) : s_claim[g];
-    // A tagged launch rewrites EVERY word of the frame's capacity, the ones past this frame's count as "no match": a word can
-    // then only carry the current sequence number if this launch stored it (the numbers cycle after 2047 launches; a word
-    // left alone since its last use -- the count dropped, stayed low for a multiple of 2047 launches and rose again -- would
-    // otherwise show the right tag with an old value before this launch's store has crossed PCIe).
-    if (tagb) for (int g = NT + tid; g < F.n_total; g += T) match_of_feature[g] = tagb | 1;
+    write_matches(match_of_feature, s_claim, NT, tagb, tid, T);
+    write_no_match_tail(match_of_feature, NT, F.n_total, tagb, tid, T);
     if (tid == 0) { status[1] = tagb | s_red; status[2] = tagb | it; status[3] = tagb | maxcount; status[0] = tagb | 0; }
     MORB_PHASE(g_ph_res, 61);
 #ifdef MORB_PHASE_CLOCKS
@@ -476,7 +426,7 @@ __global__ __launch_bounds__(1024) void k_resolve(FrameDev F, const int2* __rest
 // So a round is: look at the claim on the current pick (one LDS read and a compare for the ~2/3 of the queries it does not
 // concern); only a displaced query walks on.  Rounds are counted as before (a claim still travels one link of a dependency
 // chain per round) but cost a tenth of a sweep.  Owners, rotation histogram and result words as in k_resolve.  POINTS (top-2 with
-// ratio test), two-window queries and states beyond LDS keep k_resolve.
+// ratio test) and states beyond LDS keep k_resolve; two-window queries (the loop search) come here like any other frame search.
 template <int RQ, bool ANG>
 __global__ __launch_bounds__(1024) void k_resolve_mono(FrameDev F, const int2* __restrict__ qmeta, int nq, int cap,
                                                        const int* __restrict__ cand_idx, const uint16_t* __restrict__ cand_dist,
@@ -485,33 +435,10 @@ __global__ __launch_bounds__(1024) void k_resolve_mono(FrameDev F, const int2* _
                                                        const int* __restrict__ topk, int* __restrict__ match_of_feature,
                                                        int* __restrict__ status, int tagb, MergeJob MJ, int worklist) {
     MORB_LATENCY_KERNEL();
-    // Workgroups behind the first one (isolated steps only) merge the slice partials of the camera-pair top-2 that rode in the projection's
-    // launch: the resolve does not need them, the step does -- one kernel and one kernel boundary less between projection and resolve.
-    if (blockIdx.x > 0) {
-        const int mq = MJ.d_range ? MJ.d_range[2] : MJ.nq;
-        const int qi = (blockIdx.x - 1) * blockDim.x + threadIdx.x;
-        if (qi < mq) top2_merge_query(MJ.p_idx, MJ.p_best, MJ.p_second, MJ.S, mq, qi, MJ.o_idx, MJ.o_best, MJ.o_second);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");   // (system scope: the results live in mapped host memory)
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_fetch_add(MJ.done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
+    if (blockIdx.x > 0) { merge_carrier_block(MJ, 1); return; }   // (the workgroups behind the resolve's: hamming_dev.h)
     extern __shared__ __attribute__((aligned(16))) int s_claim[];  // [0, n): lowest blocking claimant of a feature; [n, 2n): owner (last claimant)
     __shared__ int s_hist[ORBM_HISTO_LENGTH];
-    // Every exit of this workgroup publishes tagged result words the host takes as "the launch is over": none of them may be written
-    // before the merging workgroups of the same launch have released their results.  Called by all threads; false when
-    // the wait gave up -- the status word then says 3 and the host synchronises the stream before it reads anything.
-    __shared__ int s_merge_ok;
-    auto merge_wait = [&]() -> bool {
-        if (!(MJ.S > 1 && MJ.done)) return true;
-        if (threadIdx.x == 0) {
-            int spins = 0;
-            while ((int)(__hip_atomic_load(MJ.done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) - MJ.target) < 0 && ++spins < (1 << 22)) __builtin_amdgcn_s_sleep(2);
-            s_merge_ok = spins < (1 << 22) ? 1 : 0;
-        }
-        __syncthreads();
-        return s_merge_ok != 0;
-    };
+    __shared__ int s_merge_ok;   // (merge_wait's word: every exit below waits for the merging workgroups before its result words)
     __shared__ int s_keep[3];
     __shared__ int s_red;
     __shared__ int s_flag[3];   // "some wave changed something in round it": [it % 3]
@@ -524,18 +451,17 @@ __global__ __launch_bounds__(1024) void k_resolve_mono(FrameDev F, const int2* _
     if (tid < 3) s_flag[tid] = 0;
     const int NT = F.n_total_dev ? *F.n_total_dev : F.n_total;
     const int* tk_g = topk + RESOLVE_K * nq;
-    // LDS (mono_lds_bytes on the host): claims, owners (ints); per query: list length, pick, K shortlist features (u16: the frames
-    // this kernel takes have < 65535 features; 0xffff = none), flags (u8); with ANG the query / feature angles for the rotation
-    // histogram (else they are read from HBM in the tail: what lets 4 x 1000 or 2 x 2000 features in at all)
-    int* s_owner = s_claim + F.n_total;
-    const int nq2 = (nq + 1) & ~1;
-    unsigned short* l_cnt = reinterpret_cast<unsigned short*>(s_owner + F.n_total);
-    unsigned short* l_choice = l_cnt + nq2;
-    unsigned short* l_gd = l_choice + nq2;
-    unsigned char* l_fl = reinterpret_cast<unsigned char*>(l_gd + RESOLVE_K * nq2);  // bit0 blocks, bit1 list > K, bits 2.. rotation bin + 1
-    float* l_ang = reinterpret_cast<float*>(l_fl + ((nq + 3) & ~3));
-    float* l_fang = l_ang + nq;
-    unsigned short* l_wl = reinterpret_cast<unsigned short*>(ANG ? l_fang + F.n_total : l_ang);   // worklist of displaced queries (nq2 entries)
+    // LDS (MonoLds): claims, owners; per query: list length, pick, K shortlist features, flags; with ANG the query / feature angles
+    const MonoLds L(F.n_total, nq, ANG);
+    const int nq2 = (int)L.nq2;   // (the per-query arrays' stride: the layout's own)
+    int* s_owner = lds_at<int>(s_claim, L.owner());
+    unsigned short* l_cnt = lds_at<unsigned short>(s_claim, L.cnt());
+    unsigned short* l_choice = lds_at<unsigned short>(s_claim, L.choice());
+    unsigned short* l_gd = lds_at<unsigned short>(s_claim, L.gd());
+    unsigned char* l_fl = lds_at<unsigned char>(s_claim, L.fl());  // bit0 blocks, bit1 list > K, bits 2.. rotation bin + 1
+    float* l_ang = lds_at<float>(s_claim, L.ang());
+    float* l_fang = lds_at<float>(s_claim, L.fang());
+    unsigned short* l_wl = lds_at<unsigned short>(s_claim, L.wl());   // worklist of displaced queries (nq2 entries)
     __shared__ int s_wl_n[2];
     if (tid == 0) s_red = 0;
     if (tid < ORBM_HISTO_LENGTH) s_hist[tid] = 0;
@@ -585,108 +511,22 @@ __global__ __launch_bounds__(1024) void k_resolve_mono(FrameDev F, const int2* _
     __syncthreads();
     const int maxcount = s_red;
     if (maxcount > cap) {
-        (void)merge_wait();
+        (void)merge_wait(MJ, &s_merge_ok);
         if (tid == 0) { status[1] = tagb | 0; status[2] = tagb | 0; status[3] = tagb | maxcount; status[0] = tagb | 2; }
         return;
     }
     MORB_PHASE(g_ph_res, 2);
-    // one pass over a pair of queries: is the current pick still free of lower blocking claims (one LDS read each, issued
-    // together)?  For a displaced query the claims on ALL later shortlist entries are fetched in one batch, the first free one is
-    // taken and claimed; a dry shortlist that is not the whole list is rescanned by the whole wave (rare).  Returns "somebody in
-    // this wave was displaced".
-#ifdef MORB_PHASE_CLOCKS
-    int it_dbg = 0;
-#endif
+    // one pass over RQ queries of every thread (mono_pass, resolve_dev.h): the table spans the frame, the picks are mirrored in
+    // l_choice (what the queries beyond the registers, the worklist rounds and the tail read)
+    const RescanCtx RC{nq, cand_idx, cand_dist, occupied, th_high, 0};
+    int it = 1, changed = 1;
     auto pass = [&](const int (&qi)[RQ], const int (&e)[RQ][K], int (&c)[RQ], int (&p)[RQ], const int (&fl)[RQ]) -> bool {
-        bool disp[RQ], need_rescan[RQ];
-        int cl[RQ];
-#pragma unroll
-        for (int b = 0; b < RQ; ++b) cl[b] = s_claim[c[b] >= 0 ? (c[b] & 0xffff) : 0];   // (unconditional reads: issued together, no branch)
-#pragma unroll
-        for (int b = 0; b < RQ; ++b) { disp[b] = c[b] >= 0 && cl[b] < qi[b]; need_rescan[b] = false; }  // (only blocking queries write claims; an own claim equals the index)
-        bool any = false;
-#pragma unroll
-        for (int b = 0; b < RQ; ++b) any |= disp[b];
-        const unsigned long long wany = __ballot(any);
-        if (!wany) return false;
-        // (round 6: a register slot b none of whose 64 queries is displaced is skipped by the WAVE -- after the first pass or two a handful
-        //  of lanes are still moving, on one slot, and the wave whose queries depend on everybody else's walks eight passes while the other
-        //  fifteen wait at the round's barrier: its pass went from ~2 us to ~0.6, profiles/r06/notes_experiments.md)
-        {
-            int ck[RQ][K];
-#pragma unroll
-            for (int b = 0; b < RQ; ++b) {
-                if (!__ballot(disp[b])) continue;
-#pragma unroll
-                for (int k = 1; k < K; ++k) {
-                    const bool want = disp[b] && k > p[b] && (e[b][k] & 0xffff) != 0xffff;
-                    const int v = s_claim[want ? (e[b][k] & 0xffff) : 0];   // (the reads of a slot are in flight together.  Measured: asking
-                    ck[b][k] = want ? v : -1;                               // for the next entry alone first costs a third trip more often than it saves reads)
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < RQ; ++b) {
-                if (!__ballot(disp[b])) continue;
-                if (!disp[b]) continue;
-                const int i = qi[b];
-#ifdef MORB_PHASE_CLOCKS
-                if (it_dbg < 15) atomicAdd((unsigned long long*)&g_ph_chg[it_dbg], 1ull);
-#endif
-                int nk = K;
-#pragma unroll
-                for (int k = K - 1; k >= 1; --k) if (ck[b][k] >= i) nk = k;
-                int ne = 0xffff;
-#pragma unroll
-                for (int k = 1; k < K; ++k) if (nk == k) ne = e[b][k];
-                if (nk < K) {
-                    c[b] = ne; p[b] = nk; l_choice[i] = (unsigned short)ne;
-                    if (fl[b] & 1) atomicMin(&s_claim[ne], i);
-                } else {
-                    c[b] = -1; l_choice[i] = 0xffff;
-                    // the shortlist is exact unless it ran dry while longer lists exist: rescanned right below
-                    need_rescan[b] = (fl[b] & 2) != 0;
-                    p[b] = K;
-                }
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < RQ; ++b) {
-            unsigned long long todo = __ballot(need_rescan[b]);
-#ifdef MORB_PHASE_CLOCKS
-            if (todo && lane == 0 && it_dbg < 15) atomicAdd((unsigned long long*)&g_ph_chg[16 + it_dbg], (unsigned long long)__popcll(todo));
-#endif
-            while (todo) {
-                const int src = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                const int q = __builtin_amdgcn_readlane(qi[b], src);
-                const int full = l_cnt[q];
-                int k1 = 0x7fffffff, g1 = -1;
-                for (int k0 = 0; k0 < full; k0 += 64) {
-                    const int k = k0 + lane;
-                    int key = 0x7fffffff, gg = -1;
-                    if (k < full) {
-                        gg = cand_idx[k * nq + q];
-                        const int d = cand_dist[k * nq + q];
-                        bool avail = !(occupied && occupied[gg]);
-                        if (s_claim[gg] < q) avail = false;
-                        if (avail) key = (d << 16) | k;
-                    }
-                    const int m1 = (int)wave_min_u32((unsigned)key);
-                    if (m1 < k1) { k1 = m1; g1 = __builtin_amdgcn_readlane(gg, __ffsll((long long)__ballot(key == m1)) - 1); }
-                }
-                if (lane == src && k1 != 0x7fffffff && (k1 >> 16) <= th_high) {   // the rescanned pick is the entry under the cursor from now on
-                    c[b] = g1; l_choice[q] = (unsigned short)g1;
-                    if (fl[b] & 1) atomicMin(&s_claim[g1], q);
-                }
-            }
-        }
-        return true;
+        [[clang::always_inline]] return mono_pass<RQ>(s_claim, qi, e, c, p, fl, l_choice, RC, [&](int q) { return (int)l_cnt[q]; }, lane, MORB_CHG_SLOT(it));
     };
     // A ROUND = every wave repeats its pass until none of ITS queries is displaced (no barrier in between: what the other waves
     // claim meanwhile is seen as it lands -- the iteration is monotone, so any interleaving ends in the same place), then one
     // barrier; a round in which no wave saw anything displaced is the fixed point.  Dependency chains are followed at the pace
     // of a pass (two LDS trips), not of a barrier: the benchmark stream needs 2-3 rounds where the Jacobi form needs 9 sweeps.
-    int it = 1, changed = 1;
     if (worklist) {
         // ---- round 6: the rounds as a WORKLIST.  Above, a wave repeats its pass over its own queries until none of them is displaced,
         // and the wave whose queries depend on everybody else's walks up to eight ~1.7 us passes while fifteen waves wait at the round's
@@ -738,21 +578,9 @@ __global__ __launch_bounds__(1024) void k_resolve_mono(FrameDev F, const int2* _
                     for (int k = 0; k < K; ++k) e[k] = l_gd[k * nq2 + i];
 #pragma unroll
                     for (int k = K - 1; k >= 0; --k) if (e[k] == c) p = k;   // (a rescanned pick is not on the shortlist: cursor at the end)
-                    int ck[K];
-#pragma unroll
-                    for (int k = 1; k < K; ++k) {
-                        const bool want = k > p && e[k] != 0xffff;
-                        const int v = s_claim[want ? e[k] : 0];
-                        ck[k] = want ? v : -1;
-                    }
-                    int nk = K;
-#pragma unroll
-                    for (int k = K - 1; k >= 1; --k) if (ck[k] >= i) nk = k;
-                    int ne = 0xffff;
-#pragma unroll
-                    for (int k = 1; k < K; ++k) if (nk == k) ne = e[k];
-                    l_choice[i] = (unsigned short)ne;
-                    if (nk < K) { if (fl & 1) atomicMin(&s_claim[ne], i); }
+                    const Advance a = shortlist_advance(e, p, i, s_claim);
+                    l_choice[i] = (unsigned short)a.ne;
+                    if (a.nk < K) { if (fl & 1) atomicMin(&s_claim[a.ne], i); }
                     else need_rescan = (fl & 2) != 0;   // the shortlist ran dry while the list is longer: rescanned by the wave
                 }
                 unsigned long long todo = __ballot(need_rescan);
@@ -760,24 +588,11 @@ __global__ __launch_bounds__(1024) void k_resolve_mono(FrameDev F, const int2* _
                     const int src = __ffsll((long long)todo) - 1;
                     todo &= todo - 1;
                     const int q = __builtin_amdgcn_readlane(i, src);
-                    const int full = l_cnt[q];
-                    int k1 = 0x7fffffff, g1 = -1;
-                    for (int k0 = 0; k0 < full; k0 += 64) {
-                        const int k = k0 + lane;
-                        int key = 0x7fffffff, gg = -1;
-                        if (k < full) {
-                            gg = cand_idx[k * nq + q];
-                            const int d = cand_dist[k * nq + q];
-                            bool avail = !(occupied && occupied[gg]);
-                            if (s_claim[gg] < q) avail = false;
-                            if (avail) key = (d << 16) | k;
-                        }
-                        const int m1 = (int)wave_min_u32((unsigned)key);
-                        if (m1 < k1) { k1 = m1; g1 = __builtin_amdgcn_readlane(gg, __ffsll((long long)__ballot(key == m1)) - 1); }
-                    }
-                    if (lane == src && k1 != 0x7fffffff && (k1 >> 16) <= th_high) {
-                        l_choice[q] = (unsigned short)g1;
-                        if (fl & 1) atomicMin(&s_claim[g1], q);
+                    const Rescan r = rescan_wave<false>(q, l_cnt[q], nq, cand_idx, cand_dist, occupied, lane,
+                                                        [&](int g, int q_) { return s_claim[g] < q_; });
+                    if (lane == src && r.k1 != 0x7fffffff && (r.k1 >> 16) <= th_high) {
+                        l_choice[q] = (unsigned short)r.g1;
+                        if (fl & 1) atomicMin(&s_claim[r.g1], q);
                     }
                 }
             }
@@ -789,9 +604,6 @@ __global__ __launch_bounds__(1024) void k_resolve_mono(FrameDev F, const int2* _
 #pragma unroll
     for (int b = 0; b < RQ; ++b) qi01[b] = b * T + tid;
     for (; it < max_it && changed; ++it) {
-#ifdef MORB_PHASE_CLOCKS
-        it_dbg = it;
-#endif
         if (tid == 0) s_flag[(it + 1) % 3] = 0;   // (last read two rounds ago)
         bool ch = false;
         for (int guard = 0; guard < 4096; ++guard) {
@@ -820,8 +632,8 @@ __global__ __launch_bounds__(1024) void k_resolve_mono(FrameDev F, const int2* _
             }
             if (!w) {
 #ifdef MORB_PHASE_CLOCKS
-                if (lane == 0 && it_dbg < 15) atomicMax((unsigned long long*)&g_ph_chg[32 + it_dbg], (unsigned long long)guard);
-                if (lane == 0 && it_dbg == 1 && blockIdx.x == 0) g_ph_chg[48 + (tid >> 6)] = ((unsigned long long)guard << 32) | (unsigned long long)(wall_clock64() - g_ph_res[0]);   // when this wave left round 1, after how many passes
+                if (lane == 0 && it < 15) atomicMax((unsigned long long*)&g_ph_chg[32 + it], (unsigned long long)guard);
+                if (lane == 0 && it == 1 && blockIdx.x == 0) g_ph_chg[48 + (tid >> 6)] = ((unsigned long long)guard << 32) | (unsigned long long)(wall_clock64() - g_ph_res[0]);   // when this wave left round 1, after how many passes
 #endif
                 break;
             }
@@ -834,7 +646,7 @@ __global__ __launch_bounds__(1024) void k_resolve_mono(FrameDev F, const int2* _
     }
     }
     if (changed) {  // ran out of rounds
-        (void)merge_wait();
+        (void)merge_wait(MJ, &s_merge_ok);
         if (tid == 0) { status[1] = tagb | 0; status[2] = tagb | it; status[3] = tagb | maxcount; status[0] = tagb | 1; }
         return;
     }
@@ -842,7 +654,6 @@ __global__ __launch_bounds__(1024) void k_resolve_mono(FrameDev F, const int2* _
     __syncthreads();
     MORB_PHASE(g_ph_res, 52);
     // owners: the last claimant in query order (claims after a blocking one are impossible, so max index == final owner)
-    const float factor = 1.0f / ORBM_HISTO_LENGTH;
     int acc = 0;
     for (int i = tid; i < nq; i += T) {
         const int c = l_choice[i] == 0xffff ? -1 : (int)l_choice[i];
@@ -850,20 +661,9 @@ __global__ __launch_bounds__(1024) void k_resolve_mono(FrameDev F, const int2* _
         ++acc;
         atomicMax(&s_owner[c], i);
         if (check_ori) {
-            float rot = ANG ? l_ang[i] - l_fang[c] : __int_as_float(qmeta[i].y) - f_angle[c];
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == ORBM_HISTO_LENGTH) bin = 0;
-            const bool inr = bin >= 0 && bin < ORBM_HISTO_LENGTH;
-            l_fl[i] = (unsigned char)((l_fl[i] & 3) | ((inr ? bin + 1 : 0) << 2));
-            unsigned long long todo = __ballot(inr);
-            for (int r = 0; todo && r < 3; ++r) {
-                const int b0 = __builtin_amdgcn_readlane(bin, __ffsll((long long)todo) - 1);
-                const unsigned long long same = __ballot(inr && bin == b0);
-                if (inr && bin == b0 && lane == __ffsll((long long)same) - 1) atomicAdd(&s_hist[b0], __popcll(same));
-                todo &= ~same;
-            }
-            if (inr && ((todo >> lane) & 1)) atomicAdd(&s_hist[bin], 1);
+            const int bin = ANG ? rotation_bin(l_ang[i], l_fang[c]) : rotation_bin(__int_as_float(qmeta[i].y), f_angle[c]);
+            l_fl[i] = (unsigned char)((l_fl[i] & 3) | ((bin + 1) << 2));
+            hist_add_wave(s_hist, bin >= 0, bin, lane);
         }
     }
     acc = __builtin_amdgcn_readlane(wave_incl_scan(acc), 63);
@@ -871,22 +671,10 @@ __global__ __launch_bounds__(1024) void k_resolve_mono(FrameDev F, const int2* _
     __syncthreads();
     MORB_PHASE(g_ph_res, 53);
     if (check_ori) {
-        if (tid < 64) {   // ComputeThreeMaxima (reference src/ORBmatcher.cc:3948-3989), as in k_resolve
-            const int sv = tid < ORBM_HISTO_LENGTH ? s_hist[tid] : 0;
-            int rank = 0;
-#pragma unroll
-            for (int j = 0; j < ORBM_HISTO_LENGTH; ++j) {
-                const int sj = __builtin_amdgcn_readlane(sv, j);
-                rank += (sj > sv || (sj == sv && j < tid)) ? 1 : 0;
-            }
-            const bool in = tid < ORBM_HISTO_LENGTH && sv > 0;
-            const unsigned long long r1 = __ballot(in && rank == 0), r2 = __ballot(in && rank == 1), r3 = __ballot(in && rank == 2);
-            int i1 = r1 ? __ffsll((long long)r1) - 1 : -1, i2 = r2 ? __ffsll((long long)r2) - 1 : -1, i3 = r3 ? __ffsll((long long)r3) - 1 : -1;
-            const int m1 = i1 >= 0 ? __builtin_amdgcn_readlane(sv, i1) : 0, m2 = i2 >= 0 ? __builtin_amdgcn_readlane(sv, i2) : 0,
-                      m3 = i3 >= 0 ? __builtin_amdgcn_readlane(sv, i3) : 0;
-            if ((float)m2 < 0.1f * (float)m1) { i2 = -1; i3 = -1; }
-            else if ((float)m3 < 0.1f * (float)m1) { i3 = -1; }
-            if (tid == 0) { s_keep[0] = i1; s_keep[1] = i2; s_keep[2] = i3; }
+        if (tid < 64) {
+            int keep[3];
+            three_maxima_wave(tid < ORBM_HISTO_LENGTH ? s_hist[tid] : 0, lane, keep);
+            if (tid == 0) { s_keep[0] = keep[0]; s_keep[1] = keep[1]; s_keep[2] = keep[2]; }
         }
         __syncthreads();
         MORB_PHASE(g_ph_res, 54);
@@ -895,7 +683,7 @@ __global__ __launch_bounds__(1024) void k_resolve_mono(FrameDev F, const int2* _
             const int c = l_choice[i] == 0xffff ? -1 : (int)l_choice[i];
             if (c < 0) continue;
             const int bin = (int)(l_fl[i] >> 2) - 1;  // -1: outside the histogram, never rejected
-            if (bin >= 0 && bin < ORBM_HISTO_LENGTH && bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) {
+            if (bin >= 0 && bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) {
                 s_owner[c] = -2;  // every writer stores -2; owners were settled before the barrier
                 ++rej;
             }
@@ -905,9 +693,9 @@ __global__ __launch_bounds__(1024) void k_resolve_mono(FrameDev F, const int2* _
         __syncthreads();
     }
     MORB_PHASE(g_ph_res, 60);
-    const bool merged = merge_wait();   // (the merging workgroups of this launch finished long ago; the result words below must not say so before they have)
-    for (int g = tid; g < NT; g += T) match_of_feature[g] = tagb ? (tagb | (s_owner[g] + 2)) : s_owner[g];
-    if (tagb) for (int g = NT + tid; g < F.n_total; g += T) match_of_feature[g] = tagb | 1;   // (see k_resolve: no stale tag can match)
+    const bool merged = merge_wait(MJ, &s_merge_ok);   // (the merging workgroups of this launch finished long ago; the result words below must not say so before they have)
+    write_matches(match_of_feature, s_owner, NT, tagb, tid, T);
+    write_no_match_tail(match_of_feature, NT, F.n_total, tagb, tid, T);
     if (tid == 0) { status[1] = tagb | s_red; status[2] = tagb | it; status[3] = tagb | maxcount; status[0] = tagb | (merged ? 0 : 3); }
     MORB_PHASE(g_ph_res, 61);
 #ifdef MORB_PHASE_CLOCKS
@@ -1025,14 +813,7 @@ __global__ __launch_bounds__(256) void k_rs_owner(const orbm_query* __restrict__
     const unsigned long long any = __ballot(c >= 0);
     if (lane == 0 && any) atomicAdd(&s_hist[ORBM_HISTO_LENGTH], __popcll(any));
     if (check_ori) {
-        int bin = -1;
-        if (c >= 0) {
-            float rot = q[i].angle - f_angle[c];
-            if (rot < 0.0) rot += 360.0f;
-            bin = (int)roundf(rot * (1.0f / ORBM_HISTO_LENGTH));
-            if (bin == ORBM_HISTO_LENGTH) bin = 0;
-            if (bin < 0 || bin >= ORBM_HISTO_LENGTH) bin = -1;
-        }
+        const int bin = c >= 0 ? rotation_bin(q[i].angle, f_angle[c]) : -1;
         if (bin >= 0) atomicAdd(&s_hist[bin], 1);
     }
     __syncthreads();
@@ -1047,18 +828,7 @@ __global__ __launch_bounds__(256) void k_rs_reject(const orbm_query* __restrict_
     MORB_LATENCY_KERNEL_WIDE();
     if (state[0] > cap || state[8 + state[5] - 1] != 0) return;
     __shared__ int s_keep[3];
-    if (threadIdx.x == 0) {  // reference src/ORBmatcher.cc:3948-3989
-        int m1 = 0, m2 = 0, m3 = 0, i1 = -1, i2 = -1, i3 = -1;
-        for (int b = 0; b < ORBM_HISTO_LENGTH; ++b) {
-            const int sz = state[48 + b];
-            if (sz > m1) { m3 = m2; i3 = i2; m2 = m1; i2 = i1; m1 = sz; i1 = b; }
-            else if (sz > m2) { m3 = m2; i3 = i2; m2 = sz; i2 = b; }
-            else if (sz > m3) { m3 = sz; i3 = b; }
-        }
-        if ((float)m2 < 0.1f * (float)m1) { i2 = -1; i3 = -1; }
-        else if ((float)m3 < 0.1f * (float)m1) { i3 = -1; }
-        s_keep[0] = i1; s_keep[1] = i2; s_keep[2] = i3;
-    }
+    if (threadIdx.x == 0) three_maxima(state + 48, ORBM_HISTO_LENGTH, s_keep);
     __syncthreads();
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63;
@@ -1066,11 +836,8 @@ __global__ __launch_bounds__(256) void k_rs_reject(const orbm_query* __restrict_
     if (i < nq) {
         const int c = choice[i];
         if (c >= 0) {
-            float rot = q[i].angle - f_angle[c];
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int)roundf(rot * (1.0f / ORBM_HISTO_LENGTH));
-            if (bin == ORBM_HISTO_LENGTH) bin = 0;
-            if (bin >= 0 && bin < ORBM_HISTO_LENGTH && bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) {
+            const int bin = rotation_bin(q[i].angle, f_angle[c]);
+            if (bin >= 0 && bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) {
                 owner[c] = -2;  // every writer stores -2; the owners were settled by the previous kernel
                 rej = true;
             }
@@ -1106,11 +873,11 @@ __global__ __launch_bounds__(256) void k_rs_write(int NT_host, const int* __rest
 // (ordered compaction over the {blocks | camera << 1} words k_project left), keeps that camera's claim and owner tables in LDS
 // (8 bytes per feature: 32 KB for 4000 features, against 256 KB for the whole 8-camera frame, which is what sent these frames to
 // one launch per sweep before) and runs the monotone iteration of k_resolve_mono on them with every query in registers (four per
-// thread: up to 4096 queries per camera).  What needs the WHOLE frame -- the rotation histogram's three maxima and the rejection
-// behind them -- stays with k_rs_reject / k_rs_write, fed through the same `state` words as the per-sweep form:
-// this kernel leaves choice[] (global feature index or -1 per query), owner[] per feature, state[0] (longest list), state[1]
-// (matches), state[5] = 1 and state[8] = "did not finish" (tables or queries beyond this launch's limits, or out of rounds:
-// the exact host fallback takes over, search_finish), state[48..78) the histogram.
+// thread: up to 4096 queries per camera).  What needs the WHOLE frame -- the rotation histogram's three maxima -- is summed across the
+// workgroups in `state` (device memory, zero between launches): the cameras meet there once, then every workgroup ranks the frame's
+// histogram itself, rejects its own camera's matches outside the three fullest bins and writes its own camera's result words; the
+// last one out writes the status words and leaves `state` zeroed.  state[8] = "did not finish" (tables or queries beyond this
+// launch's limits, or out of rounds): the status says 1 and the exact host fallback takes over (search_finish).
 constexpr int RSC_RQ = 4;
 // n != 0: the queries are camera-contiguous (queries built from the previous frame's features; host lists in camera order) and camera
 // c's are [start[c], start[c + 1]) -- the workgroup then neither scans the query words for its camera nor gathers indices (8 x 4000
@@ -1124,15 +891,7 @@ __global__ __launch_bounds__(1024) void k_resolve_cams(FrameDev F, const int* __
                                                        int* __restrict__ match_of_feature, int* __restrict__ status, int tagb, int n_res,
                                                        MergeJob MJ, QRanges QR) {
     MORB_LATENCY_KERNEL();
-    if ((int)blockIdx.x >= n_res) {   // workgroups behind the cameras' (isolated steps): the slice merge of the camera-pair top-2, as in k_resolve_mono
-        const int mq = MJ.d_range ? MJ.d_range[2] : MJ.nq;
-        const int qi_ = ((int)blockIdx.x - n_res) * blockDim.x + threadIdx.x;
-        if (qi_ < mq) top2_merge_query(MJ.p_idx, MJ.p_best, MJ.p_second, MJ.S, mq, qi_, MJ.o_idx, MJ.o_best, MJ.o_second);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_fetch_add(MJ.done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
+    if ((int)blockIdx.x >= n_res) { merge_carrier_block(MJ, n_res); return; }   // (the workgroups behind the cameras', as in k_resolve_mono)
     extern __shared__ __attribute__((aligned(16))) int s_claim[];  // [0, nf_cap): lowest blocking claimant (global query index); [nf_cap, 2 nf_cap): owner
     __shared__ int s_hist[ORBM_HISTO_LENGTH];
     __shared__ int s_red, s_cnt, s_code, s_last;
@@ -1143,8 +902,9 @@ __global__ __launch_bounds__(1024) void k_resolve_cams(FrameDev F, const int* __
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cam = blockIdx.x;
     const int f0 = f_cam_start[cam], nf = f_cam_start[cam + 1] - f0;
-    int* s_owner = s_claim + nf_cap;
-    unsigned short* l_q = reinterpret_cast<unsigned short*>(s_owner + nf_cap);   // the camera's queries, ascending (global indices < 65536)
+    const CamsLds L(nf_cap, RQ * T);
+    int* s_owner = lds_at<int>(s_claim, L.owner());
+    unsigned short* l_q = lds_at<unsigned short>(s_claim, L.queries());   // the camera's queries, ascending (global indices < 65536)
     const int* tk_g = topk + K * nq;
     MORB_PHASE(g_ph_res, 0);   // (stamps of camera 0's workgroup: start, counted, gathered, set up, rounds done, owners, end; slot 1 = 2: this layout)
     if (tid < 3) s_flag[tid] = 0;
@@ -1229,81 +989,11 @@ __global__ __launch_bounds__(1024) void k_resolve_cams(FrameDev F, const int* __
     MORB_PHASE(g_ph_res, 4);
     if (tid == 0 && maxcount > 0) atomicMax(&state[0], maxcount);
     if (maxcount > cap) return 2;   // (reported through the status words, the search is repeated with more room)
-    // one pass over this thread's queries: k_resolve_mono's, with local feature indices into the tables and global query indices
-    // as the claims' values
+    // one pass over this thread's queries: k_resolve_mono's (mono_pass), with local feature indices into the camera's table and
+    // global query indices as the claims' values; the picks live in registers only
+    const RescanCtx RC{nq, cand_idx, cand_dist, occupied, th_high, f0};
     auto pass = [&]() -> bool {
-        bool disp[RQ], need_rescan[RQ];
-        int cl[RQ];
-#pragma unroll
-        for (int b = 0; b < RQ; ++b) cl[b] = s_claim[cur[b] >= 0 ? cur[b] : 0];
-#pragma unroll
-        for (int b = 0; b < RQ; ++b) { disp[b] = cur[b] >= 0 && cl[b] < qi[b]; need_rescan[b] = false; }
-        bool any = false;
-#pragma unroll
-        for (int b = 0; b < RQ; ++b) any |= disp[b];
-        if (!__ballot(any)) return false;
-        {   // (slots none of whose queries is displaced are skipped by the wave: see k_resolve_mono)
-            int ck[RQ][K];
-#pragma unroll
-            for (int b = 0; b < RQ; ++b) {
-                if (!__ballot(disp[b])) continue;
-#pragma unroll
-                for (int k = 1; k < K; ++k) {
-                    const bool want = disp[b] && k > pos[b] && sl[b][k] != 0xffff;
-                    const int v = s_claim[want ? sl[b][k] : 0];
-                    ck[b][k] = want ? v : -1;
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < RQ; ++b) {
-                if (!__ballot(disp[b])) continue;
-                if (!disp[b]) continue;
-                const int i = qi[b];
-                int nk = K;
-#pragma unroll
-                for (int k = K - 1; k >= 1; --k) if (ck[b][k] >= i) nk = k;
-                int ne = 0xffff;
-#pragma unroll
-                for (int k = 1; k < K; ++k) if (nk == k) ne = sl[b][k];
-                if (nk < K) {
-                    cur[b] = ne; pos[b] = nk;
-                    if (flr[b] & 1) atomicMin(&s_claim[ne], i);
-                } else {
-                    cur[b] = -1; pos[b] = K;
-                    need_rescan[b] = (flr[b] & 2) != 0;   // the shortlist ran dry while the list is longer: rescanned by the wave
-                }
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < RQ; ++b) {
-            unsigned long long todo = __ballot(need_rescan[b]);
-            while (todo) {
-                const int src = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                const int q = __builtin_amdgcn_readlane(qi[b], src);
-                const int full = cand_count[q];
-                int k1 = 0x7fffffff, g1 = -1;
-                for (int k0 = 0; k0 < full; k0 += 64) {
-                    const int k = k0 + lane;
-                    int key = 0x7fffffff, gg = -1;
-                    if (k < full) {
-                        const int gglob = cand_idx[k * nq + q];
-                        const int d = cand_dist[k * nq + q];
-                        gg = gglob - f0;
-                        bool avail = !(occupied && occupied[gglob]);
-                        if (s_claim[gg] < q) avail = false;
-                        if (avail) key = (d << 16) | k;
-                    }
-                    const int m1 = (int)wave_min_u32((unsigned)key);
-                    if (m1 < k1) { k1 = m1; g1 = __builtin_amdgcn_readlane(gg, __ffsll((long long)__ballot(key == m1)) - 1); }
-                }
-                if (lane == src && k1 != 0x7fffffff && (k1 >> 16) <= th_high) {
-                    cur[b] = g1;
-                    if (flr[b] & 1) atomicMin(&s_claim[g1], q);
-                }
-            }
-        }
-        return true;
+        [[clang::always_inline]] return mono_pass<RQ>(s_claim, qi, sl, cur, pos, flr, nullptr, RC, [&](int q) { return cand_count[q]; }, lane, nullptr);
     };
     int changed = 1;
     for (; it < max_it && changed; ++it) {
@@ -1320,21 +1010,13 @@ __global__ __launch_bounds__(1024) void k_resolve_cams(FrameDev F, const int* __
     if (changed) return 1;  // ran out of rounds
     MORB_PHASE(g_ph_res, 5);
     // owners (the last claimant in query order), this camera's share of the rotation histogram and of the match count
-    const float factor = 1.0f / ORBM_HISTO_LENGTH;
 #pragma unroll
     for (int b = 0; b < RQ; ++b) {
         const int i = qi[b], c = cur[b];
         bin_of[b] = -1;
         if (c >= 0) { ++acc; atomicMax(&s_owner[c], i); }
         if (check_ori) {
-            int bin = -1;
-            if (c >= 0) {
-                float rot = __int_as_float(qmeta[i].y) - f_angle[c + f0];
-                if (rot < 0.0) rot += 360.0f;
-                bin = (int)roundf(rot * factor);
-                if (bin == ORBM_HISTO_LENGTH) bin = 0;
-                if (bin < 0 || bin >= ORBM_HISTO_LENGTH) bin = -1;
-            }
+            const int bin = c >= 0 ? rotation_bin(__int_as_float(qmeta[i].y), f_angle[c + f0]) : -1;
             bin_of[b] = bin;
             if (bin >= 0) atomicAdd(&s_hist[bin], 1);
         }
@@ -1365,22 +1047,10 @@ __global__ __launch_bounds__(1024) void k_resolve_cams(FrameDev F, const int* __
     if (all == 0) {
         int kept = 0;
         if (check_ori) {
-            if (tid < 64) {   // ComputeThreeMaxima (reference src/ORBmatcher.cc:3948-3989) over the frame's histogram, by every camera alike
-                const int sv = tid < ORBM_HISTO_LENGTH ? __hip_atomic_load(&state[48 + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-                int rank = 0;
-#pragma unroll
-                for (int j = 0; j < ORBM_HISTO_LENGTH; ++j) {
-                    const int sj = __builtin_amdgcn_readlane(sv, j);
-                    rank += (sj > sv || (sj == sv && j < tid)) ? 1 : 0;
-                }
-                const bool in = tid < ORBM_HISTO_LENGTH && sv > 0;
-                const unsigned long long r1 = __ballot(in && rank == 0), r2 = __ballot(in && rank == 1), r3 = __ballot(in && rank == 2);
-                int i1 = r1 ? __ffsll((long long)r1) - 1 : -1, i2 = r2 ? __ffsll((long long)r2) - 1 : -1, i3 = r3 ? __ffsll((long long)r3) - 1 : -1;
-                const int m1 = i1 >= 0 ? __builtin_amdgcn_readlane(sv, i1) : 0, m2 = i2 >= 0 ? __builtin_amdgcn_readlane(sv, i2) : 0,
-                          m3 = i3 >= 0 ? __builtin_amdgcn_readlane(sv, i3) : 0;
-                if ((float)m2 < 0.1f * (float)m1) { i2 = -1; i3 = -1; }
-                else if ((float)m3 < 0.1f * (float)m1) { i3 = -1; }
-                if (tid == 0) { s_keep[0] = i1; s_keep[1] = i2; s_keep[2] = i3; }
+            if (tid < 64) {   // ComputeThreeMaxima over the frame's histogram, by every camera alike
+                int keep[3];
+                three_maxima_wave(tid < ORBM_HISTO_LENGTH ? __hip_atomic_load(&state[48 + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0, lane, keep);
+                if (tid == 0) { s_keep[0] = keep[0]; s_keep[1] = keep[1]; s_keep[2] = keep[2]; }
             }
             __syncthreads();
 #pragma unroll
@@ -1393,8 +1063,8 @@ __global__ __launch_bounds__(1024) void k_resolve_cams(FrameDev F, const int* __
         if (lane == 0 && kept) atomicAdd(&state[1], kept);
         __syncthreads();
         const int NT = F.n_total_dev ? *F.n_total_dev : F.n_total;
-        for (int g = tid; g < nf; g += T) match_of_feature[f0 + g] = tagb ? (tagb | (s_owner[g] + 2)) : s_owner[g];
-        if (tagb && cam == 0) for (int g = NT + tid; g < F.n_total; g += T) match_of_feature[g] = tagb | 1;   // (see k_resolve: no stale tag can match)
+        write_matches(match_of_feature + f0, s_owner, nf, tagb, tid, T);
+        if (cam == 0) write_no_match_tail(match_of_feature, NT, F.n_total, tagb, tid, T);
     }
     __threadfence_system();
     __syncthreads();
@@ -1402,16 +1072,7 @@ __global__ __launch_bounds__(1024) void k_resolve_cams(FrameDev F, const int* __
     __syncthreads();
     if (!s_last) return;
     // the last camera out: the result words (behind the merging workgroups of the same launch, as in k_resolve_mono), then `state` back to zero
-    bool merged = true;
-    if (MJ.S > 1 && MJ.done) {
-        if (tid == 0) {
-            int spins = 0;
-            while ((int)(__hip_atomic_load(MJ.done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) - MJ.target) < 0 && ++spins < (1 << 22)) __builtin_amdgcn_s_sleep(2);
-            s_code = spins < (1 << 22) ? 1 : 0;
-        }
-        __syncthreads();
-        merged = s_code != 0;
-    }
+    const bool merged = merge_wait(MJ, &s_code);   // (`all` holds what s_code said)
     if (tid == 0) {
         const int matches = __hip_atomic_load(&state[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         status[1] = tagb | (all ? 0 : matches); status[2] = tagb | __hip_atomic_load(&state[6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1426,10 +1087,6 @@ __global__ __launch_bounds__(1024) void k_resolve_cams(FrameDev F, const int* __
 #endif
 }
 
-// Multi-GPU exchange: `gathered` holds one block per rank (rank order), each = cap_rows descriptor rows (the rank's
-// cameras packed back to back) + the count trailer.  The rows in use are copied into one contiguous list in global camera
-// order; block (0, 0) also writes the camera starts, the {features, first query, queries} triple of rank `rank`, and a
-// copy of all counts into mapped pinned memory.  Every block recomputes the few prefix sums it needs from the trailers.
 }  // namespace
 
 int morb::search_raise_lds_limits() {
@@ -1616,7 +1273,6 @@ static int host_resolve(orbm_matcher* m, const orbm_frame* cur, const orbm_query
     if ((rc = project_all(m, cur, q, nq, 1, 1, &cap, cap0, d_win2))) return rc;
     for (int g = 0; g < cur->n_total; g++) match_of_feature[g] = -1;
     std::vector<int32_t> rot[ORBM_HISTO_LENGTH];
-    const float factor = 1.0f / ORBM_HISTO_LENGTH;
     int nm = 0;
     for (int i = 0; i < nq; i++) {
         const int cnt = m->h_i1.p[i];
@@ -1638,11 +1294,8 @@ static int host_resolve(orbm_matcher* m, const orbm_frame* cur, const orbm_query
             match_of_feature[bidx] = i;
             nm++;
             if (!points && check_orientation) {
-                float rotv = q[i].angle - cur->angle[bidx];
-                if (rotv < 0.0) rotv += 360.0f;
-                int bin = (int)roundf(rotv * factor);
-                if (bin == ORBM_HISTO_LENGTH) bin = 0;
-                if (bin >= 0 && bin < ORBM_HISTO_LENGTH) rot[bin].push_back(bidx);
+                const int bin = rotation_bin(q[i].angle, cur->angle[bidx]);
+                if (bin >= 0) rot[bin].push_back(bidx);
             }
         }
     }
@@ -1664,13 +1317,13 @@ int morb::search_enqueue(orbm_matcher* m, SearchJob& J, bool queries_already_on_
     J.form = ORBM_FORM_NONE;
     if (J.nq == 0 || n == 0) return ORB_OK;
     J.form = ORBM_FORM_HOST;   // (until a launch below says otherwise: host bookkeeping for orbm_debug_last_resolve_form, no kernel reads it)
-    // two claim tables (one int per feature each) + the candidate counts (u16 per query, padded); tables that do not fit LDS go
-    // to an HBM workspace (GCL variant of the kernel)
-    const size_t lds = (size_t)2 * n * sizeof(int) + (size_t)((J.nq + 1) / 2) * sizeof(int);
-    const bool multi = lds > 150 * 1024;  // multi-workgroup resolve with the tables in HBM
+    // two claim tables (one int per feature each) + the candidate counts (JacobiLds); tables that do not fit LDS go to an HBM
+    // workspace (the multi-workgroup forms)
+    constexpr size_t LDS_LIMIT = 150 * 1024;   // (the opt-in dynamic LDS limit, raised per device in orbm_create: search_raise_lds_limits)
+    const JacobiLds jacobi(n, J.nq);
+    const bool multi = jacobi.bytes(false) > LDS_LIMIT;  // multi-workgroup resolve with the tables in HBM
     if (m->host_resolve || J.nq > RESOLVE_MAX_Q) return ORB_OK;  // finish() takes the host path
     if (multi) { int rcg = m->d_gclaim.reserve((size_t)2 * n + RS_STATE_INTS); if (rcg) return rcg; }
-    // (tables beyond 48 KB use the opt-in dynamic LDS limit, raised per device in orbm_create)
     int rc;
     if ((rc = m->d_choice.reserve(J.nq)) || (rc = m->d_claim.reserve((size_t)(2 * RESOLVE_K + 1) * J.nq)) || (rc = m->d_match.reserve(n)) ||
         (rc = m->d_status.reserve(4)) || (rc = m->h_match.reserve((size_t)n + 4)) || (rc = m->d_occ.reserve(std::max(n, 16))))
@@ -1729,8 +1382,8 @@ int morb::search_enqueue(orbm_matcher* m, SearchJob& J, bool queries_already_on_
             for (int c = 0; c <= cur->n_cams; ++c) QR.start[c] = J.q_cam_start[c];
         }
     }
-    const size_t lds_cam = (size_t)8 * nf_cap + (size_t)2 * RSC_RQ * 1024;
-    const bool cams_fit = cams_want && nf_cap > 0 && q_cam_max > 0 && q_cam_max <= RSC_RQ * 1024 && nq < 65536 && lds_cam <= 150 * 1024;
+    const size_t lds_cam = CamsLds(nf_cap, RSC_RQ * 1024).bytes();
+    const bool cams_fit = cams_want && nf_cap > 0 && q_cam_max > 0 && q_cam_max <= RSC_RQ * 1024 && nq < 65536 && lds_cam <= LDS_LIMIT;
     auto launch_cams = [&](MergeJob MJc, int merge_blocks) -> int {
         int rcl;
         if (!m->d_rsync.p) {   // the meeting's words: zero between launches (the last workgroup of a launch leaves them so)
@@ -1763,17 +1416,13 @@ int morb::search_enqueue(orbm_matcher* m, SearchJob& J, bool queries_already_on_
         hipLaunchKernelGGL(k_rs_init, dim3(nb_all), dim3(256), 0, m->stream, n, nq, tab0, tab1, m->d_match.p, m->d_choice.p,
                            (const int*)m->d_i1.p, state, n_sweeps);
         J.multi = true;
+        const auto sweep = J.points ? k_rs_sweep<true> : k_rs_sweep<false>;
         for (int it = 0; it < n_sweeps; ++it) {
             const int* rd = (it & 1) ? tab1 : tab0;
             int* wr = (it & 1) ? tab0 : tab1;
-            if (J.points)
-                hipLaunchKernelGGL(k_rs_sweep<true>, dim3(nb_q), dim3(256), 0, m->stream, cur->dev(), (const orbm_query*)m->d_queries.p, nq,
-                                   cap, it, (const int*)m->d_i0.p, (const uint16_t*)m->d_u16.p, (const int*)m->d_i1.p, d_occ, th_high,
-                                   nnratio, m->d_choice.p, (const int*)m->d_claim.p, rd, wr, state);
-            else
-                hipLaunchKernelGGL(k_rs_sweep<false>, dim3(nb_q), dim3(256), 0, m->stream, cur->dev(), (const orbm_query*)m->d_queries.p, nq,
-                                   cap, it, (const int*)m->d_i0.p, (const uint16_t*)m->d_u16.p, (const int*)m->d_i1.p, d_occ, th_high,
-                                   nnratio, m->d_choice.p, (const int*)m->d_claim.p, rd, wr, state);
+            hipLaunchKernelGGL(sweep, dim3(nb_q), dim3(256), 0, m->stream, cur->dev(), (const orbm_query*)m->d_queries.p, nq,
+                               cap, it, (const int*)m->d_i0.p, (const uint16_t*)m->d_u16.p, (const int*)m->d_i1.p, d_occ, th_high,
+                               nnratio, m->d_choice.p, (const int*)m->d_claim.p, rd, wr, state);
         }
         const int ori = J.points ? 0 : J.check_ori;
         hipLaunchKernelGGL(k_rs_owner, dim3(nb_q), dim3(256), 0, m->stream, (const orbm_query*)m->d_queries.p, nq, cap,
@@ -1788,9 +1437,8 @@ int morb::search_enqueue(orbm_matcher* m, SearchJob& J, bool queries_already_on_
         return ORB_OK;
     }
     // claim table + (when it fits) the per-query sweep state
-    const size_t lds_q = lds + (size_t)nq * (sizeof(int) + sizeof(float) + RESOLVE_K * sizeof(int) + 1) + (size_t)n * sizeof(float) + 16;
-    const bool ldsq = lds_q <= 150 * 1024 && n < 65535;
-    const size_t lds_use = ldsq ? lds_q : lds;
+    const bool ldsq = jacobi.bytes(true) <= LDS_LIMIT && n < 65535;
+    const size_t lds_use = jacobi.bytes(ldsq);
 #define MORB_RESOLVE_LAUNCH(PT, LQ)                                                                                      \
     hipLaunchKernelGGL((k_resolve<PT, LQ>), dim3(1), dim3(1024), lds_use, m->stream, cur->dev(), (const int2*)m->d_qmeta.p, \
                        nq, cap, (const int*)m->d_i0.p, (const uint16_t*)m->d_u16.p, (const int*)m->d_i1.p, d_occ,            \
@@ -1801,41 +1449,37 @@ int morb::search_enqueue(orbm_matcher* m, SearchJob& J, bool queries_already_on_
     // (the worklist rounds pay from four queries per thread on: 2 x 2000 queries 30.7 -> 24.7 us, 4 x 1000 29.3 -> 27.3; at 2 x 1000 a
     //  round's two barriers cost more than the waves' own passes: 17.3 -> 20.5 us, so small rigs keep those -- profiles/r06/notes_experiments.md)
     const int mono_worklist = mono_mode == 2 && nq > 2048 ? 1 : 0;
-    // The frame search's monotone resolve keeps less per query (16-bit features, no distances; mono_lds): it takes frames of up to
+    // The frame search's monotone resolve keeps less per query (16-bit features, no distances; MonoLds): it takes frames of up to
     // ~6000 features / queries (4 x 1000, 2 x 2000: where k_resolve's Jacobi form keeps its query state in HBM and costs 53 us),
     // four queries per thread in registers beyond 2048 queries, the rotation angles from HBM when they do not fit next to the rest.
-    auto mono_lds = [&](bool ang) {
-        const size_t nq2 = ((size_t)nq + 1) & ~(size_t)1;
-        return (size_t)n * 8 + nq2 * 4 + (size_t)RESOLVE_K * nq2 * 2 + (((size_t)nq + 3) & ~(size_t)3) + (ang ? ((size_t)nq + (size_t)n) * 4 : 0) + nq2 * 2 + 16;   // (+ the worklist)
-    };
-    const bool will_mono = !J.points && mono_env && n < 65535 && mono_lds(false) <= 150 * 1024;
+    const bool will_mono = !J.points && mono_env && n < 65535 && MonoLds(n, nq, false).bytes() <= LDS_LIMIT;
     if (MJ.S > 1 && !will_mono && !cams_fit) { if ((rc = launch_merge(m->stream, MJ))) return rc; MJ.S = 0; }   // (no carrier after all: a launch of its own)
+    // A merge that waits for its carrier rides behind the resolve's workgroups (the cameras', or workgroup 0 of the monotone form):
+    // every merging workgroup adds one to the counter, the resolve waits for this launch's running total.
+    int merge_blocks = 0;
+    auto carry_merge = [&]() -> int {
+        merge_blocks = MJ.S > 1 ? (MJ.nq + 1023) / 1024 : 0;
+        if (!merge_blocks) return ORB_OK;
+        int rcm = m->d_mergecnt.reserve(4);
+        if (rcm) return rcm;
+        if (!m->merge_ready) { MORB_HIP(hipMemsetAsync(m->d_mergecnt.p, 0, 16, m->stream)); m->merge_ready = true; m->merge_target = 0; }
+        m->merge_target += (unsigned)merge_blocks;
+        MJ.done = reinterpret_cast<unsigned*>(m->d_mergecnt.p); MJ.target = m->merge_target;
+        return ORB_OK;
+    };
     if (cams_fit) {
-        const int merge_blocks = MJ.S > 1 ? (MJ.nq + 1023) / 1024 : 0;   // (behind the cameras' workgroups)
-        if (merge_blocks) {
-            if ((rc = m->d_mergecnt.reserve(4))) return rc;
-            if (!m->merge_ready) { MORB_HIP(hipMemsetAsync(m->d_mergecnt.p, 0, 16, m->stream)); m->merge_ready = true; m->merge_target = 0; }
-            m->merge_target += (unsigned)merge_blocks;
-            MJ.done = reinterpret_cast<unsigned*>(m->d_mergecnt.p); MJ.target = m->merge_target;
-        }
-        if ((rc = launch_cams(MJ, merge_blocks))) return rc;
+        if ((rc = carry_merge()) || (rc = launch_cams(MJ, merge_blocks))) return rc;
         MJ.S = 0;   // (carried)
         J.form = ORBM_FORM_CAMS;
     } else if (will_mono) {
-        const bool ang = mono_lds(true) <= 150 * 1024;
-        const size_t ml = mono_lds(ang);
+        const bool ang = MonoLds(n, nq, true).bytes() <= LDS_LIMIT;
+        const size_t ml = MonoLds(n, nq, ang).bytes();
 #define MORB_MONO_LAUNCH(RQ_, ANG_)                                                                                                       \
         hipLaunchKernelGGL((k_resolve_mono<RQ_, ANG_>), dim3(1 + merge_blocks), dim3(1024), ml, m->stream, cur->dev(), (const int2*)m->d_qmeta.p, nq, cap, \
                            (const int*)m->d_i0.p, (const uint16_t*)m->d_u16.p, (const int*)m->d_i1.p, d_occ,                                \
                            (const float*)cur->b->d_ang.p, th_high, J.check_ori, 4096, (const int*)m->d_claim.p, m->h_match.dp + 4,          \
                            m->h_match.dp, J.seq << 20, MJ, mono_worklist)
-        const int merge_blocks = MJ.S > 1 ? (MJ.nq + 1023) / 1024 : 0;   // (behind workgroup 0, the resolve)
-        if (merge_blocks) {
-            if ((rc = m->d_mergecnt.reserve(4))) return rc;
-            if (!m->merge_ready) { MORB_HIP(hipMemsetAsync(m->d_mergecnt.p, 0, 16, m->stream)); m->merge_ready = true; m->merge_target = 0; }
-            m->merge_target += (unsigned)merge_blocks;
-            MJ.done = reinterpret_cast<unsigned*>(m->d_mergecnt.p); MJ.target = m->merge_target;
-        }
+        if ((rc = carry_merge())) return rc;
         if (nq <= 2048) { if (ang) MORB_MONO_LAUNCH(2, true); else MORB_MONO_LAUNCH(2, false); }
         else { if (ang) MORB_MONO_LAUNCH(4, true); else MORB_MONO_LAUNCH(4, false); }
         MJ.S = 0;   // (carried)
