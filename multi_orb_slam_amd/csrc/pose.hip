@@ -5,14 +5,14 @@
 // core/sparse_optimizer.cpp, solvers/linear_solver_dense.h) and the Eigen operators those call.
 //   eigen_*, se3_*, g2o_huber   the Eigen operators, g2o::SE3Quat and the Huber kernel: g2o_dev.h (UNPINNED).
 //   pose_edge        one edge: error, chi2 and the Jacobian of its type, ONE statement sequence for the kernel and the host routine.
-//   pose_step        the controller: everything between two passes over the edges (Levenberg bookkeeping, the 6x6 solve, the exp map,
-//                    the round and classification logic) as a resumable state machine over a PoseCtl record.  The host routine calls it
-//                    between its passes, lane 0 of the workgroup calls it on the record in LDS: the same statements.
+//   pose_step        the controller: everything between two passes over the edges as a resumable state machine over a PoseCtl record.
+//                    The Levenberg bookkeeping and the 6x6 solve are lm_dev.h's lm_step (ONE definition, sim3opt.hip runs it too); the exp
+//                    map, rounds and classification are here.  Host routine and lane 0 (on the record in LDS) call the same statements.
 //   k_pose_optimize  one workgroup of 256 lanes per problem, resident for the whole call.  Per pass: every lane evaluates its edges
 //                    (lane l owns l, l + 256, ...; the first eight of them stay in registers, a longer tail streams from the staged
-//                    edge arrays), sums 21 + 6 + 1 + 1 doubles over them in ascending order, an xor butterfly (1, 2, 4, 8, 16, 32) sums
-//                    across the wave, lane 0 of each wave leaves its sums in LDS, and lane 0 of the workgroup adds the four waves in wave
-//                    order and runs pose_step.  Two barriers per pass, no atomics, no order that depends on arrival.
+//                    edge arrays) and sums 21 + 6 + 1 + 1 doubles over them in ascending order; lm_dev.h's summation tree (butterfly in
+//                    each wave, the four waves in wave order) gives lane 0 the pass's sums, and lane 0 runs pose_step.  Two barriers
+//                    per pass, no atomics, no order that depends on arrival.  The host routine walks the same tree (lm_pass_host).
 // No libm function runs in the kernel: + - * / sqrt in double (the correctly rounded sequences), conversions.
 #include <algorithm>
 #include <cfloat>
@@ -26,14 +26,14 @@
 #include "matcher_internal.h"
 #include "cv_dev.h"
 #include "g2o_dev.h"
+#include "lm_dev.h"
 #include "stage_pack.h"
 
 namespace {
 
-constexpr int POSE_T = 256;          // lanes of the workgroup = leaves of the summation tree
 constexpr int POSE_REG_SLOTS = 8;    // edges per lane whose constants stay in registers
-constexpr int POSE_NSUM = 29;        // H upper triangle (21, row-major i <= j), b (6), robust chi2, outlier count
-enum { POSE_CMD_FULL = 0, POSE_CMD_CHI = 1, POSE_CMD_CLASSIFY = 2, POSE_CMD_DONE = 3 };
+// the sums of a pass (lm_dev.h): H upper triangle (21, row-major i <= j), b (6), robust chi2, outlier count
+constexpr int POSE_NSUM = LmState<6>::NSUM, POSE_CHI = LmState<6>::CHI, POSE_BAD = LmState<6>::COUNT;
 
 struct PoseCam {                         // per problem: the members of the edges that do not depend on the edge
     double fx, fy, cx, cy, bf;
@@ -127,7 +127,7 @@ __host__ __device__ inline double pose_edge(const PoseCam& C, const SE3Quat& T, 
 }
 
 // One ACTIVE edge's share of a pass (computeActiveErrors + activeRobustChi2, with `system` also linearizeOplus + constructQuadraticForm,
-// core/base_unary_edge.hpp:44-72): acc[27] += rho[0]; b -= rho[1] * J^T (Omega e); H += J^T (rho[1] Omega) J.  The edge's own 6-vector
+// core/base_unary_edge.hpp:44-72): acc[POSE_CHI] += rho[0]; b -= rho[1] * J^T (Omega e); H += J^T (rho[1] Omega) J.  The edge's own 6-vector
 // and 6x6 are formed first (rows of J in order) and then added, as the edge adds its products to the vertex.  UNPINNED: Eigen's
 // evaluation order inside the two products.
 __host__ __device__ inline void pose_accumulate(const PoseCam& C, const SE3Quat& T, const PoseEdge& E, bool system, bool robust, double* acc) {
@@ -136,7 +136,7 @@ __host__ __device__ inline void pose_accumulate(const PoseCam& C, const SE3Quat&
     const double chi2 = pose_edge(C, T, E, e, system, J);
     double rho0 = chi2, rho1 = 1.;
     if (robust) g2o_huber(chi2, C.delta[stereo ? 1 : 0], C.dsqr[stereo ? 1 : 0], &rho0, &rho1);
-    acc[27] += rho0;
+    acc[POSE_CHI] += rho0;
     if (!system) return;
     const double w = (double)E.inv_sigma2, rw = rho1 * w;
     const double we[3] = {w * e[0], w * e[1], w * e[2]};
@@ -164,12 +164,20 @@ __host__ __device__ inline bool pose_classify(const PoseCam& C, const SE3Quat& e
 }
 
 // ---- the controller ---------------------------------------------------------------------------------------------------------------------
-struct PoseCtl {
-    int cmd, order, n, round, iter, qmax, n_bad_steps, robust, n_bad, ok2;
-    SE3Quat start, est, eval, last;          // eval: the pose of the next pass; last: the pose of the last FULL / CHI pass
-    double H[21], b[6], x[6], lambda, ni, current_chi, ini_chi;
-    double A[36], temp[6]; int transp[6];    // the solver's working storage (indexed at run time: LDS on the device, never registers)
+struct PoseCtl : LmState<6> {
+    static constexpr bool LM_TRY_INLINE = false;
+    int n, round, robust, n_bad;
+    // eval: the pose of the next pass; last: of the last FULL / CHI pass.  est and last aligned: the kernel reads them with 128-bit LDS loads
+    alignas(16) SE3Quat est; SE3Quat eval; alignas(16) SE3Quat last; SE3Quat start;
     orbm_pose_result res;
+    // what lm_step leaves to the port
+    __host__ __device__ __forceinline__ void lm_trial() {   // oplusImpl: setEstimate(SE3Quat::exp(update) * estimate())
+        SE3Quat d;
+        se3_exp(x, order, d);
+        se3_mul(d, est, eval);
+    }
+    __host__ __device__ __forceinline__ void lm_accept() { est = eval; }
+    __host__ __device__ __forceinline__ void lm_linearise() { eval = est; cmd = LM_CMD_FULL; }
 };
 
 // Converter::toCvMat(SE3Quat): to_homogeneous_matrix() rounded to float
@@ -185,24 +193,12 @@ __host__ __device__ inline void pose_write_estimate(PoseCtl& S) {
     for (int k = 0; k < 3; ++k) S.res.t[k] = x86_nan(S.est.t[k]);
 }
 
-// one trial of the Levenberg loop up to its pass (:103-121): H + lambda on the diagonal, the dense solve, update(x) = exp(x) * estimate
-__host__ __device__ inline void pose_try(PoseCtl& S) {
-    int k = 0;
-    for (int i = 0; i < 6; ++i)
-        for (int j = i; j < 6; ++j, ++k) { S.A[6 * i + j] = S.H[k]; S.A[6 * j + i] = S.H[k]; }
-    for (int i = 0; i < 6; ++i) S.A[7 * i] += S.lambda;
-    S.ok2 = eigen_ldlt_solve(S.A, S.b, S.x, S.temp, S.transp) ? 1 : 0;
-    SE3Quat d;
-    se3_exp(S.x, S.order, d);
-    se3_mul(d, S.est, S.eval);              // oplusImpl: setEstimate(SE3Quat::exp(update) * estimate())
-    S.cmd = POSE_CMD_CHI;
-}
 __host__ __device__ inline void pose_begin_round(PoseCtl& S) {
     S.est = S.start;                         // vSE3->setEstimate(Converter::toSE3Quat(pFrame->mTcw))
-    S.iter = 0;
+    S.iter = 0; S.max_iter = 10;             // optimizer.optimize(its[it]), its = {10, 10, 10, 10}
     // initializeOptimization(0) finds no edge of level 0 when every edge is an outlier: optimize() returns at once
-    if (S.n - S.n_bad <= 0) { S.cmd = POSE_CMD_CLASSIFY; return; }
-    S.eval = S.est; S.cmd = POSE_CMD_FULL;
+    if (S.n - S.n_bad <= 0) { S.cmd = LM_CMD_CLASSIFY; return; }
+    S.lm_linearise();
 }
 __host__ __device__ inline void pose_begin(PoseCtl& S, const float* Tcw, int n, int order) {
     S.order = order; S.n = n; S.round = 0; S.robust = 1; S.n_bad = 0; S.ok2 = 1;
@@ -216,7 +212,7 @@ __host__ __device__ inline void pose_begin(PoseCtl& S, const float* Tcw, int n, 
         for (int i = 0; i < 16; ++i) S.res.Tcw[i] = Tcw[i];
         for (int k = 0; k < 4; ++k) S.res.q[k] = x86_nan(S.start.q[k]);
         for (int k = 0; k < 3; ++k) S.res.t[k] = x86_nan(S.start.t[k]);
-        S.cmd = POSE_CMD_DONE;
+        S.cmd = LM_CMD_DONE;
         return;
     }
     pose_begin_round(S);
@@ -224,77 +220,20 @@ __host__ __device__ inline void pose_begin(PoseCtl& S, const float* Tcw, int n, 
 // Called after every pass with the pass's sums.
 __host__ __device__ inline void pose_step(PoseCtl& S, const double* sum) {
     orbm_pose_round& R = S.res.round[S.round];
-    if (S.cmd == POSE_CMD_FULL) {            // solve(), :75-101: the errors, the robust chi2 and the system at the estimate
+    if (S.cmd != LM_CMD_CLASSIFY) {          // a FULL or a CHI pass: one step of the Levenberg loop
         S.last = S.eval;
-        S.current_chi = sum[27]; S.ini_chi = S.current_chi;
-        for (int k = 0; k < 21; ++k) S.H[k] = sum[k];
-        for (int k = 0; k < 6; ++k) S.b[k] = sum[21 + k];
-        if (S.iter == 0) {                   // computeLambdaInit: tau * the largest |diagonal|
-            double max_diagonal = 0.;
-            int d = 0;
-            for (int j = 0; j < 6; ++j) { const double v = fabs(S.H[d]); if (v > max_diagonal) max_diagonal = v; d += 6 - j; }
-            S.lambda = 1e-5 * max_diagonal;
-            S.ni = 2; S.n_bad_steps = 0;
-        }
-        S.qmax = 0;
-        pose_try(S);
+        lm_step(S, sum, R);
         return;
     }
-    if (S.cmd == POSE_CMD_CHI) {             // :123-149
-        S.last = S.eval;
-        double temp_chi = sum[27];
-        if (!S.ok2) temp_chi = DBL_MAX;
-        double rho = S.current_chi - temp_chi;
-        double scale = 0.;
-        for (int j = 0; j < 6; ++j) scale += S.x[j] * (S.lambda * S.x[j] + S.b[j]);
-        scale += 1e-3;
-        rho /= scale;
-        if (rho > 0 && fabs(temp_chi) <= DBL_MAX) {
-            const double u = 2 * rho - 1;
-            double cube;
-#ifndef __HIP_DEVICE_COMPILE__
-            if (S.order == ORBM_POSE_ORDER_INDEX) cube = pow(u, 3); else
-#endif
-            cube = u * u * u;
-            double alpha = 1. - cube;
-            alpha = alpha < 2. / 3. ? alpha : 2. / 3.;             // (std::min)(alpha, _goodStepUpperScale)
-            const double scale_factor = 1. / 3. < alpha ? alpha : 1. / 3.;   // (std::max)(_goodStepLowerScale, alpha)
-            S.lambda *= scale_factor;
-            S.ni = 2;
-            S.current_chi = temp_chi;
-            S.est = S.eval;                  // discardTop
-        } else {
-            S.lambda *= S.ni;
-            S.ni *= 2;                       // pop: the estimate stays
-        }
-        S.qmax++;
-        R.trials++;
-        if (rho < 0 && S.qmax < 10) { pose_try(S); return; }
-        // the iteration is over: solve()'s result, then optimize()'s loop (core/sparse_optimizer.cpp:376-414)
-        R.iterations++;
-        bool terminate = S.qmax == 10 || rho == 0;
-        if (!terminate) {
-            if ((S.ini_chi - S.current_chi) * 1e3 < S.ini_chi) S.n_bad_steps++; else S.n_bad_steps = 0;
-            if (S.n_bad_steps >= 3) terminate = true;
-        }
-        S.iter++;
-        if (terminate || S.iter == 10) {
-            R.chi2 = x86_nan(S.current_chi); R.lambda = x86_nan(S.lambda);
-            S.cmd = POSE_CMD_CLASSIFY;
-        } else {
-            S.eval = S.est; S.cmd = POSE_CMD_FULL;
-        }
-        return;
-    }
-    // POSE_CMD_CLASSIFY
-    S.n_bad = (int)sum[28];
+    // LM_CMD_CLASSIFY: the round is over
+    S.n_bad = (int)sum[POSE_BAD];
     S.res.n_bad = S.n_bad;
     S.res.rounds = S.round + 1;
     if (S.round == 2) S.robust = 0;          // `if(it==2) e->setRobustKernel(0)`
     if (S.n < 10 || S.round == 3) {          // `if(optimizer.edges().size()<10) break;`
         S.res.n_inliers = S.res.n_initial - S.n_bad;
         pose_write_estimate(S);
-        S.cmd = POSE_CMD_DONE;
+        S.cmd = LM_CMD_DONE;
         return;
     }
     S.round++;
@@ -364,20 +303,20 @@ __device__ __forceinline__ PoseEdge pose_load(const PoseDev& A, const orbm_pose_
     return E;
 }
 
-__device__ __forceinline__ void pose_pass_edge(const PoseCam& C, const PoseCtl& S, int cmd, const PoseEdge& E, uint8_t* flag, double* acc) {
-    if (cmd == POSE_CMD_CLASSIFY) {
+__host__ __device__ __forceinline__ void pose_pass_edge(const PoseCam& C, const PoseCtl& S, int cmd, const PoseEdge& E, uint8_t* flag, double* acc) {
+    if (cmd == LM_CMD_CLASSIFY) {
         const bool out = pose_classify(C, S.est, S.last, E, *flag != 0);
         *flag = out ? 1 : 0;
-        acc[28] += out ? 1.0 : 0.0;
+        acc[POSE_BAD] += out ? 1.0 : 0.0;
     } else if (!*flag) {
-        pose_accumulate(C, S.eval, E, cmd == POSE_CMD_FULL, S.robust != 0, acc);
+        pose_accumulate(C, S.eval, E, cmd == LM_CMD_FULL, S.robust != 0, acc);
     }
 }
 
-__global__ __launch_bounds__(POSE_T) void k_pose_optimize(PoseDev A) {
+__global__ __launch_bounds__(LM_T) void k_pose_optimize(PoseDev A) {
     __shared__ PoseCtl S;
     __shared__ PoseCam C;
-    __shared__ double s_part[POSE_T / 64][POSE_NSUM];
+    __shared__ double s_part[LM_T / 64][POSE_NSUM];
     __shared__ uint8_t s_flag[ORBM_POSE_CAP];
     const int tid = threadIdx.x;
     const int pb = A.list[blockIdx.x];
@@ -385,23 +324,23 @@ __global__ __launch_bounds__(POSE_T) void k_pose_optimize(PoseDev A) {
     const int e0 = A.first[pb];
     const int n = min(A.first[pb + 1] - e0, (int)ORBM_POSE_CAP);   // (a longer problem never reaches the device)
     if (tid == 0) { pose_camera(P, C); pose_begin(S, P.Tcw, n, ORBM_POSE_ORDER_DEVICE); }
-    for (int e = tid; e < n; e += POSE_T) s_flag[e] = 0;
+    for (int e = tid; e < n; e += LM_T) s_flag[e] = 0;
     PoseEdge reg[POSE_REG_SLOTS];
 #pragma unroll
     for (int s = 0; s < POSE_REG_SLOTS; ++s) {
-        const int e = tid + s * POSE_T;
+        const int e = tid + s * LM_T;
         if (e < n) reg[s] = pose_load(A, P, e0 + e);
         else { reg[s].X[0] = reg[s].X[1] = reg[s].X[2] = 0.0f; reg[s].obs[0] = reg[s].obs[1] = reg[s].obs[2] = 0.0f; reg[s].inv_sigma2 = 0.0f; reg[s].meta = 0; }
     }
     for (;;) {
         __syncthreads();                                   // the controller's record is visible
         const int cmd = S.cmd;
-        if (cmd == POSE_CMD_DONE) break;
+        if (cmd == LM_CMD_DONE) break;
         double acc[POSE_NSUM];
 #pragma unroll
         for (int k = 0; k < POSE_NSUM; ++k) acc[k] = 0.0;
         // this lane's edges in ascending order: ONE copy of the edge code; a slot's constants are selected out of the registers
-        for (int s = 0, e = tid; e < n; ++s, e += POSE_T) {
+        for (int s = 0, e = tid; e < n; ++s, e += LM_T) {
             PoseEdge E;
             if (s < POSE_REG_SLOTS) {
                 E = reg[0];
@@ -412,14 +351,12 @@ __global__ __launch_bounds__(POSE_T) void k_pose_optimize(PoseDev A) {
             }
             pose_pass_edge(C, S, cmd, E, &s_flag[e], acc);
         }
-        // the wave's sums: xor butterfly, offsets 1, 2, 4, 8, 16, 32 (every lane ends with the same bits: a + b == b + a)
+        // lm_dev.h's lm_wave_sums, written out: as a function it costs this kernel 101 more AGPRs and 361 more copies to and from them,
+        // most of them in the loop over the edges (profiles/r17/notes_lm_refactor.md).  (Skipped: exact zeros that nobody reads.)
 #pragma unroll
         for (int k = 0; k < POSE_NSUM; ++k) {
-            if (cmd == POSE_CMD_CHI && k < 27) continue;   // (zeros: nothing was added to them in this pass)
-            double v = acc[k];
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) v = v + __shfl_xor(v, off, 64);
-            acc[k] = v;
+            if (cmd != LM_CMD_FULL && k < POSE_CHI) continue;
+            acc[k] = lm_wave_sum(acc[k]);
         }
         if ((tid & 63) == 0) {
 #pragma unroll
@@ -428,12 +365,11 @@ __global__ __launch_bounds__(POSE_T) void k_pose_optimize(PoseDev A) {
         __syncthreads();                                   // the four waves' sums are visible, every lane is done with the record
         if (tid == 0) {
             double sum[POSE_NSUM];
-#pragma unroll
-            for (int k = 0; k < POSE_NSUM; ++k) sum[k] = ((s_part[0][k] + s_part[1][k]) + s_part[2][k]) + s_part[3][k];   // wave order
+            lm_add_waves(s_part, sum);
             pose_step(S, sum);
         }
     }
-    for (int e = tid; e < n; e += POSE_T) A.flags[e0 + e] = s_flag[e];
+    for (int e = tid; e < n; e += LM_T) A.flags[e0 + e] = s_flag[e];
     if (tid == 0) A.res[pb] = S.res;
 }
 
@@ -458,33 +394,10 @@ void pose_problem_host(const orbm_pose_problem& P, const PoseEdges& G, int e0, i
     std::vector<PoseEdge> E((size_t)n);
     for (int e = 0; e < n; ++e) E[e] = host_edge(P, G, e0 + e);
     std::vector<double> part;
-    if (order == ORBM_POSE_ORDER_DEVICE) part.resize((size_t)POSE_T * POSE_NSUM);
-    while (S.cmd != POSE_CMD_DONE) {
+    while (S.cmd != LM_CMD_DONE) {
         double sum[POSE_NSUM];
         const int cmd = S.cmd;
-        auto pass_edge = [&](int e, double* acc) {
-            if (cmd == POSE_CMD_CLASSIFY) {
-                const bool out = pose_classify(C, S.est, S.last, E[e], flags[e] != 0);
-                flags[e] = out ? 1 : 0;
-                acc[28] += out ? 1.0 : 0.0;
-            } else if (!flags[e]) {
-                pose_accumulate(C, S.eval, E[e], cmd == POSE_CMD_FULL, S.robust != 0, acc);
-            }
-        };
-        if (order == ORBM_POSE_ORDER_INDEX) {
-            for (int k = 0; k < POSE_NSUM; ++k) sum[k] = 0.0;
-            for (int e = 0; e < n; ++e) pass_edge(e, sum);
-        } else {                                           // the kernel's tree: lanes, butterfly inside each wave, waves in order
-            std::fill(part.begin(), part.end(), 0.0);
-            for (int l = 0; l < POSE_T && l < n; ++l)
-                for (int e = l; e < n; e += POSE_T) pass_edge(e, &part[(size_t)l * POSE_NSUM]);
-            for (int off = 1; off < 64; off <<= 1)
-                for (int l = 0; l < POSE_T; ++l)
-                    if (!(l & off) && !(l & (off - 1)))
-                        for (int k = 0; k < POSE_NSUM; ++k) part[(size_t)l * POSE_NSUM + k] = part[(size_t)l * POSE_NSUM + k] + part[(size_t)(l | off) * POSE_NSUM + k];
-            for (int k = 0; k < POSE_NSUM; ++k)
-                sum[k] = ((part[k] + part[(size_t)64 * POSE_NSUM + k]) + part[(size_t)128 * POSE_NSUM + k]) + part[(size_t)192 * POSE_NSUM + k];
-        }
+        lm_pass_host<POSE_NSUM>(order, n, part, sum, [&](int e, double* acc) { pose_pass_edge(C, S, cmd, E[e], &flags[e], acc); });
         pose_step(S, sum);
     }
     res = S.res;
@@ -493,10 +406,8 @@ void pose_problem_host(const orbm_pose_problem& P, const PoseEdges& G, int e0, i
 int validate(const orbm_pose_problem* problems, int B, const int32_t* first, const int32_t* feat, const float* pos, const float* obs,
              const int32_t* octave, const uint8_t* outlier_out, const orbm_pose_result* results) {
     MORB_ARG(problems && first && results);
-    if (B < 1 || B > ORBM_POSE_MAX_BATCH) { morb::set_error("B = %d is outside 1..%d", B, (int)ORBM_POSE_MAX_BATCH); return ORB_E_ARG; }
-    MORB_ARG(first[0] == 0);
+    if (const int rc = lm_validate_csr(B, ORBM_POSE_MAX_BATCH, first)) return rc;
     for (int b = 0; b < B; ++b) {
-        if (first[b + 1] < first[b]) { morb::set_error("first[] decreases at problem %d", b); return ORB_E_ARG; }
         const orbm_pose_problem& P = problems[b];
         if (P.mode != ORBM_POSE_CAM0 && P.mode != ORBM_POSE_ALL_CAMS) { morb::set_error("problem %d: mode = %d", b, P.mode); return ORB_E_ARG; }
         if (P.n_levels < 1 || P.n_levels > ORBM_MAX_LEVELS) { morb::set_error("problem %d: n_levels = %d is outside 1..%d", b, P.n_levels, (int)ORBM_MAX_LEVELS); return ORB_E_ARG; }
@@ -531,7 +442,7 @@ int launch(orbm_matcher* m, const orbm_pose_problem* problems, int B, const int3
     if (A.packed) A.packed = blk.dev<uint32_t>(i_edge[0]);
     else { A.feat = blk.dev<int32_t>(i_edge[0]); A.pos = blk.dev<float>(i_edge[1]); A.obs = blk.dev<float>(i_edge[2]); A.octave = blk.dev<int32_t>(i_edge[3]); }
     *flags_off = res_bytes;
-    hipLaunchKernelGGL(k_pose_optimize, dim3((unsigned)list.size()), dim3(POSE_T), 0, m->stream, A);
+    hipLaunchKernelGGL(k_pose_optimize, dim3((unsigned)list.size()), dim3(LM_T), 0, m->stream, A);
     MORB_HIP(hipGetLastError());
     return ORB_OK;
 }
@@ -558,32 +469,16 @@ int orbm_pose_optimize(orbm_matcher* m, const orbm_pose_problem* problems, int B
     int rc = validate(problems, B, first, feat, pos, obs, octave, outlier_out, results);
     if (rc) return rc;
     const int ne = first[B];
-    std::vector<int32_t> list;
-    for (int b = 0; b < B; ++b) if (first[b + 1] - first[b] <= ORBM_POSE_CAP) list.push_back(b);
-    size_t flags_off = 0;
-    if (!list.empty()) {
-        MORB_HIP(hipSetDevice(m->device));
-        PoseDev A;
-        memset(&A, 0, sizeof(A));
-        const void* src[4] = {feat, pos, obs, octave};
-        const size_t len[4] = {(size_t)ne * 4, (size_t)ne * 12, (size_t)ne * 12, (size_t)ne * 4};
-        if ((rc = launch(m, problems, B, first, list, A, src, len, 4, &flags_off))) return rc;
-    }
-    // while the kernel runs: the problems the device does not take
     const PoseEdges G = {feat, pos, obs, octave};
-    for (int b = 0; b < B; ++b)
-        if (first[b + 1] - first[b] > ORBM_POSE_CAP)
-            pose_problem_host(problems[b], G, first[b], first[b + 1] - first[b], ORBM_POSE_ORDER_DEVICE, outlier_out + first[b], results[b]);
-    if (!list.empty()) {
-        MORB_HIP(hipStreamSynchronize(m->stream));
-        const orbm_pose_result* R = (const orbm_pose_result*)m->pose.out.p;
-        for (int b : list) {
-            results[b] = R[b];
-            memcpy(outlier_out + first[b], m->pose.out.p + flags_off + first[b], (size_t)(first[b + 1] - first[b]));
-        }
-    }
-    m->last_pose[0] = (int)list.size(); m->last_pose[1] = B - (int)list.size();
-    return ORB_OK;
+    return lm_csr_call(m, m->pose, B, first, ORBM_POSE_CAP, outlier_out, results, m->last_pose,
+        [&](const std::vector<int32_t>& list, size_t* flags_off) -> int {
+            PoseDev A;
+            memset(&A, 0, sizeof(A));
+            const void* src[4] = {feat, pos, obs, octave};
+            const size_t len[4] = {(size_t)ne * 4, (size_t)ne * 12, (size_t)ne * 12, (size_t)ne * 4};
+            return launch(m, problems, B, first, list, A, src, len, 4, flags_off);
+        },
+        [&](int b) { pose_problem_host(problems[b], G, first[b], first[b + 1] - first[b], ORBM_POSE_ORDER_DEVICE, outlier_out + first[b], results[b]); });
 }
 
 int orbm_pose_optimize_resident(orbm_matcher* m, const orbm_pose_problem* problem, const orbm_frame* cur, const orbm_points* pts,

@@ -7,13 +7,13 @@
 //                     has an analytic one) and the robust constructQuadraticForm, ONE statement sequence for kernel and host routine.
 //   sim3opt_records   the 30 transforms a pass reads: the estimate, Sim3(+-1e-9 e_d) * estimate for d = 0..6, and the inverse of each.
 //                     None depends on the edge, so the controller forms them once per pass.
-//   sim3opt_step      the controller, pose.hip's pose_step with 7 unknowns and this routine's two optimisations: a resumable state
-//                     machine over a Sim3Ctl record.  The host routine calls it between its passes, lane 0 of the workgroup calls it
-//                     on the record in LDS: the same statements.
+//   sim3opt_step      the controller: a resumable state machine over a Sim3Ctl record.  The Levenberg bookkeeping and the 7x7 solve are
+//                     lm_dev.h's lm_step (ONE definition, pose.hip runs it too); the exp map, the records and the two optimisations are
+//                     here.  The host routine calls it between its passes, lane 0 calls it on the record in LDS: the same statements.
 //   k_sim3_optimize   one workgroup of 256 lanes per problem, resident for the whole call.  Per pass every lane evaluates both edges
-//                     of its correspondences (lane l owns l, l + 256, ... in ascending order) and sums 28 + 7 + 1 + 1 doubles; the
-//                     reduction is pose.hip's: xor butterfly (1 .. 32) in each wave, the four waves added in wave order by lane 0.
-//                     Two barriers per pass, no atomics, no order that depends on arrival.
+//                     of its correspondences (lane l owns l, l + 256, ... in ascending order) and sums 28 + 7 + 1 + 1 doubles;
+//                     lm_dev.h's summation tree (butterfly in each wave, the four waves in wave order) gives lane 0 the pass's sums,
+//                     lm_pass_host walks the same tree.  Two barriers per pass, no atomics, no order that depends on arrival.
 // No libm function runs in the kernel: + - * / sqrt in double, conversions, pose_sincos and pose_exp (sincos_dev.h).
 #include <algorithm>
 #include <cfloat>
@@ -27,15 +27,14 @@
 #include "matcher_internal.h"
 #include "cv_dev.h"
 #include "g2o_dev.h"
+#include "lm_dev.h"
 #include "stage_pack.h"
 
 namespace {
 
-constexpr int S3O_T = 256;           // lanes of the workgroup = leaves of the summation tree
-constexpr int S3O_NSUM = 37;         // H upper triangle (28, row-major i <= j), b (7), robust chi2, count of failed correspondences
-constexpr int S3O_CHI = 35, S3O_BAD = 36;
+// the sums of a pass (lm_dev.h): H upper triangle (28, row-major i <= j), b (7), robust chi2, count of failed correspondences
+constexpr int S3O_NSUM = LmState<7>::NSUM, S3O_CHI = LmState<7>::CHI, S3O_BAD = LmState<7>::COUNT;
 constexpr int S3O_NREC = 30;         // 0: the estimate; 1 + 2d, 2 + 2d: Sim3(+delta e_d) * estimate, Sim3(-delta e_d) * estimate; 15 + k: inverse of k
-enum { S3O_CMD_FULL = 0, S3O_CMD_CHI = 1, S3O_CMD_CLASSIFY = 2, S3O_CMD_DONE = 3 };
 
 // A compiler-only fence for the kernel (no instruction): the 30 records are loop invariant, and hoisted out of the loop over a lane's
 // correspondences they alone would need 480 registers.  Behind a fence each is read from LDS where it is used.
@@ -124,13 +123,16 @@ __host__ __device__ inline bool sim3opt_classify(const Sim3Cam& C, const Sim3Qua
 
 // ---- the controller ---------------------------------------------------------------------------------------------------------------------
 // (Its functions are inlined by force: a call out of the kernel would save registers in scratch memory, and the kernel uses none.)
-struct Sim3Ctl {
-    int cmd, order, n, stage, iter, max_iter, qmax, n_bad_steps, n_bad, ok2, fix_scale, pad;
+struct Sim3Ctl : LmState<7> {
+    static constexpr bool LM_TRY_INLINE = true;
+    int n, stage, n_bad, fix_scale;
     Sim3Quat start, est;                     // g2oS12 as it came; the vertex's estimate
     Sim3Quat rec[S3O_NREC];                  // what the next / the last pass reads; rec[0] is the estimate of that pass
-    double H[28], b[7], x[7], lambda, ni, current_chi, ini_chi;
-    double A[49], temp[7]; int transp[7], pad2;   // the solver's working storage (indexed at run time: LDS on the device, never registers)
     orbm_sim3opt_result res;
+    // what lm_step leaves to the port (defined below, behind sim3opt_records)
+    __host__ __device__ void lm_trial();
+    __host__ __device__ __forceinline__ void lm_accept() { est = rec[0]; }
+    __host__ __device__ void lm_linearise();
 };
 
 // rec[0] is set: its inverse, and for a FULL pass the 14 perturbed estimates of the numeric Jacobian and theirs.  oplusImpl:
@@ -150,33 +152,26 @@ __host__ __device__ __forceinline__ void sim3opt_records(Sim3Ctl& S, bool full) 
             sim3_inverse(S.rec[1 + 2 * d + sg], S.rec[16 + 2 * d + sg]);
         }
 }
-__host__ __device__ __forceinline__ void sim3opt_full(Sim3Ctl& S) { S.rec[0] = S.est; sim3opt_records(S, true); S.cmd = S3O_CMD_FULL; }
+__host__ __device__ __forceinline__ void Sim3Ctl::lm_linearise() { rec[0] = est; sim3opt_records(*this, true); cmd = LM_CMD_FULL; }
+__host__ __device__ __forceinline__ void Sim3Ctl::lm_trial() {
+    if (fix_scale) x[6] = 0;                 // oplusImpl writes through the solver's x: computeScale reads the 0
+    Sim3Quat d;
+    sim3_exp(x, order, d);
+    sim3_mul(d, est, rec[0]);
+    sim3opt_records(*this, false);
+}
 
 __host__ __device__ __forceinline__ void sim3opt_write(Sim3Ctl& S, const Sim3Quat& T) {
     for (int k = 0; k < 4; ++k) S.res.q[k] = x86_nan(T.q[k]);
     for (int k = 0; k < 3; ++k) S.res.t[k] = x86_nan(T.t[k]);
     S.res.s = x86_nan(T.s);
 }
-// one trial of the Levenberg loop up to its pass (core/optimization_algorithm_levenberg.cpp:103-121)
-__host__ __device__ __forceinline__ void sim3opt_try(Sim3Ctl& S) {
-    int k = 0;
-    for (int i = 0; i < 7; ++i)
-        for (int j = i; j < 7; ++j, ++k) { S.A[7 * i + j] = S.H[k]; S.A[7 * j + i] = S.H[k]; }
-    for (int i = 0; i < 7; ++i) S.A[8 * i] += S.lambda;
-    S.ok2 = eigen_ldlt_solve<7>(S.A, S.b, S.x, S.temp, S.transp) ? 1 : 0;
-    if (S.fix_scale) S.x[6] = 0;             // oplusImpl writes through the solver's x: computeScale reads the 0
-    Sim3Quat d;
-    sim3_exp(S.x, S.order, d);
-    sim3_mul(d, S.est, S.rec[0]);
-    sim3opt_records(S, false);
-    S.cmd = S3O_CMD_CHI;
-}
 // initializeOptimization() + optimize(max_iter): the estimate stays, lambda is initialised again at iteration 0
 __host__ __device__ __forceinline__ void sim3opt_begin_optimisation(Sim3Ctl& S, int n_active, int max_iter) {
     S.iter = 0; S.max_iter = max_iter;
-    if (n_active <= 0) { S.cmd = S3O_CMD_CLASSIFY; return; }   // no active edge, no active vertex: optimize() returns at once
+    if (n_active <= 0) { S.cmd = LM_CMD_CLASSIFY; return; }   // no active edge, no active vertex: optimize() returns at once
     S.res.optimisations = S.stage + 1;
-    sim3opt_full(S);
+    S.lm_linearise();
 }
 __host__ __device__ __forceinline__ void sim3opt_begin(Sim3Ctl& S, const orbm_sim3opt_problem& P, int n, int order) {
     S.order = order; S.n = n; S.stage = 0; S.n_bad = 0; S.ok2 = 1; S.fix_scale = P.fix_scale ? 1 : 0;
@@ -194,67 +189,8 @@ __host__ __device__ __forceinline__ void sim3opt_begin(Sim3Ctl& S, const orbm_si
 // Called after every pass with the pass's sums.
 __host__ __device__ __forceinline__ void sim3opt_step(Sim3Ctl& S, const double* sum) {
     orbm_pose_round& R = S.res.round[S.stage];
-    if (S.cmd == S3O_CMD_FULL) {             // solve(), :75-101: the errors, the robust chi2 and the system at the estimate
-        S.current_chi = sum[S3O_CHI]; S.ini_chi = S.current_chi;
-        for (int k = 0; k < 28; ++k) S.H[k] = sum[k];
-        for (int k = 0; k < 7; ++k) S.b[k] = sum[28 + k];
-        if (S.iter == 0) {                   // computeLambdaInit: tau * the largest |diagonal|
-            double max_diagonal = 0.;
-            int d = 0;
-            for (int j = 0; j < 7; ++j) { const double v = fabs(S.H[d]); if (v > max_diagonal) max_diagonal = v; d += 7 - j; }
-            S.lambda = 1e-5 * max_diagonal;
-            S.ni = 2; S.n_bad_steps = 0;
-        }
-        S.qmax = 0;
-        sim3opt_try(S);
-        return;
-    }
-    if (S.cmd == S3O_CMD_CHI) {              // :123-149
-        double temp_chi = sum[S3O_CHI];
-        if (!S.ok2) temp_chi = DBL_MAX;
-        double rho = S.current_chi - temp_chi;
-        double scale = 0.;
-        for (int j = 0; j < 7; ++j) scale += S.x[j] * (S.lambda * S.x[j] + S.b[j]);
-        scale += 1e-3;
-        rho /= scale;
-        if (rho > 0 && fabs(temp_chi) <= DBL_MAX) {
-            const double u = 2 * rho - 1;
-            double cube;
-#ifndef __HIP_DEVICE_COMPILE__
-            if (S.order == ORBM_POSE_ORDER_INDEX) cube = pow(u, 3); else
-#endif
-            cube = u * u * u;
-            double alpha = 1. - cube;
-            alpha = alpha < 2. / 3. ? alpha : 2. / 3.;             // (std::min)(alpha, _goodStepUpperScale)
-            const double scale_factor = 1. / 3. < alpha ? alpha : 1. / 3.;   // (std::max)(_goodStepLowerScale, alpha)
-            S.lambda *= scale_factor;
-            S.ni = 2;
-            S.current_chi = temp_chi;
-            S.est = S.rec[0];                // discardTop
-        } else {
-            S.lambda *= S.ni;
-            S.ni *= 2;                       // pop: the estimate stays
-        }
-        S.qmax++;
-        R.trials++;
-        if (rho < 0 && S.qmax < 10) { sim3opt_try(S); return; }
-        // the iteration is over: solve()'s result, then optimize()'s loop (core/sparse_optimizer.cpp:376-414)
-        R.iterations++;
-        bool terminate = S.qmax == 10 || rho == 0;
-        if (!terminate) {
-            if ((S.ini_chi - S.current_chi) * 1e3 < S.ini_chi) S.n_bad_steps++; else S.n_bad_steps = 0;
-            if (S.n_bad_steps >= 3) terminate = true;
-        }
-        S.iter++;
-        if (terminate || S.iter == S.max_iter) {
-            R.chi2 = x86_nan(S.current_chi); R.lambda = x86_nan(S.lambda);
-            S.cmd = S3O_CMD_CLASSIFY;
-        } else {
-            sim3opt_full(S);
-        }
-        return;
-    }
-    // S3O_CMD_CLASSIFY
+    if (S.cmd != LM_CMD_CLASSIFY) { lm_step(S, sum, R); return; }   // a FULL or a CHI pass: one step of the Levenberg loop
+    // LM_CMD_CLASSIFY
     if (S.stage == 0) {                      // :2178-2211
         S.n_bad = (int)sum[S3O_BAD];
         S.res.n_bad = S.n_bad;
@@ -262,7 +198,7 @@ __host__ __device__ __forceinline__ void sim3opt_step(Sim3Ctl& S, const double* 
         if (S.n - S.n_bad < 10) {            // `return 0`: g2oS12 is not touched, the removals stay
             S.res.n_inliers = 0; S.res.written = 0;
             sim3opt_write(S, S.start);
-            S.cmd = S3O_CMD_DONE;
+            S.cmd = LM_CMD_DONE;
             return;
         }
         S.stage = 1;
@@ -272,7 +208,7 @@ __host__ __device__ __forceinline__ void sim3opt_step(Sim3Ctl& S, const double* 
     S.res.n_inliers = S.n - S.n_bad - (int)sum[S3O_BAD];   // nIn (:2218-2235)
     S.res.written = 1;
     sim3opt_write(S, S.est);
-    S.cmd = S3O_CMD_DONE;
+    S.cmd = LM_CMD_DONE;
 }
 
 // the constants of a problem (:2034-2041, :2059, :2136-2138)
@@ -289,10 +225,10 @@ __host__ __device__ inline void sim3opt_camera(const orbm_sim3opt_problem& P, Si
 // one pass's share of one correspondence; flag: 0 active, 1 removed after the first optimisation, 2 failed the final test
 __host__ __device__ inline void sim3opt_pass_pair(const Sim3Cam& C, const Sim3Ctl& S, int cmd, const Sim3Pair& P, uint8_t* flag, double* acc) {
     if (*flag) return;
-    if (cmd == S3O_CMD_CLASSIFY) {
+    if (cmd == LM_CMD_CLASSIFY) {
         if (sim3opt_classify(C, S.rec, P)) { *flag = S.stage == 0 ? 1 : 2; acc[S3O_BAD] += 1.0; }
     } else {
-        sim3opt_accumulate(C, S.rec, P, cmd == S3O_CMD_FULL, acc);
+        sim3opt_accumulate(C, S.rec, P, cmd == LM_CMD_FULL, acc);
     }
 }
 
@@ -316,10 +252,10 @@ __device__ __forceinline__ Sim3Pair sim3opt_load(const Sim3OptDev& A, const orbm
     return E;
 }
 
-__global__ __launch_bounds__(S3O_T) void k_sim3_optimize(Sim3OptDev A) {
+__global__ __launch_bounds__(LM_T) void k_sim3_optimize(Sim3OptDev A) {
     __shared__ Sim3Ctl S;
     __shared__ Sim3Cam C;
-    __shared__ double s_part[S3O_T / 64][S3O_NSUM];
+    __shared__ double s_part[LM_T / 64][S3O_NSUM];
     __shared__ uint8_t s_flag[ORBM_SIM3OPT_CAP];
     const int tid = threadIdx.x;
     const int pb = A.list[blockIdx.x];
@@ -327,42 +263,29 @@ __global__ __launch_bounds__(S3O_T) void k_sim3_optimize(Sim3OptDev A) {
     const int e0 = A.first[pb];
     const int n = min(A.first[pb + 1] - e0, (int)ORBM_SIM3OPT_CAP);   // (a longer problem never reaches the device)
     if (tid == 0) { sim3opt_camera(P, C); sim3opt_begin(S, P, n, ORBM_POSE_ORDER_DEVICE); }
-    for (int e = tid; e < n; e += S3O_T) s_flag[e] = 0;
+    for (int e = tid; e < n; e += LM_T) s_flag[e] = 0;
     for (;;) {
         __syncthreads();                                   // the controller's record is visible
         const int cmd = S.cmd;
-        if (cmd == S3O_CMD_DONE) break;
+        if (cmd == LM_CMD_DONE) break;
         double acc[S3O_NSUM];
 #pragma unroll
         for (int k = 0; k < S3O_NSUM; ++k) acc[k] = 0.0;
         // this lane's correspondences in ascending order; their constants stream from the staged arrays
-        for (int e = tid; e < n; e += S3O_T) {
+        for (int e = tid; e < n; e += LM_T) {
             if (s_flag[e]) continue;
             const Sim3Pair E = sim3opt_load(A, P, e0 + e);
             sim3opt_pass_pair(C, S, cmd, E, &s_flag[e], acc);
         }
-        // the wave's sums: xor butterfly, offsets 1, 2, 4, 8, 16, 32 (every lane ends with the same bits: a + b == b + a)
-#pragma unroll
-        for (int k = 0; k < S3O_NSUM; ++k) {
-            if (cmd != S3O_CMD_FULL && k < S3O_CHI) continue;   // (zeros: nothing was added to them in this pass)
-            double v = acc[k];
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) v = v + __shfl_xor(v, off, 64);
-            acc[k] = v;
-        }
-        if ((tid & 63) == 0) {
-#pragma unroll
-            for (int k = 0; k < S3O_NSUM; ++k) s_part[tid >> 6][k] = acc[k];
-        }
+        lm_wave_sums(acc, cmd == LM_CMD_FULL ? 0 : S3O_CHI, s_part, tid);
         __syncthreads();                                   // the four waves' sums are visible, every lane is done with the record
         if (tid == 0) {
             double sum[S3O_NSUM];
-#pragma unroll
-            for (int k = 0; k < S3O_NSUM; ++k) sum[k] = ((s_part[0][k] + s_part[1][k]) + s_part[2][k]) + s_part[3][k];   // wave order
+            lm_add_waves(s_part, sum);
             sim3opt_step(S, sum);
         }
     }
-    for (int e = tid; e < n; e += S3O_T) A.flags[e0 + e] = s_flag[e];
+    for (int e = tid; e < n; e += LM_T) A.flags[e0 + e] = s_flag[e];
     if (tid == 0) A.res[pb] = S.res;
 }
 
@@ -388,24 +311,10 @@ void sim3opt_problem_host(const orbm_sim3opt_problem& P, const Sim3OptPairs& G, 
     std::vector<Sim3Pair> E((size_t)n);
     for (int e = 0; e < n; ++e) E[e] = host_pair(P, G, e0 + e);
     std::vector<double> part;
-    if (order == ORBM_POSE_ORDER_DEVICE) part.resize((size_t)S3O_T * S3O_NSUM);
-    while (S.cmd != S3O_CMD_DONE) {
+    while (S.cmd != LM_CMD_DONE) {
         double sum[S3O_NSUM];
         const int cmd = S.cmd;
-        if (order == ORBM_POSE_ORDER_INDEX) {
-            for (int k = 0; k < S3O_NSUM; ++k) sum[k] = 0.0;
-            for (int e = 0; e < n; ++e) sim3opt_pass_pair(C, S, cmd, E[e], &flags[e], sum);
-        } else {                                           // the kernel's tree: lanes, butterfly inside each wave, waves in order
-            std::fill(part.begin(), part.end(), 0.0);
-            for (int l = 0; l < S3O_T && l < n; ++l)
-                for (int e = l; e < n; e += S3O_T) sim3opt_pass_pair(C, S, cmd, E[e], &flags[e], &part[(size_t)l * S3O_NSUM]);
-            for (int off = 1; off < 64; off <<= 1)
-                for (int l = 0; l < S3O_T; ++l)
-                    if (!(l & off) && !(l & (off - 1)))
-                        for (int k = 0; k < S3O_NSUM; ++k) part[(size_t)l * S3O_NSUM + k] = part[(size_t)l * S3O_NSUM + k] + part[(size_t)(l | off) * S3O_NSUM + k];
-            for (int k = 0; k < S3O_NSUM; ++k)
-                sum[k] = ((part[k] + part[(size_t)64 * S3O_NSUM + k]) + part[(size_t)128 * S3O_NSUM + k]) + part[(size_t)192 * S3O_NSUM + k];
-        }
+        lm_pass_host<S3O_NSUM>(order, n, part, sum, [&](int e, double* acc) { sim3opt_pass_pair(C, S, cmd, E[e], &flags[e], acc); });
         sim3opt_step(S, sum);
     }
     res = S.res;
@@ -414,10 +323,8 @@ void sim3opt_problem_host(const orbm_sim3opt_problem& P, const Sim3OptPairs& G, 
 int validate(const orbm_sim3opt_problem* problems, int B, const int32_t* first, const Sim3OptPairs& G, const uint8_t* flag_out,
              const orbm_sim3opt_result* results) {
     MORB_ARG(problems && first && results);
-    if (B < 1 || B > ORBM_SIM3OPT_MAX_BATCH) { morb::set_error("B = %d is outside 1..%d", B, (int)ORBM_SIM3OPT_MAX_BATCH); return ORB_E_ARG; }
-    MORB_ARG(first[0] == 0);
+    if (const int rc = lm_validate_csr(B, ORBM_SIM3OPT_MAX_BATCH, first)) return rc;
     for (int b = 0; b < B; ++b) {
-        if (first[b + 1] < first[b]) { morb::set_error("first[] decreases at problem %d", b); return ORB_E_ARG; }
         const orbm_sim3opt_problem& P = problems[b];
         if (P.n_levels1 < 1 || P.n_levels1 > ORBM_MAX_LEVELS || P.n_levels2 < 1 || P.n_levels2 > ORBM_MAX_LEVELS) {
             morb::set_error("problem %d: n_levels = %d, %d are outside 1..%d", b, P.n_levels1, P.n_levels2, (int)ORBM_MAX_LEVELS);
@@ -478,43 +385,29 @@ int orbm_sim3_optimize(orbm_matcher* m, const orbm_sim3opt_problem* problems, in
     int rc = validate(problems, B, first, G, flag_out, results);
     if (rc) return rc;
     const int ne = first[B];
-    std::vector<int32_t> list;
-    for (int b = 0; b < B; ++b) if (first[b + 1] - first[b] <= ORBM_SIM3OPT_CAP) list.push_back(b);
-    size_t flags_off = 0;
-    if (!list.empty()) {
-        MORB_HIP(hipSetDevice(m->device));
-        morb::StagePack pk;
-        const int i_prob = pk.add(problems, (size_t)B * sizeof(orbm_sim3opt_problem)), i_first = pk.add(first, (size_t)(B + 1) * 4),
-                  i_list = pk.add(list.data(), list.size() * 4);
-        const int i_x1 = pk.add(x3dc1, (size_t)ne * 12), i_x2 = pk.add(x3dc2, (size_t)ne * 12), i_o1 = pk.add(obs1, (size_t)ne * 8),
-                  i_o2 = pk.add(obs2, (size_t)ne * 8), i_c1 = pk.add(octave1, (size_t)ne * 4), i_c2 = pk.add(octave2, (size_t)ne * 4);
-        const size_t res_bytes = morb::align16((size_t)B * sizeof(orbm_sim3opt_result));
-        const morb::StagePack::Block blk = pk.open(m->sim3opt.stage, &rc);
-        if (rc || (rc = m->sim3opt.out.reserve(res_bytes + (size_t)std::max(ne, 1)))) return rc;
-        blk.publish();
-        Sim3OptDev A;
-        A.prob = blk.dev<orbm_sim3opt_problem>(i_prob); A.first = blk.dev<int32_t>(i_first); A.list = blk.dev<int32_t>(i_list);
-        A.x3dc1 = blk.dev<float>(i_x1); A.x3dc2 = blk.dev<float>(i_x2); A.obs1 = blk.dev<float>(i_o1); A.obs2 = blk.dev<float>(i_o2);
-        A.octave1 = blk.dev<int32_t>(i_c1); A.octave2 = blk.dev<int32_t>(i_c2);
-        A.res = (orbm_sim3opt_result*)m->sim3opt.out.dp; A.flags = m->sim3opt.out.dp + res_bytes;
-        flags_off = res_bytes;
-        hipLaunchKernelGGL(k_sim3_optimize, dim3((unsigned)list.size()), dim3(S3O_T), 0, m->stream, A);
-        MORB_HIP(hipGetLastError());
-    }
-    // while the kernel runs: the problems the device does not take
-    for (int b = 0; b < B; ++b)
-        if (first[b + 1] - first[b] > ORBM_SIM3OPT_CAP)
-            sim3opt_problem_host(problems[b], G, first[b], first[b + 1] - first[b], ORBM_POSE_ORDER_DEVICE, flag_out + first[b], results[b]);
-    if (!list.empty()) {
-        MORB_HIP(hipStreamSynchronize(m->stream));
-        const orbm_sim3opt_result* R = (const orbm_sim3opt_result*)m->sim3opt.out.p;
-        for (int b : list) {
-            results[b] = R[b];
-            memcpy(flag_out + first[b], m->sim3opt.out.p + flags_off + first[b], (size_t)(first[b + 1] - first[b]));
-        }
-    }
-    m->last_sim3opt[0] = (int)list.size(); m->last_sim3opt[1] = B - (int)list.size();
-    return ORB_OK;
+    return lm_csr_call(m, m->sim3opt, B, first, ORBM_SIM3OPT_CAP, flag_out, results, m->last_sim3opt,
+        [&](const std::vector<int32_t>& list, size_t* flags_off) -> int {
+            morb::StagePack pk;
+            const int i_prob = pk.add(problems, (size_t)B * sizeof(orbm_sim3opt_problem)), i_first = pk.add(first, (size_t)(B + 1) * 4),
+                      i_list = pk.add(list.data(), list.size() * 4);
+            const int i_x1 = pk.add(x3dc1, (size_t)ne * 12), i_x2 = pk.add(x3dc2, (size_t)ne * 12), i_o1 = pk.add(obs1, (size_t)ne * 8),
+                      i_o2 = pk.add(obs2, (size_t)ne * 8), i_c1 = pk.add(octave1, (size_t)ne * 4), i_c2 = pk.add(octave2, (size_t)ne * 4);
+            const size_t res_bytes = morb::align16((size_t)B * sizeof(orbm_sim3opt_result));
+            int rc;
+            const morb::StagePack::Block blk = pk.open(m->sim3opt.stage, &rc);
+            if (rc || (rc = m->sim3opt.out.reserve(res_bytes + (size_t)std::max(ne, 1)))) return rc;
+            blk.publish();
+            Sim3OptDev A;
+            A.prob = blk.dev<orbm_sim3opt_problem>(i_prob); A.first = blk.dev<int32_t>(i_first); A.list = blk.dev<int32_t>(i_list);
+            A.x3dc1 = blk.dev<float>(i_x1); A.x3dc2 = blk.dev<float>(i_x2); A.obs1 = blk.dev<float>(i_o1); A.obs2 = blk.dev<float>(i_o2);
+            A.octave1 = blk.dev<int32_t>(i_c1); A.octave2 = blk.dev<int32_t>(i_c2);
+            A.res = (orbm_sim3opt_result*)m->sim3opt.out.dp; A.flags = m->sim3opt.out.dp + res_bytes;
+            *flags_off = res_bytes;
+            hipLaunchKernelGGL(k_sim3_optimize, dim3((unsigned)list.size()), dim3(LM_T), 0, m->stream, A);
+            MORB_HIP(hipGetLastError());
+            return ORB_OK;
+        },
+        [&](int b) { sim3opt_problem_host(problems[b], G, first[b], first[b + 1] - first[b], ORBM_POSE_ORDER_DEVICE, flag_out + first[b], results[b]); });
 }
 
 }  // extern "C"
