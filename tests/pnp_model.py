@@ -385,10 +385,10 @@ def compute_pose(pws, us, K, svd=None):
     return best
 
 
-def check_inliers(R, t, K, p3dw, p2d, max_err):
-    """CheckInliers (:314-345) of a batch of poses on one correspondence list: R (H, 3, 3), t (H, 3) float64, K = fu fv uc vc,
-    p3dw (N, 3), p2d (N, 2), max_err (N,) float32 -> bool (H, N)."""
-    p3dw = np.asarray(p3dw, np.float32); p2d = np.asarray(p2d, np.float32); max_err = np.asarray(max_err, np.float32)
+def errors2(R, t, K, p3dw, p2d):
+    """error2 of CheckInliers (:314-341) of a batch of poses on one correspondence list: R (H, 3, 3), t (H, 3) float64, K = fu fv uc vc,
+    p3dw (N, 3), p2d (N, 2) -> float32 (H, N)."""
+    p3dw = np.asarray(p3dw, np.float32); p2d = np.asarray(p2d, np.float32)
     X = p3dw.astype(np.float64)
     fu, fv, uc, vc = [float(k) for k in K]
     with np.errstate(all="ignore"):
@@ -399,8 +399,13 @@ def check_inliers(R, t, K, p3dw, p2d, max_err):
         ve = vc + fv * Yc.astype(np.float64) * invZc.astype(np.float64)
         distX = (p2d[None, :, 0].astype(np.float64) - ue).astype(np.float32)
         distY = (p2d[None, :, 1].astype(np.float64) - ve).astype(np.float32)
-        error2 = distX * distX + distY * distY
-        return error2 < max_err[None, :]
+        return distX * distX + distY * distY
+
+
+def check_inliers(R, t, K, p3dw, p2d, max_err):
+    """CheckInliers (:314-345): `error2 < mvMaxError[i]`; max_err (N,) float32 -> bool (H, N)."""
+    with np.errstate(all="ignore"):
+        return errors2(R, t, K, p3dw, p2d) < np.asarray(max_err, np.float32)[None, :]
 
 
 def mask_words(inl):
