@@ -83,6 +83,10 @@ int orbm_debug_time_project(orbm_matcher* m, const orbm_frame* f, const orbm_que
  * workspace (inspection only; host-side bookkeeping of enqueue_join, no kernel knows it; all zero before the first one).  A test written
  * for one form of k_bow_join asserts this, so that a moved threshold fails it instead of quietly running another kernel. */
 int orbv_debug_last_join(const orbv_workspace* w, int* out4);
+/* {rounds given, rounds enqueued (a round whose search has an empty side is not), kernel launches, stream synchronisations} of the last
+ * orbv_create_new_points_keyframe on the workspace (inspection only; counted on the host where the call enqueues, as last_join is; all
+ * zero before the first call and after one that was refused). */
+int orbv_debug_last_keyframe_call(const orbv_workspace* w, int* out4);
 
 /* ---- front end: probes of the multi-GPU exchange ------------------------------------------------------------------------- */
 /* With on != 0 every step of a handle with an exchange records (HIP events) when its search and when its exchange (all-gather +

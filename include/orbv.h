@@ -220,6 +220,34 @@ int orbv_create_new_points_resident(orbv_workspace* w, const orbv_keyframe* a, c
                                     const uint8_t* flags_b, const orbv_triangulation* t, const orbv_tri_geometry* geometry, int th_low,
                                     int check_orientation, int32_t* match, orbv_tri_out* out, int* n_accepted);
 
+/* LocalMapping::CreateNewMapPoints for ALL neighbours of a keyframe (reference src/LocalMapping.cc:315-690) in one enqueue with one
+ * synchronisation.  The call is defined by the loop it replaces.  A state free[i] starts as bit 0 of flags_a[i] (flags_a == NULL: of the
+ * flags uploaded with `a`; those NULL too: every feature is free).  Round k is exactly
+ *     orbv_create_new_points_resident(w, a, <flags>, rounds[k].b, rounds[k].flags_b, &rounds[k].t, &rounds[k].geometry, ...)
+ * with <flags>[i] = flags_a[i] with bit 0 replaced by free[i] && rounds[k].geometry.cam_enabled[cam_of[i]] (the reference's vbCam
+ * filter inside SearchForTriangulation and its istrian[camIdx1] test at :414 are the same bits, so ORBV_TRI_CAM_OFF cannot occur
+ * here), and writes match + k*a->n, out + k*a->n, n_matches[k] and n_accepted[k].  After round k, free[i] = 0 wherever the round's
+ * record has outcome == ORBV_TRI_ACCEPTED (mpCurrentKeyFrame->AddMapPoint(pMP, idx1), :682; the next neighbour's search skips the
+ * feature, src/ORBmatcher.cc !pKF1->GetMapPoint(i)); no other outcome takes a feature out.  The update runs on the device
+ * (k_triangulate_round): the state and the round's flags live in the workspace, the flags stored with `a` are never written.
+ * Every output equals, byte for byte, what that loop of calls returns.  geometry.kf1 describes `a` in every round.
+ * Validation is all or nothing and precedes the first launch: everything orbv_create_new_points_resident checks, for every round
+ * (orb_last_error() names the round), and 0 <= n_rounds <= ORBV_MAX_ROUNDS.  A round whose search has an empty side launches
+ * nothing, returns all -1 / zero records and leaves free[] alone; n_rounds == 0 or a->n == 0 launches nothing at all.
+ * One deviation from the reference: it abandons the remaining neighbours when CheckNewKeyFrames() turns true between two of them
+ * (:318); one enqueue cannot, so the caller checks before the call and gets all neighbours. */
+enum { ORBV_MAX_ROUNDS = 32 };            /* the reference asks for 15 neighbours (20 monocular) */
+typedef struct orbv_new_points_round {    /* one neighbour */
+    const orbv_keyframe* b;               /* resident, with geometry */
+    const uint8_t* flags_b;               /* b->n bytes, or NULL: as in orbv_create_new_points_resident */
+    orbv_triangulation t;                 /* F12 / epipoles of (a, b), b's level tables */
+    orbv_tri_geometry geometry;           /* kf1 = a (the same in every round), kf2 = b, cam_enabled = this round's istrian, ratio_factor */
+} orbv_new_points_round;
+int orbv_create_new_points_keyframe(orbv_workspace* w, const orbv_keyframe* a, const uint8_t* flags_a,
+                                    const orbv_new_points_round* rounds, int n_rounds, int th_low, int check_orientation,
+                                    int32_t* match /* n_rounds x a->n */, orbv_tri_out* out /* n_rounds x a->n */,
+                                    int* n_matches /* n_rounds */, int* n_accepted /* n_rounds */);
+
 /* Resident keyframe database: KeyFrameDatabase's inverted-file walk and the scores behind it (reference src/KeyFrameDatabase.cc:132-153,
  * :187, :429-446, :477; LoopClosing::DetectLoop's minScore loop, src/LoopClosing.cc:150-170) without an inverted file.  Every BowVector
  * added stays in HBM (word ids strictly ascending, values double); one pass of k_db_query over all of them gives, per entry, the number

@@ -19,4 +19,4 @@ from .matcher import PnPProblem, pnp_ransac_host, pnp_walk, pnp_walk_state, pnp_
 from ._lib import PNP_PROBLEM_DTYPE, PNP_HYP_DTYPE, PNP_REFINED_DTYPE, PNP_WALK_DTYPE, PNP_CAP, PNP_MAX_ITS, PNP_MAX_BATCH, PNP_MAX_RECORDS  # noqa: F401
 from ._lib import PNP_FLAG_SINGULAR_QR, PNP_FLAG_RANDOM_SVD, PNP_WALK_NOTHING, PNP_WALK_REFINED, PNP_WALK_BEST  # noqa: F401
 from .vocabulary import Vocabulary, BowSearch, Side as BowSide, FeatureVector, score_l1, KeyFrameDatabase  # noqa: F401
-from .vocabulary import TriKeyframe, TRI_OUT_DTYPE, cos_stereo, triangulate_pairs_host  # noqa: F401
+from .vocabulary import TriKeyframe, TRI_OUT_DTYPE, cos_stereo, triangulate_pairs_host, NewPointsRound  # noqa: F401

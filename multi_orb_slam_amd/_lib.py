@@ -157,6 +157,10 @@ class TriGeometry(C.Structure):  # orbv_tri_geometry
     _fields_ = [("kf1", TriKeyframe), ("kf2", TriKeyframe), ("cam_enabled", C.c_uint8 * 2), ("ratio_factor", C.c_float)]
 
 
+class NewPointsRound(C.Structure):  # orbv_new_points_round
+    _fields_ = [("b", C.c_void_p), ("flags_b", C.c_void_p), ("t", Triangulation), ("geometry", TriGeometry)]
+
+
 def build(verbose=False):
     """Compile every HIP source for gfx950 into lib/libmorb.so (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-C", CSRC] + ([] if verbose else ["-s"])
@@ -337,6 +341,8 @@ def lib():
     L.orbv_triangulate_pairs.argtypes = [vp, vp, vp, vp, vp, i32, f32, vp]
     L.orbv_keyframe_set_geometry.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.orbv_create_new_points_resident.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
+    L.orbv_create_new_points_keyframe.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
+    L.orbv_debug_last_keyframe_call.argtypes = [vp, vp]
     L.orbv_db_create.argtypes = [i32, i32, vp]
     L.orbv_db_destroy.argtypes = [vp]; L.orbv_db_destroy.restype = None
     L.orbv_db_add.argtypes = [vp, C.c_uint64, vp, vp, i32]

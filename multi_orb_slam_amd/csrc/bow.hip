@@ -629,7 +629,7 @@ void orbv_workspace_destroy(orbv_workspace* w) {
     if (!w) return;
     (void)hipSetDevice(w->device);
     if (w->stream) { (void)hipStreamSynchronize(w->stream); (void)hipStreamDestroy(w->stream); }
-    w->h_stage.release(); w->d_stage.release(); w->d_work.release(); w->h_match.release(); w->h_tri.release(); w->tri_const.release();
+    w->h_stage.release(); w->d_stage.release(); w->d_work.release(); w->h_match.release(); w->h_tri.release(); w->tri_const.release(); w->d_chain.release();
     delete w;
 }
 
@@ -690,15 +690,25 @@ int max_node_of(const orbv_side* s) {
     return m;
 }
 
+// JoinWork of n_out output words: the words, the histogram, the bins
+inline size_t join_work_bytes(int n_out) { return morb::align16((size_t)n_out * 4) + morb::align16((HISTO + 1) * 4) + morb::align16((size_t)n_out); }
+
 // init + join + finish enqueued on the workspace's stream, no synchronisation.  *d_final (may be NULL) receives the device address of
 // the n_out filtered match words, valid for work enqueued behind this on the same stream until the workspace's next search.
+// h_match (device alias of pinned words): NULL = the start of w->h_match, reserved here with the work area; otherwise the caller has
+// reserved both (bow_chain_reserve) and nothing is reallocated here.
 int enqueue_join(orbv_workspace* w, const SideDev& A, const SideDev& B, int max_nc, int mode, const TriDev& T, int th_low, float nnratio,
-                 int check_ori, const int32_t** d_final) {
+                 int check_ori, const int32_t** d_final, int32_t* h_match = nullptr) {
     const int n_out = mode == 0 ? B.n : A.n;
     if (max_nc > JOIN_MAX_NODE) { morb::set_error("a vocabulary node holds %d features (limit %d)", max_nc, JOIN_MAX_NODE); return ORB_E_CAPACITY; }
     int rc;
-    const size_t work_bytes = morb::align16((size_t)n_out * 4) + morb::align16((HISTO + 1) * 4) + morb::align16((size_t)n_out);
-    if ((rc = w->d_work.reserve(work_bytes)) || (rc = w->h_match.reserve((size_t)n_out + 4))) return rc;
+    const size_t work_bytes = join_work_bytes(n_out);
+    if (h_match) {
+        if (w->d_work.cap < work_bytes) { morb::set_error("the join's work area was not reserved"); return ORB_E_ARG; }
+    } else {
+        if ((rc = w->d_work.reserve(work_bytes)) || (rc = w->h_match.reserve((size_t)n_out + 4))) return rc;
+        h_match = w->h_match.dp;
+    }
     JoinWork W;
     W.match = (int32_t*)w->d_work.p;
     W.hist = (int*)(w->d_work.p + morb::align16((size_t)n_out * 4));
@@ -721,16 +731,17 @@ int enqueue_join(orbv_workspace* w, const SideDev& A, const SideDev& B, int max_
         else if (mode == 1) k_bow_join<1, 1><<<A.n_nodes, 64, lds, st>>>(A, B, T, th_low, nnratio, check_ori, W, claimed_bytes, lds_cand);
         else k_bow_join<2, 1><<<A.n_nodes, 64, lds, st>>>(A, B, T, th_low, nnratio, check_ori, W, claimed_bytes, lds_cand);
     }
-    k_bow_finish<<<(n_out + 255) / 256, 256, 0, st>>>(W, n_out, check_ori, w->h_match.dp, d_final ? W.match : nullptr);
+    k_bow_finish<<<(n_out + 255) / 256, 256, 0, st>>>(W, n_out, check_ori, h_match, d_final ? W.match : nullptr);
     MORB_HIP(hipGetLastError());
     if (d_final) *d_final = W.match;
     return ORB_OK;
 }
 
-// after the synchronisation: the words out of pinned memory, counted on the way
-void collect_join(orbv_workspace* w, int n_out, int32_t* match, int* nmatches) {
+// after the synchronisation: the words out of pinned memory (slice `round` of them in the chained call), counted on the way
+void collect_join(orbv_workspace* w, int n_out, int32_t* match, int* nmatches, int round = 0) {
     int nm = 0;
-    for (int i = 0; i < n_out; ++i) { const int v = w->h_match.p[i]; match[i] = v; nm += v >= 0; }
+    const int32_t* src = w->h_match.p + (size_t)round * n_out;
+    for (int i = 0; i < n_out; ++i) { const int v = src[i]; match[i] = v; nm += v >= 0; }
     *nmatches = nm;   // == accepted - removed by the rotation filter: every accepted match owns one output word
 }
 
@@ -828,7 +839,41 @@ int bow_triangulation_search_enqueue(orbv_workspace* w, const orbv_keyframe* a, 
                                      int* nmatches, int* enqueued, const int32_t** d_final) {
     return prepare_join_resident(w, a, flags_a, b, flags_b, 2, t, th_low, 0.f, check_ori, match, nmatches, enqueued, d_final);
 }
-void bow_search_collect(orbv_workspace* w, int n_out, int32_t* match, int* nmatches) { collect_join(w, n_out, match, nmatches); }
+void bow_search_collect(orbv_workspace* w, int n_out, int32_t* match, int* nmatches, int round) { collect_join(w, n_out, match, nmatches, round); }
+
+int bow_chain_check(const orbv_workspace* w, const orbv_keyframe* a, const orbv_keyframe* b, const orbv_triangulation* t) {
+    MORB_ARG(w != nullptr && a != nullptr && b != nullptr);
+    MORB_ARG(a->device == w->device && b->device == w->device);
+    MORB_ARG(a->tri && b->tri);
+    TriDev T;
+    int rc = tri_params(t, T);
+    if (rc) return rc;
+    MORB_ARG(a->max_cam < t->n_cams && b->max_octave < t->n_levels);
+    if (b->max_node > JOIN_MAX_NODE) { morb::set_error("a vocabulary node holds %d features (limit %d)", b->max_node, JOIN_MAX_NODE); return ORB_E_CAPACITY; }
+    return ORB_OK;
+}
+bool bow_chain_runs(const orbv_keyframe* a, const orbv_keyframe* b) {
+    return !(a->D.n_nodes == 0 || b->D.n_nodes == 0 || a->D.n == 0 || b->D.n == 0);
+}
+int bow_chain_reserve(orbv_workspace* w, int n_out, int n_rounds, size_t stage_bytes) {
+    int rc;
+    if ((rc = w->d_work.reserve(join_work_bytes(n_out))) || (rc = w->h_match.reserve((size_t)n_rounds * n_out + 4))) return rc;
+    if (stage_bytes && ((rc = w->h_stage.reserve(stage_bytes)) || (rc = w->d_stage.reserve(stage_bytes)))) return rc;
+    return ORB_OK;
+}
+int bow_chain_enqueue(orbv_workspace* w, const orbv_keyframe* a, const uint8_t* d_flags_a, const orbv_keyframe* b, const uint8_t* d_flags_b,
+                      const orbv_triangulation* t, int th_low, int check_ori, int round, const int32_t** d_final, int* launches) {
+    TriDev T; memset(&T, 0, sizeof(T));
+    int rc = tri_params(t, T);
+    if (rc) return rc;
+    SideDev A = a->D, B = b->D;
+    if (d_flags_a) A.flags = d_flags_a;
+    if (d_flags_b) B.flags = d_flags_b;
+    if ((size_t)(round + 1) * A.n > w->h_match.cap) { morb::set_error("the pinned match words of round %d were not reserved", round); return ORB_E_ARG; }
+    if ((rc = enqueue_join(w, A, B, b->max_node, 2, T, th_low, 0.f, check_ori, d_final, w->h_match.dp + (size_t)round * A.n))) return rc;
+    *launches = 3;   // k_bow_init, k_bow_join, k_bow_finish
+    return ORB_OK;
+}
 }  // namespace morb
 
 extern "C" {
@@ -836,6 +881,12 @@ extern "C" {
 int orbv_debug_last_join(const orbv_workspace* w, int* out4) {
     MORB_ARG(w != nullptr && out4 != nullptr);
     for (int i = 0; i < 4; ++i) out4[i] = w->last_join[i];
+    return ORB_OK;
+}
+
+int orbv_debug_last_keyframe_call(const orbv_workspace* w, int* out4) {
+    MORB_ARG(w != nullptr && out4 != nullptr);
+    for (int i = 0; i < 4; ++i) out4[i] = w->last_kf_call[i];
     return ORB_OK;
 }
 

@@ -1,6 +1,7 @@
 // bow_internal.h -- what bow.hip and triangulate.hip share: the device-side view of a frame / keyframe, the handles behind
-// orbv_workspace / orbv_keyframe, and the two hooks through which the fused call (orbv_create_new_points_resident) runs the resident
-// triangulation search without its synchronisation.
+// orbv_workspace / orbv_keyframe, the two hooks through which the fused call (orbv_create_new_points_resident) runs the resident
+// triangulation search without its synchronisation, and the four through which the chained call (orbv_create_new_points_keyframe)
+// runs one such search per neighbour out of buffers reserved once.
 #pragma once
 #include "../../include/orbv.h"
 #include "orb_common.h"
@@ -44,6 +45,8 @@ struct orbv_workspace {
     morb::PinnedBuf<uint8_t> h_tri;   // records of the triangulation kernel
     morb::StageBuf tri_const;         // the two keyframes' constants of a triangulation call
     int last_join[4] = {0, 0, 0, 0};  // {waves per node, largest B node, lds_cand, mode} of the last enqueued join (orbv_debug_last_join)
+    morb::DevBuf<uint8_t> d_chain;    // orbv_create_new_points_keyframe: the state byte of every feature of `a`, then the round's flags
+    int last_kf_call[4] = {0, 0, 0, 0};  // {rounds given, rounds enqueued, kernel launches, synchronisations} of the last such call
 };
 
 // One frame / keyframe resident in HBM for any number of searches (descriptors, angles, FeatureVector, and the triangulation
@@ -67,5 +70,20 @@ namespace morb {
 int bow_triangulation_search_enqueue(orbv_workspace* w, const orbv_keyframe* a, const uint8_t* flags_a, const orbv_keyframe* b,
                                      const uint8_t* flags_b, const orbv_triangulation* t, int th_low, int check_ori, int32_t* match,
                                      int* nmatches, int* enqueued, const int32_t** d_final);
-void bow_search_collect(orbv_workspace* w, int n_out, int32_t* match, int* nmatches);
+void bow_search_collect(orbv_workspace* w, int n_out, int32_t* match, int* nmatches, int round = 0);   // round: the chained call's slice
+
+// The chained call (orbv_create_new_points_keyframe): every neighbour's search enqueued before the one synchronisation.
+//   bow_chain_check    what the resident triangulation search validates, and the node limit of the join: nothing is touched.
+//   bow_chain_runs     false: the search has an empty side and enqueues nothing.
+//   bow_chain_reserve  EVERY buffer the searches of one call use, before its first launch (a reserve that reallocates while an enqueued
+//                      kernel holds the old pointer is a use-after-free): the join's work area (shared by the rounds: stream order
+//                      serialises them), n_rounds slices of n_out pinned match words, stage_bytes of the pinned stage and its mirror.
+//   bow_chain_enqueue  init + join + finish of one round, no reserve and no copy: d_flags_a / d_flags_b are device addresses (NULL =
+//                      the keyframe's own), the filtered words go to slice `round` of the pinned words and to *d_final as in
+//                      bow_triangulation_search_enqueue.  *launches receives the kernels enqueued.
+int bow_chain_check(const orbv_workspace* w, const orbv_keyframe* a, const orbv_keyframe* b, const orbv_triangulation* t);
+bool bow_chain_runs(const orbv_keyframe* a, const orbv_keyframe* b);
+int bow_chain_reserve(orbv_workspace* w, int n_out, int n_rounds, size_t stage_bytes);
+int bow_chain_enqueue(orbv_workspace* w, const orbv_keyframe* a, const uint8_t* d_flags_a, const orbv_keyframe* b, const uint8_t* d_flags_b,
+                      const orbv_triangulation* t, int th_low, int check_ori, int round, const int32_t** d_final, int* launches);
 }  // namespace morb

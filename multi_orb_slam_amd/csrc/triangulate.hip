@@ -9,12 +9,18 @@
 //                    four double row norms of the Jacobi sweeps stay in registers (every index below is a compile-time constant after
 //                    unrolling; the row swaps of the sort are selects).  A few hundred flops per pair on at most a few thousand lanes:
 //                    latency-bound, sized at one wavefront per workgroup so that a batch spreads over the compute units.
+//   k_triangulate_round   the fused form of k_triangulate (pair (i, match[i])) for one neighbour of the chained call
+//                    (orbv_create_new_points_keyframe): the lane that owns feature i also keeps the feature's state byte -- bit 0 = "has
+//                    no map point yet", cleared when the pair is accepted, as mpCurrentKeyFrame->AddMapPoint does between two neighbours
+//                    (:682) -- and writes the flag byte the NEXT neighbour's search reads for i.  A feature is in at most one pair per
+//                    round and every lane touches its own bytes only: no atomics, no LDS.  k_round_flags forms the first round's flags.
 // No libm function runs in the kernel: + - * / sqrt in float and double only.  cos(2*atan2(mb/2, depth)) is a per-feature constant and
 // arrives as an array (orbv_cos_stereo, host libm), as k_frustum takes its logf.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../include/orbv.h"
@@ -291,6 +297,43 @@ __global__ __launch_bounds__(64) void k_triangulate(const TriKf* __restrict__ K,
     out[p] = o;
 }
 
+// The chained call.  state[i]: the flag byte of feature i of `a` as the call received it, with bit 0 = free[i].  The flags a round's
+// search reads: the state with bit 0 further gated by the round's camera bits (the reference's vbCam inside SearchForTriangulation).
+__device__ __forceinline__ uint8_t round_flag(uint8_t state, int cam, unsigned cam_bits) {
+    const bool on = cam >= 0 && cam <= 1 && ((cam_bits >> cam) & 1u);
+    return (uint8_t)((state & 0xFEu) | ((state & 1u) && on ? 1u : 0u));
+}
+// in: the flags of the call (NULL: every feature usable and not stereo, as the searches read a NULL array)
+__global__ __launch_bounds__(64) void k_round_flags(const uint8_t* __restrict__ in, const int32_t* __restrict__ cam_of, int n, unsigned cam_bits,
+                                                    uint8_t* __restrict__ state, uint8_t* __restrict__ flags) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t s = in ? in[i] : (uint8_t)1;
+    state[i] = s;
+    flags[i] = round_flag(s, cam_of[i], cam_bits);
+}
+// One neighbour: the record of the pair (p, match[p]) as k_triangulate's fused form writes it, then the state of feature p and, when
+// another round follows (next_flags != NULL), that round's flag byte.  match: the words k_bow_finish left in HBM.
+__global__ __launch_bounds__(64) void k_triangulate_round(const TriKf* __restrict__ K, TriArrays F1, TriArrays F2, const int32_t* __restrict__ match,
+                                                          int n, unsigned cam_bits, float ratio_factor, orbv_tri_out* __restrict__ out,
+                                                          uint8_t* __restrict__ state, uint8_t* next_flags, unsigned next_cam_bits) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n) return;
+    const TriKf& K1 = K[0];
+    const TriKf& K2 = K[1];
+    const int i2 = match[p];
+    orbv_tri_out o;
+    o.x3D[0] = o.x3D[1] = o.x3D[2] = 0.0f; o.outcome = ORBV_TRI_NONE; o.path = ORBV_TRI_PATH_NONE;
+    if (p < F1.n && i2 >= 0 && i2 < F2.n) {
+        const TriFeat f1 = tri_load(F1, p, K1.n_levels), f2 = tri_load(F2, i2, K2.n_levels);
+        tri_pair(K1, K2, f1, f2, cam_bits, ratio_factor, o);
+    }
+    out[p] = o;
+    uint8_t s = state[p];
+    if (o.outcome == ORBV_TRI_ACCEPTED) { s &= 0xFEu; state[p] = s; }
+    if (next_flags) next_flags[p] = round_flag(s, F1.cam_of[p], next_cam_bits);
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
 int check_constants(const orbv_tri_keyframe* k, const char* name) {
     if (!k) { morb::set_error("%s is NULL", name); return ORB_E_ARG; }
@@ -352,6 +395,24 @@ int stage_constants(orbv_workspace* w, const orbv_tri_keyframe* kf1, const orbv_
     return ORB_OK;
 }
 inline unsigned cam_bits_of(const uint8_t* cam_enabled) { return (cam_enabled[0] ? 1u : 0u) | (cam_enabled[1] ? 2u : 0u); }
+
+// what the fused calls validate beyond the search, for one (a, b, geometry)
+int check_fused(const orbv_keyframe* a, const orbv_keyframe* b, const orbv_tri_geometry* geometry) {
+    if (!geometry) { morb::set_error("geometry is NULL"); return ORB_E_ARG; }
+    int rc;
+    if ((rc = check_constants(&geometry->kf1, "geometry->kf1")) || (rc = check_constants(&geometry->kf2, "geometry->kf2"))) return rc;
+    if (!a->has_geometry || !b->has_geometry) { morb::set_error("keyframe %s has no geometry arrays (orbv_keyframe_set_geometry)", !a->has_geometry ? "a" : "b"); return ORB_E_ARG; }
+    if (a->max_cam > 1) { morb::set_error("keyframe a has a feature of camera %d, outside cam_enabled[2]", a->max_cam); return ORB_E_ARG; }
+    if (a->max_octave >= geometry->kf1.n_levels) { morb::set_error("keyframe a has octave %d, outside the %d levels", a->max_octave, geometry->kf1.n_levels); return ORB_E_ARG; }
+    if (b->max_octave >= geometry->kf2.n_levels) { morb::set_error("keyframe b has octave %d, outside the %d levels", b->max_octave, geometry->kf2.n_levels); return ORB_E_ARG; }
+    return ORB_OK;
+}
+TriArrays arrays_of(const orbv_keyframe* k) {
+    TriArrays F;
+    F.n = k->D.n; F.x = k->D.x; F.y = k->D.y; F.octave = k->D.octave; F.cam_of = k->D.cam_of;
+    F.xd = k->G.xd; F.yd = k->G.yd; F.uright = k->G.uright; F.depth = k->G.depth; F.cos_stereo = k->G.cos_stereo;
+    return F;
+}
 
 }  // namespace
 
@@ -445,13 +506,8 @@ int orbv_create_new_points_resident(orbv_workspace* w, const orbv_keyframe* a, c
                                     const uint8_t* flags_b, const orbv_triangulation* t, const orbv_tri_geometry* geometry, int th_low,
                                     int check_orientation, int32_t* match, orbv_tri_out* out, int* n_accepted) {
     MORB_ARG(w != nullptr && a != nullptr && b != nullptr && n_accepted != nullptr);
-    if (!geometry) { morb::set_error("geometry is NULL"); return ORB_E_ARG; }
-    int rc;
-    if ((rc = check_constants(&geometry->kf1, "geometry->kf1")) || (rc = check_constants(&geometry->kf2, "geometry->kf2"))) return rc;
-    if (!a->has_geometry || !b->has_geometry) { morb::set_error("keyframe %s has no geometry arrays (orbv_keyframe_set_geometry)", !a->has_geometry ? "a" : "b"); return ORB_E_ARG; }
-    if (a->max_cam > 1) { morb::set_error("keyframe a has a feature of camera %d, outside cam_enabled[2]", a->max_cam); return ORB_E_ARG; }
-    if (a->max_octave >= geometry->kf1.n_levels) { morb::set_error("keyframe a has octave %d, outside the %d levels", a->max_octave, geometry->kf1.n_levels); return ORB_E_ARG; }
-    if (b->max_octave >= geometry->kf2.n_levels) { morb::set_error("keyframe b has octave %d, outside the %d levels", b->max_octave, geometry->kf2.n_levels); return ORB_E_ARG; }
+    int rc = check_fused(a, b, geometry);
+    if (rc) return rc;
     const int n = a->D.n;
     if (n > 0 && !out) { morb::set_error("out is NULL"); return ORB_E_ARG; }
     *n_accepted = 0;
@@ -466,13 +522,7 @@ int orbv_create_new_points_resident(orbv_workspace* w, const orbv_keyframe* a, c
     if ((rc = morb::bow_triangulation_search_enqueue(w, a, flags_a, b, flags_b, t, th_low, check_orientation, match, &nmatches, &enqueued, &d_match))) return rc;
     if (n > 0) memset(out, 0, (size_t)n * sizeof(orbv_tri_out));
     if (!enqueued) return ORB_OK;
-    const orbv_keyframe* kf[2] = {a, b};
-    TriArrays F[2];
-    for (int s = 0; s < 2; ++s) {
-        const orbv_keyframe* k = kf[s];
-        F[s].n = k->D.n; F[s].x = k->D.x; F[s].y = k->D.y; F[s].octave = k->D.octave; F[s].cam_of = k->D.cam_of;
-        F[s].xd = k->G.xd; F[s].yd = k->G.yd; F[s].uright = k->G.uright; F[s].depth = k->G.depth; F[s].cos_stereo = k->G.cos_stereo;
-    }
+    const TriArrays F[2] = {arrays_of(a), arrays_of(b)};
     // behind the search on the same stream: the match words are read where k_bow_finish left them
     hipLaunchKernelGGL(k_triangulate, dim3((n + 63) / 64), dim3(64), 0, w->stream, d_K, F[0], F[1], (const int32_t*)nullptr, d_match, n,
                        cam_bits_of(geometry->cam_enabled), geometry->ratio_factor, (orbv_tri_out*)w->h_tri.dp);
@@ -483,6 +533,100 @@ int orbv_create_new_points_resident(orbv_workspace* w, const orbv_keyframe* a, c
     int acc = 0;
     for (int i = 0; i < n; ++i) acc += out[i].outcome == ORBV_TRI_ACCEPTED;
     *n_accepted = acc;
+    return ORB_OK;
+}
+
+int orbv_create_new_points_keyframe(orbv_workspace* w, const orbv_keyframe* a, const uint8_t* flags_a, const orbv_new_points_round* rounds,
+                                    int n_rounds, int th_low, int check_orientation, int32_t* match, orbv_tri_out* out, int* n_matches,
+                                    int* n_accepted) {
+    MORB_ARG(w != nullptr && a != nullptr);
+    for (int i = 0; i < 4; ++i) w->last_kf_call[i] = 0;
+    if (n_rounds < 0 || n_rounds > ORBV_MAX_ROUNDS) { morb::set_error("n_rounds = %d is outside 0..%d", n_rounds, ORBV_MAX_ROUNDS); return ORB_E_ARG; }
+    MORB_ARG(n_rounds == 0 || (rounds != nullptr && n_matches != nullptr && n_accepted != nullptr));
+    const int n = a->D.n;
+    if (n_rounds > 0 && n > 0 && (!match || !out)) { morb::set_error("match / out is NULL"); return ORB_E_ARG; }
+    // ---- validation, all or nothing: nothing has been touched when a round is refused
+    bool runs[ORBV_MAX_ROUNDS];
+    int n_run = 0, first = -1;
+    size_t stage_bytes = flags_a ? morb::align16((size_t)n) : 0, flags_off[ORBV_MAX_ROUNDS];
+    for (int k = 0; k < n_rounds; ++k) {
+        const orbv_new_points_round& r = rounds[k];
+        int rc = r.b ? ORB_OK : ORB_E_ARG;
+        if (rc) morb::set_error("the neighbour is NULL");
+        if (!rc) rc = check_fused(a, r.b, &r.geometry);
+        if (!rc) rc = morb::bow_chain_check(w, a, r.b, &r.t);
+        if (rc) { const std::string why = orb_last_error(); morb::set_error("round %d: %s", k, why.c_str()); return rc; }
+        runs[k] = n > 0 && morb::bow_chain_runs(a, r.b);
+        flags_off[k] = stage_bytes;
+        if (runs[k]) {
+            if (first < 0) first = k;
+            ++n_run;
+            if (r.flags_b) stage_bytes += morb::align16((size_t)r.b->D.n);
+        }
+    }
+    w->last_kf_call[0] = n_rounds;
+    for (int k = 0; k < n_rounds; ++k) {
+        n_matches[k] = 0; n_accepted[k] = 0;
+        for (int i = 0; i < n; ++i) match[(size_t)k * n + i] = -1;
+        if (n > 0) memset(out + (size_t)k * n, 0, (size_t)n * sizeof(orbv_tri_out));
+    }
+    if (n_run == 0) return ORB_OK;
+    MORB_HIP(hipSetDevice(w->device));
+    // ---- every buffer of the call, before the first launch: a round's flags_b, constants, pinned match words and pinned records have
+    //      slices of their own (the next round is enqueued while this one's are still to be read); the join's work area and the device
+    //      match words are shared, stream order serialises the rounds
+    const size_t state_bytes = morb::align16((size_t)n);
+    int rc;
+    if ((rc = morb::bow_chain_reserve(w, n, n_rounds, stage_bytes)) || (rc = w->h_tri.reserve((size_t)n_rounds * n * sizeof(orbv_tri_out))) ||
+        (rc = w->tri_const.reserve((size_t)n_rounds * 2 * sizeof(TriKf))) || (rc = w->d_chain.reserve(2 * state_bytes))) return rc;
+    if (flags_a) memcpy(w->h_stage.p, flags_a, (size_t)n);
+    for (int k = 0; k < n_rounds; ++k) {
+        if (!runs[k]) continue;
+        if (rounds[k].flags_b) memcpy(w->h_stage.p + flags_off[k], rounds[k].flags_b, (size_t)rounds[k].b->D.n);
+        TriKf K[2];
+        fill_constants(&rounds[k].geometry.kf1, K[0]); fill_constants(&rounds[k].geometry.kf2, K[1]);
+        memcpy(w->tri_const.p + (size_t)k * sizeof(K), K, sizeof(K));
+    }
+    w->tri_const.publish();
+    // ---- the enqueue.  From the first launch on an error still waits for the stream: the kernels in flight hold the workspace's buffers
+    int launches = 0;
+    hipStream_t st = w->stream;
+    auto fail = [&](int code) { (void)hipStreamSynchronize(st); return code; };
+    if (stage_bytes) MORB_HIP(hipMemcpyAsync(w->d_stage.p, w->h_stage.p, stage_bytes, hipMemcpyHostToDevice, st));
+    uint8_t* d_state = w->d_chain.p;
+    uint8_t* d_flags = w->d_chain.p + state_bytes;
+    const TriArrays F1 = arrays_of(a);
+    hipLaunchKernelGGL(k_round_flags, dim3((n + 63) / 64), dim3(64), 0, st, flags_a ? (const uint8_t*)w->d_stage.p : a->D.flags, a->D.cam_of, n,
+                       cam_bits_of(rounds[first].geometry.cam_enabled), d_state, d_flags);
+    ++launches;
+    for (int k = first; k < n_rounds; ++k) {
+        if (!runs[k]) continue;
+        const orbv_new_points_round& r = rounds[k];
+        int next = k + 1;
+        while (next < n_rounds && !runs[next]) ++next;
+        const int32_t* d_match = nullptr;
+        int l = 0;
+        if ((rc = morb::bow_chain_enqueue(w, a, d_flags, r.b, r.flags_b ? w->d_stage.p + flags_off[k] : nullptr, &r.t, th_low, check_orientation, k,
+                                          &d_match, &l))) return fail(rc);
+        launches += l;
+        hipLaunchKernelGGL(k_triangulate_round, dim3((n + 63) / 64), dim3(64), 0, st, (const TriKf*)w->tri_const.dp + 2 * k, F1, arrays_of(r.b), d_match, n,
+                           cam_bits_of(r.geometry.cam_enabled), r.geometry.ratio_factor, (orbv_tri_out*)w->h_tri.dp + (size_t)k * n, d_state,
+                           next < n_rounds ? d_flags : (uint8_t*)nullptr, next < n_rounds ? cam_bits_of(rounds[next].geometry.cam_enabled) : 0u);
+        ++launches;
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    w->last_kf_call[1] = n_run; w->last_kf_call[2] = launches; w->last_kf_call[3] = 1;
+    if (e != hipSuccess) { morb::set_error("the chained call failed: %s", hipGetErrorString(e)); return fail(ORB_E_HIP); }
+    for (int k = 0; k < n_rounds; ++k) {
+        if (!runs[k]) continue;
+        morb::bow_search_collect(w, n, match + (size_t)k * n, &n_matches[k], k);
+        orbv_tri_out* o = out + (size_t)k * n;
+        memcpy(o, (const orbv_tri_out*)w->h_tri.p + (size_t)k * n, (size_t)n * sizeof(orbv_tri_out));
+        int acc = 0;
+        for (int i = 0; i < n; ++i) acc += o[i].outcome == ORBV_TRI_ACCEPTED;
+        n_accepted[k] = acc;
+    }
     return ORB_OK;
 }
 

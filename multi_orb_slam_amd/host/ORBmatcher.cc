@@ -1015,16 +1015,14 @@ int ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint
     return nmatches;
 }
 
-// reference src/ORBmatcher.cc:1364-1786.  As there, the F12 argument is not read: one fundamental matrix per camera of
-// the rig is recomputed from the keyframe poses (:1375-1423).
-int ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, std::vector<std::pair<size_t, size_t> >& vMatchedPairs,
-                                       const bool bOnlyStereo, std::vector<bool> vbCam) {
+// reference src/ORBmatcher.cc:1375-1423, :1441-1452: one fundamental matrix and one epipole per camera of the rig from the two poses
+void ORBmatcher::TriangulationGeometry(KeyFrame* pKF1, KeyFrame* pKF2, orbv_triangulation* Tout) {
     cv::Mat R1w[2] = {pKF1->GetRotation(), pKF1->GetRotation_cam2()}, t1w[2] = {pKF1->GetTranslation(), pKF1->GetTranslation_cam2()};
     cv::Mat R2w[2] = {pKF2->GetRotation(), pKF2->GetRotation_cam2()}, t2w[2] = {pKF2->GetTranslation(), pKF2->GetTranslation_cam2()};
     cv::Mat Cw[2] = {pKF1->GetCameraCenter(), pKF1->GetCameraCenter_cam2()};
     const cv::Mat& K1 = pKF1->mK;
     const cv::Mat& K2 = pKF2->mK;
-    orbv_triangulation T;
+    orbv_triangulation& T = *Tout;
     std::memset(&T, 0, sizeof(T));
     T.n_cams = 2; T.n_levels = (int)pKF2->mvScaleFactors.size();
     T.scale_factors = pKF2->mvScaleFactors.data(); T.level_sigma2 = pKF2->mvLevelSigma2.data();
@@ -1039,6 +1037,24 @@ int ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F
         T.ex[i] = pKF2->fx * C2.at<float>(0) * invz + pKF2->cx;
         T.ey[i] = pKF2->fy * C2.at<float>(1) * invz + pKF2->cy;
     }
+}
+
+// pKF as SearchForTriangulation flattens it below, uploaded once; the flags of the moment travel with every search
+int ORBmatcher::CreateResidentKeyFrame(orbv_workspace* w, KeyFrame* pKF, orbv_keyframe** out) {
+    *out = nullptr;
+    FlatSide a;
+    flatten_side(*pKF, pKF->mvKeysUn_total, pKF->mFeatVec, (int)pKF->mvKeysUn_total.size(), a);
+    for (size_t i = 0; i < a.flags.size(); ++i) a.flags[i] = (uint8_t)(1 | (pKF->mvuRight_total[i] >= 0 ? 2 : 0));
+    if (!w) return ORB_OK;
+    return orbv_keyframe_create(w, &a.s, out);
+}
+
+// reference src/ORBmatcher.cc:1364-1786.  As there, the F12 argument is not read: one fundamental matrix per camera of
+// the rig is recomputed from the keyframe poses (TriangulationGeometry).
+int ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12, std::vector<std::pair<size_t, size_t> >& vMatchedPairs,
+                                       const bool bOnlyStereo, std::vector<bool> vbCam) {
+    orbv_triangulation T;
+    TriangulationGeometry(pKF1, pKF2, &T);
     const int n1 = (int)pKF1->mvKeysUn_total.size(), n2 = (int)pKF2->mvKeysUn_total.size();
     FlatSide a, b;
     flatten_side(*pKF1, pKF1->mvKeysUn_total, pKF1->mFeatVec, n1, a);

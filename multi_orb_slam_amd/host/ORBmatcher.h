@@ -19,6 +19,8 @@
 struct orbm_matcher;
 struct orbm_frame;
 struct orbv_workspace;
+struct orbv_keyframe;
+struct orbv_triangulation;
 
 namespace ORB_SLAM2 {
 
@@ -145,6 +147,16 @@ public:
     // internal hook for host/NewMapPoints.cc: the calling thread's BoW workspace (stream + scratch of the searches and of the
     // triangulation stage); NULL (failure reported as every search reports it) when there is no device
     orbv_workspace* GetBowWorkspace() { return Bow(); }
+    // internal hooks for host/NewMapPoints.cc (CreateNewPointsOfKeyFrame), so that the statements exist once:
+    //   TriangulationGeometry   what SearchForTriangulation computes from the two poses before it searches: one fundamental matrix
+    //                           and one epipole per camera (reference src/ORBmatcher.cc:1375-1423, :1441-1452), pKF2's level tables
+    //   CreateResidentKeyFrame  pKF as SearchForTriangulation flattens it (descriptors, angles, FeatureVector, positions, octaves,
+    //                           cameras), uploaded once with orbv_keyframe_create; the flags travel with every call.  w == NULL: the
+    //                           flattening alone (what a run without a device can check), *out = NULL.  Returns the library's code.
+    //   ChecksOrientation       this object's mbCheckOrientation
+    void TriangulationGeometry(KeyFrame* pKF1, KeyFrame* pKF2, orbv_triangulation* T);
+    static int CreateResidentKeyFrame(orbv_workspace* w, KeyFrame* pKF, orbv_keyframe** out);
+    bool ChecksOrientation() const { return mbCheckOrientation; }
 
 private:
     // The device state (matcher handle with its stream and scratch, BoW workspace, cache of uploaded frames) belongs to the

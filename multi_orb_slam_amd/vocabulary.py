@@ -320,6 +320,35 @@ class BowSearch:
                                                          C.byref(T), C.byref(G), th_low, int(check_orientation), ptr(match), ptr(out), C.byref(acc)))
         return match[:a.n], out[:a.n], acc.value
 
+    def create_new_points_keyframe(self, a, rounds, flags_a=None, th_low=50, check_orientation=True):
+        """Every neighbour of keyframe `a` in one enqueue with one synchronisation (orbv_create_new_points_keyframe): round k is
+        create_new_points_resident against rounds[k] (NewPointsRound), and a feature of `a` whose pair was accepted leaves the searches of
+        the rounds behind it -> (match[K, n], TRI_OUT_DTYPE records[K, n], n_matches[K], n_accepted[K])."""
+        K, n = len(rounds), a.n
+        R = (_lib.NewPointsRound * max(K, 1))()
+        keep = []
+        for k, r in enumerate(rounds):
+            T, kp = self._tri(r.F12, r.ex, r.ey, r.scale_factors, r.level_sigma2)
+            fb = self._flags(r.flags_b)
+            keep.append((kp, fb))
+            R[k].b = r.b._h; R[k].flags_b = None if fb is None else fb.ctypes.data; R[k].t = T
+            R[k].geometry.kf1, R[k].geometry.kf2 = r.kf1.c(), r.kf2.c()
+            R[k].geometry.cam_enabled[0], R[k].geometry.cam_enabled[1] = int(bool(r.cam_enabled[0])), int(bool(r.cam_enabled[1]))
+            R[k].geometry.ratio_factor = float(np.float32(r.ratio_factor))
+        match = np.full(max(K * n, 1), -1, np.int32); out = np.zeros(max(K * n, 1), TRI_OUT_DTYPE)
+        nm = np.zeros(max(K, 1), np.int32); acc = np.zeros(max(K, 1), np.int32)
+        fa = self._flags(flags_a)
+        check(_lib.lib().orbv_create_new_points_keyframe(self._h, a._h, None if fa is None else ptr(fa), R, K, th_low, int(check_orientation),
+                                                         ptr(match), ptr(out), ptr(nm), ptr(acc)))
+        return match[:K * n].reshape(K, n), out[:K * n].reshape(K, n), nm[:K], acc[:K]
+
+    def last_keyframe_call(self):
+        """(rounds given, rounds enqueued, kernel launches, stream synchronisations) of the last create_new_points_keyframe here
+        (orbv_debug_last_keyframe_call)."""
+        out = (C.c_int * 4)()
+        check(_lib.lib().orbv_debug_last_keyframe_call(self._h, out))
+        return tuple(out)
+
     @staticmethod
     def _tri(F12, ex, ey, scale_factors, level_sigma2):
         T = Triangulation()
@@ -349,6 +378,15 @@ class BowSearch:
         ca, cb = a.c(), b.c()
         check(_lib.lib().orbv_search_for_triangulation(self._h, C.byref(ca), C.byref(cb), C.byref(T), th_low, int(check_orientation), ptr(match), C.byref(nm)))
         return nm.value, match[:a.n]
+
+
+class NewPointsRound:
+    """One neighbour of BowSearch.create_new_points_keyframe: what create_new_points_resident takes for `b` (orbv_new_points_round).
+    kf1 is the current keyframe's TriKeyframe, the same in every round; cam_enabled is this round's istrian."""
+
+    def __init__(self, b, F12, ex, ey, scale_factors, level_sigma2, kf1, kf2, cam_enabled, ratio_factor, flags_b=None):
+        self.b, self.F12, self.ex, self.ey, self.scale_factors, self.level_sigma2 = b, F12, ex, ey, scale_factors, level_sigma2
+        self.kf1, self.kf2, self.cam_enabled, self.ratio_factor, self.flags_b = kf1, kf2, cam_enabled, ratio_factor, flags_b
 
 
 class Keyframe:
