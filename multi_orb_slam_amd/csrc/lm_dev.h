@@ -6,7 +6,7 @@
 //                         FULL pass reads, at the estimate; sets cmd = LM_CMD_FULL) and the constant LM_TRY_INLINE (lm_next_trial).
 //   lm_wave_sum, lm_wave_sums, lm_add_waves   the kernel's summation tree: xor butterfly (1 .. 32) in each wave, the four waves in wave
 //                         order.  lm_pass_host: the same tree leaf for leaf on the host (DEVICE order) or the plain loop (INDEX order).
-//   lm_validate_csr, lm_csr_call   the checks and the skeleton of a batched call over a CSR of problems.
+//   lm_csr_call           the skeleton of a batched call over a CSR of problems (its checks: morb::validate_csr, stage_pack.h).
 // The sums of a pass: N (N + 1) / 2 entries of H (upper triangle, row-major, i <= j), N of b, the robust chi2, a count.  Both kernels
 // fill the register file (256 VGPRs, no scratch): the device functions are inlined by force, the solver's storage stays in the record.
 #pragma once
@@ -173,14 +173,6 @@ inline void lm_pass_host(int order, int n, std::vector<double>& part, double* su
 }
 
 // ---- the batched call -------------------------------------------------------------------------------------------------------------------
-inline int lm_validate_csr(int B, int max_batch, const int32_t* first) {
-    if (B < 1 || B > max_batch) { morb::set_error("B = %d is outside 1..%d", B, max_batch); return ORB_E_ARG; }
-    MORB_ARG(first[0] == 0);
-    for (int b = 0; b < B; ++b)
-        if (first[b + 1] < first[b]) { morb::set_error("first[] decreases at problem %d", b); return ORB_E_ARG; }
-    return ORB_OK;
-}
-
 // The problems at or under `cap` go to the device in one launch -- launch(list, &flags_off) stages and enqueues, the kernel leaves B
 // records and behind them (at flags_off) the flags in port.out -- while the host routine, host(b), takes the longer ones; then records
 // and flags of the device's problems are copied out.  last[0], last[1]: how many problems went to the device and to the host.

@@ -221,10 +221,10 @@ void refresh_point_host(const orbm_refresh_in& in, int pt, HostScratch& S, orbm_
 int validate(const orbm_refresh_in* in, const orbm_refresh_out* out) {
     MORB_ARG(in && in->n_points >= 0 && in->n_obs >= 0 && in->first && (in->n_points == 0 || (out && in->what)));
     MORB_ARG(in->n_obs == 0 || (in->obs_desc && in->obs_centre && in->obs_alive));
-    MORB_ARG(in->first[0] == 0 && in->first[in->n_points] == in->n_obs);
+    if (const int rc = validate_first(in->n_points, in->first, "point")) return rc;
+    MORB_ARG(in->first[in->n_points] == in->n_obs);
     bool normals = false;
     for (int p = 0; p < in->n_points; ++p) {
-        if (in->first[p + 1] < in->first[p]) { morb::set_error("first[] decreases at point %d", p); return ORB_E_ARG; }
         if (in->what[p] & ~(ORBM_REFRESH_DESCRIPTOR | ORBM_REFRESH_NORMAL_DEPTH)) { morb::set_error("what[%d] = %d has unknown bits", p, (int)in->what[p]); return ORB_E_ARG; }
         normals = normals || ((in->what[p] & ORBM_REFRESH_NORMAL_DEPTH) && in->first[p + 1] > in->first[p]);
     }

@@ -1,9 +1,10 @@
 // matcher_internal.h -- types and internal entry points shared by the translation units of the matcher / front end
 // (hamming.hip: all-pairs kernels; frame.hip: frame assembly; search.hip: projection search + resolve; matcher.hip: handle
 // + host helpers; exchange.hip: RCCL / loopback transport; frontend.hip: orbf_*; mappoint.hip: map-point refresh; pose.hip: pose
-// optimisation; sim3.hip: Sim3 RANSAC; sim3opt.hip: Sim3 refinement).  Not part of the C ABI.  Next to it: cv_dev.h / g2o_dev.h (the restated OpenCV and Eigen / g2o
+// optimisation; sim3.hip: Sim3 RANSAC; sim3opt.hip: Sim3 refinement; pnp.hip: PnP RANSAC).  Not part of the C ABI.  Next to it: cv_dev.h / g2o_dev.h (the restated OpenCV and Eigen / g2o
 // operations those ports share), sincos_dev.h, hamming_dev.h, resolve_dev.h (the steps the resolve's forms share and their LDS layouts),
-// stage_pack.h (the staged input block of a batched call).
+// stage_pack.h (the staged input block of a batched call and the checks on its CSR), lm_dev.h (what the two Levenberg ports share),
+// ransac_dev.h (what the two RANSAC ports share).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <condition_variable>
@@ -54,13 +55,13 @@ struct FrameBufs {  // device storage of one frame; recycled through the matcher
     }
 };
 
-// The buffers of one batched port (orbm_refresh_points, orbm_pose_optimize, orbm_sim3_ransac, orbm_sim3_optimize): one set per port, so that the calls
+// The buffers of one batched port (orbm_refresh_points, orbm_pose_optimize, orbm_sim3_ransac, orbm_sim3_optimize, orbm_pnp_ransac): one set per port, so that the calls
 // of different ports do not reallocate each other's.
 template <typename Out>
 struct PortBufs {
     morb::StageBuf stage;      // the packed inputs of a call: host-written (stage_pack.h), read in place by the kernels
     PinnedBuf<Out> out;        // what the kernels write: mapped pinned
-    DevBuf<uint8_t> scratch;   // HBM that one kernel of the call leaves for the next: Sim3 alone has two kernels and uses it, the others leave it empty
+    DevBuf<uint8_t> scratch;   // HBM that one kernel of the call leaves for the next: the RANSAC ports (Sim3: two kernels, PnP: four) use it, the others leave it empty
     void release() { stage.release(); out.release(); scratch.release(); }
 };
 

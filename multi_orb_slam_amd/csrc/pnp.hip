@@ -13,17 +13,17 @@
 //                     address and nothing goes to scratch memory.
 //   k_pnp_hyp         one lane per (problem, hypothesis), PNP_HYP_T lanes per workgroup (the block is 3 520 B per lane: 16 lanes fill
 //                     55 KB of static LDS): gathers the quadruple, runs the four-point pnp_compute_pose, writes the record.
-//   k_pnp_inliers     one wave per hypothesis, as k_sim3_inliers: coalesced structure-of-arrays reads, a ballot for the mask word, its
-//                     population count for the count.  No atomics.
+//   k_pnp_inliers     one wave per hypothesis, as k_sim3_inliers: coalesced structure-of-arrays reads, pnp_inlier through
+//                     ransac_mask_sweep (ransac_dev.h) for the mask words and the count.  No atomics.
 //   k_pnp_refine      one workgroup per (problem, record slot): scans the problem's counts for the strict prefix maxima, leaves when
 //                     its slot is empty, else gathers the record's inlier set and runs the n-point pnp_compute_pose.
 //                     The per-point arrays (alphas, pcs) live in the port's device block, which grows and is reused.
 //   k_pnp_refine_inliers  one wave per (problem, record slot): CheckInliers with the refined pose, as k_pnp_inliers.  A kernel of its
 //                     own so that nothing it needs stays live in scalar registers across the pose.
-// The four kernels go onto the stream back to back: one enqueue, one synchronisation per call.
+// The four kernels go onto the stream back to back: one enqueue, one synchronisation per call (ransac_csr_call, ransac_dev.h; the
+// checks of a call: ransac_validate<4>, then the refined masks' table here).
 // No libm function runs anywhere: + - * / sqrt fabs in double, CheckInliers' float steps, conversions.
 #include <algorithm>
-#include <cfloat>
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -35,6 +35,7 @@
 #include "matcher_internal.h"
 #include "cv_dev.h"
 #include "stage_pack.h"
+#include "ransac_dev.h"
 
 namespace {
 
@@ -439,26 +440,16 @@ __global__ __launch_bounds__(PNP_INL_T) void k_pnp_inliers(PnpDev A) {
     const orbm_pnp_problem P = A.prob[b];
     const int n0 = A.first[b];
     const int n = A.first[b + 1] - n0;
-    const int W = (n + 63) >> 6;
     const orbm_pnp_hyp& rec = A.rec_dev[g];
     double R[9], t[3];
 #pragma unroll
     for (int k = 0; k < 9; ++k) R[k] = rec.R[k];
 #pragma unroll
     for (int k = 0; k < 3; ++k) t[k] = rec.t[k];
-    const size_t w0 = (size_t)A.mask_first[b] + (size_t)(g - A.its_first[b]) * W;
-    int count = 0;
-    for (int c = 0; c < W; ++c) {
-        const int i = c * 64 + lane;
-        bool in = false;
-        if (i < n) {
-            const int k = n0 + i;
-            in = pnp_inlier(R, t, P.fu, P.fv, P.uc, P.vc, A.x[k], A.y[k], A.z[k], A.u[k], A.v[k], A.e[k]);
-        }
-        const unsigned long long word = __ballot(in);
-        count += __popcll(word);
-        if (lane == 0) { A.mask_out[w0 + c] = word; A.mask_dev[w0 + c] = word; }
-    }
+    const size_t w0 = (size_t)A.mask_first[b] + (size_t)(g - A.its_first[b]) * ransac_words(n);
+    const int count = ransac_mask_sweep(n, lane,
+        [&](int i) { const int k = n0 + i; return pnp_inlier(R, t, P.fu, P.fv, P.uc, P.vc, A.x[k], A.y[k], A.z[k], A.u[k], A.v[k], A.e[k]); },
+        [&](int c, unsigned long long word) { A.mask_out[w0 + c] = word; A.mask_dev[w0 + c] = word; });
     if (lane == 0) { A.rec_out[g].n_inliers = count; A.cnt_dev[g] = count; }
 }
 
@@ -471,7 +462,7 @@ __global__ __launch_bounds__(PNP_REF_T) void k_pnp_refine(PnpDev A) {
     orbm_pnp_refined* const rec = A.ref_dev + (size_t)b * ORBM_PNP_MAX_RECORDS + slot;
     if (A.pp_first[b] < 0) { if (tid == 0) rec->hyp = -1; return; }   // (uniform: the host takes the problem)
     const int n0 = A.first[b], N = A.first[b + 1] - n0, h0 = A.its_first[b], H = A.its_first[b + 1] - h0;
-    const int W = (N + 63) >> 6;
+    const int W = ransac_words(N);
     // the strict prefix maxima above best_start among the counts >= min_inliers: record number `slot` is this workgroup's
     if (tid == 0) {
         const int min_inliers = A.prob[b].min_inliers;
@@ -530,25 +521,15 @@ __global__ __launch_bounds__(PNP_INL_T) void k_pnp_refine_inliers(PnpDev A) {
     if (rec.hyp < 0) return;
     const orbm_pnp_problem P = A.prob[b];
     const int n0 = A.first[b], N = A.first[b + 1] - n0;
-    const int W = (N + 63) >> 6;
     double R[9], t[3];
 #pragma unroll
     for (int k = 0; k < 9; ++k) R[k] = rec.R[k];
 #pragma unroll
     for (int k = 0; k < 3; ++k) t[k] = rec.t[k];
-    uint64_t* rwords = A.rmask_out + (size_t)A.rmask_first[b] + (size_t)slot * W;
-    int count = 0;
-    for (int c = 0; c < W; ++c) {
-        const int i = c * 64 + lane;
-        bool in = false;
-        if (i < N) {
-            const int k = n0 + i;
-            in = pnp_inlier(R, t, P.fu, P.fv, P.uc, P.vc, A.x[k], A.y[k], A.z[k], A.u[k], A.v[k], A.e[k]);
-        }
-        const unsigned long long word = __ballot(in);
-        count += __popcll(word);
-        if (lane == 0) rwords[c] = word;
-    }
+    uint64_t* rwords = A.rmask_out + (size_t)A.rmask_first[b] + (size_t)slot * ransac_words(N);
+    const int count = ransac_mask_sweep(N, lane,
+        [&](int i) { const int k = n0 + i; return pnp_inlier(R, t, P.fu, P.fv, P.uc, P.vc, A.x[k], A.y[k], A.z[k], A.u[k], A.v[k], A.e[k]); },
+        [&](int c, unsigned long long word) { rwords[c] = word; });
     if (lane == 0) {
         orbm_pnp_refined* out = A.ref_out + (size_t)b * ORBM_PNP_MAX_RECORDS + slot;
         out->hyp = rec.hyp; out->n_set = rec.n_set; out->n_inliers = count; out->flags = rec.flags;
@@ -567,20 +548,11 @@ struct PnpIn {
 
 void pnp_check_inliers_host(const PnpIn& I, int b, const double* R, const double* t, uint64_t* words, int* count_out) {
     const orbm_pnp_problem& P = I.problems[b];
-    const int n0 = I.first[b], n = I.first[b + 1] - n0, W = (n + 63) >> 6;
-    int count = 0;
-    for (int c = 0; c < W; ++c) {
-        uint64_t word = 0;
-        for (int l = 0; l < 64 && c * 64 + l < n; ++l) {
-            const size_t k = (size_t)n0 + c * 64 + l;
-            if (pnp_inlier(R, t, P.fu, P.fv, P.uc, P.vc, I.p3dw[3 * k], I.p3dw[3 * k + 1], I.p3dw[3 * k + 2], I.p2d[2 * k], I.p2d[2 * k + 1], I.max_err[k])) {
-                word |= (uint64_t)1 << l;
-                ++count;
-            }
-        }
-        words[c] = word;
-    }
-    *count_out = count;
+    const int n0 = I.first[b], n = I.first[b + 1] - n0;
+    *count_out = ransac_mask_sweep_host(n, words, [&](int i) {
+        const size_t k = (size_t)n0 + i;
+        return pnp_inlier(R, t, P.fu, P.fv, P.uc, P.vc, I.p3dw[3 * k], I.p3dw[3 * k + 1], I.p3dw[3 * k + 2], I.p2d[2 * k], I.p2d[2 * k + 1], I.max_err[k]);
+    });
 }
 
 // compute_pose on the points idx[0 .. n-1] of problem b
@@ -601,7 +573,7 @@ void pnp_pose_host(const PnpIn& I, int b, const int32_t* idx, int n, std::vector
 
 // the hypotheses of one problem: records hyp[0 .. H-1] and mask words[0 .. H*W-1]
 void pnp_hyps_host(const PnpIn& I, int b, orbm_pnp_hyp* hyp, uint64_t* words) {
-    const int n = I.first[b + 1] - I.first[b], h0 = I.its_first[b], H = I.its_first[b + 1] - h0, W = (n + 63) >> 6;
+    const int n = I.first[b + 1] - I.first[b], h0 = I.its_first[b], H = I.its_first[b + 1] - h0, W = ransac_words(n);
     std::vector<double> pp;
     for (int h = 0; h < H; ++h) {
         orbm_pnp_hyp& o = hyp[h];
@@ -621,7 +593,7 @@ void pnp_records(const orbm_pnp_problem& P, const orbm_pnp_hyp* hyp, int H, std:
 
 // Refine() on hypothesis h of problem b (its mask in hwords)
 void pnp_refine_host(const PnpIn& I, int b, int h, const uint64_t* hwords, std::vector<double>& pp, std::vector<int32_t>& idx, orbm_pnp_refined* out, uint64_t* rwords) {
-    const int n = I.first[b + 1] - I.first[b], W = (n + 63) >> 6;
+    const int n = I.first[b + 1] - I.first[b], W = ransac_words(n);
     idx.clear();
     for (int c = 0; c < W; ++c)
         for (int l = 0; l < 64; ++l) if (hwords[c] >> l & 1) idx.push_back(c * 64 + l);
@@ -635,35 +607,17 @@ void pnp_refine_host(const PnpIn& I, int b, int h, const uint64_t* hwords, std::
 // Argument checks; mask_first[b] = the first mask word of problem b, rmask_first[b] = the first word of its refined masks.
 int validate(const PnpIn& I, int B, const orbm_pnp_hyp* hyp_out, const uint64_t* mask_out, const int32_t* n_records_out, const orbm_pnp_refined* refined_out,
              const uint64_t* refined_mask_out, int extra_cap, std::vector<int32_t>& mask_first, std::vector<int32_t>& rmask_first) {
-    MORB_ARG(I.problems && I.first && I.its_first && n_records_out && refined_out && extra_cap >= 0);
-    if (B < 1 || B > ORBM_PNP_MAX_BATCH) { morb::set_error("B = %d is outside 1..%d", B, (int)ORBM_PNP_MAX_BATCH); return ORB_E_ARG; }
-    MORB_ARG(I.first[0] == 0 && I.its_first[0] == 0);
-    mask_first.assign((size_t)B + 1, 0);
+    MORB_ARG(I.problems && n_records_out && refined_out && extra_cap >= 0);
+    if (const int rc = ransac_validate<4>(B, ORBM_PNP_MAX_BATCH, ORBM_PNP_MAX_ITS, I.first, I.its_first, I.quads, hyp_out, mask_out, mask_first)) return rc;
+    if (I.first[B] > 0 && !(I.p3dw && I.p2d && I.max_err)) { morb::set_error("a correspondence array is NULL"); return ORB_E_ARG; }
     rmask_first.assign((size_t)B + 1, 0);
-    long long words = 0, rwords = 0;
+    long long rwords = 0;
     for (int b = 0; b < B; ++b) {
-        if (I.first[b + 1] < I.first[b]) { morb::set_error("first[] decreases at problem %d", b); return ORB_E_ARG; }
-        const int H = I.its_first[b + 1] - I.its_first[b];
-        if (H < 0 || H > ORBM_PNP_MAX_ITS) { morb::set_error("problem %d: %d hypotheses are outside 0..%d", b, H, (int)ORBM_PNP_MAX_ITS); return ORB_E_ARG; }
-        const int W = (I.first[b + 1] - I.first[b] + 63) >> 6;
-        words += (long long)H * W;
-        rwords += (long long)ORBM_PNP_MAX_RECORDS * W;
-        if (words > INT_MAX || rwords > INT_MAX) { morb::set_error("the masks of the call exceed 2^31 words"); return ORB_E_CAPACITY; }
-        mask_first[(size_t)b + 1] = (int32_t)words;
+        rwords += (long long)ORBM_PNP_MAX_RECORDS * ransac_words(I.first[b + 1] - I.first[b]);
+        if (rwords > INT_MAX) { morb::set_error("the refined masks of the call exceed 2^31 words"); return ORB_E_CAPACITY; }
         rmask_first[(size_t)b + 1] = (int32_t)rwords;
     }
-    if (I.first[B] > 0 && !(I.p3dw && I.p2d && I.max_err)) { morb::set_error("a correspondence array is NULL"); return ORB_E_ARG; }
-    if (I.its_first[B] > 0 && !(I.quads && hyp_out)) { morb::set_error("quads or hyp_out is NULL"); return ORB_E_ARG; }
-    if (words > 0 && !mask_out) { morb::set_error("mask_out is NULL"); return ORB_E_ARG; }
     if (rwords > 0 && !refined_mask_out) { morb::set_error("refined_mask_out is NULL"); return ORB_E_ARG; }
-    for (int b = 0; b < B; ++b) {
-        const int n = I.first[b + 1] - I.first[b];
-        for (int g = I.its_first[b]; g < I.its_first[b + 1]; ++g)
-            for (int i = 0; i < 4; ++i) {
-                const int t = I.quads[4 * (size_t)g + i];
-                if (t < 0 || t >= n) { morb::set_error("hypothesis %d: position %d is outside the %d correspondences of problem %d", g, t, n, b); return ORB_E_ARG; }
-            }
-    }
     return ORB_OK;
 }
 
@@ -685,7 +639,7 @@ int pnp_finish_host(const PnpIn& I, int B, const int* host_from, const std::vect
     size_t xr = (size_t)B * ORBM_PNP_MAX_RECORDS, xw = (size_t)rmask_first[B];
     *n_host = 0;
     for (int b = 0; b < B; ++b) {
-        const int W = (I.first[b + 1] - I.first[b] + 63) >> 6, nr = (int)recs[b].size();
+        const int W = ransac_words(I.first[b + 1] - I.first[b]), nr = (int)recs[b].size();
         for (int r = 0; r < std::max(nr, (int)ORBM_PNP_MAX_RECORDS); ++r) {
             const bool extra = r >= ORBM_PNP_MAX_RECORDS;
             orbm_pnp_refined* out = extra ? refined_out + xr : refined_out + (size_t)b * ORBM_PNP_MAX_RECORDS + r;
@@ -699,8 +653,6 @@ int pnp_finish_host(const PnpIn& I, int B, const int* host_from, const std::vect
     }
     return ORB_OK;
 }
-
-inline int cvtt(double d) { return (d >= -2147483648.0 && d < 2147483648.0) ? (int)d : INT_MIN; }   // cvttsd2si / cvttss2si's answer to a NaN or an overflow
 
 }  // namespace
 
@@ -727,105 +679,88 @@ int orbm_pnp_ransac(orbm_matcher* m, const orbm_pnp_problem* problems, int B, co
     int rc = validate(I, B, hyp_out, mask_out, n_records_out, refined_out, refined_mask_out, extra_cap, mask_first, rmask_first);
     if (rc) return rc;
     const int N = first[B], HT = its_first[B];
-    // a problem goes to the device when it has hypotheses and at most ORBM_PNP_CAP correspondences
-    std::vector<int32_t> hyp_prob((size_t)HT, -1), pp_first((size_t)B, -1);
+    // the device refines the records of the problems it runs hypotheses for: those with hypotheses and at most ORBM_PNP_CAP correspondences
+    std::vector<int32_t> pp_first((size_t)B, -1);
     int host_from[ORBM_PNP_MAX_BATCH] = {0};
-    int n_dev = 0, n_host = 0, hyp_dev = 0;
     long long pp_points = 0;
     for (int b = 0; b < B; ++b) {
-        const int n = first[b + 1] - first[b], H = its_first[b + 1] - its_first[b];
-        if (n <= ORBM_PNP_CAP) {
-            ++n_dev;
-            if (H == 0) continue;                      // nothing to run; pp_first stays -1 and the host zeroes the slots
-            for (int g = its_first[b]; g < its_first[b + 1]; ++g) hyp_prob[g] = b;
-            hyp_dev += H;
-            host_from[b] = ORBM_PNP_MAX_RECORDS;
-            pp_first[b] = (int32_t)pp_points;
-            pp_points += (long long)ORBM_PNP_MAX_RECORDS * n;
-            if (pp_points > INT_MAX) { morb::set_error("the per-point blocks of the call exceed 2^31 points"); return ORB_E_CAPACITY; }
-        } else ++n_host;
+        const int n = first[b + 1] - first[b];
+        if (n > ORBM_PNP_CAP || its_first[b + 1] == its_first[b]) continue;   // without hypotheses pp_first stays -1 and the host zeroes the slots
+        host_from[b] = ORBM_PNP_MAX_RECORDS;
+        pp_first[b] = (int32_t)pp_points;
+        pp_points += (long long)ORBM_PNP_MAX_RECORDS * n;
+        if (pp_points > INT_MAX) { morb::set_error("the per-point blocks of the call exceed 2^31 points"); return ORB_E_CAPACITY; }
     }
-    size_t o_mask = 0, o_ref = 0, o_rmask = 0;
-    if (hyp_dev > 0) {
-        MORB_HIP(hipSetDevice(m->device));
-        morb::StagePack pk;
-        const int i_prob = pk.add(problems, (size_t)B * sizeof(orbm_pnp_problem)), i_first = pk.add(first, (size_t)(B + 1) * 4),
-                  i_its = pk.add(its_first, (size_t)(B + 1) * 4), i_mf = pk.add(mask_first.data(), (size_t)(B + 1) * 4),
-                  i_rmf = pk.add(rmask_first.data(), (size_t)(B + 1) * 4), i_ppf = pk.add(pp_first.data(), (size_t)B * 4),
-                  i_hp = pk.add(hyp_prob.data(), (size_t)HT * 4), i_quads = pk.add(quads, (size_t)HT * 16);
-        int i_soa[6];                                      // x y z u v e, transposed below
-        for (int k = 0; k < 6; ++k) i_soa[k] = pk.add_in_place((size_t)N * 4);
-        // what the kernels write for the host: records, masks, refined records, refined masks
-        o_mask = morb::align16((size_t)HT * sizeof(orbm_pnp_hyp));
-        o_ref = morb::align16(o_mask + (size_t)mask_first[B] * 8);
-        o_rmask = morb::align16(o_ref + (size_t)B * ORBM_PNP_MAX_RECORDS * sizeof(orbm_pnp_refined));
-        const size_t out_bytes = o_rmask + (size_t)rmask_first[B] * 8 + 16;
-        // what one kernel leaves for the next: records, counts, masks, the records' inlier sets and per-point arrays
-        morb::BlockLayout sl;
-        const size_t s_rec = sl.take((size_t)HT * sizeof(orbm_pnp_hyp)), s_cnt = sl.take((size_t)HT * 4), s_mask = sl.take((size_t)mask_first[B] * 8),
-                     s_idx = sl.take((size_t)pp_points * 4), s_pp = sl.take((size_t)pp_points * 7 * 8),
-                     s_ref = sl.take((size_t)B * ORBM_PNP_MAX_RECORDS * sizeof(orbm_pnp_refined));
-        const morb::StagePack::Block blk = pk.open(m->pnp.stage, &rc);
-        if (rc || (rc = m->pnp.scratch.reserve(sl.off + 16)) || (rc = m->pnp.out.reserve(out_bytes))) return rc;
-        float* soa[6];
-        for (int k = 0; k < 6; ++k) soa[k] = blk.host<float>(i_soa[k]);
-        for (int k = 0; k < N; ++k) {                      // array of structures -> structure of arrays, once per call
-            soa[0][k] = p3dw[3 * (size_t)k]; soa[1][k] = p3dw[3 * (size_t)k + 1]; soa[2][k] = p3dw[3 * (size_t)k + 2];
-            soa[3][k] = p2d[2 * (size_t)k]; soa[4][k] = p2d[2 * (size_t)k + 1]; soa[5][k] = max_err[k];
-        }
-        blk.publish();
-        PnpDev A;
-        A.prob = blk.dev<orbm_pnp_problem>(i_prob); A.first = blk.dev<int32_t>(i_first); A.its_first = blk.dev<int32_t>(i_its);
-        A.mask_first = blk.dev<int32_t>(i_mf); A.rmask_first = blk.dev<int32_t>(i_rmf); A.pp_first = blk.dev<int32_t>(i_ppf);
-        A.hyp_prob = blk.dev<int32_t>(i_hp); A.quads = blk.dev<int32_t>(i_quads);
-        A.x = blk.dev<float>(i_soa[0]); A.y = blk.dev<float>(i_soa[1]); A.z = blk.dev<float>(i_soa[2]);
-        A.u = blk.dev<float>(i_soa[3]); A.v = blk.dev<float>(i_soa[4]); A.e = blk.dev<float>(i_soa[5]);
-        A.n_hyp = HT;
-        A.soa_stride = (int)(A.y - A.x);
-        uint8_t* S = m->pnp.scratch.p;
-        A.rec_dev = (orbm_pnp_hyp*)(S + s_rec); A.cnt_dev = (int32_t*)(S + s_cnt); A.mask_dev = (uint64_t*)(S + s_mask);
-        A.idx_dev = (int32_t*)(S + s_idx); A.pp_dev = (double*)(S + s_pp); A.ref_dev = (orbm_pnp_refined*)(S + s_ref);
-        uint8_t* O = m->pnp.out.dp;
-        A.rec_out = (orbm_pnp_hyp*)O; A.mask_out = (uint64_t*)(O + o_mask); A.ref_out = (orbm_pnp_refined*)(O + o_ref); A.rmask_out = (uint64_t*)(O + o_rmask);
-        hipLaunchKernelGGL(k_pnp_hyp, dim3((unsigned)((HT + PNP_HYP_T - 1) / PNP_HYP_T)), dim3(PNP_HYP_T), 0, m->stream, A);
-        hipLaunchKernelGGL(k_pnp_inliers, dim3((unsigned)HT), dim3(PNP_INL_T), 0, m->stream, A);
-        hipLaunchKernelGGL(k_pnp_refine, dim3((unsigned)(B * ORBM_PNP_MAX_RECORDS)), dim3(PNP_REF_T), 0, m->stream, A);
-        hipLaunchKernelGGL(k_pnp_refine_inliers, dim3((unsigned)(B * ORBM_PNP_MAX_RECORDS)), dim3(PNP_INL_T), 0, m->stream, A);
-        MORB_HIP(hipGetLastError());
-    }
-    // while the kernels run: the hypotheses of the problems the device does not take
-    for (int b = 0; b < B; ++b)
-        if (first[b + 1] - first[b] > ORBM_PNP_CAP) pnp_hyps_host(I, b, hyp_out + its_first[b], mask_out + mask_first[b]);
-    int n_rec_dev = 0;
-    if (hyp_dev > 0) {
-        MORB_HIP(hipStreamSynchronize(m->stream));
-        const uint8_t* O = m->pnp.out.p;
-        const orbm_pnp_hyp* R = (const orbm_pnp_hyp*)O;
-        const uint64_t* Wd = (const uint64_t*)(O + o_mask);
-        const orbm_pnp_refined* Rf = (const orbm_pnp_refined*)(O + o_ref);
-        const uint64_t* Rw = (const uint64_t*)(O + o_rmask);
-        std::vector<int> rec;
-        for (int b = 0; b < B; ++b) {
-            if (pp_first[b] < 0) continue;
-            const int H = its_first[b + 1] - its_first[b];
-            memcpy(hyp_out + its_first[b], R + its_first[b], (size_t)H * sizeof(orbm_pnp_hyp));
-            const size_t nw = (size_t)(mask_first[b + 1] - mask_first[b]);
-            if (nw) memcpy(mask_out + mask_first[b], Wd + mask_first[b], nw * 8);
-            // the slots the device filled: the first min(records, ORBM_PNP_MAX_RECORDS)
-            pnp_records(problems[b], hyp_out + its_first[b], H, rec);
-            const int nd = std::min((int)rec.size(), (int)ORBM_PNP_MAX_RECORDS), W = (first[b + 1] - first[b] + 63) >> 6;
+    size_t o_ref = 0, o_rmask = 0;
+    int split[2] = {0, 0}, n_rec_dev = 0;
+    std::vector<int> rec;
+    rc = ransac_csr_call(m, m->pnp, B, first, its_first, mask_first, ORBM_PNP_CAP, hyp_out, mask_out, split,
+        [&](const std::vector<int32_t>& hyp_prob, size_t* o_mask) -> int {
+            morb::StagePack pk;
+            const int i_prob = pk.add(problems, (size_t)B * sizeof(orbm_pnp_problem)), i_first = pk.add(first, (size_t)(B + 1) * 4),
+                      i_its = pk.add(its_first, (size_t)(B + 1) * 4), i_mf = pk.add(mask_first.data(), (size_t)(B + 1) * 4),
+                      i_rmf = pk.add(rmask_first.data(), (size_t)(B + 1) * 4), i_ppf = pk.add(pp_first.data(), (size_t)B * 4),
+                      i_hp = pk.add(hyp_prob.data(), (size_t)HT * 4), i_quads = pk.add(quads, (size_t)HT * 16);
+            int i_soa[6];                                      // x y z u v e, transposed below
+            for (int k = 0; k < 6; ++k) i_soa[k] = pk.add_in_place((size_t)N * 4);
+            // what the kernels write for the host: records, masks, refined records, refined masks
+            *o_mask = morb::align16((size_t)HT * sizeof(orbm_pnp_hyp));
+            o_ref = morb::align16(*o_mask + (size_t)mask_first[B] * 8);
+            o_rmask = morb::align16(o_ref + (size_t)B * ORBM_PNP_MAX_RECORDS * sizeof(orbm_pnp_refined));
+            const size_t out_bytes = o_rmask + (size_t)rmask_first[B] * 8 + 16;
+            // what one kernel leaves for the next: records, counts, masks, the records' inlier sets and per-point arrays
+            morb::BlockLayout sl;
+            const size_t s_rec = sl.take((size_t)HT * sizeof(orbm_pnp_hyp)), s_cnt = sl.take((size_t)HT * 4), s_mask = sl.take((size_t)mask_first[B] * 8),
+                         s_idx = sl.take((size_t)pp_points * 4), s_pp = sl.take((size_t)pp_points * 7 * 8),
+                         s_ref = sl.take((size_t)B * ORBM_PNP_MAX_RECORDS * sizeof(orbm_pnp_refined));
+            int rc;
+            const morb::StagePack::Block blk = pk.open(m->pnp.stage, &rc);
+            if (rc || (rc = m->pnp.scratch.reserve(sl.off + 16)) || (rc = m->pnp.out.reserve(out_bytes))) return rc;
+            float* soa[6];
+            for (int k = 0; k < 6; ++k) soa[k] = blk.host<float>(i_soa[k]);
+            for (int k = 0; k < N; ++k) {                      // array of structures -> structure of arrays, once per call
+                soa[0][k] = p3dw[3 * (size_t)k]; soa[1][k] = p3dw[3 * (size_t)k + 1]; soa[2][k] = p3dw[3 * (size_t)k + 2];
+                soa[3][k] = p2d[2 * (size_t)k]; soa[4][k] = p2d[2 * (size_t)k + 1]; soa[5][k] = max_err[k];
+            }
+            blk.publish();
+            PnpDev A;
+            A.prob = blk.dev<orbm_pnp_problem>(i_prob); A.first = blk.dev<int32_t>(i_first); A.its_first = blk.dev<int32_t>(i_its);
+            A.mask_first = blk.dev<int32_t>(i_mf); A.rmask_first = blk.dev<int32_t>(i_rmf); A.pp_first = blk.dev<int32_t>(i_ppf);
+            A.hyp_prob = blk.dev<int32_t>(i_hp); A.quads = blk.dev<int32_t>(i_quads);
+            A.x = blk.dev<float>(i_soa[0]); A.y = blk.dev<float>(i_soa[1]); A.z = blk.dev<float>(i_soa[2]);
+            A.u = blk.dev<float>(i_soa[3]); A.v = blk.dev<float>(i_soa[4]); A.e = blk.dev<float>(i_soa[5]);
+            A.n_hyp = HT;
+            A.soa_stride = (int)(A.y - A.x);
+            uint8_t* S = m->pnp.scratch.p;
+            A.rec_dev = (orbm_pnp_hyp*)(S + s_rec); A.cnt_dev = (int32_t*)(S + s_cnt); A.mask_dev = (uint64_t*)(S + s_mask);
+            A.idx_dev = (int32_t*)(S + s_idx); A.pp_dev = (double*)(S + s_pp); A.ref_dev = (orbm_pnp_refined*)(S + s_ref);
+            uint8_t* O = m->pnp.out.dp;
+            A.rec_out = (orbm_pnp_hyp*)O; A.mask_out = (uint64_t*)(O + *o_mask); A.ref_out = (orbm_pnp_refined*)(O + o_ref); A.rmask_out = (uint64_t*)(O + o_rmask);
+            hipLaunchKernelGGL(k_pnp_hyp, dim3((unsigned)((HT + PNP_HYP_T - 1) / PNP_HYP_T)), dim3(PNP_HYP_T), 0, m->stream, A);
+            hipLaunchKernelGGL(k_pnp_inliers, dim3((unsigned)HT), dim3(PNP_INL_T), 0, m->stream, A);
+            hipLaunchKernelGGL(k_pnp_refine, dim3((unsigned)(B * ORBM_PNP_MAX_RECORDS)), dim3(PNP_REF_T), 0, m->stream, A);
+            hipLaunchKernelGGL(k_pnp_refine_inliers, dim3((unsigned)(B * ORBM_PNP_MAX_RECORDS)), dim3(PNP_INL_T), 0, m->stream, A);
+            MORB_HIP(hipGetLastError());
+            return ORB_OK;
+        },
+        [&](int b) { pnp_hyps_host(I, b, hyp_out + its_first[b], mask_out + mask_first[b]); },
+        [&](int b) {   // the slots the device filled: the first min(records, ORBM_PNP_MAX_RECORDS)
+            const orbm_pnp_refined* Rf = (const orbm_pnp_refined*)(m->pnp.out.p + o_ref);
+            const uint64_t* Rw = (const uint64_t*)(m->pnp.out.p + o_rmask);
+            pnp_records(problems[b], hyp_out + its_first[b], its_first[b + 1] - its_first[b], rec);
+            const int nd = std::min((int)rec.size(), (int)ORBM_PNP_MAX_RECORDS), W = ransac_words(first[b + 1] - first[b]);
             if (nd) memcpy(refined_out + (size_t)b * ORBM_PNP_MAX_RECORDS, Rf + (size_t)b * ORBM_PNP_MAX_RECORDS, (size_t)nd * sizeof(orbm_pnp_refined));
             if (nd && W) memcpy(refined_mask_out + rmask_first[b], Rw + rmask_first[b], (size_t)nd * W * 8);
             n_rec_dev += nd;
-        }
-    }
+        });
+    if (rc) return rc;
     int n_rec_host = 0;
     rc = pnp_finish_host(I, B, host_from, mask_first, rmask_first, hyp_out, mask_out, n_records_out, refined_out, refined_mask_out, extra_cap, &n_rec_host);
     if (rc) return rc;
     // (records of host problems are not "the tail": count only those beyond ORBM_PNP_MAX_RECORDS of device problems)
     int tail = 0;
     for (int b = 0; b < B; ++b) if (host_from[b]) tail += std::max(0, n_records_out[b] - (int)ORBM_PNP_MAX_RECORDS);
-    m->last_pnp[0] = n_dev; m->last_pnp[1] = n_host; m->last_pnp[2] = n_rec_dev; m->last_pnp[3] = tail;
+    m->last_pnp[0] = split[0]; m->last_pnp[1] = split[1]; m->last_pnp[2] = n_rec_dev; m->last_pnp[3] = tail;
     return ORB_OK;
 }
 
@@ -862,14 +797,11 @@ int orbm_pnp_walk(const int32_t* counts, int H, int block_start, const int32_t* 
 
 int orbm_pnp_parameters(double probability, int min_inliers, int max_its, int min_set, float epsilon, int N, int32_t* out2, float* epsilon_out) {
     if (!out2 || !epsilon_out) return -1;
-    int nMinInliers = cvtt((double)((float)N * epsilon));
+    int nMinInliers = ransac_cvtt((double)((float)N * epsilon));
     if (nMinInliers < min_inliers) nMinInliers = min_inliers;
     if (nMinInliers < min_set) nMinInliers = min_set;
     if (epsilon < (float)nMinInliers / (float)N) epsilon = (float)nMinInliers / (float)N;
-    int n;
-    if (nMinInliers == N) n = 1;
-    else n = cvtt(ceil(log(1 - probability) / log(1 - pow((double)epsilon, 3))));
-    out2[0] = std::max(1, std::min(n, max_its));
+    out2[0] = ransac_iterations(probability, epsilon, max_its, nMinInliers == N);
     out2[1] = nMinInliers;
     *epsilon_out = epsilon;
     return 0;

@@ -406,7 +406,7 @@ void pose_problem_host(const orbm_pose_problem& P, const PoseEdges& G, int e0, i
 int validate(const orbm_pose_problem* problems, int B, const int32_t* first, const int32_t* feat, const float* pos, const float* obs,
              const int32_t* octave, const uint8_t* outlier_out, const orbm_pose_result* results) {
     MORB_ARG(problems && first && results);
-    if (const int rc = lm_validate_csr(B, ORBM_POSE_MAX_BATCH, first)) return rc;
+    if (const int rc = morb::validate_csr(B, ORBM_POSE_MAX_BATCH, first)) return rc;
     for (int b = 0; b < B; ++b) {
         const orbm_pose_problem& P = problems[b];
         if (P.mode != ORBM_POSE_CAM0 && P.mode != ORBM_POSE_ALL_CAMS) { morb::set_error("problem %d: mode = %d", b, P.mode); return ORB_E_ARG; }

@@ -10,16 +10,13 @@
 //   sim3_inlier      one correspondence under one hypothesis: both projections, both threshold tests.
 //   k_sim3_hyp       one lane per (problem, hypothesis), workgroups of 64: gathers the triple, runs sim3_horn in registers, writes the
 //                    record to HBM (for the second kernel) and to the mapped result.
-//   k_sim3_inliers   one wave per hypothesis: lane l takes correspondences l, l + 64, ... of the structure-of-arrays (coalesced), a
-//                    ballot gives the mask word of 64 consecutive correspondences, its population count the inlier count.  No atomics,
-//                    no LDS, no floating-point value crosses lanes.
-// The two kernels go onto the stream back to back: one enqueue, one synchronisation per call.
+//   k_sim3_inliers   one wave per hypothesis: lane l takes correspondences l, l + 64, ... of the structure-of-arrays (coalesced);
+//                    the sweep that turns sim3_inlier into mask words and a count is ransac_mask_sweep (ransac_dev.h).
+// The two kernels go onto the stream back to back: one enqueue, one synchronisation per call (ransac_csr_call, ransac_dev.h; the
+// checks of a call: ransac_validate<3>).
 // No libm function runs in the kernels: + - * / sqrt in float and double, conversions.
-#include <algorithm>
 #include <cfloat>
-#include <climits>
 #include <cmath>
-#include <cstring>
 #include <vector>
 
 #include "../../include/orbm.h"
@@ -29,6 +26,7 @@
 #include "sincos_dev.h"
 #include "cv_dev.h"
 #include "stage_pack.h"
+#include "ransac_dev.h"
 
 namespace {
 
@@ -332,25 +330,18 @@ __global__ __launch_bounds__(SIM3_T) void k_sim3_inliers(Sim3Dev A) {
     const orbm_sim3_problem P = A.prob[b];
     const int n0 = A.first[b];
     const int n = A.first[b + 1] - n0;
-    const int W = (n + 63) >> 6;
     const orbm_sim3_hyp& rec = A.rec_dev[g];
     float T12[12], T21[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) { T12[k] = rec.T12[k]; T21[k] = rec.T21[k]; }
-    uint64_t* words = A.mask_out + (size_t)A.mask_first[b] + (size_t)(g - A.its_first[b]) * W;
-    int count = 0;
-    for (int c = 0; c < W; ++c) {
-        const int i = c * 64 + lane;
-        bool in = false;
-        if (i < n) {
+    uint64_t* words = A.mask_out + (size_t)A.mask_first[b] + (size_t)(g - A.its_first[b]) * ransac_words(n);
+    const int count = ransac_mask_sweep(n, lane,
+        [&](int i) {
             const int k = n0 + i;
             const float X1[3] = {A.x1[k], A.y1[k], A.z1[k]}, X2[3] = {A.x2[k], A.y2[k], A.z2[k]};
-            in = sim3_inlier(P, T12, T21, X1, X2, A.cams[k], A.e1[k], A.e2[k]);
-        }
-        const unsigned long long word = __ballot(in);
-        count += __popcll(word);
-        if (lane == 0) words[c] = word;
-    }
+            return sim3_inlier(P, T12, T21, X1, X2, A.cams[k], A.e1[k], A.e2[k]);
+        },
+        [&](int c, unsigned long long word) { words[c] = word; });
     if (lane == 0) A.rec_out[g].n_inliers = count;
 }
 
@@ -366,7 +357,7 @@ inline int sim3_cams(const Sim3In& I, int k) { return (I.cam1[k] == 1 ? 1 : 0) |
 void sim3_problem_host(const Sim3In& I, int b, int math, orbm_sim3_hyp* hyp, uint64_t* words) {
     const orbm_sim3_problem& P = I.problems[b];
     const int n0 = I.first[b], n = I.first[b + 1] - n0, h0 = I.its_first[b], H = I.its_first[b + 1] - h0;
-    const int W = (n + 63) >> 6;
+    const int W = ransac_words(n);
     for (int h = 0; h < H; ++h) {
         float P1[3][3], P2[3][3];
         for (int i = 0; i < 3; ++i) {
@@ -375,45 +366,18 @@ void sim3_problem_host(const Sim3In& I, int b, int math, orbm_sim3_hyp* hyp, uin
         }
         orbm_sim3_hyp& o = hyp[h];
         sim3_horn(P1, P2, P.fix_scale != 0, math, o);
-        int count = 0;
-        for (int c = 0; c < W; ++c) {
-            uint64_t word = 0;
-            for (int l = 0; l < 64 && c * 64 + l < n; ++l) {
-                const size_t k = (size_t)n0 + c * 64 + l;
-                if (sim3_inlier(P, o.T12, o.T21, I.x3dc1 + 3 * k, I.x3dc2 + 3 * k, sim3_cams(I, (int)k), I.max_err1[k], I.max_err2[k])) { word |= (uint64_t)1 << l; ++count; }
-            }
-            words[(size_t)h * W + c] = word;
-        }
-        o.n_inliers = count;
+        o.n_inliers = ransac_mask_sweep_host(n, words + (size_t)h * W, [&](int i) {
+            const size_t k = (size_t)n0 + i;
+            return sim3_inlier(P, o.T12, o.T21, I.x3dc1 + 3 * k, I.x3dc2 + 3 * k, sim3_cams(I, (int)k), I.max_err1[k], I.max_err2[k]);
+        });
     }
 }
 
 // Argument checks; mask_first[b] = the first mask word of problem b, mask_first[B] = all of them.
 int validate(const Sim3In& I, int B, const orbm_sim3_hyp* hyp_out, const uint64_t* mask_out, std::vector<int32_t>& mask_first) {
-    MORB_ARG(I.problems && I.first && I.its_first);
-    if (B < 1 || B > ORBM_SIM3_MAX_BATCH) { morb::set_error("B = %d is outside 1..%d", B, (int)ORBM_SIM3_MAX_BATCH); return ORB_E_ARG; }
-    MORB_ARG(I.first[0] == 0 && I.its_first[0] == 0);
-    mask_first.assign((size_t)B + 1, 0);
-    long long words = 0;
-    for (int b = 0; b < B; ++b) {
-        if (I.first[b + 1] < I.first[b]) { morb::set_error("first[] decreases at problem %d", b); return ORB_E_ARG; }
-        const int H = I.its_first[b + 1] - I.its_first[b];
-        if (H < 0 || H > ORBM_SIM3_MAX_ITS) { morb::set_error("problem %d: %d hypotheses are outside 0..%d", b, H, (int)ORBM_SIM3_MAX_ITS); return ORB_E_ARG; }
-        words += (long long)H * ((I.first[b + 1] - I.first[b] + 63) >> 6);
-        if (words > INT_MAX) { morb::set_error("the masks of the call exceed 2^31 words"); return ORB_E_CAPACITY; }
-        mask_first[(size_t)b + 1] = (int32_t)words;
-    }
+    MORB_ARG(I.problems != nullptr);
+    if (const int rc = ransac_validate<3>(B, ORBM_SIM3_MAX_BATCH, ORBM_SIM3_MAX_ITS, I.first, I.its_first, I.triples, hyp_out, mask_out, mask_first)) return rc;
     if (I.first[B] > 0 && !(I.x3dc1 && I.x3dc2 && I.cam1 && I.cam2 && I.max_err1 && I.max_err2)) { morb::set_error("a correspondence array is NULL"); return ORB_E_ARG; }
-    if (I.its_first[B] > 0 && !(I.triples && hyp_out)) { morb::set_error("triples or hyp_out is NULL"); return ORB_E_ARG; }
-    if (words > 0 && !mask_out) { morb::set_error("mask_out is NULL"); return ORB_E_ARG; }
-    for (int b = 0; b < B; ++b) {
-        const int n = I.first[b + 1] - I.first[b];
-        for (int g = I.its_first[b]; g < I.its_first[b + 1]; ++g)
-            for (int i = 0; i < 3; ++i) {
-                const int t = I.triples[3 * (size_t)g + i];
-                if (t < 0 || t >= n) { morb::set_error("hypothesis %d: position %d is outside the %d correspondences of problem %d", g, t, n, b); return ORB_E_ARG; }
-            }
-    }
     return ORB_OK;
 }
 
@@ -441,72 +405,50 @@ int orbm_sim3_ransac(orbm_matcher* m, const orbm_sim3_problem* problems, int B, 
     MORB_ARG(m != nullptr);
     const Sim3In I = {problems, first, x3dc1, x3dc2, cam1, cam2, max_err1, max_err2, its_first, triples};
     std::vector<int32_t> mask_first;
-    int rc = validate(I, B, hyp_out, mask_out, mask_first);
-    if (rc) return rc;
+    if (const int rc = validate(I, B, hyp_out, mask_out, mask_first)) return rc;
     const int N = first[B], HT = its_first[B];
-    // a problem goes to the device when it has hypotheses and at most ORBM_SIM3_CAP correspondences
-    std::vector<int32_t> hyp_prob((size_t)HT, -1);
-    int n_dev = 0, n_host = 0, hyp_dev = 0;
-    for (int b = 0; b < B; ++b) {
-        const bool dev = first[b + 1] - first[b] <= ORBM_SIM3_CAP;
-        if (dev) { ++n_dev; for (int g = its_first[b]; g < its_first[b + 1]; ++g) hyp_prob[g] = b; hyp_dev += its_first[b + 1] - its_first[b]; }
-        else ++n_host;
-    }
-    size_t o_rec = 0, o_mask = 0;
-    if (hyp_dev > 0) {
-        MORB_HIP(hipSetDevice(m->device));
-        morb::StagePack pk;
-        const int i_prob = pk.add(problems, (size_t)B * sizeof(orbm_sim3_problem)), i_first = pk.add(first, (size_t)(B + 1) * 4),
-                  i_its = pk.add(its_first, (size_t)(B + 1) * 4), i_mf = pk.add(mask_first.data(), (size_t)(B + 1) * 4),
-                  i_hp = pk.add(hyp_prob.data(), (size_t)HT * 4), i_tri = pk.add(triples, (size_t)HT * 12);
-        int i_soa[8];                                      // x1 y1 z1 x2 y2 z2 e1 e2, transposed below
-        for (int k = 0; k < 8; ++k) i_soa[k] = pk.add_in_place((size_t)N * 4);
-        const int i_cams = pk.add_in_place((size_t)N * 4);
-        o_mask = morb::align16((size_t)HT * sizeof(orbm_sim3_hyp));
-        const size_t out_bytes = o_mask + (size_t)mask_first[B] * 8 + 16;
-        const morb::StagePack::Block blk = pk.open(m->sim3.stage, &rc);
-        if (rc || (rc = m->sim3.scratch.reserve((size_t)HT * sizeof(orbm_sim3_hyp))) || (rc = m->sim3.out.reserve(out_bytes))) return rc;
-        float* soa[8];
-        for (int k = 0; k < 8; ++k) soa[k] = blk.host<float>(i_soa[k]);
-        int32_t* cams = blk.host<int32_t>(i_cams);
-        for (int k = 0; k < N; ++k) {                      // array of structures -> structure of arrays, once per call
-            soa[0][k] = x3dc1[3 * (size_t)k]; soa[1][k] = x3dc1[3 * (size_t)k + 1]; soa[2][k] = x3dc1[3 * (size_t)k + 2];
-            soa[3][k] = x3dc2[3 * (size_t)k]; soa[4][k] = x3dc2[3 * (size_t)k + 1]; soa[5][k] = x3dc2[3 * (size_t)k + 2];
-            soa[6][k] = max_err1[k]; soa[7][k] = max_err2[k];
-            cams[k] = sim3_cams(I, k);
-        }
-        blk.publish();
-        Sim3Dev A;
-        A.prob = blk.dev<orbm_sim3_problem>(i_prob); A.first = blk.dev<int32_t>(i_first); A.its_first = blk.dev<int32_t>(i_its);
-        A.mask_first = blk.dev<int32_t>(i_mf); A.hyp_prob = blk.dev<int32_t>(i_hp); A.triples = blk.dev<int32_t>(i_tri);
-        A.x1 = blk.dev<float>(i_soa[0]); A.y1 = blk.dev<float>(i_soa[1]); A.z1 = blk.dev<float>(i_soa[2]);
-        A.x2 = blk.dev<float>(i_soa[3]); A.y2 = blk.dev<float>(i_soa[4]); A.z2 = blk.dev<float>(i_soa[5]);
-        A.e1 = blk.dev<float>(i_soa[6]); A.e2 = blk.dev<float>(i_soa[7]); A.cams = blk.dev<int32_t>(i_cams);
-        A.n_hyp = HT;
-        A.rec_dev = (orbm_sim3_hyp*)m->sim3.scratch.p;
-        A.rec_out = (orbm_sim3_hyp*)(m->sim3.out.dp + o_rec);
-        A.mask_out = (uint64_t*)(m->sim3.out.dp + o_mask);
-        hipLaunchKernelGGL(k_sim3_hyp, dim3((unsigned)((HT + SIM3_T - 1) / SIM3_T)), dim3(SIM3_T), 0, m->stream, A);
-        hipLaunchKernelGGL(k_sim3_inliers, dim3((unsigned)HT), dim3(SIM3_T), 0, m->stream, A);
-        MORB_HIP(hipGetLastError());
-    }
-    // while the kernels run: the problems the device does not take
-    for (int b = 0; b < B; ++b)
-        if (first[b + 1] - first[b] > ORBM_SIM3_CAP) sim3_problem_host(I, b, ORBM_SIM3_MATH_DEVICE, hyp_out + its_first[b], mask_out + mask_first[b]);
-    if (hyp_dev > 0) {
-        MORB_HIP(hipStreamSynchronize(m->stream));
-        const orbm_sim3_hyp* R = (const orbm_sim3_hyp*)(m->sim3.out.p + o_rec);
-        const uint64_t* Wd = (const uint64_t*)(m->sim3.out.p + o_mask);
-        for (int b = 0; b < B; ++b) {
-            if (first[b + 1] - first[b] > ORBM_SIM3_CAP) continue;
-            const int H = its_first[b + 1] - its_first[b];
-            if (H) memcpy(hyp_out + its_first[b], R + its_first[b], (size_t)H * sizeof(orbm_sim3_hyp));
-            const size_t nw = (size_t)(mask_first[b + 1] - mask_first[b]);
-            if (nw) memcpy(mask_out + mask_first[b], Wd + mask_first[b], nw * 8);
-        }
-    }
-    m->last_sim3[0] = n_dev; m->last_sim3[1] = n_host;
-    return ORB_OK;
+    // a problem goes to the device when it has at most ORBM_SIM3_CAP correspondences; the others to the host routine in DEVICE order
+    return ransac_csr_call(m, m->sim3, B, first, its_first, mask_first, ORBM_SIM3_CAP, hyp_out, mask_out, m->last_sim3,
+        [&](const std::vector<int32_t>& hyp_prob, size_t* o_mask) -> int {
+            morb::StagePack pk;
+            const int i_prob = pk.add(problems, (size_t)B * sizeof(orbm_sim3_problem)), i_first = pk.add(first, (size_t)(B + 1) * 4),
+                      i_its = pk.add(its_first, (size_t)(B + 1) * 4), i_mf = pk.add(mask_first.data(), (size_t)(B + 1) * 4),
+                      i_hp = pk.add(hyp_prob.data(), (size_t)HT * 4), i_tri = pk.add(triples, (size_t)HT * 12);
+            int i_soa[8];                                      // x1 y1 z1 x2 y2 z2 e1 e2, transposed below
+            for (int k = 0; k < 8; ++k) i_soa[k] = pk.add_in_place((size_t)N * 4);
+            const int i_cams = pk.add_in_place((size_t)N * 4);
+            *o_mask = morb::align16((size_t)HT * sizeof(orbm_sim3_hyp));
+            const size_t out_bytes = *o_mask + (size_t)mask_first[B] * 8 + 16;
+            int rc;
+            const morb::StagePack::Block blk = pk.open(m->sim3.stage, &rc);
+            if (rc || (rc = m->sim3.scratch.reserve((size_t)HT * sizeof(orbm_sim3_hyp))) || (rc = m->sim3.out.reserve(out_bytes))) return rc;
+            float* soa[8];
+            for (int k = 0; k < 8; ++k) soa[k] = blk.host<float>(i_soa[k]);
+            int32_t* cams = blk.host<int32_t>(i_cams);
+            for (int k = 0; k < N; ++k) {                      // array of structures -> structure of arrays, once per call
+                soa[0][k] = x3dc1[3 * (size_t)k]; soa[1][k] = x3dc1[3 * (size_t)k + 1]; soa[2][k] = x3dc1[3 * (size_t)k + 2];
+                soa[3][k] = x3dc2[3 * (size_t)k]; soa[4][k] = x3dc2[3 * (size_t)k + 1]; soa[5][k] = x3dc2[3 * (size_t)k + 2];
+                soa[6][k] = max_err1[k]; soa[7][k] = max_err2[k];
+                cams[k] = sim3_cams(I, k);
+            }
+            blk.publish();
+            Sim3Dev A;
+            A.prob = blk.dev<orbm_sim3_problem>(i_prob); A.first = blk.dev<int32_t>(i_first); A.its_first = blk.dev<int32_t>(i_its);
+            A.mask_first = blk.dev<int32_t>(i_mf); A.hyp_prob = blk.dev<int32_t>(i_hp); A.triples = blk.dev<int32_t>(i_tri);
+            A.x1 = blk.dev<float>(i_soa[0]); A.y1 = blk.dev<float>(i_soa[1]); A.z1 = blk.dev<float>(i_soa[2]);
+            A.x2 = blk.dev<float>(i_soa[3]); A.y2 = blk.dev<float>(i_soa[4]); A.z2 = blk.dev<float>(i_soa[5]);
+            A.e1 = blk.dev<float>(i_soa[6]); A.e2 = blk.dev<float>(i_soa[7]); A.cams = blk.dev<int32_t>(i_cams);
+            A.n_hyp = HT;
+            A.rec_dev = (orbm_sim3_hyp*)m->sim3.scratch.p;
+            A.rec_out = (orbm_sim3_hyp*)m->sim3.out.dp;
+            A.mask_out = (uint64_t*)(m->sim3.out.dp + *o_mask);
+            hipLaunchKernelGGL(k_sim3_hyp, dim3((unsigned)((HT + SIM3_T - 1) / SIM3_T)), dim3(SIM3_T), 0, m->stream, A);
+            hipLaunchKernelGGL(k_sim3_inliers, dim3((unsigned)HT), dim3(SIM3_T), 0, m->stream, A);
+            MORB_HIP(hipGetLastError());
+            return ORB_OK;
+        },
+        [&](int b) { sim3_problem_host(I, b, ORBM_SIM3_MATH_DEVICE, hyp_out + its_first[b], mask_out + mask_first[b]); },
+        [](int) {});
 }
 
 int orbm_sim3_walk(const int32_t* counts, int H, int N, int min_inliers, int start_iteration, int n_iterations, orbm_sim3_walk_state* state) {
@@ -530,14 +472,7 @@ int orbm_sim3_walk(const int32_t* counts, int H, int N, int min_inliers, int sta
 }
 
 int orbm_sim3_iterations(double probability, int min_inliers, int max_its, int N) {
-    const float epsilon = (float)min_inliers / N;
-    int n;
-    if (min_inliers == N) n = 1;
-    else {
-        const double d = ceil(log(1 - probability) / log(1 - pow((double)epsilon, 3)));
-        n = (d >= -2147483648.0 && d < 2147483648.0) ? (int)d : INT_MIN;   // cvttsd2si's answer to a NaN or an overflow
-    }
-    return std::max(1, std::min(n, max_its));
+    return ransac_iterations(probability, (float)min_inliers / N, max_its, min_inliers == N);
 }
 
 }  // extern "C"

@@ -323,7 +323,7 @@ void sim3opt_problem_host(const orbm_sim3opt_problem& P, const Sim3OptPairs& G, 
 int validate(const orbm_sim3opt_problem* problems, int B, const int32_t* first, const Sim3OptPairs& G, const uint8_t* flag_out,
              const orbm_sim3opt_result* results) {
     MORB_ARG(problems && first && results);
-    if (const int rc = lm_validate_csr(B, ORBM_SIM3OPT_MAX_BATCH, first)) return rc;
+    if (const int rc = morb::validate_csr(B, ORBM_SIM3OPT_MAX_BATCH, first)) return rc;
     for (int b = 0; b < B; ++b) {
         const orbm_sim3opt_problem& P = problems[b];
         if (P.n_levels1 < 1 || P.n_levels1 > ORBM_MAX_LEVELS || P.n_levels2 < 1 || P.n_levels2 > ORBM_MAX_LEVELS) {

@@ -1,6 +1,7 @@
 // stage_pack.h -- how the batched entry points lay out and stage the arrays of one call: one block, every array 16-byte aligned, in the
 // order the arrays are added.  The one definition of the round-up (align16), of the running layout (BlockLayout: bow.hip's keyframe block,
-// kfdb.hip's query block) and of the staging sequence (StagePack: mappoint.hip, pose.hip, sim3.hip, sim3opt.hip, triangulate.hip).
+// kfdb.hip's query block), of the staging sequence (StagePack: mappoint.hip, pose.hip, sim3.hip, sim3opt.hip, pnp.hip, triangulate.hip)
+// and of the checks on a call's CSR (validate_first: mappoint.hip; validate_csr: pose.hip, sim3opt.hip, ransac_dev.h).
 #pragma once
 #include <string.h>
 #include "orb_common.h"
@@ -13,6 +14,19 @@ struct BlockLayout {   // offsets of consecutive 16-byte aligned arrays; `off` =
     size_t off = 0;
     size_t take(size_t bytes) { const size_t o = off; off = align16(off + bytes); return o; }
 };
+
+// What every CSR of a batched call must satisfy: first[0] == 0, first[] not decreasing over its B entries.  noun: what an entry is in
+// the caller's words ("problem", "point").  validate_csr: a batch of problems, 1..max_batch of them.
+inline int validate_first(int B, const int32_t* first, const char* noun) {
+    MORB_ARG(first[0] == 0);
+    for (int b = 0; b < B; ++b)
+        if (first[b + 1] < first[b]) { set_error("first[] decreases at %s %d", noun, b); return ORB_E_ARG; }
+    return ORB_OK;
+}
+inline int validate_csr(int B, int max_batch, const int32_t* first) {
+    if (B < 1 || B > max_batch) { set_error("B = %d is outside 1..%d", B, max_batch); return ORB_E_ARG; }
+    return validate_first(B, first, "problem");
+}
 
 // An array is named once where it is added -- with where its bytes come from -- and once more where its typed pointer is taken:
 //     StagePack pk;

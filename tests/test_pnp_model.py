@@ -5,6 +5,7 @@ so that nothing passes vacuously.  No device is needed."""
 import numpy as np
 import pytest
 import multi_orb_slam_amd as m
+from multi_orb_slam_amd._lib import ORB_E_ARG
 import pnp_model as pm
 import pnp_worlds as pw
 
@@ -206,3 +207,27 @@ def test_compute_pose_hook_equals_model():
         mod = pm.compute_pose(pws[None], us[None], np.array([[float(np.float32(k)) for k in w["K"]]]))
         assert bits(R).tolist() == bits(mod["R"][0]).tolist() and bits(t).tolist() == bits(mod["t"][0]).tolist()
         assert bits(err).tolist() == bits(mod["err"][0]).tolist() and choice == mod["choice"][0] and flags == mod["flags"][0]
+
+
+def test_bad_arguments_are_refused_and_the_edges_accepted():
+    """The checks the port shares with Sim3 (ransac_validate, csrc/ransac_dev.h), on the smallest shapes: every refusal one step beyond
+    its limit, and the limit itself accepted, so that a `<` turned `<=` fails on one side or the other."""
+    w = pw.world(4, 0.0, 0.0, seed=31, H=1)
+    run = lambda quads, copies=1: m.pnp_ransac_host([pw.problem(m, w, quads=np.asarray(quads, np.int32))] * copies)
+    tile = lambda H: np.tile(np.array([0, 1, 2, 3], np.int32), (H, 1))
+    for refused in (lambda: run([[0, 1, 2, -1]]),                    # a position before the problem
+                    lambda: run([[0, 1, 2, 4]]),                     # position n
+                    lambda: run(tile(1), m.PNP_MAX_BATCH + 1),
+                    lambda: run(tile(m.PNP_MAX_ITS + 1))):
+        with pytest.raises(m.OrbError) as e:
+            refused()
+        assert e.value.code == ORB_E_ARG
+    (hyp, words, _, _), = run([[3, 2, 1, 0]])                        # position n - 1
+    assert len(hyp) == 1 and words.shape == (1, 1) and np.isfinite(hyp["R"]).all()
+    one, = run(tile(1))
+    batch = run(tile(1), m.PNP_MAX_BATCH)
+    assert len(batch) == m.PNP_MAX_BATCH
+    assert all(got[0].tobytes() == one[0].tobytes() and got[1].tobytes() == one[1].tobytes() for got in batch)
+    (hyp, words, _, _), = run(tile(m.PNP_MAX_ITS))
+    assert len(hyp) == m.PNP_MAX_ITS and words.shape == (m.PNP_MAX_ITS, 1)
+    assert hyp.tobytes() == one[0].tobytes() * m.PNP_MAX_ITS and (words == one[1][0, 0]).all()

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import multi_orb_slam_amd as m
+from multi_orb_slam_amd._lib import ORB_E_ARG
 import sim3_model as sm
 import sim3_worlds as sw
 from pose_model import poly_sincos
@@ -320,3 +321,24 @@ def test_bad_arguments_are_refused():
         m.sim3_ransac_host([sw.to_problem(m, W, triples=W["triples"][:1])] * (m.SIM3_MAX_BATCH + 1))
     with pytest.raises(m.OrbError):
         host(W, "libm", triples=np.zeros((m.SIM3_MAX_ITS + 1, 3), np.int32) + np.array([0, 1, 2], np.int32))
+
+
+def test_the_limits_themselves_are_accepted():
+    """The other side of every refusal above, on the smallest shapes (three correspondences, one-hypothesis problems): the checks are
+    shared with PnP (ransac_validate, csrc/ransac_dev.h), and a `<` turned `<=` there fails here or above."""
+    W = sw.generate(31, 3, s=1.0, noise=0.0, H=1)
+    run = lambda triples, copies=1: m.sim3_ransac_host([sw.to_problem(m, W, np.asarray(triples, np.int32))] * copies)
+    tile = lambda H: np.tile(np.array([0, 1, 2], np.int32), (H, 1))
+    for refused in (lambda: run([[0, 1, 3]]), lambda: run([[0, 1, -1]])):    # position n and position -1 of the smallest problem
+        with pytest.raises(m.OrbError) as e:
+            refused()
+        assert e.value.code == ORB_E_ARG
+    (rec, masks), = run([[2, 1, 0]])                                         # position n - 1
+    assert len(rec) == 1 and masks.shape == (1, 1) and np.isfinite(rec["T12"]).all()
+    one, = run(tile(1))
+    batch = run(tile(1), m.SIM3_MAX_BATCH)
+    assert len(batch) == m.SIM3_MAX_BATCH
+    assert all(got[0].tobytes() == one[0].tobytes() and got[1].tobytes() == one[1].tobytes() for got in batch)
+    (rec, masks), = run(tile(m.SIM3_MAX_ITS))
+    assert len(rec) == m.SIM3_MAX_ITS and masks.shape == (m.SIM3_MAX_ITS, 1)
+    assert rec.tobytes() == one[0].tobytes() * m.SIM3_MAX_ITS and (masks == one[1][0, 0]).all()
