@@ -553,6 +553,92 @@ double orbm_sim3opt_exp(double x);
 int orbm_sim3opt_expmap(const double* update7, int order, double* out8);
 int orbm_sim3opt_ldlt7(double* A49, const double* b7, double* x7);
 
+/* -- local bundle adjustment ---------------------------------------------------------------------------------------------
+ * Optimizer::LocalBundleAdjustment (reference src/Optimizer.cc:921-1353) from the graph on: free and fixed keyframe poses, marginalised
+ * points, one binary edge per observation (EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ with Tcim_quat, mono by ur < 0), Huber kernels,
+ * optimize(5), the chi-square / depth test that moves edges to level 1 and drops the kernels, initializeOptimization(0), optimize(10),
+ * the final test.  g2o's block solver is restated: Hpp, Hll, Hpl and b summed in active-edge order, computeLambdaInit over every
+ * diagonal entry of every active vertex, setLambda on both diagonals (the undamped diagonals are kept, not recovered by subtraction),
+ * the Schur loop of BlockSolver::solve landmark by landmark in ascending order, computeScale over all of x, the lambda rules.
+ *   poses    n_poses of them: the free ones first (the local keyframes except mnId == 0, in ascending mnId: g2o's VertexIDCompare order),
+ *            then the fixed ones.  Tcw: the float 4x4 Converter::toSE3Quat reads, row-major; K: fx fy cx cy mbf per pose.
+ *   points   in ascending vertex id; bad[l] != 0 reproduces `pMP->isBad()` at both tests: the point's edges are skipped there, so they
+ *            keep level 0 and their kernels and are never marked.
+ *   edges    a CSR per point: point l owns edges first[l] .. first[l+1]-1.  edge_pose: index into the poses; edge_cam: 0 or 1 selects
+ *            Tcim; obs: u, v, ur (ur < 0: the mono form); inv_sigma2: mvInvLevelSigma2[octave].  A (pose, point) pair occurs once.  The
+ *            edge position IS the active-edge order (g2o: insertion order): a caller that inserts its points in another order than
+ *            ascending vertex id gets the sums of its own order by handing the points in that order -- the landmark order follows.
+ *   stop     g2o polls the flag at core/sparse_optimizer.cpp:376 and optimization_algorithm_levenberg.cpp:149, the reference at
+ *            Optimizer.cc:1204 and :1217; stop(ctx) is called at exactly those points in that order (not at all when stop is NULL).
+ * Stated deviations from the reference: (a) the reduced system is solved by a dense LDL^T WITHOUT pivoting in the natural order of
+ * the free poses, every inner product sequential in ascending index, failing on a zero or non-finite pivot -- not by Eigen's
+ * SimplicialLDLT behind an AMD ordering; the same factorisation up to the order of its sums, parity with g2o / Eigen is not claimed for
+ * it, nor for Matrix3d::inverse() and what csrc/g2o_dev.h marks UNPINNED.  (b) Inside std::map<KeyFrame*, size_t> a point's
+ * observations are ordered by heap address; here the order is the caller's (the class orders them by mnId).  An edge that no
+ * computeActiveErrors ever reached (the call was stopped before the first iteration) is tested with chi2 = 0; g2o leaves its error
+ * uninitialised.  After a failed solve the update is the previous x, position by position, as g2o's vector is.
+ * Two orders of ONE host routine, as for the pose: ORBM_POSE_ORDER_INDEX (the C library's sin / cos / pow, the total chi2 summed
+ * sequentially over the active edges: the restatement of the reference) and ORBM_POSE_ORDER_DEVICE (orbm_pose_sincos, the cube by
+ * multiplication, the total chi2 in the kernels' tree: edge positions 256 k .. 256 k + 255 through lm_dev.h's butterfly and wave sum,
+ * an inactive edge counting 0.0, then the partials in ascending k): what the device computes, bit for bit. */
+enum { ORBM_LBA_MAX_FREE = 64, ORBM_LBA_MAX_POSES = 4096, ORBM_LBA_MAX_POINTS = 65536, ORBM_LBA_MAX_EDGES = 262144 };
+enum { ORBM_LBA_ENDED_COMPLETE = 0,        /* both optimisations and both tests                                                      */
+       ORBM_LBA_ENDED_STOPPED_AT_START = 1,/* the flag was set at :1204: the reference returns, nothing is to be written              */
+       ORBM_LBA_ENDED_NO_SECOND = 2 };     /* the flag was set at :1217 (bDoMore = false): the final test follows optimize(5)         */
+enum { ORBM_LBA_FLAG_LEVEL1 = 1,           /* setLevel(1) at the test after optimize(5)                                              */
+       ORBM_LBA_FLAG_ERASE = 2 };          /* the pair goes to vToErase at the final test                                            */
+typedef int (*orbm_lba_stop_fn)(void* ctx);
+
+typedef struct orbm_lba_problem {
+    int32_t n_free, n_poses, n_points, reserved;
+    const float* Tcw;              /* n_poses x 16                                                                      */
+    const float* K;                /* n_poses x 5                                                                       */
+    const float* points;           /* n_points x 3: pMP->GetWorldPos()                                                  */
+    const uint8_t* bad;            /* n_points, or NULL: no point is bad                                                */
+    const int32_t* first;          /* n_points + 1                                                                      */
+    const int32_t* edge_pose;      /* per edge                                                                          */
+    const uint8_t* edge_cam;
+    const float* obs;              /* 3 per edge                                                                        */
+    const float* inv_sigma2;
+    float Tcim[2][16];             /* Tcam11 (the identity) and Tcam21 as the reference builds them (:1048-1061)        */
+} orbm_lba_problem;
+
+typedef struct orbm_lba_result {
+    double* pose;                  /* n_poses x 7: the estimates, quaternion x y z w and translation                    */
+    float* Tcw;                    /* n_poses x 16: Converter::toCvMat of them, what SetPose receives                   */
+    double* point;                 /* n_points x 3                                                                      */
+    float* point_f;                /* n_points x 3: Converter::toCvMat(Vector3d), what SetWorldPos receives             */
+    uint8_t* flags;                /* per edge: ORBM_LBA_FLAG_*                                                         */
+    orbm_pose_round round[2];      /* optimize(5) and optimize(10)                                                      */
+    int32_t ended;                 /* ORBM_LBA_ENDED_*                                                                  */
+    int32_t optimisations;         /* optimize() calls that had an active vertex                                        */
+    int32_t polls;                 /* calls of stop                                                                     */
+    int32_t n_level1, n_erase;     /* edges flagged at either test                                                      */
+    int32_t active_poses[2], active_points[2], active_edges[2];   /* of either initializeOptimization                   */
+    int32_t reserved;
+} orbm_lba_result;
+
+/* One local bundle adjustment on the device: the Levenberg loop is driven by the host, which synchronises once per trial and reads
+ * one 4-byte command word; every step is a short chain of kernels, every sum has the order it has in the host routine, no atomics.  A
+ * problem beyond a cap (ORBM_LBA_MAX_*), or one without a free pose, runs through the host routine in DEVICE order inside the same
+ * call (orbm_debug_last_local_ba, include/orb_debug.h).  Same bytes as orbm_local_ba_host(..., ORBM_POSE_ORDER_DEVICE). */
+int orbm_local_ba(orbm_matcher* m, const orbm_lba_problem* problem, orbm_lba_stop_fn stop, void* stop_ctx, orbm_lba_result* result);
+/* The same statements on the host, no device needed, in either order. */
+int orbm_local_ba_host(const orbm_lba_problem* problem, orbm_lba_stop_fn stop, void* stop_ctx, int order, orbm_lba_result* result);
+/* (test hooks, host only) One edge at a pose (q x y z w, t) and a point: out[0..2] the error, out[3] chi2, out[4] the depth,
+ * out[5..13] the 3x3 Jacobian by the point, out[14..31] the 3x6 Jacobian by the pose (row 2 is zero for a mono edge). */
+int orbm_lba_edge_eval(const float* Tcim2x16, const float* K5, const double* pose7, const double* point3, int cam, const float* obs3,
+                       float inv_sigma2, double* out32);
+/* The dense LDL^T without pivoting of the reduced system (deviation (a)): H n x n row-major, its upper triangle is read; returns 1 and
+ * writes x, or 0 on a zero or non-finite pivot (x untouched). */
+int orbm_lba_ldlt(int n, const double* H, const double* b, double* x);
+/* The controller of the local BA and lm_step of the dense ports on ONE stream of chi2 values (the first of an iteration is the pass at
+ * the estimate, the others its trials; the stream ends the run), a 6-vector problem H = diag(hdiag6), b = b6, max_iter iterations:
+ * per step both write lambda, ni and a verdict (1 a trial follows, 2 the next iteration, 3 optimize() returned) into out_lba / out_lm
+ * (3 doubles per step).  Returns the steps taken. */
+int orbm_lba_controller_trace(const double* chi, int n_chi, const double* hdiag6, const double* b6, int max_iter, int order, int max_steps,
+                              double* out_lba, double* out_lm);
+
 /* -- PnPsolver: every EPnP RANSAC hypothesis of a relocalisation in one call ---------------------------------------------
  * PnPsolver (reference src/PnPsolver.cc) between SearchByBoW_cam1 and Optimizer::PoseOptimization of Tracking::Relocalization: per
  * hypothesis the four-point EPnP (compute_pose: choose_control_points, compute_barycentric_coordinates, M^T M, its 12x12 SVD, the three

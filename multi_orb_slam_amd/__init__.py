@@ -14,6 +14,9 @@ from ._lib import POSE_PROBLEM_DTYPE, POSE_RESULT_DTYPE, POSE_CAM0, POSE_ALL_CAM
 from .matcher import Sim3Problem, sim3_ransac_host, sim3_walk, sim3_iterations, sim3_atan2  # noqa: F401
 from ._lib import SIM3_PROBLEM_DTYPE, SIM3_HYP_DTYPE, SIM3_MATH_LIBM, SIM3_MATH_DEVICE, SIM3_CAP, SIM3_MAX_ITS, SIM3_MAX_BATCH  # noqa: F401
 from .matcher import Sim3OptProblem, sim3_optimize_host, sim3opt_exp, sim3opt_expmap, sim3opt_ldlt7  # noqa: F401
+from .matcher import LocalBAProblem, LocalBAResult, local_ba_host, lba_edge_eval, lba_controller_trace, lba_ldlt  # noqa: F401
+from ._lib import LBA_MAX_FREE, LBA_MAX_POSES, LBA_MAX_POINTS, LBA_MAX_EDGES, LBA_ENDED_COMPLETE, LBA_ENDED_STOPPED_AT_START  # noqa: F401
+from ._lib import LBA_ENDED_NO_SECOND, LBA_FLAG_LEVEL1, LBA_FLAG_ERASE  # noqa: F401
 from ._lib import SIM3OPT_PROBLEM_DTYPE, SIM3OPT_RESULT_DTYPE, SIM3OPT_CAP, SIM3OPT_MAX_BATCH  # noqa: F401
 from .matcher import PnPProblem, pnp_ransac_host, pnp_walk, pnp_walk_state, pnp_parameters, pnp_svd, pnp_qr_solve, pnp_compute_pose  # noqa: F401
 from ._lib import PNP_PROBLEM_DTYPE, PNP_HYP_DTYPE, PNP_REFINED_DTYPE, PNP_WALK_DTYPE, PNP_CAP, PNP_MAX_ITS, PNP_MAX_BATCH, PNP_MAX_RECORDS  # noqa: F401

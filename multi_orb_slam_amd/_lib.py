@@ -48,6 +48,9 @@ SIM3OPT_RESULT_DTYPE = np.dtype([("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "
                                  ("round", POSE_ROUND_DTYPE, (2,))])   # orbm_sim3opt_result
 assert SIM3OPT_PROBLEM_DTYPE.itemsize == 356 and SIM3OPT_RESULT_DTYPE.itemsize == 136
 SIM3OPT_CAP, SIM3OPT_MAX_BATCH = 8192, 64
+LBA_MAX_FREE, LBA_MAX_POSES, LBA_MAX_POINTS, LBA_MAX_EDGES = 64, 4096, 65536, 262144
+LBA_ENDED_COMPLETE, LBA_ENDED_STOPPED_AT_START, LBA_ENDED_NO_SECOND = 0, 1, 2
+LBA_FLAG_LEVEL1, LBA_FLAG_ERASE = 1, 2
 PNP_PROBLEM_DTYPE = np.dtype([("fu", "<f8"), ("fv", "<f8"), ("uc", "<f8"), ("vc", "<f8"), ("min_inliers", "<i4"), ("best_start", "<i4")])   # orbm_pnp_problem
 PNP_HYP_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("rep_error", "<f8"), ("choice", "<i4"), ("n_inliers", "<i4"), ("flags", "<i4"),
                           ("reserved", "<i4")])   # orbm_pnp_hyp
@@ -66,6 +69,26 @@ class OrbError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libmorb error %d: %s" % (code, msg))
         self.code = code
+
+
+class LbaProblem(C.Structure):  # orbm_lba_problem
+    _fields_ = [("n_free", C.c_int32), ("n_poses", C.c_int32), ("n_points", C.c_int32), ("reserved", C.c_int32), ("Tcw", C.c_void_p),
+                ("K", C.c_void_p), ("points", C.c_void_p), ("bad", C.c_void_p), ("first", C.c_void_p), ("edge_pose", C.c_void_p),
+                ("edge_cam", C.c_void_p), ("obs", C.c_void_p), ("inv_sigma2", C.c_void_p), ("Tcim", C.c_float * 32)]
+
+
+class PoseRound(C.Structure):  # orbm_pose_round
+    _fields_ = [("iterations", C.c_int32), ("trials", C.c_int32), ("chi2", C.c_double), ("lambda_", C.c_double)]
+
+
+class LbaResult(C.Structure):  # orbm_lba_result
+    _fields_ = [("pose", C.c_void_p), ("Tcw", C.c_void_p), ("point", C.c_void_p), ("point_f", C.c_void_p), ("flags", C.c_void_p),
+                ("round", PoseRound * 2), ("ended", C.c_int32), ("optimisations", C.c_int32), ("polls", C.c_int32), ("n_level1", C.c_int32),
+                ("n_erase", C.c_int32), ("active_poses", C.c_int32 * 2), ("active_points", C.c_int32 * 2), ("active_edges", C.c_int32 * 2),
+                ("reserved", C.c_int32)]
+
+
+LBA_STOP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)   # orbm_lba_stop_fn
 
 
 class Params(C.Structure):  # orbx_params
@@ -304,6 +327,12 @@ def lib():
     L.orbm_sim3opt_expmap.argtypes = [vp, i32, vp]
     L.orbm_sim3opt_ldlt7.argtypes = [vp, vp, vp]
     L.orbm_debug_last_sim3opt.argtypes = [vp, vp]
+    L.orbm_local_ba.argtypes = [vp, vp, LBA_STOP_FN, vp, vp]
+    L.orbm_local_ba_host.argtypes = [vp, LBA_STOP_FN, vp, i32, vp]
+    L.orbm_lba_edge_eval.argtypes = [vp, vp, vp, vp, i32, vp, f32, vp]
+    L.orbm_lba_ldlt.argtypes = [i32, vp, vp, vp]
+    L.orbm_lba_controller_trace.argtypes = [vp, i32, vp, vp, i32, i32, i32, vp, vp]
+    L.orbm_debug_last_local_ba.argtypes = [vp, vp]
     L.orbm_pnp_ransac.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbm_pnp_ransac_host.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbm_pnp_walk.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]

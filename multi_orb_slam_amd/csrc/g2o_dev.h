@@ -122,6 +122,23 @@ __host__ __device__ inline bool eigen_ldlt_solve(double* A, const double* b, dou
     return true;
 }
 
+// Matrix3d::inverse() (LU/InverseImpl.h, compute_inverse<Matrix3d, Matrix3d, 3>: the cofactor form).  cofactor_3x3<i, j> =
+// m(i1, j1) m(i2, j2) - m(i1, j2) m(i2, j1) with i1 = (i + 1) % 3, i2 = (i + 2) % 3 and j1, j2 alike; det = the first column of cofactors
+// times the first column of m, summed in order; result(i, j) = cofactor<j, i> * (1 / det).  m, inv: row-major, inv is not m.  No test of
+// the determinant, as Eigen has none.
+__host__ __device__ inline double eigen_cofactor3(const double* m, int i, int j) {
+    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+    return m[3 * i1 + j1] * m[3 * i2 + j2] - m[3 * i1 + j2] * m[3 * i2 + j1];
+}
+__host__ __device__ inline void eigen_inverse3(const double* m, double* inv) {
+    const double c00 = eigen_cofactor3(m, 0, 0), c10 = eigen_cofactor3(m, 1, 0), c20 = eigen_cofactor3(m, 2, 0);
+    const double det = (c00 * m[0] + c10 * m[3]) + c20 * m[6];
+    const double invdet = 1.0 / det;
+    inv[0] = c00 * invdet; inv[1] = c10 * invdet; inv[2] = c20 * invdet;
+    inv[3] = eigen_cofactor3(m, 0, 1) * invdet; inv[4] = eigen_cofactor3(m, 1, 1) * invdet; inv[5] = eigen_cofactor3(m, 2, 1) * invdet;
+    inv[6] = eigen_cofactor3(m, 0, 2) * invdet; inv[7] = eigen_cofactor3(m, 1, 2) * invdet; inv[8] = eigen_cofactor3(m, 2, 2) * invdet;
+}
+
 // ---- SE(3) (types/se3quat.h) ------------------------------------------------------------------------------------------------------------
 __host__ __device__ inline void se3_normalize_rotation(SE3Quat& T) {   // SE3Quat::normalizeRotation
     if (T.q[3] < 0) { T.q[0] *= -1; T.q[1] *= -1; T.q[2] *= -1; T.q[3] *= -1; }

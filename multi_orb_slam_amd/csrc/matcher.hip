@@ -123,7 +123,7 @@ void orbm_destroy(orbm_matcher* m) {
     m->d_i0.release(); m->d_i1.release(); m->d_i2.release(); m->d_choice.release(); m->d_claim.release(); m->d_qmeta.release(); m->d_win2.release();
     m->d_match.release(); m->d_status.release(); m->d_gclaim.release(); m->d_rsync.release(); m->d_mergecnt.release(); m->d_u16.release(); m->d_x0.release(); m->d_x1.release(); m->d_x2.release();
     m->h_i0.release(); m->h_i1.release(); m->h_i2.release(); m->h_match.release(); m->h_u16.release(); m->h_ring.release();
-    m->stage_f.release(); m->stage_q.release(); m->refresh.release(); m->pose.release(); m->sim3.release(); m->sim3opt.release(); m->pnp.release();
+    m->stage_f.release(); m->stage_q.release(); m->refresh.release(); m->pose.release(); m->sim3.release(); m->sim3opt.release(); m->pnp.release(); m->lba.release();
     if (m->ev_stage_f) (void)hipEventDestroy(m->ev_stage_f);
     for (FrameBufs* b : m->pool) { b->release(); delete b; }
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
@@ -159,6 +159,12 @@ int orbm_debug_last_sim3(const orbm_matcher* m, int* out2) {
 int orbm_debug_last_sim3opt(const orbm_matcher* m, int* out2) {
     MORB_ARG(m != nullptr && out2 != nullptr);
     out2[0] = m->last_sim3opt[0]; out2[1] = m->last_sim3opt[1];
+    return ORB_OK;
+}
+
+int orbm_debug_last_local_ba(const orbm_matcher* m, int* out4) {
+    MORB_ARG(m && out4);
+    for (int k = 0; k < 4; ++k) out4[k] = m->last_lba[k];
     return ORB_OK;
 }
 

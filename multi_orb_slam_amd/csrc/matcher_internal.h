@@ -1,7 +1,7 @@
 // matcher_internal.h -- types and internal entry points shared by the translation units of the matcher / front end
 // (hamming.hip: all-pairs kernels; frame.hip: frame assembly; search.hip: projection search + resolve; matcher.hip: handle
 // + host helpers; exchange.hip: RCCL / loopback transport; frontend.hip: orbf_*; mappoint.hip: map-point refresh; pose.hip: pose
-// optimisation; sim3.hip: Sim3 RANSAC; sim3opt.hip: Sim3 refinement; pnp.hip: PnP RANSAC).  Not part of the C ABI.  Next to it: cv_dev.h / g2o_dev.h (the restated OpenCV and Eigen / g2o
+// optimisation; sim3.hip: Sim3 RANSAC; sim3opt.hip: Sim3 refinement; pnp.hip: PnP RANSAC; lba.hip: local bundle adjustment).  Not part of the C ABI.  Next to it: cv_dev.h / g2o_dev.h (the restated OpenCV and Eigen / g2o
 // operations those ports share), sincos_dev.h, hamming_dev.h, resolve_dev.h (the steps the resolve's forms share and their LDS layouts),
 // stage_pack.h (the staged input block of a batched call and the checks on its CSR), lm_dev.h (what the two Levenberg ports share),
 // ransac_dev.h (what the two RANSAC ports share).
@@ -138,6 +138,10 @@ struct orbm_matcher {
     // records and mask words the kernels write and where the work of the last call went
     PortBufs<uint8_t> pnp;
     int last_pnp[4] = {0, 0, 0, 0};
+    // orbm_local_ba (lba.hip): the packed graph of a call and the index arrays of either optimisation (stage), everything the kernels
+    // leave for one another (scratch), the command word, flags and results they write and what the last call did
+    PortBufs<uint8_t> lba;
+    int last_lba[4] = {0, 0, 0, 0};
 };
 namespace morb { hipStream_t side_stream(orbm_matcher* m); }   // (lazily created; NULL after a reported failure)
 

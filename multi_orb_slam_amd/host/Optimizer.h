@@ -4,8 +4,8 @@
 // The reference builds a g2o graph per call (one `new` per edge and per robust kernel) around a single 6-dof vertex.  The two statics
 // below keep its signatures and replace the body: they fill the edge arrays from the frame (mvpMapPoints, mvKeysUn[_total],
 // mvuRight[_total], mvInvLevelSigma2), hand them to orbm_pose_optimize (include/orbm.h: one workgroup carries the problem through all
-// four rounds), write mvbOutlier and call SetPose.  Only this translation unit replaces the reference's: bundle adjustment, the
-// essential graph and OptimizeSim3 (all cameras) stay with g2o.  INTEGRATION.md shows the swap.
+// four rounds), write mvbOutlier and call SetPose.  Only this translation unit and host/LocalBA.cc (LocalBundleAdjustment, below) replace the reference's: global bundle
+// adjustment, the essential graph and OptimizeSim3 (all cameras) stay with g2o.  INTEGRATION.md shows the swap.
 //
 // Optimizer::OptimizeSim3_cam1 (reference include/Optimizer.h:62-63, src/Optimizer.cc:1984-2243), the refinement LoopClosing::ComputeSim3
 // runs between SearchBySim3 and the acceptance of a loop, likewise: the reference's filtering of vpMatches1 statement by statement, the
@@ -23,6 +23,7 @@ namespace ORB_SLAM2 {
 
 class KeyFrame;
 class MapPoint;
+class Map;
 
 class Optimizer {
 public:
@@ -48,6 +49,12 @@ public:
     // leaves them.  Returns false, nothing written, when the library refuses the call.
     bool static OptimizeSim3Batch(KeyFrame* pKF1, const std::vector<KeyFrame*>& vpKF2, std::vector<std::vector<MapPoint*> >& vvpMatches1,
                                   std::vector<g2o::Sim3>& vg2oS12, const float th2, const bool bFixScale, std::vector<int>& vnInliers);
+
+    // The local bundle adjustment of the mapping thread (reference include/Optimizer.h, src/Optimizer.cc:921-1353), defined in
+    // host/LocalBA.cc: steps 1-4 and 12-13 are the reference's, the g2o graph between them is one orbm_local_ba call (include/orbm.h
+    // lists what differs: the dense solver of the reduced system, the order of a point's observations and of the points).  *pbStopFlag
+    // is read exactly where the reference and g2o read it.
+    void static LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap);
 };
 
 // The edge count below which a single call is computed by the library's host routine (the same statements in the kernel's order, no
@@ -56,6 +63,8 @@ extern const int POSE_HOST_BELOW;
 // The same for OptimizeSim3_cam1, in correspondences: where tools/sim3opt_bench.py found the two to cross for a single problem
 // (profiles/r14/notes_sim3opt.md; a batched call always takes the device).
 extern const int SIM3OPT_HOST_BELOW;
+// The same for LocalBundleAdjustment, in edges: where tools/local_ba_bench.py found the two to cross (profiles/r20/notes_local_ba.md).
+extern const int LBA_HOST_BELOW;
 
 }  // namespace ORB_SLAM2
 

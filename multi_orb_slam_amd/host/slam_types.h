@@ -12,6 +12,7 @@
 #include <atomic>
 #include <cmath>
 #include <map>
+#include <mutex>
 #include <set>
 #include <unordered_map>
 #include <vector>
@@ -25,6 +26,12 @@ namespace ORB_SLAM2 {
 
 class KeyFrame;
 class Frame;
+
+// A record of the calls host/LocalBA.cc makes on the map, for its driver (host/test_local_ba.cc): off unless the driver hands in a
+// vector.  One entry per call: what was called and the mnIds it was called on.
+struct CallLogEntry { const char* what; long unsigned int a, b; };
+inline std::vector<CallLogEntry>*& CallLog() { static std::vector<CallLogEntry>* log = nullptr; return log; }
+inline void LogCall(const char* what, long unsigned int a = 0, long unsigned int b = 0) { if (CallLog()) CallLog()->push_back({what, a, b}); }
 
 class MapPoint {
 public:
@@ -63,9 +70,20 @@ public:
     KeyFrame* GetReferenceKeyFrame() { return mpRefKF; }
     void SetDistinctiveDescriptor(const cv::Mat& d) { mDescriptor = d.clone(); }
     void SetNormalAndDepth(const cv::Mat& normal, float minDistance, float maxDistance) {
+        LogCall("SetNormalAndDepth", mnId);
         mNormalVector = normal.clone(); mfMinDistance = minDistance; mfMaxDistance = maxDistance;
     }
     KeyFrame* mpRefKF = nullptr;
+    // members host/LocalBA.cc reads or writes (include/MapPoint.h:  mnId, mnBALocalForKF, SetWorldPos, EraseObservation; the stand-in's
+    // EraseObservation drops the observation and moves the reference keyframe on, without SetBadFlag)
+    long unsigned int mnId = 0, mnBALocalForKF = 0;
+    void SetWorldPos(const cv::Mat& Pos) { LogCall("SetWorldPos", mnId); mWorldPos = Pos.clone(); }
+    void EraseObservation(KeyFrame* pKF);   // (defined behind KeyFrame: it logs the keyframe's mnId)
+    void EraseObservationImpl(KeyFrame* pKF) {
+        if (!mObservations.count(pKF)) return;
+        mObservations.erase(pKF); nObs--;
+        if (mpRefKF == pKF) mpRefKF = mObservations.empty() ? nullptr : mObservations.begin()->first;
+    }
 
     cv::Mat mWorldPos;    // 3x1 CV_32F
     cv::Mat mDescriptor;  // 1x32 CV_8U
@@ -217,9 +235,30 @@ public:
     // the covisibility graph itself is not modelled: plain containers the caller fills (ordered: best covisibility first)
     std::set<KeyFrame*> mConnectedKeyFrames, mConnectedKeyFrames_cam1;
     std::vector<KeyFrame*> mvpOrderedConnectedKeyFrames, mvpOrderedConnectedKeyFrames_cam1;
+    // members host/LocalBA.cc reads or writes (include/KeyFrame.h: GetVectorCovisibleKeyFrames, GetPose, SetPose, EraseMapPointMatch,
+    // mnBALocalForKF, mnBAFixedForKF)
+    std::vector<KeyFrame*> GetVectorCovisibleKeyFrames() { return mvpOrderedConnectedKeyFrames; }
+    cv::Mat GetPose() { return Tcw.clone(); }
+    void SetPose(const cv::Mat& Tcw_) { LogCall("SetPose", mnId); Tcw = Tcw_.clone(); }
+    void EraseMapPointMatch(MapPoint* pMP) { LogCall("EraseMapPointMatch", mnId, pMP->mnId); const int idx = pMP->GetIndexInKeyFrame(this); if (idx >= 0) mvpMapPoints[idx] = nullptr; }
+    long unsigned int mnBALocalForKF = 0, mnBAFixedForKF = 0;
     static std::vector<KeyFrame*> FirstN(const std::vector<KeyFrame*>& v, int N) {   // src/KeyFrame.cc GetBestCovisibilityKeyFrames
         return (int)v.size() < N ? v : std::vector<KeyFrame*>(v.begin(), v.begin() + N);
     }
+};
+
+inline void MapPoint::EraseObservation(KeyFrame* pKF) { LogCall("EraseObservation", mnId, pKF->mnId); EraseObservationImpl(pKF); }
+
+// Map: what host/LocalBA.cc takes of it (include/Map.h).  The stand-in's mutex is a std::mutex that records when it is taken and given back.
+struct LoggedMutex {
+    void lock() { m.lock(); LogCall("lock"); }
+    void unlock() { LogCall("unlock"); m.unlock(); }
+    bool try_lock() { if (!m.try_lock()) return false; LogCall("lock"); return true; }
+    std::mutex m;
+};
+class Map {
+public:
+    LoggedMutex mMutexMapUpdate;
 };
 
 }  // namespace ORB_SLAM2

@@ -427,6 +427,121 @@ def sim3opt_ldlt7(A, b):
     return bool(ok), x
 
 
+class LocalBAProblem:
+    """One Optimizer::LocalBundleAdjustment from its graph on (orbm_lba_problem): Tcw n_poses x 4 x 4 float (the free poses first, n_free
+    of them), K n_poses x 5 (fx fy cx cy mbf), points n_points x 3, first n_points + 1 (the CSR of the edges per point), edge_pose,
+    edge_cam, obs n_edges x 3 (u v ur; ur < 0: mono), inv_sigma2, Tcim 2 x 4 x 4, bad n_points or None."""
+
+    def __init__(self, n_free, Tcw, K, points, first, edge_pose, edge_cam, obs, inv_sigma2, Tcim, bad=None):
+        self.Tcw = np.ascontiguousarray(Tcw, np.float32).reshape(-1, 16); self.K = np.ascontiguousarray(K, np.float32).reshape(-1, 5)
+        self.points = np.ascontiguousarray(points, np.float32).reshape(-1, 3); self.first = np.ascontiguousarray(first, np.int32)
+        self.edge_pose = np.ascontiguousarray(edge_pose, np.int32); self.edge_cam = np.ascontiguousarray(edge_cam, np.uint8)
+        self.obs = np.ascontiguousarray(obs, np.float32).reshape(-1, 3); self.inv_sigma2 = np.ascontiguousarray(inv_sigma2, np.float32)
+        self.Tcim = np.ascontiguousarray(Tcim, np.float32).reshape(32)
+        self.bad = None if bad is None else np.ascontiguousarray(bad, np.uint8)
+        self.n_free = int(n_free); self.n_poses = len(self.Tcw); self.n_points = len(self.points); self.n_edges = len(self.edge_pose)
+        assert len(self.K) == self.n_poses and len(self.first) == self.n_points + 1 and int(self.first[-1]) == self.n_edges
+        assert len(self.edge_cam) == len(self.obs) == len(self.inv_sigma2) == self.n_edges
+        assert self.bad is None or len(self.bad) == self.n_points
+
+    def native(self):
+        P = _lib.LbaProblem()
+        P.n_free, P.n_poses, P.n_points, P.reserved = self.n_free, self.n_poses, self.n_points, 0
+        for k in ("Tcw", "K", "points", "first", "edge_pose", "edge_cam", "obs", "inv_sigma2"):
+            setattr(P, k, getattr(self, k).ctypes.data)
+        P.bad = None if self.bad is None else self.bad.ctypes.data
+        P.Tcim[:] = [float(v) for v in self.Tcim]
+        return P
+
+
+class LocalBAResult:
+    """orbm_lba_result: pose n_poses x 7 (q x y z w, t) and Tcw n_poses x 16 (what SetPose receives), point / point_f n_points x 3, flags per
+    edge (LBA_FLAG_LEVEL1 | LBA_FLAG_ERASE), rounds [(iterations, trials, chi2, lambda)] x 2, ended (LBA_ENDED_*), optimisations, polls,
+    n_level1, n_erase, active_poses / active_points / active_edges of either optimisation."""
+    FIELDS = ("pose", "Tcw", "point", "point_f", "flags", "rounds", "ended", "optimisations", "polls", "n_level1", "n_erase", "active_poses",
+              "active_points", "active_edges")
+
+    def __init__(self, problem):
+        self.pose = np.zeros((problem.n_poses, 7)); self.Tcw = np.zeros((problem.n_poses, 16), np.float32)
+        self.point = np.zeros((problem.n_points, 3)); self.point_f = np.zeros((problem.n_points, 3), np.float32)
+        self.flags = np.zeros(problem.n_edges, np.uint8)
+        self._pad = [np.zeros(1, a.dtype) if a.size == 0 else a for a in (self.pose, self.Tcw, self.point, self.point_f, self.flags)]
+
+    def native(self):
+        R = _lib.LbaResult()
+        R.pose, R.Tcw, R.point, R.point_f, R.flags = [a.ctypes.data for a in self._pad]
+        return R
+
+    def take(self, R):
+        self.rounds = np.zeros(2, _lib.POSE_ROUND_DTYPE)
+        for s in range(2):
+            self.rounds[s] = (R.round[s].iterations, R.round[s].trials, R.round[s].chi2, R.round[s].lambda_)
+        for k in ("ended", "optimisations", "polls", "n_level1", "n_erase"):
+            setattr(self, k, int(getattr(R, k)))
+        for k in ("active_poses", "active_points", "active_edges"):
+            setattr(self, k, (int(getattr(R, k)[0]), int(getattr(R, k)[1])))
+        return self
+
+    def same_bytes(self, other):
+        """The first field that differs from `other` bit for bit, or None."""
+        for k in self.FIELDS:
+            a, b = getattr(self, k), getattr(other, k)
+            if (a.tobytes() != b.tobytes()) if isinstance(a, np.ndarray) else (a != b):
+                return k
+        return None
+
+
+def _lba_stop(stop):
+    """stop: None (no flag: nothing is polled), a callable -> truth value, or an int n: true from the n-th poll on (n = 0: at once)."""
+    if stop is None:
+        return _lib.LBA_STOP_FN(), None
+    if callable(stop):
+        fn = stop
+    else:
+        state = {"polls": 0}
+
+        def fn():
+            state["polls"] += 1
+            return state["polls"] > int(stop)
+    cb = _lib.LBA_STOP_FN(lambda ctx: 1 if fn() else 0)
+    return cb, cb
+
+
+def local_ba_host(problem, order=POSE_ORDER_INDEX, stop=None):
+    """orbm_local_ba_host: one local bundle adjustment entirely on the host (no device needed), in the index order with the C library's
+    sin / cos / pow (the restatement of the reference) or in the device's order -> LocalBAResult."""
+    res = LocalBAResult(problem); P = problem.native(); R = res.native()
+    cb, keep = _lba_stop(stop)
+    check(_lib.lib().orbm_local_ba_host(C.byref(P), cb, None, int(order), C.byref(R)))
+    return res.take(R)
+
+
+def lba_edge_eval(Tcim, K5, pose7, point3, cam, obs3, inv_sigma2):
+    """One edge of the local BA (orbm_lba_edge_eval) -> (error 3, chi2, depth, Jacobian by the point 3 x 3, by the pose 3 x 6)."""
+    Tcim = np.ascontiguousarray(Tcim, np.float32).reshape(32); K5 = np.ascontiguousarray(K5, np.float32)
+    pose7 = np.ascontiguousarray(pose7, np.float64); point3 = np.ascontiguousarray(point3, np.float64)
+    obs3 = np.ascontiguousarray(obs3, np.float32); out = np.zeros(32)
+    check(_lib.lib().orbm_lba_edge_eval(ptr(Tcim), ptr(K5), ptr(pose7), ptr(point3), int(cam), ptr(obs3), float(inv_sigma2), ptr(out)))
+    return out[:3].copy(), float(out[3]), float(out[4]), out[5:14].reshape(3, 3).copy(), out[14:32].reshape(3, 6).copy()
+
+
+def lba_ldlt(H, b):
+    """The dense LDL^T without pivoting of the local BA's reduced system (orbm_lba_ldlt) -> x, or None on a zero or non-finite pivot."""
+    H = np.ascontiguousarray(H, np.float64); b = np.ascontiguousarray(b, np.float64); x = np.zeros(len(b))
+    return x if _lib.lib().orbm_lba_ldlt(len(b), ptr(H), ptr(b), ptr(x)) == 1 else None
+
+
+def lba_controller_trace(chi, hdiag6, b6, max_iter, order=POSE_ORDER_INDEX):
+    """The local BA's controller and lm_step on one stream of chi2 values (orbm_lba_controller_trace) -> (steps x 3 of the local BA,
+    steps x 3 of lm_step): lambda, ni, verdict (1 a trial follows, 2 the next iteration, 3 optimize() returned)."""
+    chi = np.ascontiguousarray(chi, np.float64); h = np.ascontiguousarray(hdiag6, np.float64); b = np.ascontiguousarray(b6, np.float64)
+    a = np.zeros((len(chi) + 1, 3)); l = np.zeros((len(chi) + 1, 3))
+    n = _lib.lib().orbm_lba_controller_trace(ptr(chi), len(chi), ptr(h), ptr(b), int(max_iter), int(order), len(chi), ptr(a), ptr(l))
+    if n < 0:
+        raise AssertionError("the two controllers took a different number of steps (%d)" % (-1 - n))
+    return a[:n].copy(), l[:n].copy()
+
+
 class LocalPoints:
     """A table of map points resident in HBM (orbm_points): what isInFrustum and the search read of each MapPoint."""
 
@@ -818,6 +933,25 @@ class Matcher:
         recs, first, arrays, flags, res = _sim3opt_pack(problems)
         check(_lib.lib().orbm_sim3_optimize(self._h, ptr(recs), len(problems), ptr(first), *[ptr(a) for a in arrays], ptr(flags), ptr(res)))
         return _sim3opt_unpack(problems, first, flags, res)
+
+    def local_ba(self, problem, stop=None):
+        """Optimizer::LocalBundleAdjustment (reference src/Optimizer.cc:921-1353) from its graph on, on the device (orbm_local_ba): the
+        Levenberg loop is driven from the host, one synchronisation per trial -> LocalBAResult.  stop: see local_ba_host."""
+        res = LocalBAResult(problem); P = problem.native(); R = res.native()
+        cb, keep = _lba_stop(stop)
+        check(_lib.lib().orbm_local_ba(self._h, C.byref(P), cb, None, C.byref(R)))
+        return res.take(R)
+
+    def local_ba_host(self, problem, order=POSE_ORDER_INDEX, stop=None):
+        """The same call through the host routine (orbm_local_ba_host); no device is used."""
+        return local_ba_host(problem, order, stop)
+
+    def last_local_ba(self):
+        """What the last local_ba did: (path: 0 the device, 1 the host routine because a cap LBA_MAX_* is exceeded, 2 the host routine
+        because no pose is free; kernel launches; stream synchronisations; polls of stop) (orbm_debug_last_local_ba)."""
+        out = (C.c_int * 4)()
+        check(_lib.lib().orbm_debug_last_local_ba(self._h, out))
+        return tuple(out)
 
     def last_sim3opt(self):
         """Problems of the last sim3_optimize by path: (device, host routine because of more than SIM3OPT_CAP correspondences)
