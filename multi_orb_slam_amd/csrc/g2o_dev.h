@@ -1,6 +1,7 @@
 // g2o_dev.h -- the Eigen / g2o boundary: the parts of Eigen and g2o that the reference's optimisers run and this library restates, ONE
-// definition each, for the kernels and the host routines (pose.hip, sim3opt.hip).  Restated from the published sources (Eigen's Geometry and
-// Cholesky modules; Thirdparty/g2o/g2o/types/se3quat.h, core/robust_kernel_impl.cpp) and UNPINNED: Eigen is not linked and g2o was never
+// definition each, for the kernels and the host routines (pose.hip, sim3opt.hip, lba.hip).  Restated from the published sources (Eigen's
+// Geometry, Cholesky and LU modules; Thirdparty/g2o/g2o/types/se3quat.h, types/sim3.h, types/types_six_dof_expmap.cpp as far as its edges
+// share their Jacobian, core/robust_kernel_impl.cpp with the deltas the reference sets) and UNPINNED: Eigen is not linked and g2o was never
 // compiled against this code, so each is ONE function that a later pin changes.  The library is built without
 // contraction and without fast-math, and the tests compare bytes: nothing inside these bodies is to be reordered.
 #pragma once
@@ -8,6 +9,7 @@
 #include <cmath>
 #include <hip/hip_runtime.h>
 #include "../../include/orbm.h"
+#include "cv_dev.h"   // x86_nan
 #include "sincos_dev.h"
 
 struct SE3Quat { double q[4], t[3]; };   // g2o::SE3Quat: quaternion in Eigen's coefficient order x y z w, translation
@@ -198,6 +200,64 @@ __host__ __device__ inline void se3_exp(const double* update, int order, SE3Quat
     se3_from_matrix(R, t, T);   // SE3Quat(Quaterniond(R), V*upsilon)
 }
 
+// an SE3Quat as seven doubles, q (x y z w) then t: how a port keeps its poses outside a record
+__host__ __device__ inline void se3_load7(const double* v, SE3Quat& T) {
+    T.q[0] = v[0]; T.q[1] = v[1]; T.q[2] = v[2]; T.q[3] = v[3]; T.t[0] = v[4]; T.t[1] = v[5]; T.t[2] = v[6];
+}
+__host__ __device__ inline void se3_store7(const SE3Quat& T, double* v) {
+    v[0] = T.q[0]; v[1] = T.q[1]; v[2] = T.q[2]; v[3] = T.q[3]; v[4] = T.t[0]; v[5] = T.t[1]; v[6] = T.t[2];
+}
+// Converter::toCvMat(SE3Quat): to_homogeneous_matrix() rounded to float, M: 4x4 row-major
+__host__ __device__ inline void se3_to_cv(const SE3Quat& T, float* M) {
+    double R[9];
+    eigen_quat_to_matrix(T.q, R);
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) M[4 * r + c] = x86_nan((float)R[3 * r + c]);
+        M[4 * r + 3] = x86_nan((float)T.t[r]);
+    }
+    M[12] = 0.0f; M[13] = 0.0f; M[14] = 0.0f; M[15] = 1.0f;
+}
+
+// ---- the edges through Tcim (types/types_six_dof_expmap.cpp) ------------------------------------------------------------------------------
+// linearizeOplus of the _multi edges and of EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ as far as they share it (:627-696, :952-1036,
+// :103-218, :318-461): t2 = t1 * Rcim, t1 the projection's derivative at pc = Tcim.map(p) (its zeros are not multiplied); with `row2`
+// also the stereo row, row 2 = row 0 - bf / zc^2 * (the last row of Rcim), else row 2 is not written.  r: Rcim, row-major.  (row2 is
+// the caller's and not "the edge is stereo": k_pose_optimize asks for it always and reads it for a stereo edge only, because a branch
+// here costs its loop over the edges 1.4 - 2.2 % from 800 edges on, profiles/r21/notes_lba_shared.md.)
+__host__ __device__ __forceinline__ void g2o_cam_jacobian_rows(double fx, double fy, double bf, const double* r, const double* pc, bool row2,
+                                                               double (*t2)[3]) {
+    const double xc = pc[0], yc = pc[1], zc = pc[2], zc_2 = zc * zc;
+    const double t00 = -fx / zc, t02 = fx * xc / zc_2, t11 = -fy / zc, t12 = fy * yc / zc_2;
+    t2[0][0] = t00 * r[0] + t02 * r[6];
+    t2[0][1] = t00 * r[1] + t02 * r[7];
+    t2[0][2] = t00 * r[2] + t02 * r[8];
+    t2[1][0] = t11 * r[3] + t12 * r[6];
+    t2[1][1] = t11 * r[4] + t12 * r[7];
+    t2[1][2] = t11 * r[5] + t12 * r[8];
+    if (!row2) return;
+    const double a1 = bf / zc_2;
+    t2[2][0] = t2[0][0] - a1 * r[6];
+    t2[2][1] = t2[0][1] - a1 * r[7];
+    t2[2][2] = t2[0][2] - a1 * r[8];
+}
+// one row of the pose block: t2's row times [-skew(p) | I], p = the point in the body frame
+__host__ __device__ __forceinline__ void g2o_cam_jacobian_pose(const double* t2k, const double* p, double* Jk) {
+    const double x = p[0], y = p[1], z = p[2];
+    Jk[0] = -t2k[1] * z + t2k[2] * y;
+    Jk[1] = t2k[0] * z - t2k[2] * x;
+    Jk[2] = -t2k[0] * y + t2k[1] * x;
+    Jk[3] = t2k[0];
+    Jk[4] = t2k[1];
+    Jk[5] = t2k[2];
+}
+
+// ---- the Huber kernel (core/robust_kernel_impl.cpp) ---------------------------------------------------------------------------------------
+// `const float deltaMono = sqrt(5.991)` / `thHuberMono`, `sqrt(7.815)` for a stereo edge, rk->setDelta(th): _delta = the float as a
+// double, dsqr = (float)(delta * delta), a FLOAT member.  Index 0: a mono edge, 1: a stereo one.
+__host__ __device__ inline void g2o_huber_constants(double* delta, double* dsqr) {
+    const float th[2] = {(float)sqrt(5.991), (float)sqrt(7.815)};
+    for (int s = 0; s < 2; ++s) { delta[s] = (double)th[s]; dsqr[s] = (double)(float)(delta[s] * delta[s]); }
+}
 // RobustKernelHuber::robustify as far as rho[0] and rho[1] go (core/robust_kernel_impl.cpp:78-91); dsqr is the kernel's float member
 __host__ __device__ inline void g2o_huber(double e, double delta, double dsqr, double* rho0, double* rho1) {
     if (e <= dsqr) { *rho0 = e; *rho1 = 1.; }

@@ -1,6 +1,7 @@
 // lba.hip -- local bundle adjustment on the device (include/orbm.h, "local bundle adjustment"): Optimizer::LocalBundleAdjustment
-// (reference src/Optimizer.cc:921-1353) from the graph on.  The arithmetic of one edge, of one landmark and of the controller is
-// lba_dev.h's; here are the steps over the whole graph, ONE definition each, called by the host routine's loops and by the kernels:
+// (reference src/Optimizer.cc:921-1353) from the graph on.  The arithmetic of one edge, of one landmark and of the controller's driver is
+// lba_dev.h's, the Levenberg rules and the summation tree are lm_dev.h's, what is g2o's is g2o_dev.h's; here are the steps over the
+// whole graph, ONE definition each, called by the host routine's loops and by the kernels:
 //   lba_pass_edge      computeActiveErrors (+ linearizeOplus + constructQuadraticForm) of one edge, its share of activeRobustChi2
 //   lba_point_sum, lba_pose_sum   a vertex's Hll / bl, Hpp / bp: its active edges in ascending edge position
 //   lba_schur_entry, lba_schur_b  the reduced system: Hschur(i1, i2) -= (Bi Dinv) Bj^T over the landmarks both poses see, in ascending
@@ -256,8 +257,7 @@ void lba_graph(const orbm_lba_problem* P, LbaGraph& G) {
     for (int p = 0; p < P->n_poses; ++p) {
         SE3Quat T;
         se3_from_cv(P->Tcw + 16 * (size_t)p, T);
-        for (int k = 0; k < 4; ++k) G.pose0[7 * (size_t)p + k] = T.q[k];
-        for (int k = 0; k < 3; ++k) G.pose0[7 * (size_t)p + 4 + k] = T.t[k];
+        se3_store7(T, &G.pose0[7 * (size_t)p]);
     }
     for (size_t k = 0; k < 3 * (size_t)P->n_points; ++k) G.point0[k] = (double)P->points[k];
     lba_camera(P->Tcim, G.C);
@@ -304,18 +304,13 @@ void lba_structure(const LbaGraph& G, const uint8_t* flags, LbaStructure& T) {
     }
 }
 
-// Converter::toCvMat(SE3Quat) (to_homogeneous_matrix() rounded to float), Converter::toCvMat(Vector3d)
+// Converter::toCvMat(SE3Quat) (g2o_dev.h's se3_to_cv), Converter::toCvMat(Vector3d)
 void lba_write_result(const orbm_lba_problem* P, const double* pose, const double* point, orbm_lba_result* R) {
     for (int p = 0; p < P->n_poses; ++p) {
         const double* T = pose + 7 * (size_t)p;
-        double Rm[9];
-        eigen_quat_to_matrix(T, Rm);
-        float* M = R->Tcw + 16 * (size_t)p;
-        for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) M[4 * r + c] = x86_nan((float)Rm[3 * r + c]);
-            M[4 * r + 3] = x86_nan((float)T[4 + r]);
-        }
-        M[12] = 0.0f; M[13] = 0.0f; M[14] = 0.0f; M[15] = 1.0f;
+        SE3Quat Q;
+        se3_load7(T, Q);
+        se3_to_cv(Q, R->Tcw + 16 * (size_t)p);
         for (int k = 0; k < 7; ++k) R->pose[7 * (size_t)p + k] = x86_nan(T[k]);
     }
     for (size_t k = 0; k < 3 * (size_t)P->n_points; ++k) { R->point[k] = x86_nan(point[k]); R->point_f[k] = x86_nan((float)point[k]); }
@@ -462,7 +457,7 @@ struct LbaHost {
         for (int i = 0; i < V.na; ++i) for (int k = 0; k < 42; ++k) lba_pose_sum(V, i, k);
         double m = 0.;
         for (int v = 0; v < V.na + V.n_points; ++v) m = lba_max_diag(V, v, m);
-        lba_ctl_full(S, chi, m);
+        lm_rule_full(S, chi, m);
         return trial(rep);
     }
     int trial(LbaReport* rep) {
@@ -532,15 +527,14 @@ __global__ __launch_bounds__(LBA_T) void k_lba_begin_optimisation(LbaView V, int
 // one lane per edge position; the workgroup's chi2 partial through lm_dev.h's tree
 template <bool SYSTEM>
 __global__ __launch_bounds__(LBA_T) void k_lba_edges(LbaView V, LbaCam C) {
-    __shared__ double s_w[LBA_T / 64];
+    __shared__ double s_part[LBA_T / 64][1];
     const int e = blockIdx.x * LBA_T + threadIdx.x;
     const int buf = SYSTEM ? V.S->cur : V.S->cur ^ 1;
-    double rho0 = 0.0;
-    if (e < V.n_edges) rho0 = lba_pass_edge<SYSTEM>(V, C, e, buf);
-    rho0 = lm_wave_sum(rho0);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = rho0;
+    double rho0[1] = {0.0};
+    if (e < V.n_edges) rho0[0] = lba_pass_edge<SYSTEM>(V, C, e, buf);
+    lm_wave_sums(rho0, 0, s_part, threadIdx.x);
     __syncthreads();
-    if (threadIdx.x == 0) V.partial[blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+    if (threadIdx.x == 0) { lm_add_waves(s_part, rho0); V.partial[blockIdx.x] = rho0[0]; }
 }
 __global__ __launch_bounds__(LBA_T) void k_lba_point_sum(LbaView V) {
     const int l = blockIdx.x * LBA_T + threadIdx.x;
@@ -561,7 +555,7 @@ __global__ __launch_bounds__(LBA_T) void k_lba_ctl_full(LbaView V, int n_partial
     for (int l = 1; l < LBA_T; ++l) if (s_m[l] > m) m = s_m[l];
     double chi = 0.0;
     for (int k = 0; k < n_partials; ++k) chi += V.partial[k];
-    lba_ctl_full(*V.S, chi, m);
+    lm_rule_full(*V.S, chi, m);
 }
 __global__ __launch_bounds__(LBA_T) void k_lba_point_damp(LbaView V) {
     const int l = blockIdx.x * LBA_T + threadIdx.x;
@@ -882,6 +876,8 @@ int orbm_lba_ldlt(int n, const double* H, const double* b, double* x) {
 int orbm_lba_controller_trace(const double* chi, int n_chi, const double* hdiag6, const double* b6, int max_iter, int order, int max_steps,
                               double* out_lba, double* out_lm) {
     MORB_ARG(chi && hdiag6 && b6 && out_lba && out_lm && n_chi >= 0 && max_iter >= 1 && max_steps >= 0);
+    // The two DRIVERS of lm_dev.h's rules on one chi2 stream: the rules are one definition, so what can still drift apart is the
+    // sequencing -- lm_step's commands against the local BA's cuts (want_trial / more / ok) -- and that is what the two traces hold.
     // lm_step on its record
     TraceCtl L;
     memset(&L, 0, sizeof(L));
@@ -898,7 +894,7 @@ int orbm_lba_controller_trace(const double* chi, int n_chi, const double* hdiag6
         out_lm[3 * steps_lm + 2] = L.cmd == LM_CMD_CHI ? 1. : L.cmd == LM_CMD_FULL ? 2. : 3.;
         ++steps_lm;
     }
-    // the local BA's controller on the same stream: the same 6x6 solve, computeScale over x
+    // the local BA's driver on the same stream: the same 6x6 solve, computeScale over x
     LbaCtl S;
     lba_ctl_begin(S, order);
     lba_ctl_begin_optimisation(S, 0, max_iter);
@@ -909,7 +905,7 @@ int orbm_lba_controller_trace(const double* chi, int n_chi, const double* hdiag6
         if (full) {
             double md = 0.;
             for (int j = 0; j < 6; ++j) if (fabs(hdiag6[j]) > md) md = fabs(hdiag6[j]);
-            lba_ctl_full(S, chi[k++], md);
+            lm_rule_full(S, chi[k++], md);
         } else {
             double scale = 0.;
             for (int j = 0; j < 6; ++j) scale += x[j] * (S.lambda * x[j] + b6[j]);

@@ -7,8 +7,11 @@
 //   lba_point_damp    setLambda on a landmark block, Dinv = D.inverse(), db = Dinv * db (block_solver.hpp:381-395)
 //   lba_pose_oplus    oplus of a pose vertex
 // (the steps over the whole graph -- the sums per vertex, the Schur entries, the landmarks' back-substitution -- are lba.hip's)
-//   LbaCtl, lba_ctl_* the Levenberg controller: the statements of lm_dev.h's lm_step for a vector of unknowns, cut where g2o polls the
-//                     stop flag (the host polls; tests hold both controllers to one lambda / ni / verdict sequence)
+//   LbaCtl, lba_ctl_* the Levenberg controller's driver for a vector of unknowns: lm_dev.h's rules (lm_rule_full, lm_rule_trial,
+//                     lm_rule_iter_end, the ones lm_step runs) cut where g2o polls the stop flag (the host polls), with what is this
+//                     port's own: the stage, the choice of estimate buffer, the words for the host.  A test holds this driver and
+//                     lm_step to one lambda / ni / verdict sequence.
+// What is g2o's and not this port's -- the edges' Jacobian chain, the Huber constants, SE3Quat to and from seven doubles -- is g2o_dev.h's.
 // Stated deviations (include/orbm.h): (a) the reduced system is solved by a dense LDL^T without pivoting in the natural
 // order of the free poses, not by Eigen's SimplicialLDLT behind an AMD ordering; (b) the order of a point's observations is the
 // caller's.  Everything g2o_dev.h marks UNPINNED is unpinned here too, eigen_inverse3 and the order inside Eigen's small products
@@ -20,6 +23,7 @@
 #include "../../include/orbm.h"
 #include "cv_dev.h"   // x86_nan
 #include "g2o_dev.h"
+#include "lm_dev.h"
 
 constexpr int LBA_T = 256;            // lanes of a workgroup of the per-edge kernels = leaves of one chi2 partial (lm_dev.h's tree)
 constexpr int LBA_EDGE_DOUBLES = 72;  // what a linearised edge leaves in HBM, structure of arrays: array k of edge e is at k * n_edges + e
@@ -32,9 +36,7 @@ struct LbaCam {                          // per problem
 };
 __host__ __device__ inline void lba_camera(const float (*Tcim)[16], LbaCam& C) {
     for (int c = 0; c < 2; ++c) { se3_from_cv(Tcim[c], C.Tc[c]); eigen_quat_to_matrix(C.Tc[c].q, C.Rc[c]); }
-    // `const float thHuberMono = sqrt(5.991)`, `thHuberStereo = sqrt(7.815)`; rk->setDelta(th)
-    const float th[2] = {(float)sqrt(5.991), (float)sqrt(7.815)};
-    for (int s = 0; s < 2; ++s) { C.delta[s] = (double)th[s]; C.dsqr[s] = (double)(float)(C.delta[s] * C.delta[s]); }
+    g2o_huber_constants(C.delta, C.dsqr);
 }
 
 struct LbaEval { double e[3], chi2, zc, A[3][3], B[3][6]; };   // _error, chi2(), the depth, _jacobianOplusXi (point), _jacobianOplusXj (pose)
@@ -45,7 +47,7 @@ template <bool JAC>
 __host__ __device__ __forceinline__ void lba_edge(const LbaCam& C, const float* K5, const double* T7, const double* X, int cam, bool stereo,
                                                   const float* obs, double w, LbaEval& o) {
     SE3Quat T;
-    T.q[0] = T7[0]; T.q[1] = T7[1]; T.q[2] = T7[2]; T.q[3] = T7[3]; T.t[0] = T7[4]; T.t[1] = T7[5]; T.t[2] = T7[6];
+    se3_load7(T7, T);
     const double fx = (double)K5[0], fy = (double)K5[1], cx = (double)K5[2], cy = (double)K5[3], bf = (double)K5[4];
     double p[3], pc[3];
     se3_map(T, X, p);                                    // v1->estimate().map(v2->estimate())
@@ -61,31 +63,17 @@ __host__ __device__ __forceinline__ void lba_edge(const LbaCam& C, const float* 
         const float invz = (float)(1.0 / pc[2]);                               // `const float invz = 1.0f/trans_xyz[2]`
         const double r0 = pc[0] * (double)invz * fx + cx;
         const double r1 = pc[1] * (double)invz * fy + cy;
-        const double r2 = r0 - (double)(K5[4] * invz);                         // `bf*invz`: bf arrives as `const float&`, a float product
+        // the one term where this edge and pose.hip's pose_edge differ: here `bf*invz` is a FLOAT product (cam_project takes
+        // `const float& bf`), there a double one with the member: two reference functions, not to be merged
+        const double r2 = r0 - (double)(K5[4] * invz);
         o.e[0] = (double)obs[0] - r0; o.e[1] = (double)obs[1] - r1; o.e[2] = (double)obs[2] - r2;
         o.chi2 = (o.e[0] * (w * o.e[0]) + o.e[1] * (w * o.e[1])) + o.e[2] * (w * o.e[2]);
     }
     if (!JAC) return;
     double rm[9];
     eigen_quat_to_matrix(T.q, rm);                       // T.rotation().toRotationMatrix()
-    const double* r = C.Rc[cam];
-    const double x = p[0], y = p[1], z = p[2];
-    const double xc = pc[0], yc = pc[1], zc = pc[2], zc_2 = zc * zc;
-    double t1[3][3], t2[3][3];
-    t1[0][0] = -fx / zc; t1[0][1] = 0; t1[0][2] = fx * xc / zc_2;
-    t1[1][0] = 0; t1[1][1] = -fy / zc; t1[1][2] = fy * yc / zc_2;
-    t2[0][0] = t1[0][0] * r[0] + t1[0][2] * r[6];
-    t2[0][1] = t1[0][0] * r[1] + t1[0][2] * r[7];
-    t2[0][2] = t1[0][0] * r[2] + t1[0][2] * r[8];
-    t2[1][0] = t1[1][1] * r[3] + t1[1][2] * r[6];
-    t2[1][1] = t1[1][1] * r[4] + t1[1][2] * r[7];
-    t2[1][2] = t1[1][1] * r[5] + t1[1][2] * r[8];
-    if (stereo) {
-        const double a1 = bf / zc_2;
-        t2[2][0] = t2[0][0] - a1 * r[6];
-        t2[2][1] = t2[0][1] - a1 * r[7];
-        t2[2][2] = t2[0][2] - a1 * r[8];
-    } else { t2[2][0] = 0; t2[2][1] = 0; t2[2][2] = 0; }
+    double t2[3][3];
+    g2o_cam_jacobian_rows(fx, fy, bf, C.Rc[cam], pc, stereo, t2);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         if (k == 2 && !stereo) {
@@ -98,12 +86,7 @@ __host__ __device__ __forceinline__ void lba_edge(const LbaCam& C, const float* 
         o.A[k][0] = t2[k][0] * rm[0] + t2[k][1] * rm[3] + t2[k][2] * rm[6];
         o.A[k][1] = t2[k][0] * rm[1] + t2[k][1] * rm[4] + t2[k][2] * rm[7];
         o.A[k][2] = t2[k][0] * rm[2] + t2[k][1] * rm[5] + t2[k][2] * rm[8];
-        o.B[k][0] = -t2[k][1] * z + t2[k][2] * y;
-        o.B[k][1] = t2[k][0] * z - t2[k][2] * x;
-        o.B[k][2] = -t2[k][0] * y + t2[k][1] * x;
-        o.B[k][3] = t2[k][0];
-        o.B[k][4] = t2[k][1];
-        o.B[k][5] = t2[k][2];
+        g2o_cam_jacobian_pose(t2[k], p, o.B[k]);
     }
 }
 
@@ -162,10 +145,10 @@ __host__ __device__ __forceinline__ void lba_point_damp(const double* Hll, const
 // oplus of a pose vertex: exp(x) * estimate
 __host__ __device__ __forceinline__ void lba_pose_oplus(const double* est7, const double* x6, int order, double* out7) {
     SE3Quat E, d, T;
-    E.q[0] = est7[0]; E.q[1] = est7[1]; E.q[2] = est7[2]; E.q[3] = est7[3]; E.t[0] = est7[4]; E.t[1] = est7[5]; E.t[2] = est7[6];
+    se3_load7(est7, E);
     se3_exp(x6, order, d);
     se3_mul(d, E, T);
-    out7[0] = T.q[0]; out7[1] = T.q[1]; out7[2] = T.q[2]; out7[3] = T.q[3]; out7[4] = T.t[0]; out7[5] = T.t[1]; out7[6] = T.t[2];
+    se3_store7(T, out7);
 }
 
 // ---- the controller ---------------------------------------------------------------------------------------------------------------------
@@ -186,54 +169,19 @@ __host__ __device__ inline void lba_ctl_begin(LbaCtl& S, int order) {
 __host__ __device__ inline void lba_ctl_begin_optimisation(LbaCtl& S, int stage, int max_iter) {
     S.stage = stage; S.iter = 0; S.max_iter = max_iter; S.ok = 1; S.more = max_iter > 0 ? 1 : 0; S.want_trial = 0;
 }
-// after computeActiveErrors + buildSystem at the estimate (:75-101); max_diagonal: computeLambdaInit's maximum (read at iteration 0)
-__host__ __device__ inline void lba_ctl_full(LbaCtl& S, double chi, double max_diagonal) {
-    S.current_chi = chi; S.ini_chi = chi;
-    if (S.iter == 0) { S.lambda = 1e-5 * max_diagonal; S.ni = 2; S.n_bad_steps = 0; }
-    S.qmax = 0;
-}
-// after a trial's computeActiveErrors (:123-149); scale: computeScale() over all of x.  Leaves want_trial = `rho<0 && qmax < 10`.
+// after a trial's computeActiveErrors; scale: computeScale() over all of x.  Accepting is a choice of buffer (discardTop: the trial is the
+// estimate).  Leaves want_trial = `rho<0 && qmax < 10`: the caller polls the stop flag before the next trial.
 __host__ __device__ inline void lba_ctl_trial_end(LbaCtl& S, double temp_chi, double scale) {
-    orbm_pose_round& R = S.round[S.stage];
-    if (!S.ok2) temp_chi = DBL_MAX;
-    double rho = S.current_chi - temp_chi;
-    scale += 1e-3;
-    rho /= scale;
-    if (rho > 0 && fabs(temp_chi) <= DBL_MAX) {
-        const double u = 2 * rho - 1;
-        double cube;
-#ifndef __HIP_DEVICE_COMPILE__
-        if (S.order == ORBM_POSE_ORDER_INDEX) cube = pow(u, 3); else
-#endif
-        cube = u * u * u;
-        double alpha = 1. - cube;
-        alpha = alpha < 2. / 3. ? alpha : 2. / 3.;             // (std::min)(alpha, _goodStepUpperScale)
-        const double scale_factor = 1. / 3. < alpha ? alpha : 1. / 3.;   // (std::max)(_goodStepLowerScale, alpha)
-        S.lambda *= scale_factor;
-        S.ni = 2;
-        S.current_chi = temp_chi;
-        S.cur ^= 1;                          // discardTop: the trial is the estimate
-    } else {
-        S.lambda *= S.ni;
-        S.ni *= 2;                           // pop: the estimate stays
-    }
-    S.qmax++;
-    R.trials++;
-    S.rho = rho;
-    S.want_trial = (rho < 0 && S.qmax < 10) ? 1 : 0;
+    const LmTrial t = lm_rule_trial(S, temp_chi, scale, S.round[S.stage]);
+    if (t.accepted) S.cur ^= 1;
+    S.rho = t.rho;
+    S.want_trial = (t.rho < 0 && S.qmax < 10) ? 1 : 0;
 }
-// the trial loop is over (by its own condition or by the stop flag): solve()'s result and optimize()'s bookkeeping.  Leaves
-// more = `i < iterations` and ok = `result == OK`; the caller polls the stop flag when more is set, before it reads ok.
+// the trial loop is over (by its own condition or by the stop flag).  Leaves more = `i < iterations` and ok = `result == OK`; the caller
+// polls the stop flag when more is set, before it reads ok.
 __host__ __device__ inline void lba_ctl_iter_end(LbaCtl& S) {
     orbm_pose_round& R = S.round[S.stage];
-    R.iterations++;
-    bool terminate = S.qmax == 10 || S.rho == 0;
-    if (!terminate) {
-        if ((S.ini_chi - S.current_chi) * 1e3 < S.ini_chi) S.n_bad_steps++; else S.n_bad_steps = 0;
-        if (S.n_bad_steps >= 3) terminate = true;
-    }
-    S.iter++;
-    S.ok = terminate ? 0 : 1;
+    S.ok = lm_rule_iter_end(S, S.rho, R) ? 0 : 1;
     S.more = S.iter < S.max_iter ? 1 : 0;
     S.want_trial = 0;
     R.chi2 = x86_nan(S.current_chi); R.lambda = x86_nan(S.lambda);

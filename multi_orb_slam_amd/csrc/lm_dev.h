@@ -1,9 +1,15 @@
-// lm_dev.h -- what the Levenberg ports share (pose.hip: 6 unknowns, sim3opt.hip: 7), ONE definition each, for the kernels and the host
-// routines.  Restated from Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp, core/sparse_optimizer.cpp (the loop of optimize).
-//   LmState<N>, lm_step   the controller between two passes over the edges as far as it does not depend on the vertex.  The port's record
+// lm_dev.h -- what the Levenberg ports share (pose.hip: 6 unknowns, sim3opt.hip: 7, lba.hip: a vector of them), ONE definition each, for
+// the kernels and the host routines.  Restated from Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp, core/sparse_optimizer.cpp
+// (the loop of optimize).
+//   lm_rule_full, lm_rule_trial, lm_rule_iter_end   the Levenberg rules themselves -- lambda's start, its scaling after a trial, the
+//                         verdict on a trial, the end of an iteration -- over any record that has the members they touch.  Every port
+//                         runs these three; its driver decides what lies between them.
+//   LmState<N>, lm_step   the driver for a fixed-size vertex: the controller between two passes over the edges as far as it does not
+//                         depend on the vertex (the sums into H and b, the dense solve, computeScale).  The port's record
 //                         derives from LmState<N> and supplies the points where the ports differ inside an optimisation: lm_trial()
 //                         (oplusImpl: exp(x) * estimate into what the next pass reads), lm_accept() (discardTop), lm_linearise() (what a
 //                         FULL pass reads, at the estimate; sets cmd = LM_CMD_FULL) and the constant LM_TRY_INLINE (lm_next_trial).
+//                         (The local BA's driver is lba_dev.h's lba_ctl_*: the same three calls, cut where g2o polls the stop flag.)
 //   lm_wave_sum, lm_wave_sums, lm_add_waves   the kernel's summation tree: xor butterfly (1 .. 32) in each wave, the four waves in wave
 //                         order.  lm_pass_host: the same tree leaf for leaf on the host (DEVICE order) or the plain loop (INDEX order).
 //   lm_csr_call           the skeleton of a batched call over a CSR of problems (its checks: morb::validate_csr, stage_pack.h).
@@ -51,36 +57,32 @@ __host__ __device__ __forceinline__ void lm_next_trial(Ctl& S) {
     if constexpr (Ctl::LM_TRY_INLINE) { [[clang::always_inline]] lm_try(S); } else { [[clang::noinline]] lm_try(S); }
 }
 
-// Called after a FULL or a CHI pass with the pass's sums; R: where this optimisation's counters go.  Leaves cmd = LM_CMD_CHI (a trial),
-// LM_CMD_FULL (the next iteration) or LM_CMD_CLASSIFY (optimize() returned).  lambda is initialised at iteration 0 of EVERY optimisation;
-// after a rejected last trial the estimate is the last accepted one while the pass's transform stays the rejected one.
-template <class Ctl>
-__host__ __device__ __forceinline__ void lm_step(Ctl& S, const double* sum, orbm_pose_round& R) {
-    constexpr int N = Ctl::N;
-    if (S.cmd == LM_CMD_FULL) {              // solve(), :75-101: the errors, the robust chi2 and the system at the estimate
-        S.current_chi = sum[Ctl::CHI]; S.ini_chi = S.current_chi;
-        for (int k = 0; k < Ctl::NH; ++k) S.H[k] = sum[k];
-        for (int k = 0; k < N; ++k) S.b[k] = sum[Ctl::NH + k];
-        if (S.iter == 0) {                   // computeLambdaInit: tau * the largest |diagonal|
-            double max_diagonal = 0.;
-            int d = 0;
-            for (int j = 0; j < N; ++j) { const double v = fabs(S.H[d]); if (v > max_diagonal) max_diagonal = v; d += N - j; }
-            S.lambda = 1e-5 * max_diagonal;
-            S.ni = 2; S.n_bad_steps = 0;
-        }
-        S.qmax = 0;
-        lm_next_trial(S);
-        return;
-    }
-    // LM_CMD_CHI, :123-149
-    double temp_chi = sum[Ctl::CHI];
+// ---- the Levenberg rules of g2o ------------------------------------------------------------------------------------------------------------
+// optimization_algorithm_levenberg.cpp:61-164 and the bookkeeping of SparseOptimizer::optimize's loop (core/sparse_optimizer.cpp:376-414),
+// ONE definition for every port, over any record with the members order, iter, max_iter, qmax, n_bad_steps, ok2, lambda, ni,
+// current_chi, ini_chi (LmState<N>, lba_dev.h's LbaCtl): templates and no base struct, so that no record's layout depends on them
+// (profiles/r17/notes_lm_refactor.md).  What differs between the ports stays with their drivers: the sums, the solve, computeScale's
+// sum over x, what accepting a trial means, and where g2o polls the stop flag.
+// after computeActiveErrors + buildSystem at the estimate (:75-101); max_diagonal: computeLambdaInit's maximum, read at iteration 0
+template <class S_>
+__host__ __device__ __forceinline__ void lm_rule_full(S_& S, double chi, double max_diagonal) {
+    S.current_chi = chi; S.ini_chi = chi;
+    if (S.iter == 0) { S.lambda = 1e-5 * max_diagonal; S.ni = 2; S.n_bad_steps = 0; }   // computeLambdaInit: tau * the largest |diagonal|
+    S.qmax = 0;
+}
+// after a trial's computeActiveErrors (:123-149); scale: computeScale() over all of x.  The caller does discardTop when accepted (pop
+// otherwise: its estimate stays) and goes on with the next trial while `rho < 0 && qmax < 10`.
+struct LmTrial { double rho; bool accepted; };
+template <class S_>
+__host__ __device__ __forceinline__ LmTrial lm_rule_trial(S_& S, double temp_chi, double scale, orbm_pose_round& R) {
     if (!S.ok2) temp_chi = DBL_MAX;          // the solve failed: the trial counts as rejected whatever its pass summed
     double rho = S.current_chi - temp_chi;
-    double scale = 0.;
-    for (int j = 0; j < N; ++j) scale += S.x[j] * (S.lambda * S.x[j] + S.b[j]);
     scale += 1e-3;
     rho /= scale;
-    if (rho > 0 && fabs(temp_chi) <= DBL_MAX) {
+    S.qmax++;                                // (counted here and not behind the verdict, where g2o counts: the verdict reads neither,
+    R.trials++;                              //  and so the caller's discardTop joins the accepting branch: profiles/r21/notes_lba_shared.md)
+    const bool accepted = rho > 0 && fabs(temp_chi) <= DBL_MAX;
+    if (accepted) {
         const double u = 2 * rho - 1;
         double cube;
 #ifndef __HIP_DEVICE_COMPILE__
@@ -93,15 +95,16 @@ __host__ __device__ __forceinline__ void lm_step(Ctl& S, const double* sum, orbm
         S.lambda *= scale_factor;
         S.ni = 2;
         S.current_chi = temp_chi;
-        S.lm_accept();                       // discardTop
     } else {
         S.lambda *= S.ni;
-        S.ni *= 2;                           // pop: the estimate stays
+        S.ni *= 2;
     }
-    S.qmax++;
-    R.trials++;
-    if (rho < 0 && S.qmax < 10) { lm_next_trial(S); return; }
-    // the iteration is over: solve()'s result, then optimize()'s loop (core/sparse_optimizer.cpp:376-414); rho == 0 terminates
+    return {rho, accepted};
+}
+// the trial loop is over: solve()'s result, then optimize()'s loop; rho == 0 terminates.  Returns terminate (`result != OK`); the
+// caller's loop also ends at iter == max_iter.
+template <class S_>
+__host__ __device__ __forceinline__ bool lm_rule_iter_end(S_& S, double rho, orbm_pose_round& R) {
     R.iterations++;
     bool terminate = S.qmax == 10 || rho == 0;
     if (!terminate) {
@@ -109,7 +112,35 @@ __host__ __device__ __forceinline__ void lm_step(Ctl& S, const double* sum, orbm
         if (S.n_bad_steps >= 3) terminate = true;
     }
     S.iter++;
-    if (terminate || S.iter == S.max_iter) {
+    return terminate;
+}
+
+// The driver of the rules for a fixed-size vertex.  Called after a FULL or a CHI pass with the pass's sums; R: where this optimisation's
+// counters go.  Leaves cmd = LM_CMD_CHI (a trial), LM_CMD_FULL (the next iteration) or LM_CMD_CLASSIFY (optimize() returned).  lambda is
+// initialised at iteration 0 of EVERY optimisation; after a rejected last trial the estimate is the last accepted one while the pass's
+// transform stays the rejected one.
+template <class Ctl>
+__host__ __device__ __forceinline__ void lm_step(Ctl& S, const double* sum, orbm_pose_round& R) {
+    constexpr int N = Ctl::N;
+    if (S.cmd == LM_CMD_FULL) {              // the errors, the robust chi2 and the system at the estimate
+        for (int k = 0; k < Ctl::NH; ++k) S.H[k] = sum[k];
+        for (int k = 0; k < N; ++k) S.b[k] = sum[Ctl::NH + k];
+        double max_diagonal = 0.;
+        if (S.iter == 0) {
+            int d = 0;
+            for (int j = 0; j < N; ++j) { const double v = fabs(S.H[d]); if (v > max_diagonal) max_diagonal = v; d += N - j; }
+        }
+        lm_rule_full(S, sum[Ctl::CHI], max_diagonal);
+        lm_next_trial(S);
+        return;
+    }
+    // LM_CMD_CHI
+    double scale = 0.;
+    for (int j = 0; j < N; ++j) scale += S.x[j] * (S.lambda * S.x[j] + S.b[j]);
+    const LmTrial t = lm_rule_trial(S, sum[Ctl::CHI], scale, R);
+    if (t.accepted) S.lm_accept();           // discardTop
+    if (t.rho < 0 && S.qmax < 10) { lm_next_trial(S); return; }
+    if (lm_rule_iter_end(S, t.rho, R) || S.iter == S.max_iter) {
         R.chi2 = x86_nan(S.current_chi); R.lambda = x86_nan(S.lambda);
         S.cmd = LM_CMD_CLASSIFY;
     } else {

@@ -3,7 +3,7 @@
 // + host helpers; exchange.hip: RCCL / loopback transport; frontend.hip: orbf_*; mappoint.hip: map-point refresh; pose.hip: pose
 // optimisation; sim3.hip: Sim3 RANSAC; sim3opt.hip: Sim3 refinement; pnp.hip: PnP RANSAC; lba.hip: local bundle adjustment).  Not part of the C ABI.  Next to it: cv_dev.h / g2o_dev.h (the restated OpenCV and Eigen / g2o
 // operations those ports share), sincos_dev.h, hamming_dev.h, resolve_dev.h (the steps the resolve's forms share and their LDS layouts),
-// stage_pack.h (the staged input block of a batched call and the checks on its CSR), lm_dev.h (what the two Levenberg ports share),
+// stage_pack.h (the staged input block of a batched call and the checks on its CSR), lm_dev.h (what the Levenberg ports share),
 // ransac_dev.h (what the two RANSAC ports share).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -3,10 +3,11 @@
 // g2o they run restated (Thirdparty/g2o/g2o/: types/types_six_dof_expmap.{h,cpp}, types/se3quat.h, types/se3_ops.hpp,
 // core/base_unary_edge.hpp, core/base_edge.h, core/robust_kernel_impl.cpp, core/optimization_algorithm_levenberg.cpp,
 // core/sparse_optimizer.cpp, solvers/linear_solver_dense.h) and the Eigen operators those call.
-//   eigen_*, se3_*, g2o_huber   the Eigen operators, g2o::SE3Quat and the Huber kernel: g2o_dev.h (UNPINNED).
+//   eigen_*, se3_*, g2o_*   the Eigen operators, g2o::SE3Quat, the Huber kernel and the Jacobian chain of the edges through Tcim, which
+//                    the local bundle adjustment runs too: g2o_dev.h (UNPINNED).
 //   pose_edge        one edge: error, chi2 and the Jacobian of its type, ONE statement sequence for the kernel and the host routine.
 //   pose_step        the controller: everything between two passes over the edges as a resumable state machine over a PoseCtl record.
-//                    The Levenberg bookkeeping and the 6x6 solve are lm_dev.h's lm_step (ONE definition, sim3opt.hip runs it too); the exp
+//                    The Levenberg rules and the 6x6 solve are lm_dev.h's lm_step (ONE definition, sim3opt.hip runs it too); the exp
 //                    map, rounds and classification are here.  Host routine and lane 0 (on the record in LDS) call the same statements.
 //   k_pose_optimize  one workgroup of 256 lanes per problem, resident for the whole call.  Per pass: every lane evaluates its edges
 //                    (lane l owns l, l + 256, ...; the first eight of them stay in registers, a longer tail streams from the staged
@@ -64,6 +65,8 @@ __host__ __device__ inline double pose_edge(const PoseCam& C, const SE3Quat& T, 
         const float invz = (float)(1.0 / pc[2]);                               // `const float invz = 1.0f/trans_xyz[2]`
         const double r0 = pc[0] * (double)invz * C.fx + C.cx;
         const double r1 = pc[1] * (double)invz * C.fy + C.cy;
+        // the one term where this edge (EdgeStereoSE3ProjectXYZOnlyPose::cam_project: the member bf, a double product) and lba_dev.h's
+        // lba_edge (EdgeStereoSE3ProjectXYZ::cam_project: `const float& bf`, a float product) differ: two reference functions, not to be merged
         const double r2 = r0 - C.bf * (double)invz;
         e[0] = (double)E.obs[0] - r0; e[1] = (double)E.obs[1] - r1; e[2] = (double)E.obs[2] - r2;
     }
@@ -94,33 +97,13 @@ __host__ __device__ inline double pose_edge(const PoseCam& C, const SE3Quat& T, 
             J[2][5] = J[0][5] - C.bf * invz_2;
         }
     } else {                                              // the _multi edges multiply by Rcim, the identity included (:627-696, :952-1036)
-        const double* r = C.Rc[cam];
-        const double x = p[0], y = p[1], z = p[2];
-        const double xc = pc[0], yc = pc[1], zc = pc[2], zc_2 = zc * zc;
-        const double a1 = C.bf / zc_2;
-        double t1[3][3], t2[3][3];
-        t1[0][0] = -C.fx / zc; t1[0][1] = 0; t1[0][2] = C.fx * xc / zc_2;
-        t1[1][0] = 0; t1[1][1] = -C.fy / zc; t1[1][2] = C.fy * yc / zc_2;
-        t1[2][0] = t1[0][0]; t1[2][1] = 0; t1[2][2] = t1[0][2] - a1;
-        t2[0][0] = t1[0][0] * r[0] + t1[0][2] * r[6];
-        t2[0][1] = t1[0][0] * r[1] + t1[0][2] * r[7];
-        t2[0][2] = t1[0][0] * r[2] + t1[0][2] * r[8];
-        t2[1][0] = t1[1][1] * r[3] + t1[1][2] * r[6];
-        t2[1][1] = t1[1][1] * r[4] + t1[1][2] * r[7];
-        t2[1][2] = t1[1][1] * r[5] + t1[1][2] * r[8];
-        t2[2][0] = t2[0][0] - a1 * r[6];
-        t2[2][1] = t2[0][1] - a1 * r[7];
-        t2[2][2] = t2[0][2] - a1 * r[8];
+        double t2[3][3];
+        g2o_cam_jacobian_rows(C.fx, C.fy, C.bf, C.Rc[cam], pc, true, t2);   // row 2 always, read below for a stereo edge only
         const int D = stereo ? 3 : 2;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             if (k >= D) continue;
-            J[k][0] = -t2[k][1] * z + t2[k][2] * y;
-            J[k][1] = t2[k][0] * z - t2[k][2] * x;
-            J[k][2] = -t2[k][0] * y + t2[k][1] * x;
-            J[k][3] = t2[k][0];
-            J[k][4] = t2[k][1];
-            J[k][5] = t2[k][2];
+            g2o_cam_jacobian_pose(t2[k], p, J[k]);
         }
     }
     return chi2;
@@ -180,15 +163,8 @@ struct PoseCtl : LmState<6> {
     __host__ __device__ __forceinline__ void lm_linearise() { eval = est; cmd = LM_CMD_FULL; }
 };
 
-// Converter::toCvMat(SE3Quat): to_homogeneous_matrix() rounded to float
 __host__ __device__ inline void pose_write_estimate(PoseCtl& S) {
-    double R[9];
-    eigen_quat_to_matrix(S.est.q, R);
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) S.res.Tcw[4 * r + c] = x86_nan((float)R[3 * r + c]);
-        S.res.Tcw[4 * r + 3] = x86_nan((float)S.est.t[r]);
-    }
-    S.res.Tcw[12] = 0.0f; S.res.Tcw[13] = 0.0f; S.res.Tcw[14] = 0.0f; S.res.Tcw[15] = 1.0f;
+    se3_to_cv(S.est, S.res.Tcw);
     for (int k = 0; k < 4; ++k) S.res.q[k] = x86_nan(S.est.q[k]);
     for (int k = 0; k < 3; ++k) S.res.t[k] = x86_nan(S.est.t[k]);
 }
@@ -257,10 +233,7 @@ __host__ __device__ inline void pose_camera(const orbm_pose_problem& P, PoseCam&
     se3_from_cv(T21, C.Tc[1]);
     eigen_quat_to_matrix(C.Tc[0].q, C.Rc[0]);
     eigen_quat_to_matrix(C.Tc[1].q, C.Rc[1]);
-    // `const float deltaMono = sqrt(5.991)`, rk->setDelta(deltaMono): _delta = the float as a double, dsqr = (float)(delta*delta)
-    const float delta_mono = (float)sqrt(5.991), delta_stereo = (float)sqrt(7.815);
-    C.delta[0] = (double)delta_mono; C.delta[1] = (double)delta_stereo;
-    C.dsqr[0] = (double)(float)(C.delta[0] * C.delta[0]); C.dsqr[1] = (double)(float)(C.delta[1] * C.delta[1]);
+    g2o_huber_constants(C.delta, C.dsqr);
 }
 
 __host__ __device__ inline int pose_meta(const orbm_pose_problem& P, int feat, float uright) {
