@@ -17,6 +17,9 @@
 //                          of the 39x39 neighbourhood actually sampled, 256 steered rBRIEF tests, keypoint record.
 // The reference's 19-px reflect-101 border of every level is never read by a later stage and is
 // not materialised.
+// The host side of the geometry -- level and cell layout, resize tables, tile spans, the choice of pyramid form -- is planned in
+// extract_plan.h (plain C++, no HIP call); below the kernels: the handle, rebuild_geometry (plan, reserve, upload), the orbx_* ABI,
+// and a run as a sequence of steps (orbx_run_impl).
 #include <algorithm>
 #include <cfloat>
 #include <cstdlib>
@@ -36,35 +39,12 @@
 #include "orb_common.h"
 #include "frame_sink.h"
 
+#include "extract_plan.h"
+
 namespace {
 
 using morb::DevBuf;
 
-constexpr int EDGE_THRESHOLD = 19;   // reference src/ORBextractor.cc:74
-constexpr int MIN_BORDER = 16;       // EDGE_THRESHOLD - 3, :772
-constexpr int PATCH_SIZE = 31;       // :72
-constexpr int HALF_PATCH = 15;       // :73
-constexpr int CELL_MAX = 64;         // largest wCell/hCell this build stages in LDS
-constexpr int TILE_PITCH = 76;       // LDS pitch of the image tile (CELL_MAX + 6, plus up to 3 bytes of dword alignment, rounded up to 4)
-constexpr int SCORE_PITCH = 68;      // LDS pitch of the score map (CELL_MAX + 2 rounded up)
-constexpr int MAX_LEVELS = 16;
-constexpr int COEF_BITS = 11;        // OpenCV INTER_RESIZE_COEF_BITS
-
-struct LevelInfo {
-    int w, h, stride;        // level size, row pitch in bytes (multiple of 64)
-    int pyr_off;             // byte offset inside the camera's pyramid buffer
-    int n_cols, n_rows, w_cell, h_cell;  // reference :782-788
-    int cell_base;           // first global cell id
-    int slot_base, slot_cap; // per-cell candidate slots: slot_base + local_cell*slot_cap (u32 units)
-    int cand_base;           // dense candidate list of this level (u32 units, in the pinned host buffer)
-    int xtab_off, ytab_off;  // resize coefficient tables (valid for level >= 1)
-    int xgrp_off;            // the x table once more per group of four destination columns (k_pyramid_tiled4), in groups
-    int ini_th, min_th;
-    float scale;             // mvScaleFactor[level]
-    float patch_size;        // (float)(int)(31 * scale)
-    int quota;               // mnFeaturesPerLevel[level]
-    int sel_base;            // first slot of this (camera, level) in the device quadtree's output list (quota + 4 slots)
-};
 
 struct MirrorArgs {  // optional pinned-host (device-mapped) copy of the results in global, camera-major order
     orb_keypoint* kps; uint8_t* desc;
@@ -218,8 +198,6 @@ MORB_PHASE_DECL(g_ph_pyr);
 #endif
 struct PyrArgs { const uint8_t* src[64]; int stride[64]; short tx[64], ty[64], w[64], h[64]; };   // src NULL: level 0 is already in place
 constexpr int PYR_L0_DW = 8;   // dwords of the level-0 block a thread holds: (64 + 16) / 4 x (64 + 16) / 256 rounded up
-constexpr int PYR_HALO = 16;   // what a tile needs of level 0 beyond its own T x T pixels (13 for 8 levels at 1.2; checked by the host)
-constexpr int PYR_MAX_LEVELS = 12;
 
 // LDS: [x table entries of all levels (int2)] [y table entries of all levels (int4)] [the regions, level after level]
 template <int NT>
@@ -423,7 +401,6 @@ struct Tile4Args {
     int max_levels, base, last, tw, th, halo_x, halo_y, tx_max, ty_max, gcap, rcap;
     short tx[64], ty[64];
 };
-constexpr int T4_MAX_DW = 16;   // dwords of the base block a thread holds while the tables are on their way: (tw + halo) / 4 x (th + halo) <= 16 x threads (host)
 
 template <int NT>
 __global__ __launch_bounds__(NT) void k_pyramid_tiled4(Tile4Args A) {
@@ -1916,103 +1893,6 @@ __global__ __launch_bounds__(256) void k_describe(const LevelInfo* __restrict__ 
     DPH(7);
 }
 
-// ------------------------------------------------------------------------------------------------ host tables
-inline int cv_round(double v) { return (int)std::nearbyint(v); }
-inline int cv_floor(double v) { int i = (int)v; return i - (i > v); }
-inline int cv_ceil(double v) { int i = (int)v; return i + (i < v); }
-inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
-
-struct CamTables {
-    orbx_params p;
-    std::vector<float> scale, inv_scale, sigma2, inv_sigma2;
-    std::vector<int> quota;
-};
-
-void build_cam_tables(const orbx_params& p, CamTables& T) {
-    T.p = p;
-    const int n = p.nlevels;
-    const double sf = (double)p.scale_factor;  // the reference stores scaleFactor in a double member
-    T.scale.assign(n, 1.0f); T.sigma2.assign(n, 1.0f); T.inv_scale.assign(n, 1.0f); T.inv_sigma2.assign(n, 1.0f);
-    for (int i = 1; i < n; ++i) {
-        T.scale[i] = (float)((double)T.scale[i - 1] * sf);
-        T.sigma2[i] = T.scale[i] * T.scale[i];
-    }
-    for (int i = 0; i < n; ++i) { T.inv_scale[i] = 1.0f / T.scale[i]; T.inv_sigma2[i] = 1.0f / T.sigma2[i]; }
-    T.quota.assign(n, 0);
-    const float factor = (float)(1.0 / sf);
-    float desired = (float)p.nfeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)n));
-    int sum = 0;
-    for (int l = 0; l < n - 1; ++l) {
-        T.quota[l] = cv_round(desired);
-        sum += T.quota[l];
-        desired *= factor;
-    }
-    T.quota[n - 1] = std::max(p.nfeatures - sum, 0);
-}
-
-void compute_umax(int* umax) {
-    int v, v0, vmax = cv_floor(HALF_PATCH * std::sqrt(2.f) / 2 + 1);
-    int vmin = cv_ceil(HALF_PATCH * std::sqrt(2.f) / 2);
-    const double hp2 = HALF_PATCH * HALF_PATCH;
-    for (v = 0; v <= vmax; ++v) umax[v] = cv_round(std::sqrt(hp2 - v * v));
-    for (v = HALF_PATCH, v0 = 0; v >= vmin; --v) {
-        while (umax[v0] == umax[v0 + 1]) ++v0;
-        umax[v] = v0;
-        ++v0;
-    }
-}
-
-// OpenCV resize(INTER_LINEAR) coefficient tables for one axis pair (imgwarp.cpp, 8-bit fixed point path)
-void build_resize_tables(int sw, int sh, int dw, int dh, std::vector<int2>& xt, std::vector<int4>& yt) {
-    const int ONE = 1 << COEF_BITS;
-    const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
-    auto sat_short = [](int v) { return v < -32768 ? -32768 : v > 32767 ? 32767 : v; };
-    for (int dx = 0; dx < dw; ++dx) {
-        float fx = (float)((dx + 0.5) * scale_x - 0.5);
-        int sx = cv_floor(fx);
-        fx -= sx;
-        if (sx < 0) { fx = 0; sx = 0; }
-        if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
-        const int a0 = sat_short(cv_round((1.f - fx) * ONE)), a1 = sat_short(cv_round(fx * ONE));
-        const int sx1 = std::min(sx + 1, sw - 1);
-        int2 e;
-        e.x = (sx & 0xffff) | (sx1 << 16);
-        e.y = (a0 & 0xffff) | (a1 << 16);
-        xt.push_back(e);
-    }
-    for (int dy = 0; dy < dh; ++dy) {
-        float fy = (float)((dy + 0.5) * scale_y - 0.5);
-        int sy = cv_floor(fy);
-        fy -= sy;
-        int4 e;
-        e.x = std::min(std::max(sy, 0), sh - 1);      // each tap's row is clipped, coefficients stay
-        e.y = std::min(std::max(sy + 1, 0), sh - 1);
-        e.z = sat_short(cv_round((1.f - fy) * ONE));
-        e.w = sat_short(cv_round(fy * ONE));
-        yt.push_back(e);
-    }
-}
-
-// k_pyramid_tiled4's view of the x table: per group of four destination columns {c, sel0, sel1, sel2} {sel3, alpha0..2} {alpha3}, c = the
-// first tap's source column, sel_j = (left tap - c) | 0x0c << 8 | (right tap - c) << 16 | 0x0c << 24 (v_perm_b32 selector over the
-// row's eight bytes from c on: tap | 0 | tap | 0), alpha_j = the column's coefficient pair.  Columns past the level's width repeat
-// its last one (they land in the row pitch's padding).
-void build_resize_groups(const std::vector<int2>& xt, int xtab_off, int dw, std::vector<int4>& xg) {
-    for (int x4 = 0; x4 < dw; x4 += 4) {
-        const int c = xt[xtab_off + x4].x & 0xffff;
-        uint32_t sel[4], al[4];
-        for (int j = 0; j < 4; ++j) {
-            const int2 e = xt[xtab_off + std::min(x4 + j, dw - 1)];
-            const uint32_t l = (uint32_t)((e.x & 0xffff) - c) & 7u, r = (uint32_t)(((unsigned)e.x >> 16) - c) & 7u;
-            sel[j] = l | (0x0cu << 8) | (r << 16) | (0x0cu << 24);
-            al[j] = (uint32_t)e.y;
-        }
-        xg.push_back(make_int4(c, (int)sel[0], (int)sel[1], (int)sel[2]));
-        xg.push_back(make_int4((int)sel[3], (int)al[0], (int)al[1], (int)al[2]));
-        xg.push_back(make_int4((int)al[3], 0, 0, 0));
-    }
-}
-
 }  // namespace
 
 // Small persistent worker pool for the host quadtree: the (camera, level) problems of one call are independent.
@@ -2092,6 +1972,52 @@ struct OctreeTask {
 // before they create a handle; the product never does)
 static int g_t4_plan[3] = {128, 64, 3};
 
+// Level 0 of the next run: the pending sources (k_ingest, or the fused read of k_pyramid_tiled) and the in-place table (k_set_l0);
+// place_level0 owns the transitions.
+struct Level0State {
+    IngestArgs ingest;               // device-resident sources to copy into level 0 at the start of the next run
+    bool pending = false;
+    bool host = false;               // a pending ingest source lives in host memory (read across PCIe)
+    bool pinned_ingest = false;      // page-locked host images are read by k_ingest directly (orbx_set_pinned_ingest) instead of hipMemcpy2DAsync
+    // level 0 in place (orbx_set_inplace_level0): taken when the caller opted in and the geometry allows it (geo.l0_on);
+    // active = the device table holds pointers of the last run's images; tab = what it holds (inspection hook)
+    bool optin = false, active = false;
+    DevBuf<L0Src> d_tab;
+    std::vector<L0Src> tab;
+    std::vector<uint8_t> uploaded;   // cameras handed an image (any kind, also an empty one) since the last run
+};
+
+// Everything the launches of a captured chain carry: a chain is replayed only for the key it was captured under.
+struct ChainKey {
+    int epoch = -1; orb_keypoint* mirror_kps = nullptr; uint8_t* mirror_desc = nullptr; int tail_tag = 0; FrameSink sink;
+    bool operator==(const ChainKey& o) const {
+        return epoch == o.epoch && mirror_kps == o.mirror_kps && mirror_desc == o.mirror_desc && tail_tag == o.tail_tag &&
+               memcmp(&sink, &o.sink, sizeof(FrameSink)) == 0;
+    }
+};
+struct ChainGraph {  // captured kernel chain of one count slot (see enqueue_chain)
+    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
+    ChainKey key;
+    void destroy() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        exec = nullptr; graph = nullptr; key.epoch = -1;
+    }
+};
+constexpr int CHAIN_WAYS = 4;
+struct ChainCache {
+    ChainGraph way[2][CHAIN_WAYS];   // a few graphs per slot: a caller rotates through more result sets / frames than there are slots
+    int next[2] = {0, 0};            // replacement cursor per slot
+    bool use_graph = true;           // MORB_CHAIN_GRAPH=0 keeps plain launches
+};
+
+struct StageProfile {
+    bool on = false;
+    bool valid[2] = {false, false};  // the stage events were recorded for the run in this slot
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    float stage_us[6] = {0, 0, 0, 0, 0, 0};
+};
+
 struct orbx_extractor {
     int device = 0, n_cams = 0, max_w = 0, max_h = 0, max_levels = 0;
     hipStream_t stream = nullptr;
@@ -2099,16 +2025,10 @@ struct orbx_extractor {
     std::vector<CamTables> cams;
     std::vector<int> cur_w, cur_h;   // size of the resident image per camera (0 = none)
     FrameSink sink;                  // orbf_step: merged-frame destination of the describe kernel (x == nullptr: off)
-    IngestArgs ingest;               // device-resident sources to copy into level 0 at the start of the next run
-    bool ingest_pending = false;
+    Level0State l0;
     bool tables_dirty = true;
 
-    // geometry (host copies)
-    std::vector<LevelInfo> levels;   // [cam * max_levels + level]
-    std::vector<int2> cell_map;
-    int cell_h_max = 1, cell_px_max = 1;   // tallest cell / most pixels in a cell over all cameras and levels (k_fast_cells' LDS)
-    int total_cells = 0;
-    size_t total_slots = 0;
+    GeometryPlan geo;                // host copy of the geometry (extract_plan.h), rebuilt by rebuild_geometry
     size_t cam_pitch = 0;            // bytes of pyramid memory per camera
     std::vector<int> out_cap;        // per camera keypoint capacity of the output buffers
 
@@ -2118,68 +2038,29 @@ struct orbx_extractor {
     DevBuf<int2> d_cell_map, d_xtab;
     DevBuf<int4> d_xgrp;              // k_pyramid_tiled4's per-group view of the x table
     DevBuf<uint8_t> d_desc_tabs;      // k_describe's DescribeTables (IC_Angle items + float test locations)
-    // the tiled whole-pyramid launch (k_pyramid_tiled): spans per (camera, level, tile column / row), tiles per camera, LDS need
-    DevBuf<int4> d_pyr_sx, d_pyr_sy;
-    int pyr_tx_max = 0, pyr_ty_max = 0, pyr_lds = 0, pyr_tile = 0, pyr_tab_cap = 0;
-    short pyr_tx[64] = {}, pyr_ty[64] = {};
-    bool ingest_host = false;         // a pending ingest source lives in host memory (read across PCIe)
-    bool tiled_ok = false;            // ... and this geometry fits it (LDS, halo, level count) and is small enough to prefer it
-    bool v4_ok = false;               // level steps <= 1.6: the four-pixels-per-lane arithmetic of k_pyramid_tiled4 applies (taps of four neighbours within 8 bytes)
-    bool generic_chain = false;       // MORB_PYR_CHAIN=2: neither tile form, one k_resize launch per level
-    // large rigs (round 5): the pyramid as TWO tile launches with four pixels per lane (k_pyramid_tiled4): levels 1..m below level 0
-    // and levels m+1.. below level m
-    struct TilePlan {
-        int base = 0, last = 0, tw = 0, th = 0, halo_x = 16, halo_y = 16, tx_max = 0, ty_max = 0, gcap = 0, rcap = 0, lds = 0, threads = 256;
-        short tx[64] = {}, ty[64] = {};
-        DevBuf<int4> d_sx, d_sy;
-        std::vector<int4> sx, sy;     // (host copies while the geometry is being built)
-        bool ok = false;
-    } tp[2];
-    bool tiled4 = false;              // this geometry takes the two tile launches
+    DevBuf<int4> d_pyr_sx, d_pyr_sy;  // spans of k_pyramid_tiled
+    DevBuf<int4> d_tp_sx[2], d_tp_sy[2];   // spans of the two k_pyramid_tiled4 launches (geo.tp)
     DevBuf<int4> d_ytab;
     DevBuf<int> d_cell_cnt, d_cell_off;
     DevBuf<uint32_t> d_cell_items;
     DevBuf<SelKp> d_sel, d_sel_oct;
     DevBuf<uint32_t> d_cand_dev;
     DevBuf<int> d_level_cnt_dev, d_sel_cnt, d_oct_status, d_n_out;
-    bool pinned_ingest = false;       // page-locked host images are read by k_ingest directly (orbx_set_pinned_ingest) instead of hipMemcpy2DAsync
-    // level 0 in place (orbx_set_inplace_level0): l0_on = the geometry takes it (the large-rig tile launches) and the caller opted in;
-    // l0_active = the device table holds pointers of the last run's images; l0_host = what it holds (inspection hook)
-    bool l0_optin = false, l0_on = false, l0_active = false;
-    DevBuf<L0Src> d_l0;
-    std::vector<L0Src> l0_host;
-    std::vector<uint8_t> uploaded;    // cameras handed an image (any kind, also an empty one) since the last run
     int oct_max_keys = OCT_RK;        // candidates per (camera, level) the device quadtree takes (MORB_OCT_MAX_KEYS lowers it: tests of the fallback)
     int last_path = 0;                // inspection: 0 device quadtree, 2 host quadtree
     DevBuf<unsigned short> d_slot_blk;
-    int total_sel_slots = 0;
     int* h_oct = nullptr;            // pinned, mapped: [0..n_cams) n_out, [n_cams] status
     bool device_octree = true;
     bool cand_valid = false;         // h_cand / h_level_cnt hold the last run's candidates (k_compact ran)
-    // (in-flight bookkeeping: see `inflight` below), orbx_finish not yet called
     std::chrono::steady_clock::time_point t_begin_async;
-    // MORB_EXTRACT_TIMELINE=1: where the synchronous orbx_extract spends its host time (sums, printed by orbx_destroy)
     // up to two asynchronous runs may be in flight (the second one is the next timestep's, enqueued while the first one's
     // results are being matched): run r uses slot r & 1 of the count mirrors and of the completion events
-    struct ChainGraph {  // captured kernel chain of one count slot (see orbx_run_impl)
-        hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-        int epoch = -1; orb_keypoint* mirror_kps = nullptr; uint8_t* mirror_desc = nullptr; FrameSink sink; int tail_tag = 0;
-        void destroy() {
-            if (exec) (void)hipGraphExecDestroy(exec);
-            if (graph) (void)hipGraphDestroy(graph);
-            exec = nullptr; graph = nullptr; epoch = -1;
-        }
-    };
-    static constexpr int CHAIN_WAYS = 4;
-    ChainGraph chain[2][CHAIN_WAYS];
-    int chain_next[2] = {0, 0};      // replacement cursor per slot
-    bool use_graph = true;           // MORB_CHAIN_GRAPH=0 keeps plain launches
+    ChainCache chains;
     bool defer_done = false;      // orbx_set_defer_done: the caller records ev_done of the next asynchronous runs itself (orbx_record_done)
     bool graph_next_run = true;  // orbx_set_chain_graph: plain launches for the next run (its consumer follows on the same stream)
     orbx_tail_fn tail_fn = nullptr; void* tail_user = nullptr; int tail_tag = 0;  // orbx_set_chain_tail
     int geom_epoch = 0;              // bumped by every rebuild_geometry
-    int inflight = 0; unsigned run_seq = 0;
-    bool prof_valid[2] = {false, false};  // the stage events were recorded for the run in this slot
+    int inflight = 0; unsigned run_seq = 0;   // runs enqueued and not yet finished (orbx_finish); runs enqueued so far
     hipEvent_t ev_done[2] = {nullptr, nullptr};
     hipEvent_t ev_foreign = nullptr;   // orbx_wait_for_stream
     int* d_h_oct = nullptr;          // device alias of h_oct
@@ -2208,341 +2089,84 @@ struct orbx_extractor {
     std::vector<OctreeTask> tasks;
     std::unique_ptr<TaskPool> pool;
 
-    bool profiling = false;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    float stage_us[6] = {0, 0, 0, 0, 0, 0};
+    StageProfile prof;
 };
 
-static int rebuild_geometry(orbx_extractor* ex) {
-    const int ML = ex->max_levels;
-    ++ex->geom_epoch;  // captured launch chains carry the old geometry
-    ex->levels.assign((size_t)ex->n_cams * ML, LevelInfo{});
-    ex->cell_map.clear();
-    ex->cell_h_max = 1; ex->cell_px_max = 1;
-    std::vector<int2> xt;
-    std::vector<int4> yt, xg;
-    int cell_base = 0;
-    size_t slot_base = 0, cand_base = 0;
-    for (int c = 0; c < ex->n_cams; ++c) {
-        const CamTables& T = ex->cams[c];
-        const int W = ex->cur_w[c], H = ex->cur_h[c];
-        if (W == 0 || H == 0) continue;
-        int pyr_off = 0, pw = 0, ph = 0;
-        for (int l = 0; l < T.p.nlevels; ++l) {
-            LevelInfo& Lv = ex->levels[(size_t)c * ML + l];
-            const float s = T.inv_scale[l];
-            Lv.w = cv_round((double)((float)W * s));  // reference :1113-1114
-            Lv.h = cv_round((double)((float)H * s));
-            Lv.stride = align_up(Lv.w, 64);
-            Lv.pyr_off = pyr_off;
-            pyr_off += align_up(Lv.stride * Lv.h, 256);
-            Lv.ini_th = T.p.ini_th_fast; Lv.min_th = T.p.min_th_fast;
-            Lv.scale = T.scale[l];
-            Lv.patch_size = (float)(int)(PATCH_SIZE * T.scale[l]);  // :838
-            // cell grid, :774-788
-            const float width = (float)(Lv.w - 2 * MIN_BORDER), height = (float)(Lv.h - 2 * MIN_BORDER);
-            const int nCols = (int)(width / 30.f), nRows = (int)(height / 30.f);
-            if (nCols < 1 || nRows < 1) {
-                morb::set_error("camera %d level %d is %dx%d: too small for the 30-px detection grid", c, l, Lv.w, Lv.h);
-                return ORB_E_ARG;
-            }
-            Lv.n_cols = nCols; Lv.n_rows = nRows;
-            Lv.w_cell = (int)std::ceil(width / nCols);
-            Lv.h_cell = (int)std::ceil(height / nRows);
-            if (Lv.w_cell > CELL_MAX || Lv.h_cell > CELL_MAX || Lv.w > 4096 + 2 * MIN_BORDER || Lv.h > 4096 + 2 * MIN_BORDER) {
-                morb::set_error("camera %d level %d (%dx%d): cell %dx%d or level size outside the supported range", c, l,
-                                Lv.w, Lv.h, Lv.w_cell, Lv.h_cell);
-                return ORB_E_ARG;
-            }
-            ex->cell_h_max = std::max(ex->cell_h_max, Lv.h_cell); ex->cell_px_max = std::max(ex->cell_px_max, Lv.w_cell * Lv.h_cell);
-            Lv.quota = T.quota[l];
-            Lv.cell_base = cell_base;
-            Lv.slot_cap = ((Lv.w_cell + 1) / 2) * ((Lv.h_cell + 1) / 2);  // strict 8-neighbour maxima cannot be denser
-            Lv.slot_base = (int)slot_base;
-            Lv.cand_base = (int)cand_base;
-            const int ncell = nCols * nRows;
-            for (int k = 0; k < ncell; ++k)   // {block | cell column << 12 | cell row << 22, local cell index}
-                ex->cell_map.push_back(make_int2((c * ML + l) | ((k % Lv.n_cols) << 12) | ((k / Lv.n_cols) << 22), k));
-            cell_base += ncell;
-            slot_base += (size_t)ncell * Lv.slot_cap;
-            cand_base += (size_t)ncell * Lv.slot_cap;
-            if (l > 0) {
-                Lv.xtab_off = (int)xt.size(); Lv.ytab_off = (int)yt.size(); Lv.xgrp_off = (int)(xg.size() / 3);
-                build_resize_tables(pw, ph, Lv.w, Lv.h, xt, yt);
-                build_resize_groups(xt, Lv.xtab_off, Lv.w, xg);
-            }
-            pw = Lv.w; ph = Lv.h;
-        }
-        if ((size_t)pyr_off > ex->cam_pitch) { morb::set_error("image larger than the size given at create"); return ORB_E_ARG; }
-    }
-    // ---- spans of the tiled whole-pyramid launch (k_pyramid_tiled): tile k of a camera owns, on level l, the destination
-    // columns whose left source tap lies in what it owns on level l - 1 ([k T, (k + 1) T) on level 0), and needs them plus the
-    // taps of everything it needs one level down; rows alike.  Small rigs take 32-pixel tiles (more workgroups: the launch is
-    // one round of short workgroups), large ones 64 (less of the halo recomputed).
-    std::vector<int4> psx, psy;
-    {
-        long long px0 = 0;
-        for (int c = 0; c < ex->n_cams; ++c) px0 += (long long)ex->cur_w[c] * ex->cur_h[c];
-        const int T = px0 <= 1500000 ? 32 : 64;
-        ex->pyr_tile = T; ex->pyr_tx_max = 1; ex->pyr_ty_max = 1; ex->pyr_lds = 0; ex->pyr_tab_cap = 0;
-        bool halo_ok = true;
-        for (int c = 0; c < ex->n_cams; ++c) {
-            ex->pyr_tx[c] = (short)((ex->cur_w[c] + T - 1) / T); ex->pyr_ty[c] = (short)((ex->cur_h[c] + T - 1) / T);
-            ex->pyr_tx_max = std::max<int>(ex->pyr_tx_max, ex->pyr_tx[c]); ex->pyr_ty_max = std::max<int>(ex->pyr_ty_max, ex->pyr_ty[c]);
-        }
-        psx.assign((size_t)ex->n_cams * ML * ex->pyr_tx_max, make_int4(0, 0, 0, 0));
-        psy.assign((size_t)ex->n_cams * ML * ex->pyr_ty_max, make_int4(0, 0, 0, 0));
-        // one axis: dims[l], first / last source index of destination d on level l (l >= 1)
-        auto axis = [&](int c, int ntiles, int tmax, bool is_x, std::vector<int4>& out) {
-            const int NL = ex->cams[c].p.nlevels;
-            auto dim = [&](int l) { const LevelInfo& Lv = ex->levels[(size_t)c * ML + l]; return is_x ? Lv.w : Lv.h; };
-            auto s0 = [&](int l, int d) { const LevelInfo& Lv = ex->levels[(size_t)c * ML + l]; return is_x ? (xt[Lv.xtab_off + d].x & 0xffff) : yt[Lv.ytab_off + d].x; };
-            auto s1 = [&](int l, int d) { const LevelInfo& Lv = ex->levels[(size_t)c * ML + l]; return is_x ? (int)((unsigned)xt[Lv.xtab_off + d].x >> 16) : yt[Lv.ytab_off + d].y; };
-            std::vector<std::vector<int> > b(NL, std::vector<int>(ntiles + 1, 0));
-            for (int k = 0; k <= ntiles; ++k) b[0][k] = std::min(k * T, dim(0));
-            for (int l = 1; l < NL; ++l) {
-                int d = 0;
-                for (int k = 0; k <= ntiles; ++k) {   // first destination whose left tap is not in front of the boundary
-                    while (d < dim(l) && s0(l, d) < b[l - 1][k]) ++d;
-                    b[l][k] = k == ntiles ? dim(l) : d;
-                }
-            }
-            for (int k = 0; k < ntiles; ++k) {
-                int n1 = b[NL - 1][k + 1];
-                for (int l = NL - 1; l >= 0; --l) {
-                    const int nn = n1 - b[l][k];   // .w: 2^20 / needed extent, rounded up (index / extent by multiplication in the kernel)
-                    out[((size_t)c * ML + l) * tmax + k] = make_int4(b[l][k], b[l][k + 1], n1, nn > 0 ? (int)(((1u << 20) + nn - 1) / nn) : 0);
-                    if (l > 0) n1 = std::max(b[l - 1][k + 1], n1 > b[l][k] ? s1(l, n1 - 1) + 1 : b[l - 1][k]);
-                }
-            }
-        };
-        for (int c = 0; c < ex->n_cams; ++c) {
-            if (ex->cur_w[c] == 0 || ex->cur_h[c] == 0) { ex->pyr_tx[c] = ex->pyr_ty[c] = 0; continue; }
-            axis(c, ex->pyr_tx[c], ex->pyr_tx_max, true, psx);
-            axis(c, ex->pyr_ty[c], ex->pyr_ty_max, false, psy);
-            for (int ky = 0; ky < ex->pyr_ty[c]; ++ky)
-                for (int kx = 0; kx < ex->pyr_tx[c]; ++kx) {
-                    int bytes = 0, tx_n = 0, ty_n = 0;
-                    for (int l = 0; l < ex->cams[c].p.nlevels; ++l) {
-                        const int4 X = psx[((size_t)c * ML + l) * ex->pyr_tx_max + kx], Y = psy[((size_t)c * ML + l) * ex->pyr_ty_max + ky];
-                        if (l == 0) {   // the kernel stages a fixed (T + halo)^2 block of level 0: what the tile needs must lie inside it
-                            bytes += (T + PYR_HALO) * (T + PYR_HALO);
-                            if (X.z - X.x > T + PYR_HALO || Y.z - Y.x > T + PYR_HALO) halo_ok = false;
-                            continue;
-                        }
-                        bytes += ((std::max(X.z - X.x, 0) + 3) & ~3) * std::max(Y.z - Y.x, 0);
-                        tx_n += std::max(X.z - X.x, 0); ty_n += std::max(Y.z - Y.x, 0);
-                    }
-                    ex->pyr_lds = std::max(ex->pyr_lds, bytes);
-                    ex->pyr_tab_cap = std::max(ex->pyr_tab_cap, std::max(tx_n, ty_n));
-                }
-        }
-        ex->pyr_tab_cap = (ex->pyr_tab_cap + 3) & ~3;
-        ex->pyr_lds += ex->pyr_tab_cap * 24;   // the table entries of a tile's columns (int2) and rows (int4) in front of the regions
-        ex->tiled_ok = !(ex->pyr_lds > 60 * 1024 || ML > PYR_MAX_LEVELS || !halo_ok || ex->max_w > 32767 || ex->max_h > 32767);   // (cannot happen for tiles of 64 and scale factors >= 1.05)
-        // Large rigs take two tile launches with four pixels per lane instead (k_pyramid_tiled4 below): the one-launch tile kernel is a
-        // latency design and costs three times the instructions per pixel.  Their arithmetic needs level steps of at most 1.6 (the taps of
-        // four neighbouring pixels within 8 bytes).  MORB_PYR_CHAIN: 1 = the large-rig form at every size, 2 = neither tile form (the
-        // generic one-launch-per-level chain, k_resize: what odd parameter sets fall back to), 0 = never the large-rig form; default: the
-        // large-rig form above 4 M level-0 pixels over all cameras (8 x 1080p yes, 2 x 1280x720 no).
-        ex->v4_ok = true;
-        for (int c = 0; c < ex->n_cams && ex->v4_ok; ++c)
-            for (int l = 1; l < ex->cams[c].p.nlevels; ++l) {
-                const LevelInfo &Ls = ex->levels[(size_t)c * ML + l - 1], &Ld = ex->levels[(size_t)c * ML + l];
-                if (Ld.w > 0 && (long long)Ls.w * 10 > (long long)Ld.w * 16) ex->v4_ok = false;
-            }
-        static const int chain_env = [] { const char* e = getenv("MORB_PYR_CHAIN"); return e ? atoi(e) : -1; }();
-        ex->generic_chain = chain_env == 2;
-        const bool prefer_large = ex->v4_ok && (chain_env == 1 || (chain_env < 0 && (long long)px0 > 4000000ll));
-        if (prefer_large || ex->generic_chain) ex->tiled_ok = false;
-    }
-    // ---- large rigs: the two tile launches of k_pyramid_tiled4 (TilePlan).  Along x a tile owns whole groups of four destination
-    // columns (the group whose first tap lies in what the tile owns one level up), along y rows by their upper tap; what it needs
-    // beyond that is the taps of everything it needs one level down (rounded up to whole groups below the base).
-    ex->tiled4 = false;
-    {
-        // tile 128 x 64 below level 0 and below the split level 3, 256 threads (orbx_debug_pyramid_plan: other tiles / another split, for
-        // the tests of the plan's geometry)
-        const int split_env = g_t4_plan[2], tw_env = g_t4_plan[0], th_env = g_t4_plan[1], tw1_env = 0, th1_env = 0, nt0_env = 256, nt1_env = 256;
-        int nl_max = 0;
-        for (int c = 0; c < ex->n_cams; ++c) nl_max = std::max(nl_max, ex->cams[c].p.nlevels);
-        const bool want = ex->v4_ok && !ex->tiled_ok && !ex->generic_chain && nl_max >= 2 && ML <= PYR_MAX_LEVELS &&
-                          tw_env >= 16 && tw_env % 4 == 0 && th_env >= 8 && ex->max_w <= 32767 && ex->max_h <= 32767;
-        const int split = std::min(std::max(split_env, 1), nl_max - 1);
-        bool all_ok = want;
-        for (int pi = 0; pi < 2 && all_ok; ++pi) {
-            orbx_extractor::TilePlan& P = ex->tp[pi];
-            P.ok = false;
-            P.base = pi == 0 ? 0 : split; P.last = pi == 0 ? split : nl_max - 1;
-            if (P.last <= P.base) { P.ok = true; P.tx_max = P.ty_max = 0; continue; }   // (nothing left for the second launch)
-            P.tw = pi == 1 && tw1_env >= 16 && tw1_env % 4 == 0 ? tw1_env : tw_env; P.th = pi == 1 && th1_env >= 8 ? th1_env : th_env; P.halo_x = 16; P.halo_y = 16;
-            P.threads = (pi == 0 ? nt0_env : nt1_env) == 512 ? 512 : 256;
-            P.tx_max = P.ty_max = 1; P.gcap = P.rcap = 0; P.lds = 0;
-            for (int c = 0; c < ex->n_cams; ++c) {
-                const LevelInfo& Lb = ex->levels[(size_t)c * ML + P.base];
-                P.tx[c] = (short)(Lb.w > 0 ? (Lb.w + P.tw - 1) / P.tw : 0); P.ty[c] = (short)(Lb.w > 0 ? (Lb.h + P.th - 1) / P.th : 0);
-                P.tx_max = std::max<int>(P.tx_max, P.tx[c]); P.ty_max = std::max<int>(P.ty_max, P.ty[c]);
-            }
-            P.sx.assign((size_t)ex->n_cams * ML * P.tx_max, make_int4(0, 0, 0, 0));
-            P.sy.assign((size_t)ex->n_cams * ML * P.ty_max, make_int4(0, 0, 0, 0));
-            bool ok = true;
-            int need_x = P.tw, need_y = P.th;   // what a tile needs of the base level, at most (the staged block: tile + halo)
-            for (int c = 0; c < ex->n_cams && ok; ++c) {
-                if (P.tx[c] == 0) continue;
-                const int NL = std::min(ex->cams[c].p.nlevels - 1, P.last);   // last level this camera has inside the plan
-                auto LV = [&](int l) -> const LevelInfo& { return ex->levels[(size_t)c * ML + l]; };
-                // x: boundaries in pixels, multiples of four below the base
-                {
-                    const int nt = P.tx[c];
-                    std::vector<std::vector<int> > b(ML, std::vector<int>(nt + 1, 0));
-                    for (int k = 0; k <= nt; ++k) b[P.base][k] = std::min(k * P.tw, LV(P.base).w);
-                    for (int l = P.base + 1; l <= NL; ++l) {
-                        const int G = (LV(l).w + 3) / 4;
-                        int g = 0;
-                        for (int k = 0; k <= nt; ++k) {
-                            while (g < G && (xt[LV(l).xtab_off + 4 * g].x & 0xffff) < b[l - 1][k]) ++g;
-                            b[l][k] = k == nt ? 4 * G : 4 * g;
-                        }
-                    }
-                    for (int k = 0; k < nt; ++k) {
-                        int n1 = b[NL][k + 1];
-                        for (int l = NL; l >= P.base; --l) {
-                            const int ngn = l > P.base ? std::max(n1 - b[l][k], 0) / 4 : 0;
-                            P.sx[((size_t)c * ML + l) * P.tx_max + k] = make_int4(b[l][k], b[l][k + 1], n1, ngn > 0 ? (int)(((1u << 20) + ngn - 1) / ngn) : 0);
-                            if (l == P.base) { need_x = std::max(need_x, n1 - b[l][k]); break; }
-                            // what level l - 1 must hold: its own run, and the right tap of the last column this level needs (padding
-                            // columns repeat the level's last one)
-                            int up = b[l - 1][k + 1];
-                            if (n1 > b[l][k]) up = std::max(up, (int)((unsigned)xt[LV(l).xtab_off + std::min(n1 - 1, LV(l).w - 1)].x >> 16) + 1);
-                            n1 = l - 1 > P.base ? std::min((up + 3) & ~3, 4 * ((LV(l - 1).w + 3) / 4)) : up;
-                        }
-                    }
-                }
-                // y: rows
-                {
-                    const int nt = P.ty[c];
-                    std::vector<std::vector<int> > b(ML, std::vector<int>(nt + 1, 0));
-                    for (int k = 0; k <= nt; ++k) b[P.base][k] = std::min(k * P.th, LV(P.base).h);
-                    for (int l = P.base + 1; l <= NL; ++l) {
-                        int d = 0;
-                        for (int k = 0; k <= nt; ++k) {
-                            while (d < LV(l).h && yt[LV(l).ytab_off + d].x < b[l - 1][k]) ++d;
-                            b[l][k] = k == nt ? LV(l).h : d;
-                        }
-                    }
-                    for (int k = 0; k < nt; ++k) {
-                        int n1 = b[NL][k + 1];
-                        for (int l = NL; l >= P.base; --l) {
-                            P.sy[((size_t)c * ML + l) * P.ty_max + k] = make_int4(b[l][k], b[l][k + 1], n1, 0);
-                            if (l == P.base) { need_y = std::max(need_y, n1 - b[l][k]); break; }
-                            int up = b[l - 1][k + 1];
-                            if (n1 > b[l][k]) up = std::max(up, yt[LV(l).ytab_off + n1 - 1].y + 1);
-                            n1 = up;
-                        }
-                    }
-                }
-            }
-            P.halo_x = ((need_x - P.tw + 3) & ~3); P.halo_y = need_y - P.th;
-            // what a workgroup holds in LDS: the staged base block, the regions of its levels, the table entries of their groups and rows
-            for (int c = 0; c < ex->n_cams && ok; ++c) {
-                if (P.tx[c] == 0) continue;
-                const int NL = std::min(ex->cams[c].p.nlevels - 1, P.last);
-                for (int ky = 0; ky < P.ty[c]; ++ky)
-                    for (int kx = 0; kx < P.tx[c]; ++kx) {
-                        int bytes = (P.tw + P.halo_x) * (P.th + P.halo_y), ng = 0, nr = 0;
-                        for (int l = P.base + 1; l <= NL; ++l) {
-                            const int4 X = P.sx[((size_t)c * ML + l) * P.tx_max + kx], Y = P.sy[((size_t)c * ML + l) * P.ty_max + ky];
-                            const int w = std::max(X.z - X.x, 0), h = std::max(Y.z - Y.x, 0);
-                            if ((long long)(w / 4) * h * (w / 4) >= (1 << 20)) ok = false;   // (index split by multiplication: tasks x groups < 2^20)
-                            bytes += w * h; ng += w / 4; nr += h;
-                        }
-                        P.lds = std::max(P.lds, bytes); P.gcap = std::max(P.gcap, ng); P.rcap = std::max(P.rcap, nr);
-                    }
-            }
-            P.gcap = std::max(P.gcap, 1); P.rcap = std::max(P.rcap, 1);
-            P.lds += P.gcap * 48 + P.rcap * 16 + 32;
-            if (P.lds > 64 * 1024 || (P.tw + P.halo_x) / 4 * (P.th + P.halo_y) > T4_MAX_DW * P.threads || (P.halo_x & 3)) ok = false;
-            P.ok = ok;
-            all_ok = all_ok && ok;
-        }
-        ex->tiled4 = all_ok;
-    }
-    {
-        // level 0 is read where the caller's device image lies (orbx_set_inplace_level0) by the large-rig tile launches only: they take
-        // the {pointer, pitch} table; the one-launch tile kernel of small rigs and the generic chain read the pyramid buffer
-        ex->l0_on = ex->l0_optin && ex->tiled4;
-    }
-    if (slot_base > (size_t)INT32_MAX) { morb::set_error("candidate slot space exceeds 2^31 entries"); return ORB_E_ARG; }
-    ex->total_cells = cell_base;
-    ex->total_slots = slot_base;
-    // slotted output list of the device quadtree: quota + 4 slots per (camera, level)
-    std::vector<unsigned short> slot_blk;
-    for (size_t b = 0; b < ex->levels.size(); ++b) {
-        LevelInfo& Lv = ex->levels[b];
-        Lv.sel_base = (int)slot_blk.size();
-        if (Lv.w == 0) continue;
-        for (int k = 0; k < Lv.quota + 4; ++k) slot_blk.push_back((unsigned short)b);
-    }
-    ex->total_sel_slots = (int)slot_blk.size();
-    int rc;
-    if ((rc = ex->d_levels.reserve(ex->levels.size())) || (rc = ex->d_cell_map.reserve(std::max<size_t>(ex->cell_map.size(), 1))) ||
-        (rc = ex->d_xtab.reserve(std::max<size_t>(xt.size(), 1))) || (rc = ex->d_ytab.reserve(std::max<size_t>(yt.size(), 1))) ||
-        (rc = ex->d_xgrp.reserve(std::max<size_t>(xg.size(), 1))) ||
-        (rc = ex->d_pyr_sx.reserve(std::max<size_t>(psx.size(), 1))) || (rc = ex->d_pyr_sy.reserve(std::max<size_t>(psy.size(), 1))) ||
-        (rc = ex->d_cell_cnt.reserve(std::max(cell_base, 1))) || (rc = ex->d_cell_off.reserve(std::max(cell_base, 1))) ||
-        (rc = ex->d_cell_items.reserve(std::max<size_t>(slot_base, 1))) || (rc = ex->d_cand_dev.reserve(std::max<size_t>(slot_base, 1))) ||
-        (rc = ex->d_level_cnt_dev.reserve(ex->levels.size())) || (rc = ex->d_sel_cnt.reserve(ex->levels.size())) ||
-        (rc = ex->d_oct_status.reserve(ex->levels.size())) ||
-        (rc = ex->d_n_out.reserve(2 * (ex->n_cams + 1))) ||
-        (rc = ex->d_sel_oct.reserve(std::max<size_t>(slot_blk.size(), 1))) || (rc = ex->d_slot_blk.reserve(std::max<size_t>(slot_blk.size(), 1))))
-        return rc;
-    if (!slot_blk.empty())
-        MORB_HIP(hipMemcpyAsync(ex->d_slot_blk.p, slot_blk.data(), slot_blk.size() * sizeof(unsigned short), hipMemcpyHostToDevice, ex->stream));
-    // (the level-0 table starts empty with every geometry: level 0 is in the pyramid buffer until a run says otherwise)
-    if ((rc = ex->d_l0.reserve(64))) return rc;
-    MORB_HIP(hipMemsetAsync(ex->d_l0.p, 0, 64 * sizeof(L0Src), ex->stream));
-    ex->l0_host.assign(64, L0Src{nullptr, 0, 0});
-    ex->l0_active = false;
-    if (slot_base > ex->h_cand_cap) {
-        if (ex->h_cand) (void)hipHostFree(ex->h_cand);
-        ex->h_cand = nullptr; ex->h_cand_cap = 0;
-        MORB_HIP(hipHostMalloc((void**)&ex->h_cand, slot_base * sizeof(uint32_t), hipHostMallocMapped));
-        ex->h_cand_cap = slot_base;
-    }
-    MORB_HIP(hipMemcpyAsync(ex->d_levels.p, ex->levels.data(), ex->levels.size() * sizeof(LevelInfo), hipMemcpyHostToDevice, ex->stream));
-    if (!ex->cell_map.empty())
-        MORB_HIP(hipMemcpyAsync(ex->d_cell_map.p, ex->cell_map.data(), ex->cell_map.size() * sizeof(int2), hipMemcpyHostToDevice, ex->stream));
-    if (!xt.empty()) MORB_HIP(hipMemcpyAsync(ex->d_xtab.p, xt.data(), xt.size() * sizeof(int2), hipMemcpyHostToDevice, ex->stream));
-    if (!xg.empty()) MORB_HIP(hipMemcpyAsync(ex->d_xgrp.p, xg.data(), xg.size() * sizeof(int4), hipMemcpyHostToDevice, ex->stream));
-    {
-        static constexpr DescribeTables k_tabs = DescribeTables();   // (compile-time; the copy below is synchronised with the others)
-        int rc_t = ex->d_desc_tabs.reserve(sizeof(DescribeTables));
-        if (rc_t) return rc_t;
-        MORB_HIP(hipMemcpyAsync(ex->d_desc_tabs.p, &k_tabs, sizeof(DescribeTables), hipMemcpyHostToDevice, ex->stream));
-    }
-    if (!yt.empty()) MORB_HIP(hipMemcpyAsync(ex->d_ytab.p, yt.data(), yt.size() * sizeof(int4), hipMemcpyHostToDevice, ex->stream));
-    if (!psx.empty()) MORB_HIP(hipMemcpyAsync(ex->d_pyr_sx.p, psx.data(), psx.size() * sizeof(int4), hipMemcpyHostToDevice, ex->stream));
-    if (!psy.empty()) MORB_HIP(hipMemcpyAsync(ex->d_pyr_sy.p, psy.data(), psy.size() * sizeof(int4), hipMemcpyHostToDevice, ex->stream));
-    for (int pi = 0; pi < 2 && ex->tiled4; ++pi) {
-        orbx_extractor::TilePlan& P = ex->tp[pi];
-        if (P.sx.empty() || P.sy.empty()) continue;
-        int rc_p;
-        if ((rc_p = P.d_sx.reserve(P.sx.size())) || (rc_p = P.d_sy.reserve(P.sy.size()))) return rc_p;
-        MORB_HIP(hipMemcpyAsync(P.d_sx.p, P.sx.data(), P.sx.size() * sizeof(int4), hipMemcpyHostToDevice, ex->stream));
-        MORB_HIP(hipMemcpyAsync(P.d_sy.p, P.sy.data(), P.sy.size() * sizeof(int4), hipMemcpyHostToDevice, ex->stream));
-    }
-    MORB_HIP(hipStreamSynchronize(ex->stream));  // xt / yt are locals
-    ex->tables_dirty = false;
+// The planner's tables go to the device as they are: its plain structs have the layout of the kernels' int2 / int4.
+static_assert(sizeof(plan_int2) == sizeof(int2) && sizeof(plan_int4) == sizeof(int4), "planner tables must match the device vector types");
+template <typename D, typename H>
+static int upload_table(DevBuf<D>& dst, const std::vector<H>& src, hipStream_t st) {
+    static_assert(sizeof(D) == sizeof(H), "host and device element differ in size");
+    if (!src.empty()) MORB_HIP(hipMemcpyAsync(dst.p, src.data(), src.size() * sizeof(H), hipMemcpyHostToDevice, st));
     return ORB_OK;
 }
 
-static size_t pyramid_bytes(const CamTables& T, int W, int H) {
-    size_t off = 0;
-    for (int l = 0; l < T.p.nlevels; ++l) {
-        const int w = cv_round((double)((float)W * T.inv_scale[l])), h = cv_round((double)((float)H * T.inv_scale[l]));
-        off += (size_t)align_up(align_up(w, 64) * h, 256);
+static int reserve_geometry(orbx_extractor* ex) {
+    const GeometryPlan& G = ex->geo;
+    const size_t cells = std::max(G.total_cells, 1), slots = std::max<size_t>(G.total_slots, 1), sel = std::max<size_t>(G.slot_blk.size(), 1);
+    int rc;
+    if ((rc = ex->d_levels.reserve(G.levels.size())) || (rc = ex->d_cell_map.reserve(std::max<size_t>(G.cell_map.size(), 1))) ||
+        (rc = ex->d_xtab.reserve(std::max<size_t>(G.xt.size(), 1))) || (rc = ex->d_ytab.reserve(std::max<size_t>(G.yt.size(), 1))) ||
+        (rc = ex->d_xgrp.reserve(std::max<size_t>(G.xg.size(), 1))) ||
+        (rc = ex->d_pyr_sx.reserve(std::max<size_t>(G.psx.size(), 1))) || (rc = ex->d_pyr_sy.reserve(std::max<size_t>(G.psy.size(), 1))) ||
+        (rc = ex->d_cell_cnt.reserve(cells)) || (rc = ex->d_cell_off.reserve(cells)) ||
+        (rc = ex->d_cell_items.reserve(slots)) || (rc = ex->d_cand_dev.reserve(slots)) ||
+        (rc = ex->d_level_cnt_dev.reserve(G.levels.size())) || (rc = ex->d_sel_cnt.reserve(G.levels.size())) ||
+        (rc = ex->d_oct_status.reserve(G.levels.size())) ||
+        (rc = ex->d_n_out.reserve(2 * (ex->n_cams + 1))) ||
+        (rc = ex->d_sel_oct.reserve(sel)) || (rc = ex->d_slot_blk.reserve(sel)))
+        return rc;
+    return ORB_OK;
+}
+
+static int upload_geometry(orbx_extractor* ex) {
+    const GeometryPlan& G = ex->geo;
+    hipStream_t st = ex->stream;
+    int rc;
+    if ((rc = upload_table(ex->d_slot_blk, G.slot_blk, st))) return rc;
+    // (the level-0 table starts empty with every geometry: level 0 is in the pyramid buffer until a run says otherwise)
+    if ((rc = ex->l0.d_tab.reserve(64))) return rc;
+    MORB_HIP(hipMemsetAsync(ex->l0.d_tab.p, 0, 64 * sizeof(L0Src), st));
+    ex->l0.tab.assign(64, L0Src{nullptr, 0, 0});
+    ex->l0.active = false;
+    if (G.total_slots > ex->h_cand_cap) {
+        if (ex->h_cand) (void)hipHostFree(ex->h_cand);
+        ex->h_cand = nullptr; ex->h_cand_cap = 0;
+        MORB_HIP(hipHostMalloc((void**)&ex->h_cand, G.total_slots * sizeof(uint32_t), hipHostMallocMapped));
+        ex->h_cand_cap = G.total_slots;
     }
-    return off;
+    MORB_HIP(hipMemcpyAsync(ex->d_levels.p, G.levels.data(), G.levels.size() * sizeof(LevelInfo), hipMemcpyHostToDevice, st));
+    if ((rc = upload_table(ex->d_cell_map, G.cell_map, st)) || (rc = upload_table(ex->d_xtab, G.xt, st)) || (rc = upload_table(ex->d_xgrp, G.xg, st))) return rc;
+    {
+        static constexpr DescribeTables k_tabs = DescribeTables();   // (compile-time; the copy below is synchronised with the others)
+        if ((rc = ex->d_desc_tabs.reserve(sizeof(DescribeTables)))) return rc;
+        MORB_HIP(hipMemcpyAsync(ex->d_desc_tabs.p, &k_tabs, sizeof(DescribeTables), hipMemcpyHostToDevice, st));
+    }
+    if ((rc = upload_table(ex->d_ytab, G.yt, st)) || (rc = upload_table(ex->d_pyr_sx, G.psx, st)) || (rc = upload_table(ex->d_pyr_sy, G.psy, st))) return rc;
+    for (int pi = 0; pi < 2 && G.tiled4; ++pi) {
+        const TilePlan& P = G.tp[pi];
+        if (P.sx.empty() || P.sy.empty()) continue;
+        if ((rc = ex->d_tp_sx[pi].reserve(P.sx.size())) || (rc = ex->d_tp_sy[pi].reserve(P.sy.size()))) return rc;
+        if ((rc = upload_table(ex->d_tp_sx[pi], P.sx, st)) || (rc = upload_table(ex->d_tp_sy[pi], P.sy, st))) return rc;
+    }
+    MORB_HIP(hipStreamSynchronize(st));  // the copies read the plan's host vectors
+    return ORB_OK;
+}
+
+static int rebuild_geometry(orbx_extractor* ex) {
+    ++ex->geom_epoch;  // captured launch chains carry the old geometry
+    static const int chain_env = [] { const char* e = getenv("MORB_PYR_CHAIN"); return e ? atoi(e) : -1; }();
+    PlanInput in;
+    in.cams = ex->cams.data(); in.cur_w = ex->cur_w.data(); in.cur_h = ex->cur_h.data();
+    in.n_cams = ex->n_cams; in.max_levels = ex->max_levels; in.max_w = ex->max_w; in.max_h = ex->max_h; in.cam_pitch = ex->cam_pitch;
+    in.l0_optin = ex->l0.optin; in.pyr_chain = chain_env;
+    for (int i = 0; i < 3; ++i) in.t4_plan[i] = g_t4_plan[i];
+    std::string why;
+    int rc;
+    if ((rc = plan_geometry(in, ex->geo, &why))) { morb::set_error("%s", why.c_str()); return rc; }
+    if ((rc = reserve_geometry(ex)) || (rc = upload_geometry(ex))) return rc;
+    ex->tables_dirty = false;
+    return ORB_OK;
 }
 
 extern "C" {
@@ -2584,6 +2208,9 @@ int orbx_create(const orbx_params* params, int n_cams, int max_width, int max_he
     // are then free for the matcher's stream -- whose resolve is ONE workgroup that otherwise shares its CU with extraction waves.
     // Measured (round 6, profiles/r06/notes_experiments.md section 10): 4 x 640x480 overlapped 15 200 -> 17 900-18 600 steps/s with k = 4,
     // 2 x 640x480 and 2 x 1280x720 unchanged or slightly worse, 8 x 1080p 9 % worse, every isolated step 3-6 % slower: a tunable.
+    // The masked stream is a BLOCKING stream (hipExtStreamCreateWithCUMask takes no flags; the default below is hipStreamNonBlocking):
+    // it orders against every legacy null-stream call in the process -- a hipMemset / hipMemcpy without a stream waits for it and
+    // holds it back.
     if (const char* rs = getenv("MORB_RESERVE_CUS"); rs && atoi(rs) != 0) {
         const int k = std::max(0, atoi(rs));   // (negative: a masked queue with every unit allowed -- what the mask itself costs or buys)
         uint32_t mask[8];
@@ -2595,7 +2222,7 @@ int orbx_create(const orbx_params* params, int n_cams, int max_width, int max_he
     if (e != hipSuccess) { morb::set_error("hipStreamCreate: %s", hipGetErrorString(e)); delete ex; return ORB_E_HIP; }
     ex->cams.resize(n_cams);
     ex->cur_w.assign(n_cams, 0); ex->cur_h.assign(n_cams, 0);
-    memset(&ex->ingest, 0, sizeof(ex->ingest));
+    memset(&ex->l0.ingest, 0, sizeof(ex->l0.ingest));
     memset(&ex->sink, 0, sizeof(ex->sink));
     ex->n_out.assign(n_cams, 0);
     ex->d_kps.resize(n_cams); ex->d_desc.resize(n_cams);
@@ -2628,13 +2255,13 @@ int orbx_create(const orbx_params* params, int n_cams, int max_width, int max_he
     ORBX_TRY_HIP(hipHostGetDevicePointer((void**)&ex->d_h_oct, ex->h_oct, 0));
     for (int i = 0; i < 2; ++i) ORBX_TRY_HIP(hipEventCreateWithFlags(&ex->ev_done[i], hipEventDisableTiming | hipEventReleaseToSystem));
     { const char* e = getenv("MORB_HOST_OCTREE"); ex->device_octree = !(e && atoi(e) != 0); }
-    { const char* e = getenv("MORB_CHAIN_GRAPH"); ex->use_graph = !(e && atoi(e) == 0); }
+    { const char* e = getenv("MORB_CHAIN_GRAPH"); ex->chains.use_graph = !(e && atoi(e) == 0); }
     if (const char* e = getenv("MORB_OCT_MAX_KEYS")) ex->oct_max_keys = std::min(OCT_RK, std::max(1, atoi(e)));
     ORBX_TRY_HIP(hipFuncSetAttribute((const void*)k_octree, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(OctLdsR)));
-    for (int i = 0; i < 6; ++i) ORBX_TRY_HIP(hipEventCreate(&ex->ev[i]));
+    for (int i = 0; i < 6; ++i) ORBX_TRY_HIP(hipEventCreate(&ex->prof.ev[i]));
     ex->level_cnt_last.assign((size_t)n_cams * ex->max_levels, 0);
-    ex->uploaded.assign(n_cams, 0);
-    ex->l0_host.assign(64, L0Src{nullptr, 0, 0});
+    ex->l0.uploaded.assign(n_cams, 0);
+    ex->l0.tab.assign(64, L0Src{nullptr, 0, 0});
     {   // host quadtree fallback: four threads (the calling one works too)
         const int hw = (int)std::thread::hardware_concurrency();
         ex->pool.reset(new TaskPool(std::max(1, std::min(4, hw > 1 ? hw : 1)) - 1));
@@ -2647,9 +2274,9 @@ void orbx_destroy(orbx_extractor* ex) {
     if (!ex) return;
     (void)hipSetDevice(ex->device);
     if (ex->stream) (void)hipStreamSynchronize(ex->stream);
-    for (int sl = 0; sl < 2; ++sl) for (int w = 0; w < orbx_extractor::CHAIN_WAYS; ++w) ex->chain[sl][w].destroy();
-    ex->d_l0.release(); ex->d_pyr.release(); ex->d_levels.release(); ex->d_cell_map.release(); ex->d_xtab.release(); ex->d_xgrp.release(); ex->d_desc_tabs.release(); ex->d_ytab.release(); ex->d_pyr_sx.release(); ex->d_pyr_sy.release();
-    for (auto& P : ex->tp) { P.d_sx.release(); P.d_sy.release(); }
+    for (int sl = 0; sl < 2; ++sl) for (int w = 0; w < CHAIN_WAYS; ++w) ex->chains.way[sl][w].destroy();
+    ex->l0.d_tab.release(); ex->d_pyr.release(); ex->d_levels.release(); ex->d_cell_map.release(); ex->d_xtab.release(); ex->d_xgrp.release(); ex->d_desc_tabs.release(); ex->d_ytab.release(); ex->d_pyr_sx.release(); ex->d_pyr_sy.release();
+    for (int pi = 0; pi < 2; ++pi) { ex->d_tp_sx[pi].release(); ex->d_tp_sy[pi].release(); }
     ex->d_cell_cnt.release(); ex->d_cell_off.release(); ex->d_cell_items.release(); ex->d_sel.release(); ex->d_sel_oct.release();
     ex->d_cand_dev.release(); ex->d_level_cnt_dev.release(); ex->d_sel_cnt.release(); ex->d_oct_status.release();
     ex->d_n_out.release(); ex->d_slot_blk.release();
@@ -2663,7 +2290,7 @@ void orbx_destroy(orbx_extractor* ex) {
     if (ex->h_oct) (void)hipHostFree(ex->h_oct);
     for (int i = 0; i < 2; ++i) if (ex->ev_done[i]) (void)hipEventDestroy(ex->ev_done[i]);
     if (ex->ev_foreign) (void)hipEventDestroy(ex->ev_foreign);
-    for (int i = 0; i < 6; ++i) if (ex->ev[i]) (void)hipEventDestroy(ex->ev[i]);
+    for (int i = 0; i < 6; ++i) if (ex->prof.ev[i]) (void)hipEventDestroy(ex->prof.ev[i]);
     if (ex->stream && ex->stream_owned) (void)hipStreamDestroy(ex->stream);
     delete ex;
 }
@@ -2684,10 +2311,10 @@ int orbx_wait_for_stream(orbx_extractor* ex, void* other_stream) {
 static int upload_common(orbx_extractor* ex, int cam, const uint8_t* src, int width, int height, int stride, hipMemcpyKind kind) {
     MORB_ARG(ex && cam >= 0 && cam < ex->n_cams);
     MORB_HIP(hipSetDevice(ex->device));
-    ex->uploaded[cam] = 1;
+    ex->l0.uploaded[cam] = 1;
     if (!src || width <= 0 || height <= 0) {  // empty image: camera produces nothing (reference :1047-1048)
         if (ex->cur_w[cam] != 0) { ex->cur_w[cam] = ex->cur_h[cam] = 0; ex->tables_dirty = true; }
-        ex->ingest.src[cam] = nullptr;
+        ex->l0.ingest.src[cam] = nullptr;
         return ORB_OK;
     }
     MORB_ARG(width <= ex->max_w && height <= ex->max_h && stride >= width);
@@ -2697,7 +2324,7 @@ static int upload_common(orbx_extractor* ex, int cam, const uint8_t* src, int wi
     }
     // level 0 lives at offset 0 of the camera's pyramid buffer with pitch align64(width)
     if (kind == hipMemcpyDeviceToDevice) {  // copied by k_ingest at the start of the run, all cameras in one launch
-        ex->ingest.src[cam] = src; ex->ingest.stride[cam] = stride; ex->ingest_pending = true;
+        ex->l0.ingest.src[cam] = src; ex->l0.ingest.stride[cam] = stride; ex->l0.pending = true;
         return ORB_OK;
     }
     // A host image in pageable memory (a cv::Mat): the runtime would stage it through an internal pinned buffer and a DMA of
@@ -2717,20 +2344,20 @@ static int upload_common(orbx_extractor* ex, int cam, const uint8_t* src, int wi
             if (stride == width) memcpy(d, src, (size_t)width * height);
             else for (int y = 0; y < height; ++y) memcpy(d + (size_t)y * width, src + (size_t)y * stride, width);
             S.publish();
-            ex->ingest.src[cam] = S.dp + per_cam * cam; ex->ingest.stride[cam] = width; ex->ingest_pending = true;
-            if (!S.in_hbm) ex->ingest_host = true;
+            ex->l0.ingest.src[cam] = S.dp + per_cam * cam; ex->l0.ingest.stride[cam] = width; ex->l0.pending = true;
+            if (!S.in_hbm) ex->l0.host = true;
             return ORB_OK;
         }
     }
     // A page-locked image is device-visible as it is: when the caller asks for it (orbx_set_pinned_ingest: a run somebody
     // is waiting for), the ingest kernel of the run reads it across PCIe, all cameras in ONE launch (in stream order, like the
-    // copy it replaces: a pitched hipMemcpy2DAsync per camera costs ~10 us of host time each).  MORB_PINNED_INGEST=0: never.
-    if (pinned && ex->pinned_ingest && attr.devicePointer) {
-        ex->ingest.src[cam] = static_cast<const uint8_t*>(attr.devicePointer); ex->ingest.stride[cam] = stride; ex->ingest_pending = true;
-        ex->ingest_host = true;
+    // copy it replaces: a pitched hipMemcpy2DAsync per camera costs ~10 us of host time each).
+    if (pinned && ex->l0.pinned_ingest && attr.devicePointer) {
+        ex->l0.ingest.src[cam] = static_cast<const uint8_t*>(attr.devicePointer); ex->l0.ingest.stride[cam] = stride; ex->l0.pending = true;
+        ex->l0.host = true;
         return ORB_OK;
     }
-    ex->ingest.src[cam] = nullptr;
+    ex->l0.ingest.src[cam] = nullptr;
     MORB_HIP(hipMemcpy2DAsync(ex->d_pyr.p + (size_t)cam * ex->cam_pitch, align_up(width, 64), src, stride, width, height, kind, ex->stream));
     return ORB_OK;
 }
@@ -2767,7 +2394,7 @@ int orbx_debug_last_path(const orbx_extractor* ex) { return ex ? ex->last_path :
 int orbx_debug_level0_in_place(const orbx_extractor* ex) {
     if (!ex) return ORB_E_ARG;
     int n = 0;
-    if (ex->l0_active) for (int c = 0; c < ex->n_cams; ++c) n += ex->l0_host[c].ptr != nullptr;
+    if (ex->l0.active) for (int c = 0; c < ex->n_cams; ++c) n += ex->l0.tab[c].ptr != nullptr;
     return n;
 }
 
@@ -2776,7 +2403,7 @@ int orbx_debug_level0_in_place(const orbx_extractor* ex) {
 int orbx_debug_pyramid_form(const orbx_extractor* ex) {
     if (!ex) return ORB_E_ARG;
     if (ex->tables_dirty) return -1;
-    return ex->tiled_ok ? 0 : (ex->tiled4 ? 3 : 2);
+    return ex->geo.tiled_ok ? 0 : (ex->geo.tiled4 ? 3 : 2);
 }
 
 // tests of the large-rig plan's geometry: other tiles, another split level (all handles created afterwards; 0 = keep)
@@ -2789,13 +2416,13 @@ int orbx_debug_pyramid_plan(int tile_w, int tile_h, int split) {
 
 int orbx_set_profiling(orbx_extractor* ex, int on) {
     MORB_ARG(ex != nullptr);
-    ex->profiling = on != 0;
+    ex->prof.on = on != 0;
     return ORB_OK;
 }
 
 int orbx_stage_times_us(const orbx_extractor* ex, float* out6) {
     MORB_ARG(ex && out6);
-    for (int i = 0; i < 6; ++i) out6[i] = ex->stage_us[i];
+    for (int i = 0; i < 6; ++i) out6[i] = ex->prof.stage_us[i];
     return ORB_OK;
 }
 
@@ -2867,16 +2494,16 @@ int orbx_record_done(orbx_extractor* ex) {   // the completion event of the most
 
 // 1: device images handed to orbx_upload_device are read IN PLACE as pyramid level 0 by every run until the camera's next upload
 // (large rigs only: the resize-chain pyramid; see k_set_l0).  The caller promises that such an image stays valid and unchanged
-// until then -- orbf's own contract for the images of a step.  MORB_L0_INPLACE=0: never.
+// until then -- orbf's own contract for the images of a step.
 int orbx_set_inplace_level0(orbx_extractor* ex, int on) {
     MORB_ARG(ex != nullptr);
-    if (ex->l0_optin != (on != 0)) { ex->l0_optin = on != 0; ex->tables_dirty = true; }   // (captured chains carry the table pointer: new epoch)
+    if (ex->l0.optin != (on != 0)) { ex->l0.optin = on != 0; ex->tables_dirty = true; }   // (captured chains carry the table pointer: new epoch)
     return ORB_OK;
 }
 
 int orbx_set_pinned_ingest(orbx_extractor* ex, int on) {
     MORB_ARG(ex != nullptr);
-    ex->pinned_ingest = on != 0;
+    ex->l0.pinned_ingest = on != 0;
     return ORB_OK;
 }
 
@@ -2911,42 +2538,42 @@ int orbx_peek_status(const orbx_extractor* ex) {
 }
 void* orbx_done_event(const orbx_extractor* ex) { return ex ? (void*)ex->ev_done[(ex->run_seq - 1u) & 1u] : nullptr; }
 
-// K1 + K2/K3 of a run: the pyramid chain and the per-cell FAST kernel
-// fused: the level-0 sources of a pending ingest (k_pyramid_tiled then reads them itself: no k_ingest launch); NULL: level 0 is in place
 // the {pointer, pitch} table of level 0 the kernels are handed: the handle's table while the geometry reads level 0 in place
 // (part of what a captured chain carries: the flag only changes together with the geometry epoch), else none
-static inline const L0Src* l0_table(const orbx_extractor* ex) { return ex->l0_on ? (const L0Src*)ex->d_l0.p : nullptr; }
+static inline const L0Src* l0_table(const orbx_extractor* ex) { return ex->geo.l0_on ? (const L0Src*)ex->l0.d_tab.p : nullptr; }
 
+// K1 + K2/K3 of a run: the pyramid chain and the per-cell FAST kernel
+// fused: the level-0 sources of a pending ingest (k_pyramid_tiled then reads them itself: no k_ingest launch); NULL: level 0 is in place
 static int launch_pyramid_fast(orbx_extractor* ex, hipStream_t st, const IngestArgs* fused = nullptr) {
     const int ML = ex->max_levels;
-    if (ex->profiling) MORB_HIP(hipEventRecord(ex->ev[0], st));
-    if (ex->tiled_ok) {
+    if (ex->prof.on) MORB_HIP(hipEventRecord(ex->prof.ev[0], st));
+    if (ex->geo.tiled_ok) {
         PyrArgs A;
         for (int c = 0; c < 64; ++c) {
             A.src[c] = fused && c < ex->n_cams ? fused->src[c] : nullptr; A.stride[c] = fused ? fused->stride[c] : 0;
-            A.tx[c] = c < ex->n_cams ? ex->pyr_tx[c] : 0; A.ty[c] = c < ex->n_cams ? ex->pyr_ty[c] : 0;
+            A.tx[c] = c < ex->n_cams ? ex->geo.pyr_tx[c] : 0; A.ty[c] = c < ex->n_cams ? ex->geo.pyr_ty[c] : 0;
             A.w[c] = c < ex->n_cams ? (short)ex->cur_w[c] : 0; A.h[c] = c < ex->n_cams ? (short)ex->cur_h[c] : 0;
         }
-        hipLaunchKernelGGL(k_pyramid_tiled<256>, dim3(ex->pyr_tx_max, ex->pyr_ty_max, ex->n_cams), dim3(256), (size_t)ex->pyr_lds, st, A,
+        hipLaunchKernelGGL(k_pyramid_tiled<256>, dim3(ex->geo.pyr_tx_max, ex->geo.pyr_ty_max, ex->n_cams), dim3(256), (size_t)ex->geo.pyr_lds, st, A,
                            (const LevelInfo*)ex->d_levels.p, ML, ex->d_pyr.p, ex->cam_pitch, (const int2*)ex->d_xtab.p,
-                           (const int4*)ex->d_ytab.p, (const int4*)ex->d_pyr_sx.p, (const int4*)ex->d_pyr_sy.p, ex->pyr_tx_max, ex->pyr_ty_max,
-                           ex->pyr_tab_cap, ex->pyr_tile);
+                           (const int4*)ex->d_ytab.p, (const int4*)ex->d_pyr_sx.p, (const int4*)ex->d_pyr_sy.p, ex->geo.pyr_tx_max, ex->geo.pyr_ty_max,
+                           ex->geo.pyr_tab_cap, ex->geo.pyr_tile);
     } else {
     auto level_dims = [&](int l, int* mw, int* mh) {
         *mw = 0; *mh = 0;
         if (l >= ML) return;
         for (int c = 0; c < ex->n_cams; ++c) {
-            const LevelInfo& Lv = ex->levels[(size_t)c * ML + l];
+            const LevelInfo& Lv = ex->geo.levels[(size_t)c * ML + l];
             *mw = std::max(*mw, Lv.w); *mh = std::max(*mh, Lv.h);
         }
     };
-    if (ex->tiled4) {
+    if (ex->geo.tiled4) {
         for (int pi = 0; pi < 2; ++pi) {
-            const orbx_extractor::TilePlan& P = ex->tp[pi];
+            const TilePlan& P = ex->geo.tp[pi];
             if (P.last <= P.base || P.tx_max == 0) continue;
             Tile4Args T;
             T.L = (const LevelInfo*)ex->d_levels.p; T.pyr = ex->d_pyr.p; T.cam_pitch = ex->cam_pitch; T.xgrp = (const int4*)ex->d_xgrp.p;
-            T.ytab = (const int4*)ex->d_ytab.p; T.sx = (const int4*)P.d_sx.p; T.sy = (const int4*)P.d_sy.p; T.l0 = l0_table(ex);
+            T.ytab = (const int4*)ex->d_ytab.p; T.sx = (const int4*)ex->d_tp_sx[pi].p; T.sy = (const int4*)ex->d_tp_sy[pi].p; T.l0 = l0_table(ex);
             T.max_levels = ML; T.base = P.base; T.last = P.last; T.tw = P.tw; T.th = P.th; T.halo_x = P.halo_x; T.halo_y = P.halo_y;
             T.tx_max = P.tx_max; T.ty_max = P.ty_max; T.gcap = P.gcap; T.rcap = P.rcap;
             for (int c = 0; c < 64; ++c) { T.tx[c] = c < ex->n_cams ? P.tx[c] : 0; T.ty[c] = c < ex->n_cams ? P.ty[c] : 0; }
@@ -2963,20 +2590,20 @@ static int launch_pyramid_fast(orbx_extractor* ex, hipStream_t st, const IngestA
                            (const int2*)ex->d_xtab.p, (const int4*)ex->d_ytab.p);
     }
     }
-    if (ex->profiling) MORB_HIP(hipEventRecord(ex->ev[1], st));
+    if (ex->prof.on) MORB_HIP(hipEventRecord(ex->prof.ev[1], st));
     // per-cell FAST / NMS / threshold / compaction
     // (throughput form from ~4 rounds of the chip's 2048 resident two-wave cells on; MORB_FAST_FORM=1 / 2 forces the latency / throughput form)
     static const int form_env = [] { const char* e = getenv("MORB_FAST_FORM"); return e ? atoi(e) : 0; }();
-    const bool throughput = form_env ? form_env == 2 : ex->total_cells >= 8192;
+    const bool throughput = form_env ? form_env == 2 : ex->geo.total_cells >= 8192;
     if (throughput)
-        hipLaunchKernelGGL((k_fast_cells<128, 8>), dim3(ex->total_cells), dim3(128), fast_cells_lds(ex->cell_h_max, ex->cell_px_max), st,
+        hipLaunchKernelGGL((k_fast_cells<128, 8>), dim3(ex->geo.total_cells), dim3(128), fast_cells_lds(ex->geo.cell_h_max, ex->geo.cell_px_max), st,
                            (const LevelInfo*)ex->d_levels.p, (const int2*)ex->d_cell_map.p, (const uint8_t*)ex->d_pyr.p, ex->cam_pitch, ML,
-                           ex->d_cell_cnt.p, ex->d_cell_items.p, ex->cell_h_max, ex->cell_px_max, l0_table(ex));
+                           ex->d_cell_cnt.p, ex->d_cell_items.p, ex->geo.cell_h_max, ex->geo.cell_px_max, l0_table(ex));
     else
-        hipLaunchKernelGGL((k_fast_cells<256, 4>), dim3(ex->total_cells), dim3(256), fast_cells_lds(ex->cell_h_max, ex->cell_px_max), st,
+        hipLaunchKernelGGL((k_fast_cells<256, 4>), dim3(ex->geo.total_cells), dim3(256), fast_cells_lds(ex->geo.cell_h_max, ex->geo.cell_px_max), st,
                            (const LevelInfo*)ex->d_levels.p, (const int2*)ex->d_cell_map.p, (const uint8_t*)ex->d_pyr.p, ex->cam_pitch, ML,
-                           ex->d_cell_cnt.p, ex->d_cell_items.p, ex->cell_h_max, ex->cell_px_max, l0_table(ex));
-    if (ex->profiling) MORB_HIP(hipEventRecord(ex->ev[2], st));
+                           ex->d_cell_cnt.p, ex->d_cell_items.p, ex->geo.cell_h_max, ex->geo.cell_px_max, l0_table(ex));
+    if (ex->prof.on) MORB_HIP(hipEventRecord(ex->prof.ev[2], st));
     MORB_HIP(hipGetLastError());
     return ORB_OK;
 }
@@ -2992,187 +2619,159 @@ static int launch_tree_describe(orbx_extractor* ex, hipStream_t st, unsigned slo
     hipLaunchKernelGGL(k_octree, dim3(ex->n_cams * ML), dim3(1024), sizeof(OctLdsR), st, (const LevelInfo*)ex->d_levels.p,
                        (const int*)ex->d_cell_cnt.p, (const uint32_t*)ex->d_cell_items.p, ex->d_sel_oct.p, ex->d_sel_cnt.p,
                        ex->d_oct_status.p, ML, ex->oct_max_keys);
-    if (ex->profiling) MORB_HIP(hipEventRecord(ex->ev[4], st));
-    hipLaunchKernelGGL(k_describe, dim3((ex->total_sel_slots + 3) / 4), dim3(256), 0, st, (const LevelInfo*)ex->d_levels.p, ML,
-                       (const uint8_t*)ex->d_pyr.p, ex->cam_pitch, (const SelKp*)ex->d_sel_oct.p, ex->total_sel_slots,
+    if (ex->prof.on) MORB_HIP(hipEventRecord(ex->prof.ev[4], st));
+    hipLaunchKernelGGL(k_describe, dim3((ex->geo.total_sel_slots + 3) / 4), dim3(256), 0, st, (const LevelInfo*)ex->d_levels.p, ML,
+                       (const uint8_t*)ex->d_pyr.p, ex->cam_pitch, (const SelKp*)ex->d_sel_oct.p, ex->geo.total_sel_slots,
                        (orb_keypoint* const*)ex->d_out_kps.p, (uint8_t* const*)ex->d_out_desc.p, mir,
                        SelListArgs{(const unsigned short*)ex->d_slot_blk.p, (const int*)ex->d_sel_cnt.p,
                                    (const int*)ex->d_oct_status.p, ex->d_n_out.p + slot * (ex->n_cams + 1), d_h_oct, ex->n_cams},
                        sink, l0_table(ex), (const DescribeTables*)ex->d_desc_tabs.p);
-    if (ex->profiling) MORB_HIP(hipEventRecord(ex->ev[5], st));
+    if (ex->prof.on) MORB_HIP(hipEventRecord(ex->prof.ev[5], st));
     MORB_HIP(hipGetLastError());
     return ORB_OK;
 }
 
-static int orbx_run_impl(orbx_extractor* ex, bool allow_async) {
-    MORB_HIP(hipSetDevice(ex->device));
-    const auto t_begin = std::chrono::steady_clock::now();
-    int rc;
-    if (ex->tables_dirty && (rc = rebuild_geometry(ex))) return rc;
-    if (ex->out_ptrs_dirty) {
-        MORB_HIP(hipMemcpyAsync(ex->d_out_kps.p, ex->out_kps.data(), ex->n_cams * sizeof(void*), hipMemcpyHostToDevice, ex->stream));
-        MORB_HIP(hipMemcpyAsync(ex->d_out_desc.p, ex->out_desc.data(), ex->n_cams * sizeof(void*), hipMemcpyHostToDevice, ex->stream));
-        MORB_HIP(hipStreamSynchronize(ex->stream));
-        ex->out_ptrs_dirty = false;
-    }
-    const int ML = ex->max_levels;
-    hipStream_t st = ex->stream;
-    if (allow_async && ex->inflight >= 2) { morb::set_error("two runs are already in flight: orbx_finish the older one first"); return ORB_E_ARG; }
-    if (!allow_async && ex->inflight > 0) {  // a synchronous run abandons whatever was still in flight
-        MORB_HIP(hipStreamSynchronize(st));
-        ex->inflight = 0;
-    }
-    if (ex->inflight == 0) std::fill(ex->n_out.begin(), ex->n_out.end(), 0);
-    if (ex->total_cells == 0) {  // every camera empty
-        memset(&ex->ingest, 0, sizeof(ex->ingest)); ex->ingest_pending = false; ex->ingest_host = false;
-        return ORB_OK;
-    }
-    uint32_t* d_cand = nullptr; int* d_level_cnt = nullptr;
-    MORB_HIP(hipHostGetDevicePointer((void**)&d_cand, ex->h_cand, 0));
-    MORB_HIP(hipHostGetDevicePointer((void**)&d_level_cnt, ex->h_level_cnt, 0));
+static int upload_output_pointers(orbx_extractor* ex) {
+    if (!ex->out_ptrs_dirty) return ORB_OK;
+    MORB_HIP(hipMemcpyAsync(ex->d_out_kps.p, ex->out_kps.data(), ex->n_cams * sizeof(void*), hipMemcpyHostToDevice, ex->stream));
+    MORB_HIP(hipMemcpyAsync(ex->d_out_desc.p, ex->out_desc.data(), ex->n_cams * sizeof(void*), hipMemcpyHostToDevice, ex->stream));
+    MORB_HIP(hipStreamSynchronize(ex->stream));
+    ex->out_ptrs_dirty = false;
+    return ORB_OK;
+}
 
-    // Level 0 of the images that are not in place yet (device images, staged pageable images, page-locked images read in place).
-    // A run whose launches are issued one by one hands the sources to the tiled pyramid launch, which reads them itself; a
-    // run that replays a captured chain (its launches carry no per-run pointers) copies them first with k_ingest.
-    const bool dev_tree = ex->device_octree && ex->total_sel_slots > 0;
-    const bool will_replay = dev_tree && ex->use_graph && ex->graph_next_run && allow_async && !ex->profiling;
-    IngestArgs fused_src;
-    const IngestArgs* fused = nullptr;
+// Level 0 of the images that are not in place yet (device images, staged pageable images, page-locked images read in place).
+// A run whose launches are issued one by one hands the sources to the tiled pyramid launch, which reads them itself (*fused, kept
+// in *storage); a run that replays a captured chain (its launches carry no per-run pointers) copies them first with k_ingest.
+static int place_level0(orbx_extractor* ex, hipStream_t st, bool will_replay, IngestArgs* storage, const IngestArgs** fused) {
+    Level0State& Z = ex->l0;
+    *fused = nullptr;
     bool any_upload = false;
-    for (int c = 0; c < ex->n_cams; ++c) any_upload |= ex->uploaded[c] != 0;
-    if (ex->ingest_pending || (ex->l0_active && any_upload)) {
+    for (int c = 0; c < ex->n_cams; ++c) any_upload |= Z.uploaded[c] != 0;
+    if (Z.pending || (Z.active && any_upload)) {
         // (sources in host memory are copied exactly once by k_ingest: the tiles' halos would cross PCIe twice)
-        if (ex->ingest_pending && ex->tiled_ok && !will_replay && !ex->ingest_host) {
-            fused_src = ex->ingest; fused = &fused_src;
+        if (Z.pending && ex->geo.tiled_ok && !will_replay && !Z.host) {
+            *storage = Z.ingest; *fused = storage;
         } else {
-            // Level 0 in place (k_set_l0 above): every camera that has an image must have been handed a device image for THIS run,
+            // Level 0 in place (k_set_l0): every camera that has an image must have been handed a device image for THIS run,
             // 4-byte aligned with a pitch that is a multiple of 4.  Otherwise the images are copied -- and a camera that was read in
             // place so far and got no new image in this run is copied too, from where it lies (valid until its next upload), before
             // the table is emptied: no run ever finds a camera's level 0 in neither place.
-            bool inplace = ex->l0_on && ex->ingest_pending && !ex->ingest_host;
+            bool inplace = ex->geo.l0_on && Z.pending && !Z.host;
             for (int c = 0; c < ex->n_cams && inplace; ++c) {
                 if (ex->cur_w[c] == 0) continue;
-                const uint8_t* p = ex->ingest.src[c];
-                if (!p || (reinterpret_cast<uintptr_t>(p) & 3) || (ex->ingest.stride[c] & 3)) inplace = false;
+                const uint8_t* p = Z.ingest.src[c];
+                if (!p || (reinterpret_cast<uintptr_t>(p) & 3) || (Z.ingest.stride[c] & 3)) inplace = false;
             }
             if (inplace) {
-                IngestArgs T = ex->ingest;
+                IngestArgs T = Z.ingest;
                 for (int c = 0; c < 64; ++c) if (c >= ex->n_cams || ex->cur_w[c] == 0) { T.src[c] = nullptr; T.stride[c] = 0; }
-                hipLaunchKernelGGL(k_set_l0, dim3(1), dim3(64), 0, st, T, ex->d_l0.p, ex->n_cams);
-                for (int c = 0; c < ex->n_cams; ++c) ex->l0_host[c] = L0Src{T.src[c], T.stride[c], 0};
-                ex->l0_active = true;
+                hipLaunchKernelGGL(k_set_l0, dim3(1), dim3(64), 0, st, T, Z.d_tab.p, ex->n_cams);
+                for (int c = 0; c < ex->n_cams; ++c) Z.tab[c] = L0Src{T.src[c], T.stride[c], 0};
+                Z.active = true;
             } else {
-                IngestArgs I = ex->ingest;
-                if (ex->l0_active) {
+                IngestArgs I = Z.ingest;
+                if (Z.active) {
                     for (int c = 0; c < ex->n_cams; ++c)
-                        if (!ex->uploaded[c] && ex->cur_w[c] > 0 && ex->l0_host[c].ptr) { I.src[c] = ex->l0_host[c].ptr; I.stride[c] = ex->l0_host[c].stride; }
-                    MORB_HIP(hipMemsetAsync(ex->d_l0.p, 0, 64 * sizeof(L0Src), st));
-                    ex->l0_host.assign(64, L0Src{nullptr, 0, 0});
-                    ex->l0_active = false;
+                        if (!Z.uploaded[c] && ex->cur_w[c] > 0 && Z.tab[c].ptr) { I.src[c] = Z.tab[c].ptr; I.stride[c] = Z.tab[c].stride; }
+                    MORB_HIP(hipMemsetAsync(Z.d_tab.p, 0, 64 * sizeof(L0Src), st));
+                    Z.tab.assign(64, L0Src{nullptr, 0, 0});
+                    Z.active = false;
                 }
                 int mw = 0, mh = 0;
                 for (int c = 0; c < ex->n_cams; ++c)
                     if (I.src[c]) { mw = std::max(mw, ex->cur_w[c]); mh = std::max(mh, ex->cur_h[c]); }
                 if (mw > 0)
                     hipLaunchKernelGGL(k_ingest, dim3((mw + 1023) / 1024, (mh + 3) / 4, ex->n_cams), dim3(64, 4, 1), 0, st, I,
-                                       (const LevelInfo*)ex->d_levels.p, ML, ex->d_pyr.p, ex->cam_pitch);
+                                       (const LevelInfo*)ex->d_levels.p, ex->max_levels, ex->d_pyr.p, ex->cam_pitch);
             }
         }
-        for (int c = 0; c < ex->n_cams; ++c) ex->ingest.src[c] = nullptr;
-        ex->ingest_pending = false; ex->ingest_host = false;
+        for (int c = 0; c < ex->n_cams; ++c) Z.ingest.src[c] = nullptr;
+        Z.pending = false; Z.host = false;
     }
-    std::fill(ex->uploaded.begin(), ex->uploaded.end(), 0);
-    if (!dev_tree) {
-        if ((rc = launch_pyramid_fast(ex, st, fused))) return rc;
-        // K3b (only on the host-quadtree path and for the inspection hook): dense cell-major lists, also into pinned host memory
-        hipLaunchKernelGGL(k_compact, dim3(ex->n_cams * ML), dim3(1024), 0, st, (const LevelInfo*)ex->d_levels.p,
-                           (const int*)ex->d_cell_cnt.p, (const uint32_t*)ex->d_cell_items.p, ex->d_cell_off.p, d_cand, d_level_cnt,
-                           ex->d_cand_dev.p, ex->d_level_cnt_dev.p);
-        if (ex->profiling) MORB_HIP(hipEventRecord(ex->ev[3], st));
-        MORB_HIP(hipGetLastError());
-    }
-    ex->cand_valid = !dev_tree;
+    std::fill(Z.uploaded.begin(), Z.uploaded.end(), 0);
+    return ORB_OK;
+}
 
-    // K4 on the device: quadtree -> K5-K7 straight from the slotted list; ONE sync afterwards.  Falls through to the host
-    // quadtree when a level is outside the device limits.
-    if (dev_tree) {
-        const unsigned slot = ex->run_seq & 1u;
-        // The ten launches of the chain are captured once per slot into a kernel-only graph and replayed with one
-        // hipGraphLaunch (the host cost of enqueueing them is what bounds overlapped timesteps).  Everything the launches
-        // carry is in the key: geometry epoch, result mirrors, frame sink.
-        const FrameSink sink = allow_async ? ex->sink : FrameSink{};
-        const bool graphable = will_replay;
-        bool done = false;
-        if (graphable) {
-            // a few graphs per slot: a caller rotates through more result sets / frames than there are slots
-            int way = -1;
-            for (int w = 0; w < orbx_extractor::CHAIN_WAYS; ++w) {
-                const orbx_extractor::ChainGraph& C = ex->chain[slot][w];
-                if (C.exec && C.epoch == ex->geom_epoch && C.mirror_kps == ex->mirror_kps && C.mirror_desc == ex->mirror_desc &&
-                    C.tail_tag == (ex->tail_fn ? ex->tail_tag : 0) && memcmp(&C.sink, &sink, sizeof(FrameSink)) == 0) { way = w; break; }
-            }
-            const bool hit = way >= 0;
-            if (!hit) { way = ex->chain_next[slot]; ex->chain_next[slot] = (way + 1) % orbx_extractor::CHAIN_WAYS; }
-            orbx_extractor::ChainGraph& G = ex->chain[slot][way];
-            if (hit) {
-                MORB_HIP(hipGraphLaunch(G.exec, st));
-                done = true;
-            } else {
-                G.destroy();
-                hipGraph_t g = nullptr;
-                hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-                if (e == hipSuccess) {
-                    const int rc1 = launch_pyramid_fast(ex, st);
-                    int rc2 = rc1 ? rc1 : launch_tree_describe(ex, st, slot, sink);
-                    if (!rc2 && ex->tail_fn) { ++ex->run_seq; rc2 = ex->tail_fn(ex->tail_user, (void*)st); --ex->run_seq; }  // (the tail sees this run as the most recent one)
-                    e = hipStreamEndCapture(st, &g);
-                    if (!rc2 && e == hipSuccess && g && hipGraphInstantiate(&G.exec, g, nullptr, nullptr, 0) == hipSuccess) {
-                        G.graph = g; G.epoch = ex->geom_epoch; G.mirror_kps = ex->mirror_kps; G.mirror_desc = ex->mirror_desc; G.sink = sink;
-                        G.tail_tag = ex->tail_fn ? ex->tail_tag : 0;
-                        MORB_HIP(hipGraphLaunch(G.exec, st));
-                        done = true;
-                    } else {
-                        if (g) (void)hipGraphDestroy(g);
-                        G.exec = nullptr;
-                    }
-                }
-                if (!done) { (void)hipGetLastError(); ex->use_graph = false; }  // plain launches from now on
-            }
-        }
-        if (!done) {
-            if ((rc = launch_pyramid_fast(ex, st, fused))) return rc;
-            if (ex->profiling) MORB_HIP(hipEventRecord(ex->ev[3], st));
-            if ((rc = launch_tree_describe(ex, st, slot, sink))) return rc;
-            if (ex->tail_fn) { ++ex->run_seq; rc = ex->tail_fn(ex->tail_user, (void*)st); --ex->run_seq; if (rc) return rc; }
-        }
-        // (a caller that puts the run's consumer on the same stream records the completion event itself, behind that work:
-        // an event record with system-scope release standing between two dependent kernels costs ~10 us of queue time each)
-        if (!(allow_async && ex->defer_done)) MORB_HIP(hipEventRecord(ex->ev_done[slot], st));
-        ex->prof_valid[slot] = ex->profiling && ex->inflight == 0;  // (one set of stage events: not for overlapped runs)
-        ++ex->run_seq; ++ex->inflight; ex->t_begin_async = t_begin;
-        if (allow_async) return ORB_OK;
-        MORB_HIP(hipStreamSynchronize(st));
-        if (ex->h_oct[slot * (ex->n_cams + 1) + ex->n_cams] == 0) return finish_device_path(ex);
-        ex->inflight = 0;
-        std::fill(ex->n_out.begin(), ex->n_out.end(), 0);  // a level exceeded the device limits: redo the selection on the host
-        hipLaunchKernelGGL(k_compact, dim3(ex->n_cams * ML), dim3(1024), 0, st, (const LevelInfo*)ex->d_levels.p,
-                           (const int*)ex->d_cell_cnt.p, (const uint32_t*)ex->d_cell_items.p, ex->d_cell_off.p, d_cand, d_level_cnt,
-                           ex->d_cand_dev.p, ex->d_level_cnt_dev.p);
-        MORB_HIP(hipGetLastError());
-        MORB_HIP(hipStreamSynchronize(st));
-        ex->cand_valid = true;
-    } else {
-        MORB_HIP(hipStreamSynchronize(st));
-    }
-    const auto t_host0 = std::chrono::steady_clock::now();
+// K3b (only on the host-quadtree path and for the inspection hook): dense cell-major lists, also into pinned host memory
+static void launch_compact(orbx_extractor* ex, hipStream_t st, uint32_t* d_cand, int* d_level_cnt) {
+    hipLaunchKernelGGL(k_compact, dim3(ex->n_cams * ex->max_levels), dim3(1024), 0, st, (const LevelInfo*)ex->d_levels.p,
+                       (const int*)ex->d_cell_cnt.p, (const uint32_t*)ex->d_cell_items.p, ex->d_cell_off.p, d_cand, d_level_cnt,
+                       ex->d_cand_dev.p, ex->d_level_cnt_dev.p);
+}
 
-    ex->last_path = 2;
-    // K4 (host): quadtree per (camera, level) on the worker pool; output order = level-major, list order inside a level
+// The tail a caller hangs behind the chain (orbx_set_chain_tail) sees this run as the most recent one.
+static int call_chain_tail(orbx_extractor* ex, hipStream_t st) {
+    ++ex->run_seq;
+    const int rc = ex->tail_fn(ex->tail_user, (void*)st);
+    --ex->run_seq;
+    return rc;
+}
+
+// The ten launches of the chain are captured once per slot and key into a kernel-only graph and replayed with one hipGraphLaunch
+// (the host cost of enqueueing them is what bounds overlapped timesteps).  *enqueued false: fall back to plain launches -- and, when
+// the capture itself failed, for every later run too.
+static int replay_chain(orbx_extractor* ex, hipStream_t st, unsigned slot, const FrameSink& sink, bool* enqueued) {
+    ChainCache& C = ex->chains;
+    *enqueued = false;
+    ChainKey key;
+    key.epoch = ex->geom_epoch; key.mirror_kps = ex->mirror_kps; key.mirror_desc = ex->mirror_desc;
+    key.tail_tag = ex->tail_fn ? ex->tail_tag : 0; key.sink = sink;
+    int way = -1;
+    for (int w = 0; w < CHAIN_WAYS; ++w)
+        if (C.way[slot][w].exec && C.way[slot][w].key == key) { way = w; break; }
+    if (way >= 0) {
+        MORB_HIP(hipGraphLaunch(C.way[slot][way].exec, st));
+        *enqueued = true;
+        return ORB_OK;
+    }
+    way = C.next[slot]; C.next[slot] = (way + 1) % CHAIN_WAYS;
+    ChainGraph& G = C.way[slot][way];
+    G.destroy();
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+    if (e == hipSuccess) {
+        const int rc1 = launch_pyramid_fast(ex, st);
+        int rc2 = rc1 ? rc1 : launch_tree_describe(ex, st, slot, sink);
+        if (!rc2 && ex->tail_fn) rc2 = call_chain_tail(ex, st);
+        e = hipStreamEndCapture(st, &g);
+        if (!rc2 && e == hipSuccess && g && hipGraphInstantiate(&G.exec, g, nullptr, nullptr, 0) == hipSuccess) {
+            G.graph = g; G.key = key;
+            MORB_HIP(hipGraphLaunch(G.exec, st));
+            *enqueued = true;
+        } else {
+            if (g) (void)hipGraphDestroy(g);
+            G.exec = nullptr;
+        }
+    }
+    if (!*enqueued) { (void)hipGetLastError(); C.use_graph = false; }  // plain launches from now on
+    return ORB_OK;
+}
+
+// The stage times of a profiled run whose events have completed; stage 3 is the device quadtree's (host_tree_us == nullptr) or the
+// host quadtree's wall time.
+static int read_stage_times(orbx_extractor* ex, const float* host_tree_us, std::chrono::steady_clock::time_point t_begin) {
+    StageProfile& P = ex->prof;
+    float ms;
+    MORB_HIP(hipEventElapsedTime(&ms, P.ev[0], P.ev[1])); P.stage_us[0] = ms * 1000.f;
+    MORB_HIP(hipEventElapsedTime(&ms, P.ev[1], P.ev[2])); P.stage_us[1] = ms * 1000.f;
+    MORB_HIP(hipEventElapsedTime(&ms, P.ev[2], P.ev[3])); P.stage_us[2] = ms * 1000.f;
+    if (host_tree_us) P.stage_us[3] = *host_tree_us;
+    else { MORB_HIP(hipEventElapsedTime(&ms, P.ev[3], P.ev[4])); P.stage_us[3] = ms * 1000.f; }
+    MORB_HIP(hipEventElapsedTime(&ms, P.ev[4], P.ev[5])); P.stage_us[4] = ms * 1000.f;
+    P.stage_us[5] = std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - t_begin).count();
+    return ORB_OK;
+}
+
+// K4 (host): quadtree per (camera, level) on the worker pool over the candidates k_compact left in pinned memory; the selection goes
+// to h_sel in output order = level-major, list order inside a level
+static int host_quadtree_select(orbx_extractor* ex, int* nsel_out) {
+    const int ML = ex->max_levels;
     int n_tasks = 0;
     for (int c = 0; c < ex->n_cams; ++c) {
         const CamTables& T = ex->cams[c];
         for (int l = 0; l < T.p.nlevels; ++l) {
-            const LevelInfo& Lv = ex->levels[(size_t)c * ML + l];
+            const LevelInfo& Lv = ex->geo.levels[(size_t)c * ML + l];
             const int n = Lv.w ? ex->h_level_cnt[c * ML + l] : 0;
             ex->level_cnt_last[(size_t)c * ML + l] = n;
             if (n == 0) continue;
@@ -3187,7 +2786,7 @@ static int orbx_run_impl(orbx_extractor* ex, bool allow_async) {
     });
     ex->pool->run(n_tasks, [ex, ML](int i) {
         OctreeTask& t = ex->tasks[i];
-        const LevelInfo& Lv = ex->levels[(size_t)t.cam * ML + t.level];
+        const LevelInfo& Lv = ex->geo.levels[(size_t)t.cam * ML + t.level];
         const uint32_t* cand = ex->h_cand + Lv.cand_base;
         t.cx.resize(t.n); t.cy.resize(t.n); t.cr.resize(t.n);
         for (int k = 0; k < t.n; ++k) {
@@ -3204,28 +2803,29 @@ static int orbx_run_impl(orbx_extractor* ex, bool allow_async) {
         const OctreeTask &x = ex->tasks[a], &y = ex->tasks[b];
         return x.cam != y.cam ? x.cam < y.cam : x.level < y.level;
     });
-    int nsel = 0;
-    {
-        int cur_cam = -1, out_idx = 0;
-        for (int oi = 0; oi < n_tasks; ++oi) {
-            const OctreeTask& t = ex->tasks[order[oi]];
-            if (t.cam != cur_cam) { if (cur_cam >= 0) ex->n_out[cur_cam] = out_idx; cur_cam = t.cam; out_idx = 0; }
-            for (int s : t.selected) {
-                if (out_idx >= ex->out_cap_active[t.cam] || (size_t)nsel >= ex->h_sel_cap) {
-                    morb::set_error("camera %d produced more keypoints than its output capacity %d", t.cam, ex->out_cap_active[t.cam]);
-                    return ORB_E_CAPACITY;
-                }
-                SelKp& K = ex->h_sel[nsel++];
-                K.x = t.cx[s] + MIN_BORDER; K.y = t.cy[s] + MIN_BORDER;  // :843-844
-                K.camlevel = (t.cam << 8) | t.level;
-                K.resp_out = (int)(((unsigned)t.cr[s] << 24) | (unsigned)out_idx);
-                ++out_idx;
+    int nsel = 0, cur_cam = -1, out_idx = 0;
+    for (int oi = 0; oi < n_tasks; ++oi) {
+        const OctreeTask& t = ex->tasks[order[oi]];
+        if (t.cam != cur_cam) { if (cur_cam >= 0) ex->n_out[cur_cam] = out_idx; cur_cam = t.cam; out_idx = 0; }
+        for (int s : t.selected) {
+            if (out_idx >= ex->out_cap_active[t.cam] || (size_t)nsel >= ex->h_sel_cap) {
+                morb::set_error("camera %d produced more keypoints than its output capacity %d", t.cam, ex->out_cap_active[t.cam]);
+                return ORB_E_CAPACITY;
             }
+            SelKp& K = ex->h_sel[nsel++];
+            K.x = t.cx[s] + MIN_BORDER; K.y = t.cy[s] + MIN_BORDER;  // :843-844
+            K.camlevel = (t.cam << 8) | t.level;
+            K.resp_out = (int)(((unsigned)t.cr[s] << 24) | (unsigned)out_idx);
+            ++out_idx;
         }
-        if (cur_cam >= 0) ex->n_out[cur_cam] = out_idx;
     }
-    const auto t_host1 = std::chrono::steady_clock::now();
-    if (ex->profiling) MORB_HIP(hipEventRecord(ex->ev[4], st));
+    if (cur_cam >= 0) ex->n_out[cur_cam] = out_idx;
+    *nsel_out = nsel;
+    return ORB_OK;
+}
+
+// K5-K7 from the host-built list h_sel[0 .. nsel)
+static int describe_host_list(orbx_extractor* ex, hipStream_t st, int nsel) {
     MirrorArgs mir;
     mir.kps = nullptr; mir.desc = nullptr;
     if (ex->mirror_kps && nsel <= ex->mirror_cap) {
@@ -3235,25 +2835,98 @@ static int orbx_run_impl(orbx_extractor* ex, bool allow_async) {
     }
     if (nsel > 0) {
         MORB_HIP(hipMemcpyAsync(ex->d_sel.p, ex->h_sel, (size_t)nsel * sizeof(SelKp), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_describe, dim3((nsel + 3) / 4), dim3(256), 0, st, (const LevelInfo*)ex->d_levels.p, ML,
+        hipLaunchKernelGGL(k_describe, dim3((nsel + 3) / 4), dim3(256), 0, st, (const LevelInfo*)ex->d_levels.p, ex->max_levels,
                            (const uint8_t*)ex->d_pyr.p, ex->cam_pitch, (const SelKp*)ex->d_sel.p, nsel,
                            (orb_keypoint* const*)ex->d_out_kps.p, (uint8_t* const*)ex->d_out_desc.p, mir,
                            SelListArgs{nullptr, nullptr, nullptr, nullptr, nullptr, 0}, FrameSink{}, l0_table(ex),
                            (const DescribeTables*)ex->d_desc_tabs.p);
         MORB_HIP(hipGetLastError());
     }
-    if (ex->profiling) {
-        MORB_HIP(hipEventRecord(ex->ev[5], st));
+    return ORB_OK;
+}
+
+// The synchronous tail behind a drained stream whose candidates are in pinned memory: host quadtree, then describe
+static int run_host_tree(orbx_extractor* ex, hipStream_t st, std::chrono::steady_clock::time_point t_begin) {
+    const auto t_host0 = std::chrono::steady_clock::now();
+    ex->last_path = 2;
+    int rc, nsel = 0;
+    if ((rc = host_quadtree_select(ex, &nsel))) return rc;
+    const float host_tree_us = std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - t_host0).count();
+    if (ex->prof.on) MORB_HIP(hipEventRecord(ex->prof.ev[4], st));
+    if ((rc = describe_host_list(ex, st, nsel))) return rc;
+    if (ex->prof.on) {
+        MORB_HIP(hipEventRecord(ex->prof.ev[5], st));
         MORB_HIP(hipStreamSynchronize(st));
-        float ms;
-        MORB_HIP(hipEventElapsedTime(&ms, ex->ev[0], ex->ev[1])); ex->stage_us[0] = ms * 1000.f;
-        MORB_HIP(hipEventElapsedTime(&ms, ex->ev[1], ex->ev[2])); ex->stage_us[1] = ms * 1000.f;
-        MORB_HIP(hipEventElapsedTime(&ms, ex->ev[2], ex->ev[3])); ex->stage_us[2] = ms * 1000.f;
-        ex->stage_us[3] = std::chrono::duration<float, std::micro>(t_host1 - t_host0).count();
-        MORB_HIP(hipEventElapsedTime(&ms, ex->ev[4], ex->ev[5])); ex->stage_us[4] = ms * 1000.f;
-        ex->stage_us[5] = std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - t_begin).count();
+        if ((rc = read_stage_times(ex, &host_tree_us, t_begin))) return rc;
     }
     return ORB_OK;
+}
+
+static int orbx_run_impl(orbx_extractor* ex, bool allow_async) {
+    MORB_HIP(hipSetDevice(ex->device));
+    const auto t_begin = std::chrono::steady_clock::now();
+    int rc;
+    if (ex->tables_dirty && (rc = rebuild_geometry(ex))) return rc;
+    if ((rc = upload_output_pointers(ex))) return rc;
+    hipStream_t st = ex->stream;
+    // in flight: at most two asynchronous runs; a synchronous run abandons whatever was still in flight
+    if (allow_async && ex->inflight >= 2) { morb::set_error("two runs are already in flight: orbx_finish the older one first"); return ORB_E_ARG; }
+    if (!allow_async && ex->inflight > 0) {
+        MORB_HIP(hipStreamSynchronize(st));
+        ex->inflight = 0;
+    }
+    if (ex->inflight == 0) std::fill(ex->n_out.begin(), ex->n_out.end(), 0);
+    if (ex->geo.total_cells == 0) {  // every camera empty
+        memset(&ex->l0.ingest, 0, sizeof(ex->l0.ingest)); ex->l0.pending = false; ex->l0.host = false;
+        return ORB_OK;
+    }
+    uint32_t* d_cand = nullptr; int* d_level_cnt = nullptr;
+    MORB_HIP(hipHostGetDevicePointer((void**)&d_cand, ex->h_cand, 0));
+    MORB_HIP(hipHostGetDevicePointer((void**)&d_level_cnt, ex->h_level_cnt, 0));
+
+    const bool dev_tree = ex->device_octree && ex->geo.total_sel_slots > 0;
+    const bool will_replay = dev_tree && ex->chains.use_graph && ex->graph_next_run && allow_async && !ex->prof.on;
+    IngestArgs fused_src;
+    const IngestArgs* fused = nullptr;
+    if ((rc = place_level0(ex, st, will_replay, &fused_src, &fused))) return rc;
+    if (!dev_tree) {
+        if ((rc = launch_pyramid_fast(ex, st, fused))) return rc;
+        launch_compact(ex, st, d_cand, d_level_cnt);
+        if (ex->prof.on) MORB_HIP(hipEventRecord(ex->prof.ev[3], st));
+        MORB_HIP(hipGetLastError());
+        ex->cand_valid = true;
+        MORB_HIP(hipStreamSynchronize(st));
+        return run_host_tree(ex, st, t_begin);
+    }
+    ex->cand_valid = false;
+    // K4 on the device: quadtree -> K5-K7 straight from the slotted list; ONE sync afterwards.  Falls through to the host
+    // quadtree when a level is outside the device limits.
+    const unsigned slot = ex->run_seq & 1u;
+    const FrameSink sink = allow_async ? ex->sink : FrameSink{};
+    bool enqueued = false;
+    if (will_replay && (rc = replay_chain(ex, st, slot, sink, &enqueued))) return rc;
+    if (!enqueued) {
+        if ((rc = launch_pyramid_fast(ex, st, fused))) return rc;
+        if (ex->prof.on) MORB_HIP(hipEventRecord(ex->prof.ev[3], st));
+        if ((rc = launch_tree_describe(ex, st, slot, sink))) return rc;
+        if (ex->tail_fn && (rc = call_chain_tail(ex, st))) return rc;
+    }
+    // (a caller that puts the run's consumer on the same stream records the completion event itself, behind that work:
+    // an event record with system-scope release standing between two dependent kernels costs ~10 us of queue time each)
+    if (!(allow_async && ex->defer_done)) MORB_HIP(hipEventRecord(ex->ev_done[slot], st));
+    ex->prof.valid[slot] = ex->prof.on && ex->inflight == 0;  // (one set of stage events: not for overlapped runs)
+    ++ex->run_seq; ++ex->inflight; ex->t_begin_async = t_begin;
+    if (allow_async) return ORB_OK;
+    // synchronous tail
+    MORB_HIP(hipStreamSynchronize(st));
+    if (ex->h_oct[slot * (ex->n_cams + 1) + ex->n_cams] == 0) return finish_device_path(ex);
+    ex->inflight = 0;
+    std::fill(ex->n_out.begin(), ex->n_out.end(), 0);  // a level exceeded the device limits: redo the selection on the host
+    launch_compact(ex, st, d_cand, d_level_cnt);
+    MORB_HIP(hipGetLastError());
+    MORB_HIP(hipStreamSynchronize(st));
+    ex->cand_valid = true;
+    return run_host_tree(ex, st, t_begin);
 }
 
 // After the stream has drained: adopt the device path's counts, or redo the selection on the host if a level was outside
@@ -3268,15 +2941,7 @@ static int finish_device_path(orbx_extractor* ex) {
             ex->n_out[c] = h_oct[c];
             if (ex->n_out[c] > ex->out_cap_active[c]) { morb::set_error("a camera produced more keypoints than its output capacity"); return ORB_E_CAPACITY; }
         }
-        if (ex->profiling && ex->prof_valid[oldest]) {
-            float ms;
-            MORB_HIP(hipEventElapsedTime(&ms, ex->ev[0], ex->ev[1])); ex->stage_us[0] = ms * 1000.f;
-            MORB_HIP(hipEventElapsedTime(&ms, ex->ev[1], ex->ev[2])); ex->stage_us[1] = ms * 1000.f;
-            MORB_HIP(hipEventElapsedTime(&ms, ex->ev[2], ex->ev[3])); ex->stage_us[2] = ms * 1000.f;
-            MORB_HIP(hipEventElapsedTime(&ms, ex->ev[3], ex->ev[4])); ex->stage_us[3] = ms * 1000.f;  // device quadtree
-            MORB_HIP(hipEventElapsedTime(&ms, ex->ev[4], ex->ev[5])); ex->stage_us[4] = ms * 1000.f;
-            ex->stage_us[5] = std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - ex->t_begin_async).count();
-        }
+        if (ex->prof.on && ex->prof.valid[oldest]) return read_stage_times(ex, nullptr, ex->t_begin_async);
         return ORB_OK;
     }
     // a level exceeded the device limits.  With a newer run in flight the resident images are already being replaced:
@@ -3357,13 +3022,13 @@ int orbx_debug_level(orbx_extractor* ex, int cam, int level, uint8_t* out, int c
     MORB_ARG(ex && cam >= 0 && cam < ex->n_cams && level >= 0 && level < ex->cams[cam].p.nlevels && w && h);
     MORB_ARG(!ex->tables_dirty);
     MORB_HIP(hipSetDevice(ex->device));
-    const LevelInfo& Lv = ex->levels[(size_t)cam * ex->max_levels + level];
+    const LevelInfo& Lv = ex->geo.levels[(size_t)cam * ex->max_levels + level];
     *w = Lv.w; *h = Lv.h;
     if (Lv.w == 0) return ORB_OK;
     if (Lv.w * Lv.h > cap_bytes) { morb::set_error("level needs %d bytes", Lv.w * Lv.h); return ORB_E_CAPACITY; }
     const uint8_t* lsrc = ex->d_pyr.p + (size_t)cam * ex->cam_pitch + Lv.pyr_off;
     size_t lpitch = (size_t)Lv.stride;
-    if (level == 0 && ex->l0_active && ex->l0_host[cam].ptr) { lsrc = ex->l0_host[cam].ptr; lpitch = (size_t)ex->l0_host[cam].stride; }   // (read in place)
+    if (level == 0 && ex->l0.active && ex->l0.tab[cam].ptr) { lsrc = ex->l0.tab[cam].ptr; lpitch = (size_t)ex->l0.tab[cam].stride; }   // (read in place)
     MORB_HIP(hipMemcpy2DAsync(out, Lv.w, lsrc, lpitch, Lv.w, Lv.h,
                               hipMemcpyDeviceToHost, ex->stream));
     MORB_HIP(hipStreamSynchronize(ex->stream));
@@ -3378,15 +3043,13 @@ int orbx_debug_candidates(orbx_extractor* ex, int cam, int level, orb_keypoint* 
         uint32_t* d_cand = nullptr; int* d_level_cnt = nullptr;
         MORB_HIP(hipHostGetDevicePointer((void**)&d_cand, ex->h_cand, 0));
         MORB_HIP(hipHostGetDevicePointer((void**)&d_level_cnt, ex->h_level_cnt, 0));
-        hipLaunchKernelGGL(k_compact, dim3(ex->n_cams * ex->max_levels), dim3(1024), 0, ex->stream, (const LevelInfo*)ex->d_levels.p,
-                           (const int*)ex->d_cell_cnt.p, (const uint32_t*)ex->d_cell_items.p, ex->d_cell_off.p, d_cand, d_level_cnt,
-                           ex->d_cand_dev.p, ex->d_level_cnt_dev.p);
+        launch_compact(ex, ex->stream, d_cand, d_level_cnt);
         MORB_HIP(hipGetLastError());
         MORB_HIP(hipStreamSynchronize(ex->stream));
-        for (size_t b = 0; b < ex->levels.size(); ++b) ex->level_cnt_last[b] = ex->levels[b].w ? ex->h_level_cnt[b] : 0;
+        for (size_t b = 0; b < ex->geo.levels.size(); ++b) ex->level_cnt_last[b] = ex->geo.levels[b].w ? ex->h_level_cnt[b] : 0;
         ex->cand_valid = true;
     }
-    const LevelInfo& Lv = ex->levels[(size_t)cam * ex->max_levels + level];
+    const LevelInfo& Lv = ex->geo.levels[(size_t)cam * ex->max_levels + level];
     const int cnt = ex->level_cnt_last[(size_t)cam * ex->max_levels + level];
     *n = cnt;
     const uint32_t* cand = ex->h_cand + Lv.cand_base;

@@ -1037,7 +1037,7 @@ int morb::cross_enqueue_to(hipStream_t st, const uint8_t* d_desc, int n, const i
     const int qblocks = (nq + 63) / 64;
     const Top2Plan plan = top2_plan(nq, n);   // (nq, n may be capacities: the kernels take the counts from d_n then)
     const int S = plan.S;
-    if (plan.mfma) {   // matrix-core form (default from one tile of work on; orbm_use_matrix_cores(0) / MORB_TOP2_MFMA=0: popcount form)
+    if (plan.mfma) {   // matrix-core form (default from one tile of work on; orbm_use_matrix_cores(0): popcount form)
         int* p = (int*)scratch;
         int *p_idx = S > 1 ? p : o_idx, *p_best = S > 1 ? p + (size_t)S * nq : o_best, *p_second = S > 1 ? p + 2 * (size_t)S * nq : o_second;
         if (top2_fp4())

@@ -2,6 +2,8 @@
 
 * tests/san/san_oracle     ASan + UBSan over the CPU oracle and the product's host quadtree (csrc/octree.cpp) -- whole extractions on many
                            sizes / pitches / kinds of image, the two quadtrees against each other, the matcher restatements;
+* tests/san/san_plan       ASan + UBSan over the extractor's geometry planner (csrc/extract_plan.h): a list of rigs planned and checked for what
+                           the pyramid kernels index by -- level layout, resize taps, tile spans, form selection;
 * tests/san/tsan_rendezvous  TSan over the loopback exchange's rendezvous (csrc/loop_rendezvous.h) incl. members leaving mid-round;
 * host/test_host_san       ASan + UBSan over the C++ host classes and cv_compat.h: the cv::gemm known answers, the pose algebra, and the
                            three search drivers on the GPU tests' own cases up to the first device call (no GPU here: the call reports
@@ -48,6 +50,10 @@ def built():
 
 def test_oracle_and_host_quadtree_under_asan_ubsan(built):
     assert "san_oracle: 0 failures" in _run([os.path.join(SAN, "san_oracle")])
+
+
+def test_geometry_planner_under_asan_ubsan(built):
+    assert ", 0 failures" in _run([os.path.join(SAN, "san_plan")])
 
 
 def test_loopback_rendezvous_under_tsan(built):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Overlapped loop of one configuration (default configs[4]: 8 x 1080p @4000), a few dozen steps, for a kernel trace
-(rocprofv3 --kernel-trace) of the steady state; tools/experiments/trace_timeline.py prints one period of it per stream.
+(rocprofv3 --kernel-trace) of the steady state.
 usage: c4_overlap_trace.py [steps] [width height cameras features]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
