@@ -639,6 +639,53 @@ int orbm_lba_ldlt(int n, const double* H, const double* b, double* x);
 int orbm_lba_controller_trace(const double* chi, int n_chi, const double* hdiag6, const double* b6, int max_iter, int order, int max_steps,
                               double* out_lba, double* out_lm);
 
+/* -- global bundle adjustment: Optimizer::BundleAdjustment from its graph on -----------------------------------------------
+ * Optimizer::BundleAdjustment (reference src/Optimizer.cc:47-330; LoopClosing::RunGlobalBundleAdjustment: 10 iterations, no kernels;
+ * Tracking: 20 iterations, robust) between the graph and the recovery: ONE initializeOptimization(), ONE optimize(n_iterations),
+ * no chi-square test, no flags, no second optimisation.  The problem is orbm_lba_problem as it stands (the free poses -- every
+ * keyframe but mnId == 0 -- first, a CSR per point, the caller's edge order is the active-edge order); `bad` is IGNORED: the
+ * reference skips bad points before the graph.  robust != 0 puts the Huber kernel (sqrt(5.99) / sqrt(7.815)) on every edge, 0 on
+ * none.  A vertex without an active edge is not active and its estimate is returned as it came.  stop is polled exactly where g2o
+ * polls forceStopFlag (core/sparse_optimizer.cpp:376 at the head of an iteration, optimization_algorithm_levenberg.cpp:149 in the
+ * trial loop) and nowhere else -- the reference polls nowhere in this function; after a stop the estimates reached so far are
+ * returned, as the reference writes them.
+ * Everything up to the reduced system is the local BA's, statement for statement, with its stated deviations.  The reduced system:
+ * only the block pairs (i1 <= i2) of active free poses that share an active landmark, and every diagonal block, are computed; the
+ * other blocks are exactly 0.0 (nothing is subtracted from 0.0 there), so the matrix has the bytes of the full loop.  It is solved by
+ * orbm_ba_ldlt: deviation (a) of the local BA (dense, no pivoting, natural order, failure on a zero or non-finite pivot with x
+ * untouched, parity with Eigen not claimed), factorisation and forward substitution with the statements and summation order of
+ * orbm_lba_ldlt, but the BACKWARD substitution sums in DESCENDING j: s = 0; for j = n-1 .. i+1: s += L(j,i) y_j; x_i = y_i - s.
+ * With these orders the blocked execution across workgroups (csrc/ba_ldlt_dev.h: panels of ORBM_BA_PANEL columns, every element's sum
+ * carried from panel to panel, never split or re-associated) has the bytes of the sequential routine.  Nothing of the reference is
+ * restated in the solver, so both orders of the host routine use it. */
+enum { ORBM_BA_MAX_FREE = 1024, ORBM_BA_MAX_POSES = 4096, ORBM_BA_MAX_POINTS = 1 << 19, ORBM_BA_MAX_EDGES = 1 << 22 };
+enum { ORBM_BA_PANEL = 64 };
+typedef struct orbm_ba_result {
+    double* pose;                  /* n_poses x 7: the estimates, quaternion x y z w and translation                    */
+    float* Tcw;                    /* n_poses x 16: Converter::toCvMat of them, what SetPose / mTcwGBA receive          */
+    double* point;                 /* n_points x 3                                                                      */
+    float* point_f;                /* n_points x 3: what SetWorldPos / mPosGBA receive                                  */
+    orbm_pose_round round;         /* of the one optimize()                                                             */
+    int32_t optimised;             /* 1: optimize() had an active vertex                                                */
+    int32_t polls;                 /* calls of stop                                                                     */
+    int32_t active_poses, active_points, active_edges;   /* of initializeOptimization()                                 */
+    int32_t reserved[3];
+} orbm_ba_result;
+/* On the device: the local BA's kernels per edge, point and pose, k_ba_schur_pairs over the pairs that exist and the blocked LDL^T;
+ * one synchronisation per Levenberg trial.  A problem beyond a cap (ORBM_BA_MAX_*), or without an active free pose, runs through
+ * the host routine in DEVICE order inside the same call (orbm_debug_last_bundle_adjust).  Same bytes as
+ * orbm_bundle_adjust_host(..., ORBM_POSE_ORDER_DEVICE). */
+int orbm_bundle_adjust(orbm_matcher* m, const orbm_lba_problem* problem, int n_iterations, int robust, orbm_lba_stop_fn stop, void* stop_ctx,
+                       orbm_ba_result* result);
+/* The same statements on the host, no device needed, in either order. */
+int orbm_bundle_adjust_host(const orbm_lba_problem* problem, int n_iterations, int robust, orbm_lba_stop_fn stop, void* stop_ctx, int order,
+                            orbm_ba_result* result);
+/* The solver of the reduced system, on the host: the definition.  H n x n row-major (upper triangle read), n <= 6 ORBM_BA_MAX_FREE;
+ * returns 1 and writes x, or 0 on a zero or non-finite pivot (x untouched). */
+int orbm_ba_ldlt(int n, const double* H, const double* b, double* x);
+/* (test hook) The device solver alone on host arrays: the same bytes, the same return values; negative on an error. */
+int orbm_ba_ldlt_device(orbm_matcher* m, int n, const double* H, const double* b, double* x);
+
 /* -- PnPsolver: every EPnP RANSAC hypothesis of a relocalisation in one call ---------------------------------------------
  * PnPsolver (reference src/PnPsolver.cc) between SearchByBoW_cam1 and Optimizer::PoseOptimization of Tracking::Relocalization: per
  * hypothesis the four-point EPnP (compute_pose: choose_control_points, compute_barycentric_coordinates, M^T M, its 12x12 SVD, the three

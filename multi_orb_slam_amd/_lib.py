@@ -51,6 +51,7 @@ SIM3OPT_CAP, SIM3OPT_MAX_BATCH = 8192, 64
 LBA_MAX_FREE, LBA_MAX_POSES, LBA_MAX_POINTS, LBA_MAX_EDGES = 64, 4096, 65536, 262144
 LBA_ENDED_COMPLETE, LBA_ENDED_STOPPED_AT_START, LBA_ENDED_NO_SECOND = 0, 1, 2
 LBA_FLAG_LEVEL1, LBA_FLAG_ERASE = 1, 2
+BA_MAX_FREE, BA_MAX_POSES, BA_MAX_POINTS, BA_MAX_EDGES, BA_PANEL = 1024, 4096, 1 << 19, 1 << 22, 64
 PNP_PROBLEM_DTYPE = np.dtype([("fu", "<f8"), ("fv", "<f8"), ("uc", "<f8"), ("vc", "<f8"), ("min_inliers", "<i4"), ("best_start", "<i4")])   # orbm_pnp_problem
 PNP_HYP_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("rep_error", "<f8"), ("choice", "<i4"), ("n_inliers", "<i4"), ("flags", "<i4"),
                           ("reserved", "<i4")])   # orbm_pnp_hyp
@@ -86,6 +87,12 @@ class LbaResult(C.Structure):  # orbm_lba_result
                 ("round", PoseRound * 2), ("ended", C.c_int32), ("optimisations", C.c_int32), ("polls", C.c_int32), ("n_level1", C.c_int32),
                 ("n_erase", C.c_int32), ("active_poses", C.c_int32 * 2), ("active_points", C.c_int32 * 2), ("active_edges", C.c_int32 * 2),
                 ("reserved", C.c_int32)]
+
+
+class BaResult(C.Structure):  # orbm_ba_result
+    _fields_ = [("pose", C.c_void_p), ("Tcw", C.c_void_p), ("point", C.c_void_p), ("point_f", C.c_void_p), ("round", PoseRound),
+                ("optimised", C.c_int32), ("polls", C.c_int32), ("active_poses", C.c_int32), ("active_points", C.c_int32),
+                ("active_edges", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 LBA_STOP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)   # orbm_lba_stop_fn
@@ -333,6 +340,11 @@ def lib():
     L.orbm_lba_ldlt.argtypes = [i32, vp, vp, vp]
     L.orbm_lba_controller_trace.argtypes = [vp, i32, vp, vp, i32, i32, i32, vp, vp]
     L.orbm_debug_last_local_ba.argtypes = [vp, vp]
+    L.orbm_bundle_adjust.argtypes = [vp, vp, i32, i32, LBA_STOP_FN, vp, vp]
+    L.orbm_bundle_adjust_host.argtypes = [vp, i32, i32, LBA_STOP_FN, vp, i32, vp]
+    L.orbm_ba_ldlt.argtypes = [i32, vp, vp, vp]
+    L.orbm_ba_ldlt_device.argtypes = [vp, i32, vp, vp, vp]
+    L.orbm_debug_last_bundle_adjust.argtypes = [vp, vp]
     L.orbm_pnp_ransac.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbm_pnp_ransac_host.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbm_pnp_walk.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]

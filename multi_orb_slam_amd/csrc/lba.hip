@@ -15,6 +15,11 @@
 // k_lba_schur, k_lba_solve, k_lba_update, k_lba_edges<false>, k_lba_ctl_trial, which leaves one 4-byte command word in mapped memory.  Every
 // launch ends on its own: no kernel waits for another, no atomics, no order that depends on arrival.  Accepting a trial is a choice of
 // buffer (LbaCtl::cur).  No libm function runs in a kernel.
+// The global bundle adjustment (Optimizer::BundleAdjustment, reference src/Optimizer.cc:47-330; include/orbm.h "global bundle
+// adjustment") is the same steps and backends in another sequence, ba_flow: one optimisation, the kernels on every edge or on none.
+// Its backends run `global`: the reduced system over the block pairs that exist (ba_block_pairs; k_ba_schur_pairs, the rest filled with
+// 0.0 once) and, for up to 6 * ORBM_BA_MAX_FREE rows, ba_ldlt_host / ba_ldlt_dev.h's blocked LDL^T across workgroups in place of
+// lba_ldlt_host / k_lba_solve.  Nothing the local BA computes changes: its flow, its kernels and its caps are as they were.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -30,6 +35,7 @@
 #include "g2o_dev.h"
 #include "lm_dev.h"
 #include "lba_dev.h"
+#include "ba_ldlt_dev.h"
 #include "stage_pack.h"
 
 namespace {
@@ -37,6 +43,7 @@ namespace {
 constexpr int LBA_SOLVE_T = 512;      // lanes of k_lba_solve: one per row of the reduced system (6 * ORBM_LBA_MAX_FREE = 384 rows)
 constexpr int LBA_MAX_N = 6 * ORBM_LBA_MAX_FREE;
 static_assert(LBA_MAX_N <= LBA_SOLVE_T, "one lane per row");
+static_assert(BA_PANEL == ORBM_BA_PANEL, "the panel width the header exports");
 static_assert(LBA_T == LM_T, "the chi2 partial is lm_dev.h's tree");
 
 // Everything a step reads and writes, as raw pointers: the host routine's vectors or the device's buffers.
@@ -225,6 +232,7 @@ struct LbaStructure {                    // initializeOptimization(): per optimi
     std::vector<uint8_t> active;
     std::vector<int32_t> pose_h, point_h, pose_first, pose_edge, srow, nfree;
     int na = 0, nl = 0, n_active = 0;
+    std::vector<int32_t> pairs;          // (global BA) the blocks (i1 <= i2) of the reduced system that exist, sorted, two entries each
 };
 
 int lba_validate(const orbm_lba_problem* P, const orbm_lba_result* R) {
@@ -246,13 +254,13 @@ int lba_validate(const orbm_lba_problem* P, const orbm_lba_result* R) {
         }
     return ORB_OK;
 }
-void lba_graph(const orbm_lba_problem* P, LbaGraph& G) {
+void lba_graph(const orbm_lba_problem* P, LbaGraph& G, bool use_bad = true) {
     G.P = P;
     G.n_edges = P->first[P->n_points];
     G.edge_point.resize((size_t)std::max(G.n_edges, 1));
     for (int l = 0; l < P->n_points; ++l) for (int e = P->first[l]; e < P->first[l + 1]; ++e) G.edge_point[e] = l;
     G.bad.assign((size_t)std::max(P->n_points, 1), 0);
-    if (P->bad) for (int l = 0; l < P->n_points; ++l) G.bad[l] = P->bad[l] ? 1 : 0;
+    if (P->bad && use_bad) for (int l = 0; l < P->n_points; ++l) G.bad[l] = P->bad[l] ? 1 : 0;
     G.pose0.resize(7 * (size_t)std::max(P->n_poses, 1)); G.point0.resize(3 * (size_t)std::max(P->n_points, 1));
     for (int p = 0; p < P->n_poses; ++p) {
         SE3Quat T;
@@ -303,6 +311,25 @@ void lba_structure(const LbaGraph& G, const uint8_t* flags, LbaStructure& T) {
                   [&](int32_t a, int32_t b) { return T.pose_h[P->edge_pose[a]] < T.pose_h[P->edge_pose[b]]; });
     }
 }
+// The global BA's reduced system: every diagonal block, and the pairs (i1 < i2) of active free poses that share an active landmark
+// (srow is a landmark's free poses in ascending hessian index).  For every other pair lba_schur_entry finds nothing to subtract from
+// h = 0.0, so the block is the zeros the buffer is filled with once per optimisation.
+void ba_block_pairs(const LbaGraph& G, LbaStructure& T) {
+    const orbm_lba_problem* P = G.P;
+    const size_t na = (size_t)T.na;
+    std::vector<uint8_t> hit(std::max<size_t>(na * na, 1), 0);
+    for (size_t i = 0; i < na; ++i) hit[i * na + i] = 1;
+    for (int l = 0; l < P->n_points; ++l) {
+        const int s0 = P->first[l], s1 = s0 + T.nfree[l];
+        for (int a = s0; a < s1; ++a) {
+            const size_t ha = (size_t)T.pose_h[P->edge_pose[T.srow[a]]];
+            for (int b = a + 1; b < s1; ++b) hit[ha * na + (size_t)T.pose_h[P->edge_pose[T.srow[b]]]] = 1;
+        }
+    }
+    T.pairs.clear();
+    for (size_t i1 = 0; i1 < na; ++i1)
+        for (size_t i2 = i1; i2 < na; ++i2) if (hit[i1 * na + i2]) { T.pairs.push_back((int32_t)i1); T.pairs.push_back((int32_t)i2); }
+}
 
 // Converter::toCvMat(SE3Quat) (g2o_dev.h's se3_to_cv), Converter::toCvMat(Vector3d)
 void lba_write_result(const orbm_lba_problem* P, const double* pose, const double* point, orbm_lba_result* R) {
@@ -327,6 +354,23 @@ __host__ __device__ inline uint32_t lba_command_word(const LbaCtl& S, int seq) {
 // Optimizer.cc:1204-1309 around g2o's optimize() (core/sparse_optimizer.cpp:354-419).  The backend supplies: begin_optimisation (returns
 // the number of active vertices), iteration (solve() up to and including its first trial), trial, iter_end (the trial loop was left by
 // the stop flag), classify, finish.
+// g2o's optimize() loop (core/sparse_optimizer.cpp:376-414) with its two polls, after begin_optimisation: what both flows share
+template <class Backend, class Poll>
+int lba_optimise(Backend& B, Poll& poll, int max_iter) {
+    int rc;
+    LbaReport rep = {0, max_iter > 0 ? 1 : 0, 1, 0};
+    // for (int i=0; i<iterations && ! terminate() && ok; i++)
+    while (rep.more) {
+        if (poll()) break;
+        if (!rep.ok) break;
+        if ((rc = B.iteration(&rep))) return rc;
+        while (rep.want_trial) {                      // `while (rho<0 && qmax < 10 && ! _optimizer->terminate())`
+            if (poll()) { if ((rc = B.iter_end(&rep))) return rc; break; }
+            if ((rc = B.trial(&rep))) return rc;
+        }
+    }
+    return ORB_OK;
+}
 template <class Backend>
 int lba_flow(Backend& B, orbm_lba_stop_fn stop, void* ctx, orbm_lba_result* R) {
     int polls = 0, rc;
@@ -340,17 +384,7 @@ int lba_flow(Backend& B, orbm_lba_stop_fn stop, void* ctx, orbm_lba_result* R) {
         if ((rc = B.begin_optimisation(stage, stage ? 10 : 5, &n_vertices, R))) return rc;
         if (n_vertices > 0) {                                 // else `_ivMap.size() == 0`: optimize() returns -1 before its loop
             R->optimisations = stage + 1;
-            LbaReport rep = {0, 1, 1, 0};
-            // for (int i=0; i<iterations && ! terminate() && ok; i++)
-            while (rep.more) {
-                if (poll()) break;
-                if (!rep.ok) break;
-                if ((rc = B.iteration(&rep))) return rc;
-                while (rep.want_trial) {                      // `while (rho<0 && qmax < 10 && ! _optimizer->terminate())`
-                    if (poll()) { if ((rc = B.iter_end(&rep))) return rc; break; }
-                    if ((rc = B.trial(&rep))) return rc;
-                }
-            }
+            if ((rc = lba_optimise(B, poll, stage ? 10 : 5))) return rc;
         }
         if (stage == 0) {
             if (poll()) { R->ended = ORBM_LBA_ENDED_NO_SECOND; break; }   // :1217 bDoMore = false
@@ -358,6 +392,25 @@ int lba_flow(Backend& B, orbm_lba_stop_fn stop, void* ctx, orbm_lba_result* R) {
         }
     }
     if (R->ended != ORBM_LBA_ENDED_STOPPED_AT_START && (rc = B.classify(ORBM_LBA_FLAG_ERASE))) return rc;
+    R->polls = polls;
+    return B.finish(R);
+}
+// Optimizer::BundleAdjustment (Optimizer.cc:300-302): ONE initializeOptimization(), ONE optimize(nIterations), no test, no second
+// optimisation; the reference polls nowhere, g2o where it always does.  The Huber kernels are on every edge or on none, the two forms
+// lba_pass_edge has: stage 0 is "every edge behind its kernel", stage 1 with no bad point "no kernel" -- so `robust` chooses the stage,
+// and the round and the active counts of that stage are the call's.
+template <class Backend>
+int ba_flow(Backend& B, int n_iterations, int robust, orbm_lba_stop_fn stop, void* ctx, orbm_lba_result* R) {
+    int polls = 0, rc;
+    auto poll = [&]() -> bool { if (!stop) return false; ++polls; return stop(ctx) != 0; };
+    R->ended = ORBM_LBA_ENDED_COMPLETE; R->optimisations = 0; R->reserved = 0;
+    for (int s = 0; s < 2; ++s) { R->active_poses[s] = 0; R->active_points[s] = 0; R->active_edges[s] = 0; }
+    int n_vertices = 0;
+    if ((rc = B.begin_optimisation(robust ? 0 : 1, n_iterations, &n_vertices, R))) return rc;
+    if (n_vertices > 0) {
+        R->optimisations = 1;
+        if ((rc = lba_optimise(B, poll, n_iterations))) return rc;
+    }
     R->polls = polls;
     return B.finish(R);
 }
@@ -372,7 +425,8 @@ double lba_partial_host(const double* leaf, int n) {
 
 // The reduced system: dense LDL^T without pivoting in the natural order (deviation (a)).  Hs: n x n row-major, its upper triangle is
 // read; Lt[k n + i] = L(i, k); fails on a zero or non-finite pivot; x is written only on success.
-bool lba_ldlt_host(int n, const double* Hs, const double* bs, double* Lt, double* d, double* temp, double* y, double* x) {
+// (the factorisation and the forward substitution, y = D^-1 L^-1 b: what the local and the global BA's routines share)
+bool lba_ldlt_factor_forward(int n, const double* Hs, const double* bs, double* Lt, double* d, double* temp, double* y) {
     for (int k = 0; k < n; ++k) {
         for (int j = 0; j < k; ++j) temp[j] = d[j] * Lt[(size_t)j * n + k];
         double s = 0.0;
@@ -388,7 +442,20 @@ bool lba_ldlt_host(int n, const double* Hs, const double* bs, double* Lt, double
     }
     for (int i = 0; i < n; ++i) { double s = 0.0; for (int j = 0; j < i; ++j) s += Lt[(size_t)j * n + i] * y[j]; y[i] = bs[i] - s; }
     for (int i = 0; i < n; ++i) y[i] = y[i] / d[i];
+    return true;
+}
+bool lba_ldlt_host(int n, const double* Hs, const double* bs, double* Lt, double* d, double* temp, double* y, double* x) {
+    if (!lba_ldlt_factor_forward(n, Hs, bs, Lt, d, temp, y)) return false;
     for (int i = n - 1; i >= 0; --i) { double s = 0.0; for (int j = i + 1; j < n; ++j) s += Lt[(size_t)i * n + j] * y[j]; y[i] = y[i] - s; }
+    for (int i = 0; i < n; ++i) x[i] = y[i];
+    return true;
+}
+// The global BA's routine, THE definition of what ba_ldlt_dev.h's kernels compute: the same factorisation and forward substitution;
+// the backward substitution adds a row's terms in DESCENDING j, the far ones first, so that a blocked execution that walks the panels
+// from the last to the first carries each row's sum in the order it is written here.
+bool ba_ldlt_host(int n, const double* Hs, const double* bs, double* Lt, double* d, double* temp, double* y, double* x) {
+    if (!lba_ldlt_factor_forward(n, Hs, bs, Lt, d, temp, y)) return false;
+    for (int i = n - 1; i >= 0; --i) { double s = 0.0; for (int j = n - 1; j > i; --j) s += Lt[(size_t)i * n + j] * y[j]; y[i] = y[i] - s; }
     for (int i = 0; i < n; ++i) x[i] = y[i];
     return true;
 }
@@ -397,20 +464,22 @@ bool lba_ldlt_host(int n, const double* Hs, const double* bs, double* Lt, double
 struct LbaHost {
     const LbaGraph& G;
     int order;
+    bool global;                         // the global BA: the reduced system over the pairs that exist, ba_ldlt_host, sized per optimisation
     LbaStructure T;
     LbaView V;
     LbaCtl S;
     std::vector<double> pose[2], point[2], E, chi2, Hll, bl, Dinv, db, Hpp, bp, Hs, bs, Lt, d, x, sterm, temp, y, leaf;
     uint8_t* flags;
 
-    LbaHost(const LbaGraph& g, int ord, uint8_t* fl) : G(g), order(ord), flags(fl) {
+    LbaHost(const LbaGraph& g, int ord, uint8_t* fl, bool glob = false) : G(g), order(ord), global(glob), flags(fl) {
         const orbm_lba_problem* P = G.P;
         const size_t ne = (size_t)std::max(G.n_edges, 1), nl = (size_t)std::max(P->n_points, 1);
         for (int b = 0; b < 2; ++b) { pose[b] = G.pose0; point[b] = G.point0; }
         E.assign(LBA_EDGE_DOUBLES * ne, 0.0); chi2.assign(ne, 0.0);
         Hll.assign(9 * nl, 0.0); bl.assign(3 * nl, 0.0); Dinv.assign(9 * nl, 0.0); db.assign(3 * nl, 0.0);
         const size_t nf = (size_t)std::max(P->n_free, 1), n = 6 * nf;
-        Hpp.assign(36 * nf, 0.0); bp.assign(6 * nf, 0.0); Hs.assign(n * n, 0.0); bs.assign(n, 0.0); Lt.assign(n * n, 0.0); d.assign(n, 0.0);
+        const size_t nn = global ? 1 : n * n;
+        Hpp.assign(36 * nf, 0.0); bp.assign(6 * nf, 0.0); Hs.assign(nn, 0.0); bs.assign(n, 0.0); Lt.assign(nn, 0.0); d.assign(n, 0.0);
         temp.assign(n, 0.0); y.assign(n, 0.0);
         x.assign(n + 3 * nl, 0.0); sterm.assign(n + 3 * nl, 0.0);
         leaf.assign(ne, 0.0);
@@ -427,6 +496,12 @@ struct LbaHost {
     }
     int begin_optimisation(int stage, int max_iter, int* n_vertices, orbm_lba_result* R) {
         lba_structure(G, flags, T);
+        if (global) {
+            ba_block_pairs(G, T);
+            const size_t n = 6 * (size_t)T.na;
+            Hs.assign(std::max<size_t>(n * n, 1), 0.0); Lt.assign(std::max<size_t>(n * n, 1), 0.0);
+            V.Hs = Hs.data(); V.Lt = Lt.data();
+        }
         V.stage = stage; V.na = T.na; V.nl = T.nl; V.nx = 6 * T.na + 3 * T.nl;
         V.active = T.active.data(); V.pose_h = T.pose_h.data(); V.point_h = T.point_h.data(); V.pose_first = T.pose_first.data();
         V.pose_edge = T.pose_edge.data(); V.srow = T.srow.data(); V.nfree = T.nfree.data();
@@ -463,12 +538,15 @@ struct LbaHost {
     int trial(LbaReport* rep) {
         const int n = 6 * V.na, buf = S.cur ^ 1;
         for (int l = 0; l < V.n_points; ++l) lba_point_damp_at(V, l, S.lambda);
+        auto block = [&](int i1, int i2) {
+            for (int r = 0; r < 6; ++r) for (int c = 0; c < 6; ++c) Hs[(size_t)(6 * i1 + r) * n + 6 * i2 + c] = lba_schur_entry(V, S.lambda, i1, i2, r, c);
+        };
+        if (global) for (size_t q = 0; q < T.pairs.size(); q += 2) block(T.pairs[q], T.pairs[q + 1]);
         for (int i1 = 0; i1 < V.na; ++i1) {
-            for (int i2 = i1; i2 < V.na; ++i2)
-                for (int r = 0; r < 6; ++r) for (int c = 0; c < 6; ++c) Hs[(size_t)(6 * i1 + r) * n + 6 * i2 + c] = lba_schur_entry(V, S.lambda, i1, i2, r, c);
+            if (!global) for (int i2 = i1; i2 < V.na; ++i2) block(i1, i2);
             for (int r = 0; r < 6; ++r) bs[6 * i1 + r] = lba_schur_b(V, i1, r);
         }
-        S.ok2 = lba_ldlt_host(n, Hs.data(), bs.data(), Lt.data(), d.data(), temp.data(), y.data(), x.data()) ? 1 : 0;
+        S.ok2 = (global ? ba_ldlt_host : lba_ldlt_host)(n, Hs.data(), bs.data(), Lt.data(), d.data(), temp.data(), y.data(), x.data()) ? 1 : 0;
         for (int l = 0; l < V.n_points; ++l) lba_point_update(V, l, S.ok2, S.lambda, buf);
         for (int p = 0; p < V.n_poses; ++p) lba_pose_update(V, p, S.lambda, order, buf);
         const double temp_chi = pass<false>(buf);
@@ -570,6 +648,16 @@ __global__ __launch_bounds__(64) void k_lba_schur(LbaView V) {
     const double lambda = V.S->lambda;
     if (t < 36) V.Hs[(size_t)(6 * i1 + t / 6) * n + 6 * i2 + t % 6] = lba_schur_entry(V, lambda, i1, i2, t / 6, t % 6);
     else if (t < 42 && i1 == i2) V.bs[6 * i1 + t - 36] = lba_schur_b(V, i1, t - 36);
+}
+// (global BA) the same wave per block, for the listed pairs only; the rest of the upper triangle is k_ba_fill_zero's
+__global__ __launch_bounds__(64) void k_ba_schur_pairs(LbaView V, const int32_t* pairs) {
+    const int i1 = pairs[2 * (size_t)blockIdx.x], i2 = pairs[2 * (size_t)blockIdx.x + 1], n = 6 * V.na, t = threadIdx.x;
+    const double lambda = V.S->lambda;
+    if (t < 36) V.Hs[(size_t)(6 * i1 + t / 6) * n + 6 * i2 + t % 6] = lba_schur_entry(V, lambda, i1, i2, t / 6, t % 6);
+    else if (t < 42 && i1 == i2) V.bs[6 * i1 + t - 36] = lba_schur_b(V, i1, t - 36);
+}
+__global__ __launch_bounds__(LBA_T) void k_ba_fill_zero(double* p, size_t count) {
+    for (size_t k = (size_t)blockIdx.x * LBA_T + threadIdx.x; k < count; k += (size_t)gridDim.x * LBA_T) p[k] = 0.0;
 }
 // One workgroup, lane i owns row i of the reduced system: the statements of lba_ldlt_host.  Column k: temp = D L(k, .), every row at
 // or below k forms its inner product in ascending j, row k's is the pivot; the forward substitution accumulates L(i, j) y(j) as y(j)
@@ -677,8 +765,14 @@ struct LbaDevice {
     uint8_t* flags_h;
     double* pose_h; double* pose_d; double* point_h; double* point_d;
     int n_partials, seq = 0, launches = 0, syncs = 0;
+    // the global BA: T is the caller's (one initializeOptimization() per call, known before the buffers are laid out), the reduced
+    // system has 6 T.na rows, its blocks are T.pairs, its solver ba_ldlt_dev.h's
+    bool global = false;
+    int i_pairs = 0;
+    BaSolve A;
 
     LbaDevice(orbm_matcher* mm, const LbaGraph& g) : m(mm), G(g) {}
+    LbaDevice(orbm_matcher* mm, const LbaGraph& g, const LbaStructure& T0) : m(mm), G(g), T(T0), global(true) {}
 
     int sync(LbaReport* rep) {
         MORB_HIP(hipGetLastError());
@@ -694,7 +788,7 @@ struct LbaDevice {
     int open() {
         const orbm_lba_problem* P = G.P;
         const size_t ne = (size_t)std::max(G.n_edges, 1), np = (size_t)std::max(P->n_poses, 1), nl = (size_t)std::max(P->n_points, 1),
-                     nf = (size_t)std::max(P->n_free, 1), n = 6 * nf;
+                     nf = (size_t)std::max(P->n_free, 1), n6 = 6 * nf, n = global ? 6 * (size_t)std::max(T.na, 1) : n6;
         MORB_HIP(hipSetDevice(m->device));
         // the staged block: the graph, then the index arrays of an optimisation (written in place before either)
         const int i_K = pk.add(P->K, (size_t)P->n_poses * 20), i_first = pk.add(P->first, (size_t)(P->n_points + 1) * 4),
@@ -705,6 +799,7 @@ struct LbaDevice {
         i_active = pk.add_in_place(ne); i_pose_h = pk.add_in_place(np * 4); i_point_h = pk.add_in_place(nl * 4);
         i_pose_first = pk.add_in_place((nf + 1) * 4); i_pose_edge = pk.add_in_place(ne * 4); i_srow = pk.add_in_place(ne * 4);
         i_nfree = pk.add_in_place(nl * 4);
+        if (global) i_pairs = pk.add_in_place(std::max<size_t>(T.pairs.size(), 2) * 4);
         int rc;
         blk_.emplace(pk.open(m->lba.stage, &rc));
         if (rc) return rc;
@@ -714,8 +809,9 @@ struct LbaDevice {
         const size_t o_pose0 = L.take(7 * np * 8), o_pose1 = L.take(7 * np * 8), o_pt0 = L.take(3 * nl * 8), o_pt1 = L.take(3 * nl * 8),
                      o_E = L.take((size_t)LBA_EDGE_DOUBLES * ne * 8), o_chi2 = L.take(ne * 8), o_Hll = L.take(9 * nl * 8), o_bl = L.take(3 * nl * 8),
                      o_Dinv = L.take(9 * nl * 8), o_db = L.take(3 * nl * 8), o_Hpp = L.take(36 * nf * 8), o_bp = L.take(6 * nf * 8),
-                     o_Hs = L.take(n * n * 8), o_bs = L.take(n * 8), o_Lt = L.take(n * n * 8), o_d = L.take(n * 8), o_x = L.take((n + 3 * nl) * 8),
-                     o_st = L.take((n + 3 * nl) * 8), o_part = L.take((size_t)lba_blocks(ne) * 8), o_S = L.take(sizeof(LbaCtl));
+                     o_Hs = L.take(n * n * 8), o_bs = L.take(n * 8), o_Lt = L.take(n * n * 8), o_d = L.take(n * 8), o_x = L.take((n6 + 3 * nl) * 8),
+                     o_st = L.take((n6 + 3 * nl) * 8), o_part = L.take((size_t)lba_blocks(ne) * 8), o_S = L.take(sizeof(LbaCtl));
+        const size_t o_y = global ? L.take(n * 8) : 0, o_carry = global ? L.take(n * 8) : 0, o_fail = global ? L.take(16) : 0;
         if ((rc = m->lba.scratch.reserve(L.off))) return rc;
         // what the host reads: the command word, the controller's record, the flags, the estimates (mapped pinned)
         morb::BlockLayout O;
@@ -739,6 +835,7 @@ struct LbaDevice {
         V.Hs = (double*)(sp + o_Hs); V.bs = (double*)(sp + o_bs); V.Lt = (double*)(sp + o_Lt); V.d = (double*)(sp + o_d);
         V.x = (double*)(sp + o_x); V.sterm = (double*)(sp + o_st); V.partial = (double*)(sp + o_part); V.S = (LbaCtl*)(sp + o_S);
         V.flags = dp + q_flags;
+        if (global) A = BaSolve{0, V.Hs, V.bs, V.Lt, V.d, (double*)(sp + o_y), (double*)(sp + o_carry), V.x, (int*)(sp + o_fail), &V.S->ok2};
         n_partials = G.n_edges > 0 ? (int)lba_blocks(ne) : 0;
         blk.publish();
         LbaCtl S0;
@@ -750,9 +847,10 @@ struct LbaDevice {
     int begin_optimisation(int stage, int max_iter, int* n_vertices, orbm_lba_result* R) {
         int rc;
         if ((rc = sync(nullptr))) return rc;                  // the flags of the first test have arrived; nothing reads the index arrays
-        lba_structure(G, flags_h, T);
+        if (!global) lba_structure(G, flags_h, T);
         const orbm_lba_problem* P = G.P;
         const morb::StagePack::Block& blk = *blk_;
+        if (global) memcpy(blk.host<int32_t>(i_pairs), T.pairs.data(), T.pairs.size() * 4);
         memcpy(blk.host<uint8_t>(i_active), T.active.data(), (size_t)G.n_edges);
         memcpy(blk.host<int32_t>(i_pose_h), T.pose_h.data(), (size_t)P->n_poses * 4);
         memcpy(blk.host<int32_t>(i_point_h), T.point_h.data(), (size_t)P->n_points * 4);
@@ -765,14 +863,25 @@ struct LbaDevice {
         R->active_poses[stage] = T.na; R->active_points[stage] = T.nl; R->active_edges[stage] = T.n_active;
         hipLaunchKernelGGL(k_lba_begin_optimisation, dim3(1), dim3(LBA_T), 0, m->stream, V, max_iter);
         ++launches;
+        if (global) {
+            A.n = 6 * T.na;
+            const size_t nn = (size_t)A.n * A.n;
+            hipLaunchKernelGGL(k_ba_fill_zero, dim3(std::min(lba_blocks(nn), 4096u)), dim3(LBA_T), 0, m->stream, V.Hs, nn);
+            ++launches;
+        }
         *n_vertices = T.na + T.nl;
         return ORB_OK;
     }
     void enqueue_trial() {
         hipStream_t st = m->stream;
         hipLaunchKernelGGL(k_lba_point_damp, dim3(lba_blocks((size_t)V.n_points)), dim3(LBA_T), 0, st, V);
-        if (V.na > 0) hipLaunchKernelGGL(k_lba_schur, dim3((unsigned)(V.na * (V.na + 1) / 2)), dim3(64), 0, st, V);
-        hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(LBA_SOLVE_T), 0, st, V);
+        if (global) {
+            if (V.na > 0) hipLaunchKernelGGL(k_ba_schur_pairs, dim3((unsigned)(T.pairs.size() / 2)), dim3(64), 0, st, V, blk_->dev<int32_t>(i_pairs));
+            launches += ba_ldlt_enqueue(st, A) - 1;          // (the count below holds one solve kernel)
+        } else {
+            if (V.na > 0) hipLaunchKernelGGL(k_lba_schur, dim3((unsigned)(V.na * (V.na + 1) / 2)), dim3(64), 0, st, V);
+            hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(LBA_SOLVE_T), 0, st, V);
+        }
         hipLaunchKernelGGL(k_lba_update, dim3(lba_blocks((size_t)V.n_points + (size_t)V.n_poses)), dim3(LBA_T), 0, st, V);
         hipLaunchKernelGGL(k_lba_edges<false>, dim3(lba_blocks((size_t)V.n_edges)), dim3(LBA_T), 0, st, V, G.C);
         hipLaunchKernelGGL(k_lba_ctl_trial, dim3(1), dim3(LBA_T), 0, st, V, n_partials, rep_d, ++seq);
@@ -820,9 +929,115 @@ struct TraceCtl : LmState<6> {
     __host__ __device__ void lm_linearise() { cmd = LM_CMD_FULL; }
 };
 
+// ---- the global BA's calls ---------------------------------------------------------------------------------------------------------------
+// The backends write an orbm_lba_result: the call keeps one whose arrays are the caller's and whose flags (never set: nothing is
+// tested) are its own, and takes the stage's record from it.
+struct BaCall {
+    std::vector<uint8_t> flags;
+    orbm_lba_result L;
+    int rc;
+    BaCall(const orbm_lba_problem* P, int n_iterations, const orbm_ba_result* R) : flags(1, 0) {
+        memset(&L, 0, sizeof(L));
+        rc = check(P, n_iterations, R);
+        if (rc) return;
+        flags.assign((size_t)std::max(P->first[P->n_points], 1), 0);
+        L.flags = flags.data();
+    }
+    int check(const orbm_lba_problem* P, int n_iterations, const orbm_ba_result* R) {
+        MORB_ARG(P != nullptr && R != nullptr && n_iterations >= 0);
+        L.pose = R->pose; L.Tcw = R->Tcw; L.point = R->point; L.point_f = R->point_f; L.flags = flags.data();
+        return lba_validate(P, &L);
+    }
+    void take(int robust, orbm_ba_result* R) const {
+        const int s = robust ? 0 : 1;
+        R->round = L.round[s]; R->optimised = L.optimisations; R->polls = L.polls;
+        R->active_poses = L.active_poses[s]; R->active_points = L.active_points[s]; R->active_edges = L.active_edges[s];
+        for (int k = 0; k < 3; ++k) R->reserved[k] = 0;
+    }
+};
+int ba_host(const LbaGraph& G, int n_iterations, int robust, orbm_lba_stop_fn stop, void* ctx, int order, BaCall& call, orbm_ba_result* R) {
+    LbaHost H(G, order, call.flags.data(), true);
+    const int rc = ba_flow(H, n_iterations, robust, stop, ctx, &call.L);
+    if (rc) return rc;
+    call.take(robust, R);
+    return ORB_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int orbm_bundle_adjust_host(const orbm_lba_problem* problem, int n_iterations, int robust, orbm_lba_stop_fn stop, void* stop_ctx, int order,
+                            orbm_ba_result* result) {
+    BaCall call(problem, n_iterations, result);
+    if (call.rc) return call.rc;
+    if (order != ORBM_POSE_ORDER_INDEX && order != ORBM_POSE_ORDER_DEVICE) { morb::set_error("order = %d", order); return ORB_E_ARG; }
+    LbaGraph G;
+    lba_graph(problem, G, false);
+    return ba_host(G, n_iterations, robust, stop, stop_ctx, order, call, result);
+}
+
+int orbm_bundle_adjust(orbm_matcher* m, const orbm_lba_problem* problem, int n_iterations, int robust, orbm_lba_stop_fn stop, void* stop_ctx,
+                       orbm_ba_result* result) {
+    MORB_ARG(m != nullptr);
+    BaCall call(problem, n_iterations, result);
+    int rc = call.rc;
+    if (rc) return rc;
+    const int ne = problem->first[problem->n_points];
+    const bool beyond = problem->n_free > ORBM_BA_MAX_FREE || problem->n_poses > ORBM_BA_MAX_POSES || problem->n_points > ORBM_BA_MAX_POINTS ||
+                        ne > ORBM_BA_MAX_EDGES;
+    LbaGraph G;
+    lba_graph(problem, G, false);
+    LbaStructure T;
+    if (!beyond) lba_structure(G, call.flags.data(), T);      // the call's ONE initializeOptimization(): no flag is ever set
+    for (int k = 0; k < 8; ++k) m->last_ba[k] = 0;
+    if (beyond || T.na == 0) {
+        rc = ba_host(G, n_iterations, robust, stop, stop_ctx, ORBM_POSE_ORDER_DEVICE, call, result);
+        m->last_ba[0] = beyond ? 1 : 2; m->last_ba[3] = call.L.polls;
+        return rc;
+    }
+    ba_block_pairs(G, T);
+    LbaDevice D(m, G, T);
+    if ((rc = D.open())) return rc;
+    rc = ba_flow(D, n_iterations, robust, stop, stop_ctx, &call.L);
+    if (rc) { (void)hipStreamSynchronize(m->stream); return rc; }
+    call.take(robust, result);
+    m->last_ba[1] = D.launches; m->last_ba[2] = D.syncs; m->last_ba[3] = result->polls;
+    m->last_ba[4] = (int)(T.pairs.size() / 2); m->last_ba[5] = T.na * (T.na + 1) / 2; m->last_ba[6] = (6 * T.na + BA_PANEL - 1) / BA_PANEL;
+    return ORB_OK;
+}
+
+int orbm_ba_ldlt(int n, const double* H, const double* b, double* x) {
+    MORB_ARG(n >= 0 && n <= 6 * ORBM_BA_MAX_FREE && (n == 0 || (H && b && x)));
+    std::vector<double> Lt((size_t)n * n + 1), d((size_t)n + 1), temp((size_t)n + 1), y((size_t)n + 1);
+    return ba_ldlt_host(n, H, b, Lt.data(), d.data(), temp.data(), y.data(), x) ? 1 : 0;
+}
+
+int orbm_ba_ldlt_device(orbm_matcher* m, int n, const double* H, const double* b, double* x) {
+    MORB_ARG(m != nullptr && n >= 0 && n <= 6 * ORBM_BA_MAX_FREE && (n == 0 || (H && b && x)));
+    if (n == 0) return 1;
+    MORB_HIP(hipSetDevice(m->device));
+    const size_t nn = (size_t)n * n * 8, nv = (size_t)n * 8;
+    morb::BlockLayout L;
+    const size_t o_Hs = L.take(nn), o_Lt = L.take(nn), o_bs = L.take(nv), o_d = L.take(nv), o_y = L.take(nv), o_carry = L.take(nv), o_x = L.take(nv),
+                 o_flag = L.take(16);
+    const int rc = m->lba.scratch.reserve(L.off);
+    if (rc) return rc;
+    uint8_t* sp = m->lba.scratch.p;
+    int* flag = (int*)(sp + o_flag);
+    const BaSolve A = {n, (double*)(sp + o_Hs), (double*)(sp + o_bs), (double*)(sp + o_Lt), (double*)(sp + o_d), (double*)(sp + o_y),
+                       (double*)(sp + o_carry), (double*)(sp + o_x), flag, flag + 1};
+    MORB_HIP(hipMemcpyAsync(sp + o_Hs, H, nn, hipMemcpyHostToDevice, m->stream));
+    MORB_HIP(hipMemcpyAsync(sp + o_bs, b, nv, hipMemcpyHostToDevice, m->stream));
+    (void)ba_ldlt_enqueue(m->stream, A);
+    MORB_HIP(hipGetLastError());
+    int ok[2] = {0, 0};
+    MORB_HIP(hipMemcpyAsync(ok, flag, 8, hipMemcpyDeviceToHost, m->stream));
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    if (ok[1] != 1) return 0;
+    MORB_HIP(hipMemcpy(x, sp + o_x, nv, hipMemcpyDeviceToHost));
+    return 1;
+}
 
 int orbm_local_ba_host(const orbm_lba_problem* problem, orbm_lba_stop_fn stop, void* stop_ctx, int order, orbm_lba_result* result) {
     const int rc = lba_validate(problem, result);

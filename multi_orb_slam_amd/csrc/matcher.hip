@@ -167,6 +167,11 @@ int orbm_debug_last_local_ba(const orbm_matcher* m, int* out4) {
     for (int k = 0; k < 4; ++k) out4[k] = m->last_lba[k];
     return ORB_OK;
 }
+int orbm_debug_last_bundle_adjust(const orbm_matcher* m, int* out8) {
+    MORB_ARG(m && out8);
+    for (int k = 0; k < 8; ++k) out8[k] = m->last_ba[k];
+    return ORB_OK;
+}
 
 int orbm_debug_last_pnp(const orbm_matcher* m, int* out4) {
     MORB_ARG(m && out4);

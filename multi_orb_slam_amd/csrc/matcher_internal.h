@@ -142,6 +142,7 @@ struct orbm_matcher {
     // leave for one another (scratch), the command word, flags and results they write and what the last call did
     PortBufs<uint8_t> lba;
     int last_lba[4] = {0, 0, 0, 0};
+    int last_ba[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // orbm_bundle_adjust: it shares lba's buffers
 };
 namespace morb { hipStream_t side_stream(orbm_matcher* m); }   // (lazily created; NULL after a reported failure)
 

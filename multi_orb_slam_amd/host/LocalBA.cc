@@ -19,6 +19,7 @@
 #include "Map.h"
 #endif
 #include "MapPointRefresh.h"
+#include "ba_rig.h"
 
 namespace ORB_SLAM2 {
 
@@ -87,15 +88,9 @@ void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap
     }
 
     // Tcam11, Tcam21 (:1048-1061)
-    cv::Mat Tcam21 = cv::Mat::zeros(4, 4, CV_32F);
-    cv::Mat Rcam21 = pKF->mRcam12.t();
-    cv::Mat tcam21 = -Rcam21 * pKF->mtcam12;
-    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) Tcam21.at<float>(r, c) = Rcam21.at<float>(r, c); Tcam21.at<float>(r, 3) = tcam21.at<float>(r); }
-    Tcam21.at<float>(3, 3) = 1.0;
-    cv::Mat Tcam11 = cv::Mat::eye(4, 4, CV_32F);
     orbm_lba_problem P;
     std::memset(&P, 0, sizeof(P));
-    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { P.Tcim[0][4 * r + c] = Tcam11.at<float>(r, c); P.Tcim[1][4 * r + c] = Tcam21.at<float>(r, c); }
+    FillTcim(pKF->mRcam12, pKF->mtcam12, P.Tcim);
 
     // The points in ascending vertex id (mnId + maxKFid + 1), each with its observations as edges (:1092-1202), ordered by mnId
     std::vector<MapPoint*> vpPoints(lLocalMapPoints.begin(), lLocalMapPoints.end());

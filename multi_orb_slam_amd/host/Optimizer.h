@@ -4,8 +4,9 @@
 // The reference builds a g2o graph per call (one `new` per edge and per robust kernel) around a single 6-dof vertex.  The two statics
 // below keep its signatures and replace the body: they fill the edge arrays from the frame (mvpMapPoints, mvKeysUn[_total],
 // mvuRight[_total], mvInvLevelSigma2), hand them to orbm_pose_optimize (include/orbm.h: one workgroup carries the problem through all
-// four rounds), write mvbOutlier and call SetPose.  Only this translation unit and host/LocalBA.cc (LocalBundleAdjustment, below) replace the reference's: global bundle
-// adjustment, the essential graph and OptimizeSim3 (all cameras) stay with g2o.  INTEGRATION.md shows the swap.
+// four rounds), write mvbOutlier and call SetPose.  This translation unit, host/LocalBA.cc (LocalBundleAdjustment) and host/GlobalBA.cc
+// (BundleAdjustment, GlobalBundleAdjustemnt; both below) replace the reference's: the essential graph and OptimizeSim3 (all cameras)
+// stay with g2o.  INTEGRATION.md shows the swap.
 //
 // Optimizer::OptimizeSim3_cam1 (reference include/Optimizer.h:62-63, src/Optimizer.cc:1984-2243), the refinement LoopClosing::ComputeSim3
 // runs between SearchBySim3 and the acceptance of a loop, likewise: the reference's filtering of vpMatches1 statement by statement, the
@@ -55,6 +56,19 @@ public:
     // lists what differs: the dense solver of the reduced system, the order of a point's observations and of the points).  *pbStopFlag
     // is read exactly where the reference and g2o read it.
     void static LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap);
+
+    // The bundle adjustment over a whole map that follows a closed loop (LoopClosing::RunGlobalBundleAdjustment: 10 iterations, no
+    // kernels) and the map's initialisation (reference include/Optimizer.h:40-45, src/Optimizer.cc:47-330), defined in host/GlobalBA.cc:
+    // the filtering of keyframes, points and observations and the recovery (SetPose / SetWorldPos / UpdateNormalAndDepth, or mTcwGBA /
+    // mPosGBA / mnBAGlobalForKF when nLoopKF != 0) are the reference's statement by statement, the g2o graph between them is one
+    // orbm_bundle_adjust call (include/orbm.h lists what differs: the dense solver of the reduced system; here also the order of the
+    // points, ascending mnId, and of a point's observations, ascending keyframe mnId, not heap addresses).  *pbStopFlag is read exactly
+    // where g2o reads it.  No map mutex is taken: the reference takes none here.
+    void static BundleAdjustment(const std::vector<KeyFrame*>& vpKFs, const std::vector<MapPoint*>& vpMP, int nIterations = 5,
+                                 bool* pbStopFlag = NULL, const unsigned long nLoopKF = 0, const bool bRobust = true,
+                                 cv::Mat CalibMatrix = cv::Mat::eye(4, 4, CV_32F));
+    void static GlobalBundleAdjustemnt(Map* pMap, int nIterations = 5, bool* pbStopFlag = NULL, const unsigned long nLoopKF = 0,
+                                       const bool bRobust = true, cv::Mat mCalibMatrix = cv::Mat::eye(4, 4, CV_32F));
 };
 
 // The edge count below which a single call is computed by the library's host routine (the same statements in the kernel's order, no
@@ -65,6 +79,9 @@ extern const int POSE_HOST_BELOW;
 extern const int SIM3OPT_HOST_BELOW;
 // The same for LocalBundleAdjustment, in edges: where tools/local_ba_bench.py found the two to cross (profiles/r20/notes_local_ba.md).
 extern const int LBA_HOST_BELOW;
+// The same for BundleAdjustment, in edges: the smallest world tools/global_ba_bench.py measured, where the device already wins; the
+// crossing lies below it (profiles/r21/notes_global_ba.md).
+extern const int GBA_HOST_BELOW;
 
 }  // namespace ORB_SLAM2
 

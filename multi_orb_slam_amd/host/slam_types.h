@@ -85,6 +85,10 @@ public:
         if (mpRefKF == pKF) mpRefKF = mObservations.empty() ? nullptr : mObservations.begin()->first;
     }
 
+    // members host/GlobalBA.cc writes when the adjustment belongs to a loop (include/MapPoint.h: mPosGBA, mnBAGlobalForKF)
+    cv::Mat mPosGBA;
+    long unsigned int mnBAGlobalForKF = 0;
+
     cv::Mat mWorldPos;    // 3x1 CV_32F
     cv::Mat mDescriptor;  // 1x32 CV_8U
     cv::Mat mNormalVector;  // 3x1 CV_32F
@@ -242,6 +246,9 @@ public:
     void SetPose(const cv::Mat& Tcw_) { LogCall("SetPose", mnId); Tcw = Tcw_.clone(); }
     void EraseMapPointMatch(MapPoint* pMP) { LogCall("EraseMapPointMatch", mnId, pMP->mnId); const int idx = pMP->GetIndexInKeyFrame(this); if (idx >= 0) mvpMapPoints[idx] = nullptr; }
     long unsigned int mnBALocalForKF = 0, mnBAFixedForKF = 0;
+    // members host/GlobalBA.cc writes when the adjustment belongs to a loop (include/KeyFrame.h: mTcwGBA, mnBAGlobalForKF)
+    cv::Mat mTcwGBA;
+    long unsigned int mnBAGlobalForKF = 0;
     static std::vector<KeyFrame*> FirstN(const std::vector<KeyFrame*>& v, int N) {   // src/KeyFrame.cc GetBestCovisibilityKeyFrames
         return (int)v.size() < N ? v : std::vector<KeyFrame*>(v.begin(), v.begin() + N);
     }
@@ -259,6 +266,11 @@ struct LoggedMutex {
 class Map {
 public:
     LoggedMutex mMutexMapUpdate;
+    // what host/GlobalBA.cc takes of it (include/Map.h; the reference keeps sets ordered by address, the stand-in what the caller filled)
+    std::vector<KeyFrame*> GetAllKeyFrames() { return mvpKeyFrames; }
+    std::vector<MapPoint*> GetAllMapPoints() { return mvpMapPoints; }
+    std::vector<KeyFrame*> mvpKeyFrames;
+    std::vector<MapPoint*> mvpMapPoints;
 };
 
 }  // namespace ORB_SLAM2

@@ -516,6 +516,51 @@ def local_ba_host(problem, order=POSE_ORDER_INDEX, stop=None):
     return res.take(R)
 
 
+class GlobalBAResult:
+    """orbm_ba_result: pose n_poses x 7 (q x y z w, t) and Tcw n_poses x 16 (what SetPose / mTcwGBA receive), point / point_f
+    n_points x 3, round (iterations, trials, chi2, lambda) of the one optimize(), optimised, polls, active_poses / active_points /
+    active_edges of its initializeOptimization()."""
+    FIELDS = ("pose", "Tcw", "point", "point_f", "round", "optimised", "polls", "active_poses", "active_points", "active_edges")
+
+    def __init__(self, problem):
+        self.pose = np.zeros((problem.n_poses, 7)); self.Tcw = np.zeros((problem.n_poses, 16), np.float32)
+        self.point = np.zeros((problem.n_points, 3)); self.point_f = np.zeros((problem.n_points, 3), np.float32)
+        self._pad = [np.zeros(1, a.dtype) if a.size == 0 else a for a in (self.pose, self.Tcw, self.point, self.point_f)]
+
+    def native(self):
+        R = _lib.BaResult()
+        R.pose, R.Tcw, R.point, R.point_f = [a.ctypes.data for a in self._pad]
+        return R
+
+    def take(self, R):
+        self.round = np.zeros(1, _lib.POSE_ROUND_DTYPE)
+        self.round[0] = (R.round.iterations, R.round.trials, R.round.chi2, R.round.lambda_)
+        for k in ("optimised", "polls", "active_poses", "active_points", "active_edges"):
+            setattr(self, k, int(getattr(R, k)))
+        return self
+
+    same_bytes = LocalBAResult.same_bytes
+
+
+def bundle_adjust_host(problem, iterations, robust, order=POSE_ORDER_INDEX, stop=None):
+    """orbm_bundle_adjust_host: Optimizer::BundleAdjustment from its graph on, entirely on the host (no device needed), in either
+    order -> GlobalBAResult.  problem: a LocalBAProblem (its `bad` is ignored); stop: see local_ba_host."""
+    res = GlobalBAResult(problem); P = problem.native(); R = res.native()
+    cb, keep = _lba_stop(stop)
+    check(_lib.lib().orbm_bundle_adjust_host(C.byref(P), int(iterations), 1 if robust else 0, cb, None, int(order), C.byref(R)))
+    return res.take(R)
+
+
+def ba_ldlt(H, b):
+    """The solver of the global BA's reduced system on the host (orbm_ba_ldlt: the local BA's factorisation, the backward substitution
+    in descending order) -> x, or None on a zero or non-finite pivot."""
+    H = np.ascontiguousarray(H, np.float64); b = np.ascontiguousarray(b, np.float64); x = np.zeros(len(b))
+    rc = _lib.lib().orbm_ba_ldlt(len(b), ptr(H), ptr(b), ptr(x))
+    if rc < 0:
+        check(rc)
+    return x if rc == 1 else None
+
+
 def lba_edge_eval(Tcim, K5, pose7, point3, cam, obs3, inv_sigma2):
     """One edge of the local BA (orbm_lba_edge_eval) -> (error 3, chi2, depth, Jacobian by the point 3 x 3, by the pose 3 x 6)."""
     Tcim = np.ascontiguousarray(Tcim, np.float32).reshape(32); K5 = np.ascontiguousarray(K5, np.float32)
@@ -952,6 +997,31 @@ class Matcher:
         out = (C.c_int * 4)()
         check(_lib.lib().orbm_debug_last_local_ba(self._h, out))
         return tuple(out)
+
+    def bundle_adjust(self, problem, iterations, robust, stop=None):
+        """Optimizer::BundleAdjustment (reference src/Optimizer.cc:47-330) from its graph on, on the device (orbm_bundle_adjust): the
+        local BA's kernels, the reduced system over the block pairs that exist, the blocked LDL^T across workgroups; one
+        synchronisation per Levenberg trial -> GlobalBAResult."""
+        res = GlobalBAResult(problem); P = problem.native(); R = res.native()
+        cb, keep = _lba_stop(stop)
+        check(_lib.lib().orbm_bundle_adjust(self._h, C.byref(P), int(iterations), 1 if robust else 0, cb, None, C.byref(R)))
+        return res.take(R)
+
+    def last_bundle_adjust(self):
+        """What the last bundle_adjust did: (path: 0 the device, 1 the host routine because a cap BA_MAX_* is exceeded, 2 the host
+        routine because no free pose is active; kernel launches; stream synchronisations; polls of stop; block pairs of the reduced
+        system computed; block pairs possible; panels of the blocked LDL^T; 0) (orbm_debug_last_bundle_adjust)."""
+        out = (C.c_int * 8)()
+        check(_lib.lib().orbm_debug_last_bundle_adjust(self._h, out))
+        return tuple(out)
+
+    def ba_ldlt_device(self, H, b):
+        """The device solver of the reduced system alone (orbm_ba_ldlt_device) -> x, or None on a zero or non-finite pivot."""
+        H = np.ascontiguousarray(H, np.float64); b = np.ascontiguousarray(b, np.float64); x = np.zeros(len(b))
+        rc = _lib.lib().orbm_ba_ldlt_device(self._h, len(b), ptr(H), ptr(b), ptr(x))
+        if rc < 0:
+            check(rc)
+        return x if rc == 1 else None
 
     def last_sim3opt(self):
         """Problems of the last sim3_optimize by path: (device, host routine because of more than SIM3OPT_CAP correspondences)
