@@ -70,6 +70,10 @@ int orbm_debug_last_local_ba(const orbm_matcher* m, int* out4);
  * routine because no free pose is active), kernel launches, stream synchronisations, polls of the stop function, block pairs of the
  * reduced system computed, block pairs possible (na (na + 1) / 2), panels of the blocked LDL^T, 0} (inspection only) */
 int orbm_debug_last_bundle_adjust(const orbm_matcher* m, int* out8);
+/* What the last orbm_essential_graph did: {path (0 the device, 1 the host routine because a cap of ORBM_EG_MAX_* is exceeded, 2 the
+ * host routine because no free vertex is active), kernel launches, stream synchronisations, 0, block pairs computed (the diagonal
+ * blocks included), block pairs possible (na (na + 1) / 2), panels of the blocked LDL^T, 0} (inspection only) */
+int orbm_debug_last_essential_graph(const orbm_matcher* m, int* out8);
 /* Where the work of the last orbm_pnp_ransac went: {problems on the device, problems through the host routine because they have more
  * than ORBM_PNP_CAP correspondences, records refined on the device, records refined by the host routine because they lie beyond
  * ORBM_PNP_MAX_RECORDS of a device problem} (inspection only) */

@@ -686,6 +686,73 @@ int orbm_ba_ldlt(int n, const double* H, const double* b, double* x);
 /* (test hook) The device solver alone on host arrays: the same bytes, the same return values; negative on an error. */
 int orbm_ba_ldlt_device(orbm_matcher* m, int n, const double* H, const double* b, double* x);
 
+/* -- essential graph: Optimizer::OptimizeEssentialGraph from its graph on ------------------------------------------------------
+ * Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:1373-1677, called by LoopClosing::CorrectLoop) between the graph and
+ * the recovery: VertexSim3Expmap vertices, EdgeSim3 edges with information = I and no robust kernel, setUserLambdaInit(1e-16), ONE
+ * initializeOptimization(), ONE optimize(n_iterations), then step 6 (the poses SetPose receives) and step 7 (every map point moved
+ * through its reference keyframe's input and final Sim3).  Restated from g2o: Sim3::log() with its four branches (types/sim3.h:148-230),
+ * EdgeSim3::computeError, the NUMERIC Jacobian of BaseBinaryEdge::linearizeOplus (delta = 1e-9, central differences, the perturbed
+ * estimate is Sim3(+-delta e_d) * estimate), constructQuadraticForm without a kernel, the block (i1 <= i2) an edge's off-diagonal part
+ * goes to by _hessianRowMajor, setLambda on the diagonal (the undamped diagonal is kept), computeScale over all of x, the lambda rules.
+ *   vertices  the free ones first in ascending mnId (g2o's VertexIDCompare order), then the fixed ones.  A vertex without an edge is
+ *             not active: its estimate is returned as it came.  Without an active free vertex optimize() returns before its loop.
+ *   edges     the edge position IS the active-edge order (insertion order); a pair may occur more than once, in either direction;
+ *             an edge of a vertex to itself is refused.  An edge between two fixed vertices has no Jacobian and still counts in chi2.
+ *   fix_scale `_fix_scale` of EVERY vertex: oplusImpl writes update[6] = 0 into the caller's array.  In linearizeOplus that makes both
+ *             steps along the scale the same estimate, so column 6 of both Jacobians is exactly 0 (for finite errors) and the seventh
+ *             diagonal entry of every block is the damping alone; in the trial loop update(x) runs before computeScale(), which
+ *             therefore reads the solver's x with every seventh entry zeroed.
+ *   points    point_ref: the vertex of nIDr, or -1 when vScw / vCorrectedSwc hold the default-constructed Sim3 there (identity, zero,
+ *             1): the position still goes through both maps in double and back to float.
+ * Kept products by the identity: ALL of them -- information() * _error in chi2() and in omega_r, A^T * omega, B^T * omega -- are
+ * evaluated as sums of seven products in ascending index (0 * NaN and 0 * inf are NaN, a sum of signed zeros is not its last term).
+ * Stated deviations: the linear system is solved by orbm_ba_ldlt (dense, no pivoting, natural order of the active free vertices, failure
+ * on a zero or non-finite pivot with x untouched) in both orders, not by Eigen's SimplicialLDLT behind an AMD ordering; Eigen's
+ * operators (the small products taken in ascending index, Matrix3d::lu().solve, Quaterniond(Matrix3d), toRotationMatrix) are restated
+ * and UNPINNED (csrc/g2o_dev.h).  There is no stop function: the reference passes none and g2o's forceStopFlag is null here.
+ * Two orders of ONE host routine: ORBM_POSE_ORDER_INDEX (the C library's log / acos / sin / cos / exp / pow, chi2 and computeScale
+ * summed sequentially: the restatement of the reference) and ORBM_POSE_ORDER_DEVICE (pose_log, pose_acos, orbm_pose_sincos,
+ * orbm_sim3opt_exp, the cube by multiplication; the total chi2 over edge positions 256 k .. 256 k + 255 through lm_dev.h's butterfly and
+ * wave sum, then the partials in ascending k, and computeScale's terms over positions 256 k .. of x the same way): what the device
+ * computes, bit for bit. */
+enum { ORBM_EG_MAX_FREE = 877,      /* 7 * 877 = 6139 <= 6 * ORBM_BA_MAX_FREE rows: what the blocked solver is sized for */
+       ORBM_EG_MAX_VERTICES = 4096, ORBM_EG_MAX_EDGES = 65536, ORBM_EG_MAX_POINTS = 1 << 19 };
+typedef struct orbm_eg_problem {
+    int32_t n_free, n_vertices, n_edges, n_points, fix_scale, reserved[3];
+    const double*  vertex;        /* n_vertices x 8: quaternion x y z w, translation, scale; the free ones first in ascending mnId
+                                     (VertexIDCompare), then the fixed ones                                                     */
+    const double*  measurement;   /* n_edges x 8: Sji                                                                          */
+    const int32_t* edge_v0;       /* _vertices[0] (Siw) and _vertices[1] (Sjw) as vertex indices; the edge position IS the      */
+    const int32_t* edge_v1;       /* active-edge order (EdgeIDCompare: insertion order); a pair may occur more than once       */
+    const float*   points;        /* n_points x 3: GetWorldPos()                                                               */
+    const int32_t* point_ref;     /* per point the vertex of nIDr, or -1: both Sim3 of step 7 are the default-constructed one  */
+} orbm_eg_problem;
+typedef struct orbm_eg_result {
+    double* estimate;              /* n_vertices x 8: the estimates after optimize()                                    */
+    float* Tiw;                    /* n_vertices x 16: what SetPose receives: R, t * (1./s), Converter::toCvSE3         */
+    float* point_f;                /* n_points x 3: what SetWorldPos receives                                           */
+    orbm_pose_round round;         /* of the one optimize()                                                             */
+    int32_t optimised;             /* 1: optimize() had an active free vertex                                           */
+    int32_t active_vertices, active_edges;   /* of initializeOptimization(): vertices with an edge (fixed ones included), edges */
+    int32_t reserved;
+} orbm_eg_result;
+/* On the device: per linearisation the perturbed estimates once per vertex, one lane per (edge, evaluation), the blocks over the pairs
+ * that exist; per Levenberg trial the damping, the blocked LDL^T (csrc/ba_ldlt_dev.h), the update, the errors, the controller, one
+ * synchronisation and one 4-byte command word; k_eg_correct_points behind the last iteration.  A problem beyond a cap
+ * (ORBM_EG_MAX_*), or without an active free vertex, runs through the host routine in DEVICE order inside the same call
+ * (orbm_debug_last_essential_graph).  Same bytes as orbm_essential_graph_host(..., ORBM_POSE_ORDER_DEVICE). */
+int orbm_essential_graph(orbm_matcher* m, const orbm_eg_problem* problem, int n_iterations, orbm_eg_result* result);
+/* The same statements on the host, no device needed, in either order. */
+int orbm_essential_graph_host(const orbm_eg_problem* problem, int n_iterations, int order, orbm_eg_result* result);
+/* (test hooks, host only) One edge at two estimates (8 doubles each): out[0..6] the error, out[7] chi2, out[8..56] the Jacobian by
+ * vertex 0, out[57..105] by vertex 1 (7 x 7 row-major: row the error, column the dimension).  The logarithm alone: out[0..6], returns
+ * the branch (0: |sigma| < eps and d > 1 - eps, 1: |sigma| < eps, 2: d > 1 - eps, 3: neither) or a negative error. */
+int orbm_eg_edge_eval(const double* measurement8, const double* v0_8, const double* v1_8, int fix_scale, int order, double* out106);
+int orbm_sim3_log_eval(const double* sim3_8, int order, double* out7);
+/* (test hooks, host only) The arc cosine and the natural logarithm of the DEVICE order. */
+double orbm_pose_acos(double d);
+double orbm_pose_log(double x);
+
 /* -- PnPsolver: every EPnP RANSAC hypothesis of a relocalisation in one call ---------------------------------------------
  * PnPsolver (reference src/PnPsolver.cc) between SearchByBoW_cam1 and Optimizer::PoseOptimization of Tracking::Relocalization: per
  * hypothesis the four-point EPnP (compute_pose: choose_control_points, compute_barycentric_coordinates, M^T M, its 12x12 SVD, the three

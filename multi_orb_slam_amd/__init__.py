@@ -19,6 +19,9 @@ from ._lib import LBA_MAX_FREE, LBA_MAX_POSES, LBA_MAX_POINTS, LBA_MAX_EDGES, LB
 from ._lib import LBA_ENDED_NO_SECOND, LBA_FLAG_LEVEL1, LBA_FLAG_ERASE  # noqa: F401
 from .matcher import GlobalBAResult, bundle_adjust_host, ba_ldlt  # noqa: F401
 from ._lib import BA_MAX_FREE, BA_MAX_POSES, BA_MAX_POINTS, BA_MAX_EDGES, BA_PANEL  # noqa: F401
+from .matcher import EssentialGraphProblem, EssentialGraphResult, essential_graph_host, eg_edge_eval, sim3_log_eval  # noqa: F401
+from .matcher import pose_acos, pose_log  # noqa: F401
+from ._lib import EG_MAX_FREE, EG_MAX_VERTICES, EG_MAX_EDGES, EG_MAX_POINTS  # noqa: F401
 from ._lib import SIM3OPT_PROBLEM_DTYPE, SIM3OPT_RESULT_DTYPE, SIM3OPT_CAP, SIM3OPT_MAX_BATCH  # noqa: F401
 from .matcher import PnPProblem, pnp_ransac_host, pnp_walk, pnp_walk_state, pnp_parameters, pnp_svd, pnp_qr_solve, pnp_compute_pose  # noqa: F401
 from ._lib import PNP_PROBLEM_DTYPE, PNP_HYP_DTYPE, PNP_REFINED_DTYPE, PNP_WALK_DTYPE, PNP_CAP, PNP_MAX_ITS, PNP_MAX_BATCH, PNP_MAX_RECORDS  # noqa: F401

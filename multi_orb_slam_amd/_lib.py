@@ -52,6 +52,7 @@ LBA_MAX_FREE, LBA_MAX_POSES, LBA_MAX_POINTS, LBA_MAX_EDGES = 64, 4096, 65536, 26
 LBA_ENDED_COMPLETE, LBA_ENDED_STOPPED_AT_START, LBA_ENDED_NO_SECOND = 0, 1, 2
 LBA_FLAG_LEVEL1, LBA_FLAG_ERASE = 1, 2
 BA_MAX_FREE, BA_MAX_POSES, BA_MAX_POINTS, BA_MAX_EDGES, BA_PANEL = 1024, 4096, 1 << 19, 1 << 22, 64
+EG_MAX_FREE, EG_MAX_VERTICES, EG_MAX_EDGES, EG_MAX_POINTS = 877, 4096, 65536, 1 << 19
 PNP_PROBLEM_DTYPE = np.dtype([("fu", "<f8"), ("fv", "<f8"), ("uc", "<f8"), ("vc", "<f8"), ("min_inliers", "<i4"), ("best_start", "<i4")])   # orbm_pnp_problem
 PNP_HYP_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("rep_error", "<f8"), ("choice", "<i4"), ("n_inliers", "<i4"), ("flags", "<i4"),
                           ("reserved", "<i4")])   # orbm_pnp_hyp
@@ -93,6 +94,17 @@ class BaResult(C.Structure):  # orbm_ba_result
     _fields_ = [("pose", C.c_void_p), ("Tcw", C.c_void_p), ("point", C.c_void_p), ("point_f", C.c_void_p), ("round", PoseRound),
                 ("optimised", C.c_int32), ("polls", C.c_int32), ("active_poses", C.c_int32), ("active_points", C.c_int32),
                 ("active_edges", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class EgProblem(C.Structure):  # orbm_eg_problem
+    _fields_ = [("n_free", C.c_int32), ("n_vertices", C.c_int32), ("n_edges", C.c_int32), ("n_points", C.c_int32), ("fix_scale", C.c_int32),
+                ("reserved", C.c_int32 * 3), ("vertex", C.c_void_p), ("measurement", C.c_void_p), ("edge_v0", C.c_void_p),
+                ("edge_v1", C.c_void_p), ("points", C.c_void_p), ("point_ref", C.c_void_p)]
+
+
+class EgResult(C.Structure):  # orbm_eg_result
+    _fields_ = [("estimate", C.c_void_p), ("Tiw", C.c_void_p), ("point_f", C.c_void_p), ("round", PoseRound), ("optimised", C.c_int32),
+                ("active_vertices", C.c_int32), ("active_edges", C.c_int32), ("reserved", C.c_int32)]
 
 
 LBA_STOP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p)   # orbm_lba_stop_fn
@@ -345,6 +357,13 @@ def lib():
     L.orbm_ba_ldlt.argtypes = [i32, vp, vp, vp]
     L.orbm_ba_ldlt_device.argtypes = [vp, i32, vp, vp, vp]
     L.orbm_debug_last_bundle_adjust.argtypes = [vp, vp]
+    L.orbm_essential_graph.argtypes = [vp, vp, i32, vp]
+    L.orbm_essential_graph_host.argtypes = [vp, i32, i32, vp]
+    L.orbm_eg_edge_eval.argtypes = [vp, vp, vp, i32, i32, vp]
+    L.orbm_sim3_log_eval.argtypes = [vp, i32, vp]
+    L.orbm_pose_acos.argtypes = [C.c_double]; L.orbm_pose_acos.restype = C.c_double
+    L.orbm_pose_log.argtypes = [C.c_double]; L.orbm_pose_log.restype = C.c_double
+    L.orbm_debug_last_essential_graph.argtypes = [vp, vp]
     L.orbm_pnp_ransac.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbm_pnp_ransac_host.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     L.orbm_pnp_walk.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]

@@ -1,5 +1,5 @@
 // g2o_dev.h -- the Eigen / g2o boundary: the parts of Eigen and g2o that the reference's optimisers run and this library restates, ONE
-// definition each, for the kernels and the host routines (pose.hip, sim3opt.hip, lba.hip).  Restated from the published sources (Eigen's
+// definition each, for the kernels and the host routines (pose.hip, sim3opt.hip, lba.hip, essgraph.hip).  Restated from the published sources (Eigen's
 // Geometry, Cholesky and LU modules; Thirdparty/g2o/g2o/types/se3quat.h, types/sim3.h, types/types_six_dof_expmap.cpp as far as its edges
 // share their Jacobian, core/robust_kernel_impl.cpp with the deltas the reference sets) and UNPINNED: Eigen is not linked and g2o was never
 // compiled against this code, so each is ONE function that a later pin changes.  The library is built without
@@ -355,5 +355,115 @@ __host__ __device__ inline int sim3_exp(const double* update, int order, Sim3Qua
     for (int i = 0; i < 9; ++i) W[i] = (A * O[i] + B * O2[i]) + C * (i % 4 == 0 ? 1.0 : 0.0);
     for (int i = 0; i < 3; ++i) T.t[i] = W[3 * i] * update[3] + W[3 * i + 1] * update[4] + W[3 * i + 2] * update[5];
     T.s = s;
+    return branch;
+}
+
+// Matrix3d::lu().solve(b) (LU/PartialPivLU.h: partial_lu_impl::unblocked_lu, then P b, the unit lower and the upper triangular solve).
+// Per column the pivot is the FIRST largest |entry| at or below the diagonal, whole rows are swapped, the column below is divided by
+// the pivot (not when it is exactly 0), the trailing block is updated entry by entry; each substitution subtracts its row's sum, taken
+// in ascending index.  W: row-major, destroyed.  UNPINNED like the rest of this file.
+__host__ __device__ inline void eigen_lu3_solve(double* W, const double* b, double* x) {
+    double r[3] = {b[0], b[1], b[2]};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        int row = k;
+        double big = fabs(W[3 * k + k]);
+#pragma unroll
+        for (int i = k + 1; i < 3; ++i) { const double v = fabs(W[3 * i + k]); if (v > big) { big = v; row = i; } }
+        if (big != 0.0) {
+#pragma unroll
+            for (int i = k + 1; i < 3; ++i) {
+                if (i != row) continue;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { const double t = W[3 * k + c]; W[3 * k + c] = W[3 * i + c]; W[3 * i + c] = t; }
+                const double t = r[k]; r[k] = r[i]; r[i] = t;                  // P b, transposition by transposition
+            }
+#pragma unroll
+            for (int i = k + 1; i < 3; ++i) W[3 * i + k] = W[3 * i + k] / W[3 * k + k];
+        }
+#pragma unroll
+        for (int i = k + 1; i < 3; ++i)
+#pragma unroll
+            for (int c = k + 1; c < 3; ++c) W[3 * i + c] = W[3 * i + c] - W[3 * i + k] * W[3 * k + c];
+    }
+    r[1] = r[1] - W[3] * r[0];
+    r[2] = r[2] - (W[6] * r[0] + W[7] * r[1]);
+    x[2] = r[2] / W[8];
+    x[1] = (r[1] - W[5] * x[2]) / W[4];
+    x[0] = (r[0] - (W[1] * x[1] + W[2] * x[2])) / W[0];
+}
+
+enum { SIM3_LOG_SIGMA0_D1 = 0, SIM3_LOG_SIGMA0 = 1, SIM3_LOG_D1 = 2, SIM3_LOG_GENERAL = 3 };   // the branches of Sim3::log()
+// Sim3::log() (:148-230), all four branches of fabs(sigma) < eps x d > 1 - eps, statement by statement: deltaR, skew, W = A Omega +
+// B Omega Omega + C I, W.lu().solve(t).  Nothing is normalised; near d = -1 the division by sqrt(1 - d*d) is the reference's.  order:
+// where log, acos, sin and cos come from (ORBM_POSE_ORDER_INDEX: the C library; otherwise pose_log, pose_acos, pose_sincos).  Returns
+// the branch taken.
+__host__ __device__ inline int sim3_log(const Sim3Quat& T, int order, double* res) {
+    double R[9];
+    eigen_quat_to_matrix(T.q, R);
+    const double s = T.s;
+    double sigma;
+#ifndef __HIP_DEVICE_COMPILE__
+    const bool libm = order == ORBM_POSE_ORDER_INDEX;
+    if (libm) sigma = log(s); else
+#endif
+    sigma = pose_log(s);
+    const double d = 0.5 * (((R[0] + R[4]) + R[8]) - 1);
+    const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};   // deltaR(R)
+    const double eps = 0.00001;
+    double omega[3], A, B, C;
+    int branch;
+    double theta = 0., sn = 0., cs = 0.;
+    if (!(d > 1 - eps)) {
+#ifndef __HIP_DEVICE_COMPILE__
+        if (libm) { theta = acos(d); sn = sin(theta); cs = cos(theta); } else
+#endif
+        { theta = pose_acos(d); pose_sincos(theta, &sn, &cs); }
+    }
+    if (fabs(sigma) < eps) {
+        C = 1;
+        if (d > 1 - eps) {
+            branch = SIM3_LOG_SIGMA0_D1;
+            for (int i = 0; i < 3; ++i) omega[i] = 0.5 * dR[i];
+            A = 1. / 2.;
+            B = 1. / 6.;
+        } else {
+            branch = SIM3_LOG_SIGMA0;
+            const double theta2 = theta * theta;
+            const double f = theta / (2 * sqrt(1 - d * d));
+            for (int i = 0; i < 3; ++i) omega[i] = f * dR[i];
+            A = (1 - cs) / (theta2);
+            B = (theta - sn) / (theta2 * theta);
+        }
+    } else {
+        C = (s - 1) / sigma;
+        if (d > 1 - eps) {
+            branch = SIM3_LOG_D1;
+            const double sigma2 = sigma * sigma;
+            for (int i = 0; i < 3; ++i) omega[i] = 0.5 * dR[i];
+            A = ((sigma - 1) * s + 1) / (sigma2);
+            B = ((0.5 * sigma2 - sigma + 1) * s) / (sigma2 * sigma);
+        } else {
+            branch = SIM3_LOG_GENERAL;
+            const double f = theta / (2 * sqrt(1 - d * d));
+            for (int i = 0; i < 3; ++i) omega[i] = f * dR[i];
+            const double theta2 = theta * theta;
+            const double a = s * sn;
+            const double b = s * cs;
+            const double c = theta2 + sigma * sigma;
+            A = (a * sigma + (1 - b) * theta) / (theta * c);
+            B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
+        }
+    }
+    const double O[9] = {0.0, -omega[2], omega[1], omega[2], 0.0, -omega[0], -omega[1], omega[0], 0.0};   // skew(omega)
+    double O2[9], W[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) O2[3 * i + j] = O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j] + O[3 * i + 2] * O[6 + j];
+    for (int i = 0; i < 9; ++i) W[i] = (A * O[i] + B * O2[i]) + C * (i % 4 == 0 ? 1.0 : 0.0);
+    double ups[3];
+    eigen_lu3_solve(W, T.t, ups);
+    res[0] = omega[0]; res[1] = omega[1]; res[2] = omega[2];
+    res[3] = ups[0]; res[4] = ups[1]; res[5] = ups[2];
+    res[6] = sigma;
     return branch;
 }

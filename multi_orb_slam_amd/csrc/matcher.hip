@@ -173,6 +173,12 @@ int orbm_debug_last_bundle_adjust(const orbm_matcher* m, int* out8) {
     return ORB_OK;
 }
 
+int orbm_debug_last_essential_graph(const orbm_matcher* m, int* out8) {
+    MORB_ARG(m && out8);
+    for (int k = 0; k < 8; ++k) out8[k] = m->last_eg[k];
+    return ORB_OK;
+}
+
 int orbm_debug_last_pnp(const orbm_matcher* m, int* out4) {
     MORB_ARG(m && out4);
     for (int k = 0; k < 4; ++k) out4[k] = m->last_pnp[k];

@@ -1,7 +1,7 @@
 // matcher_internal.h -- types and internal entry points shared by the translation units of the matcher / front end
 // (hamming.hip: all-pairs kernels; frame.hip: frame assembly; search.hip: projection search + resolve; matcher.hip: handle
 // + host helpers; exchange.hip: RCCL / loopback transport; frontend.hip: orbf_*; mappoint.hip: map-point refresh; pose.hip: pose
-// optimisation; sim3.hip: Sim3 RANSAC; sim3opt.hip: Sim3 refinement; pnp.hip: PnP RANSAC; lba.hip: local bundle adjustment).  Not part of the C ABI.  Next to it: cv_dev.h / g2o_dev.h (the restated OpenCV and Eigen / g2o
+// optimisation; sim3.hip: Sim3 RANSAC; sim3opt.hip: Sim3 refinement; pnp.hip: PnP RANSAC; lba.hip: local and global bundle adjustment; essgraph.hip: the essential graph).  Not part of the C ABI.  Next to it: cv_dev.h / g2o_dev.h (the restated OpenCV and Eigen / g2o
 // operations those ports share), sincos_dev.h, hamming_dev.h, resolve_dev.h (the steps the resolve's forms share and their LDS layouts),
 // stage_pack.h (the staged input block of a batched call and the checks on its CSR), lm_dev.h (what the Levenberg ports share),
 // ransac_dev.h (what the two RANSAC ports share).
@@ -143,6 +143,7 @@ struct orbm_matcher {
     PortBufs<uint8_t> lba;
     int last_lba[4] = {0, 0, 0, 0};
     int last_ba[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // orbm_bundle_adjust: it shares lba's buffers
+    int last_eg[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // orbm_essential_graph (essgraph.hip): it shares lba's buffers too
 };
 namespace morb { hipStream_t side_stream(orbm_matcher* m); }   // (lazily created; NULL after a reported failure)
 

@@ -4,7 +4,7 @@
 //   sim3_cv_*        the OpenCV operators only Sim3Solver calls (cv::eigen, cv::Rodrigues), restated from OpenCV's published sources
 //                    (2.4.x / 3.2) and UNPINNED (OpenCV is not in the build: DESIGN.md section 2): each is ONE function that a later
 //                    pin changes.  The operators other routines call as well (gemm, dot, norm, scaled matrices) are cv_dev.h's.
-//   sim3_atan2       the atan2 of ORBM_SIM3_MATH_DEVICE: + - * / sqrt in double.  Sine and cosine of that order: pose_sincos (sincos_dev.h).
+//   sim3_atan2       the atan2 of ORBM_SIM3_MATH_DEVICE: + - * / sqrt in double (sincos_dev.h, next to that order's sine and cosine, pose_sincos).
 //   sim3_horn        one hypothesis: three point pairs -> mR12i, mt12i, ms12i, mT12i, mT21i.  ONE statement sequence for the kernel and
 //                    the host routine; the 4x4 Jacobi addresses its matrices with compile-time indices only (nothing goes to scratch).
 //   sim3_inlier      one correspondence under one hypothesis: both projections, both threshold tests.
@@ -102,35 +102,7 @@ __host__ __device__ inline void sim3_cv_eigen_row0(float (&A)[4][4], float* q) {
     for (int k = 0; k < 4; ++k) q[k] = m == 0 ? V[0][k] : m == 1 ? V[1][k] : m == 2 ? V[2][k] : V[3][k];
 }
 
-// ---- atan2 of ORBM_SIM3_MATH_DEVICE: y >= 0, x in [-1, 1] ------------------------------------------------------------------------------
-// atan of |a| <= 1: three half-angle steps a <- a / (1 + sqrt(1 + a*a)) bring it below tan(pi/32), the odd series to a^19 there (the
-// first term left out is below 2^-70 of the result), times 8.
-__host__ __device__ inline double sim3_atan_unit(double a) {
-    a = a / (1.0 + sqrt(1.0 + a * a));
-    a = a / (1.0 + sqrt(1.0 + a * a));
-    a = a / (1.0 + sqrt(1.0 + a * a));
-    const double z = a * a;
-    double q = 1.0 / 19;
-    q = 1.0 / 17 - z * q;
-    q = 1.0 / 15 - z * q;
-    q = 1.0 / 13 - z * q;
-    q = 1.0 / 11 - z * q;
-    q = 1.0 / 9 - z * q;
-    q = 1.0 / 7 - z * q;
-    q = 1.0 / 5 - z * q;
-    q = 1.0 / 3 - z * q;
-    return 8.0 * (a - a * (z * q));
-}
-__host__ __device__ inline double sim3_atan2(double y, double x) {
-    const double PI_HI = 3.141592653589793116e+00, PI_LO = 1.224646799147353207e-16;
-    const double PIO2_HI = 1.570796326794896558e+00, PIO2_LO = 6.123233995736766036e-17;
-    const double ax = fabs(x);
-    if (ax >= y) {                                   // the angle is within pi/4 of the x axis
-        const double r = sim3_atan_unit((ax == 0 && y == 0) ? 0.0 : y / ax);
-        return x < 0 ? (PI_HI - r) + PI_LO : r;
-    }
-    return (PIO2_HI - sim3_atan_unit(x / y)) + PIO2_LO;
-}
+// (the atan2 of ORBM_SIM3_MATH_DEVICE, sim3_atan2, lives in sincos_dev.h since the essential graph's arc cosine is built on it)
 
 // cv::Rodrigues of a 1x3 CV_32F into a 3x3 CV_32F (cvRodrigues2, modules/calib3d/src/calibration.cpp): double inside; theta = the norm;
 // below DBL_EPSILON the identity; else c = cos, s = sin, c1 = 1 - c, r *= 1 / theta, R = c*I + c1*r*r^T + s*[r]x summed left to right,

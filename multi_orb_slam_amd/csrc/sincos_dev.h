@@ -1,7 +1,9 @@
 // sincos_dev.h -- the double sine / cosine sequence shared by the device orders of pose.hip (ORBM_POSE_ORDER_DEVICE), sim3.hip
 // (ORBM_SIM3_MATH_DEVICE) and sim3opt.hip; orbm_pose_sincos (include/orbm.h) is its test hook.  Next to it the exponential of
-// sim3opt.hip's device order (test hook: orbm_sim3opt_exp).
+// sim3opt.hip's device order (test hook: orbm_sim3opt_exp), the atan2 of sim3.hip's (orbm_sim3_atan2), and the arc cosine and natural
+// logarithm of essgraph.hip's (Sim3::log; test hook: orbm_sim3_log_eval).
 #pragma once
+#include <cmath>
 #include <hip/hip_runtime.h>
 
 // ---- sine and cosine of ORBM_POSE_ORDER_DEVICE: one sequence of + - * / in double (the det_sincos precedent of the extractor) --------
@@ -69,4 +71,68 @@ __host__ __device__ inline double pose_exp(double x) {
     const int m = k < 0 ? -k : k;
     for (int i = 0; i < m; ++i) e = e * f;
     return e;
+}
+
+// ---- atan2 of ORBM_SIM3_MATH_DEVICE: y >= 0, x in [-1, 1] ------------------------------------------------------------------------------
+// atan of |a| <= 1: three half-angle steps a <- a / (1 + sqrt(1 + a*a)) bring it below tan(pi/32), the odd series to a^19 there (the
+// first term left out is below 2^-70 of the result), times 8.
+__host__ __device__ inline double sim3_atan_unit(double a) {
+    a = a / (1.0 + sqrt(1.0 + a * a));
+    a = a / (1.0 + sqrt(1.0 + a * a));
+    a = a / (1.0 + sqrt(1.0 + a * a));
+    const double z = a * a;
+    double q = 1.0 / 19;
+    q = 1.0 / 17 - z * q;
+    q = 1.0 / 15 - z * q;
+    q = 1.0 / 13 - z * q;
+    q = 1.0 / 11 - z * q;
+    q = 1.0 / 9 - z * q;
+    q = 1.0 / 7 - z * q;
+    q = 1.0 / 5 - z * q;
+    q = 1.0 / 3 - z * q;
+    return 8.0 * (a - a * (z * q));
+}
+__host__ __device__ inline double sim3_atan2(double y, double x) {
+    const double PI_HI = 3.141592653589793116e+00, PI_LO = 1.224646799147353207e-16;
+    const double PIO2_HI = 1.570796326794896558e+00, PIO2_LO = 6.123233995736766036e-17;
+    const double ax = fabs(x);
+    if (ax >= y) {                                   // the angle is within pi/4 of the x axis
+        const double r = sim3_atan_unit((ax == 0 && y == 0) ? 0.0 : y / ax);
+        return x < 0 ? (PI_HI - r) + PI_LO : r;
+    }
+    return (PIO2_HI - sim3_atan_unit(x / y)) + PIO2_LO;
+}
+
+// ---- arc cosine of the device order of essgraph.hip: d in [-1, 1] ---------------------------------------------------------------------
+// acos d = atan2(sqrt(1 - d^2), d) with 1 - d^2 as (1 - d)(1 + d): 1 - d is exact from d = 1/2 on, where the cancellation would be.
+__host__ __device__ inline double pose_acos(double d) { return sim3_atan2(sqrt((1.0 - d) * (1.0 + d)), d); }
+
+// ---- natural logarithm of the device order of essgraph.hip: + - * / in double --------------------------------------------------------
+// x = 2^k m with m in [sqrt(1/2), sqrt(2)) by exact halvings or doublings, z = (m - 1) / (m + 1) (|z| < 0.1716), log m = 2 z (1 + z^2/3
+// + ... + z^22/23) in Horner form (the first term left out is below 2^-58 of the result), the two-part ln 2 of pose_exp.  log(1) is
+// exactly 0.  A NaN or a negative argument: NaN; 0: -infinity; infinity stays.
+__host__ __device__ inline double pose_log(double x) {
+    if (!(x == x) || x < 0) return (x - x) / (x - x);
+    if (x == 0) return -1.0 / (x * x);
+    if (x > 1.79769313486231570815e+308) return x;
+    const double SQRT2 = 1.41421356237309514547e+00, SQRT1_2 = 7.07106781186547572737e-01;
+    const double LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10;
+    int k = 0;
+    while (x >= SQRT2) { x = x * 0.5; ++k; }
+    while (x < SQRT1_2) { x = x * 2.0; --k; }
+    const double z = (x - 1.0) / (x + 1.0);
+    const double w = z * z;
+    double p = 1.0 / 23;
+    p = p * w + (1.0 / 21);
+    p = p * w + (1.0 / 19);
+    p = p * w + (1.0 / 17);
+    p = p * w + (1.0 / 15);
+    p = p * w + (1.0 / 13);
+    p = p * w + (1.0 / 11);
+    p = p * w + (1.0 / 9);
+    p = p * w + (1.0 / 7);
+    p = p * w + (1.0 / 5);
+    p = p * w + (1.0 / 3);
+    const double kf = (double)k;
+    return kf * LN2_HI + ((2.0 * z + (2.0 * z) * (w * p)) + kf * LN2_LO);
 }

@@ -5,8 +5,9 @@
 // below keep its signatures and replace the body: they fill the edge arrays from the frame (mvpMapPoints, mvKeysUn[_total],
 // mvuRight[_total], mvInvLevelSigma2), hand them to orbm_pose_optimize (include/orbm.h: one workgroup carries the problem through all
 // four rounds), write mvbOutlier and call SetPose.  This translation unit, host/LocalBA.cc (LocalBundleAdjustment) and host/GlobalBA.cc
-// (BundleAdjustment, GlobalBundleAdjustemnt; both below) replace the reference's: the essential graph and OptimizeSim3 (all cameras)
-// stay with g2o.  INTEGRATION.md shows the swap.
+// (BundleAdjustment, GlobalBundleAdjustemnt; both below) and host/EssentialGraph.cc (OptimizeEssentialGraph, below) replace the
+// reference's: only OptimizeSim3 (all cameras), commented out at its one call site, stays with g2o.
+// INTEGRATION.md shows the swap.
 //
 // Optimizer::OptimizeSim3_cam1 (reference include/Optimizer.h:62-63, src/Optimizer.cc:1984-2243), the refinement LoopClosing::ComputeSim3
 // runs between SearchBySim3 and the acceptance of a loop, likewise: the reference's filtering of vpMatches1 statement by statement, the
@@ -15,8 +16,13 @@
 #ifndef OPTIMIZER_H
 #define OPTIMIZER_H
 
+#include <map>
+#include <set>
 #include <vector>
 #include "ORBmatcher.h"
+#ifndef MORB_USE_REFERENCE_TYPES
+#include "LoopClosing.h"   // (host/LoopClosing.h: the stand-in of LoopClosing::KeyFrameAndPose)
+#endif
 
 namespace g2o { struct Sim3; }   // (the reference's Thirdparty/g2o/g2o/types/sim3.h, or host/g2o_compat.h)
 
@@ -69,6 +75,23 @@ public:
                                  cv::Mat CalibMatrix = cv::Mat::eye(4, 4, CV_32F));
     void static GlobalBundleAdjustemnt(Map* pMap, int nIterations = 5, bool* pbStopFlag = NULL, const unsigned long nLoopKF = 0,
                                        const bool bRobust = true, cv::Mat mCalibMatrix = cv::Mat::eye(4, 4, CV_32F));
+
+    // The pose graph LoopClosing::CorrectLoop optimises between OptimizeSim3_cam1 and the global bundle adjustment (reference
+    // include/Optimizer.h:51-55, src/Optimizer.cc:1373-1677), defined in host/EssentialGraph.cc: steps 2-4 (the vertices from
+    // CorrectedSim3 or the keyframe's own pose, the loop edges with the minFeat = 100 test and its exception for the current-loop
+    // pair, sInsertedEdges, the spanning-tree, loop and covisibility edges, every measurement Sjw * Swi in double, the edges in
+    // insertion order) are the reference's statement by statement, the g2o graph between them and step 6 is one
+    // orbm_essential_graph call (include/orbm.h lists what differs: the dense solver), then SetPose in vpKFs' order under
+    // mMutexMapUpdate, SetWorldPos in vpMPs' order and UpdateNormalAndDepth through the batched RefreshMapPoints.  Two stated
+    // deviations, because the reference dereferences a NULL vertex in both: an edge with an end that has no vertex (a bad keyframe) is
+    // not added, and a bad keyframe of vpKFs gets no SetPose.  Iterating LoopConnections, its sets and GetLoopEdges() follows heap
+    // addresses, as in the reference.  Declared where LoopClosing::KeyFrameAndPose is known: host/LoopClosing.h's stand-in, or the
+    // reference's LoopClosing.h included before this header.
+#if !defined(MORB_USE_REFERENCE_TYPES) || defined(LOOPCLOSING_H)
+    void static OptimizeEssentialGraph(Map* pMap, KeyFrame* pLoopKF, KeyFrame* pCurKF, const LoopClosing::KeyFrameAndPose& NonCorrectedSim3,
+                                       const LoopClosing::KeyFrameAndPose& CorrectedSim3,
+                                       const std::map<KeyFrame*, std::set<KeyFrame*> >& LoopConnections, const bool& bFixScale);
+#endif
 };
 
 // The edge count below which a single call is computed by the library's host routine (the same statements in the kernel's order, no
@@ -82,6 +105,9 @@ extern const int LBA_HOST_BELOW;
 // The same for BundleAdjustment, in edges: the smallest world tools/global_ba_bench.py measured, where the device already wins; the
 // crossing lies below it (profiles/r21/notes_global_ba.md).
 extern const int GBA_HOST_BELOW;
+// The same for OptimizeEssentialGraph, in edges: between the two worlds of tools/essential_graph_bench.py that bracket the crossing
+// (profiles/r22/notes_essential_graph.md).
+extern const int EG_HOST_BELOW;
 
 }  // namespace ORB_SLAM2
 

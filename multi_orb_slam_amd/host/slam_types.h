@@ -88,6 +88,8 @@ public:
     // members host/GlobalBA.cc writes when the adjustment belongs to a loop (include/MapPoint.h: mPosGBA, mnBAGlobalForKF)
     cv::Mat mPosGBA;
     long unsigned int mnBAGlobalForKF = 0;
+    // members host/EssentialGraph.cc reads (include/MapPoint.h:115-116: written by LoopClosing::CorrectLoop)
+    long unsigned int mnCorrectedByKF = 0, mnCorrectedReference = 0;
 
     cv::Mat mWorldPos;    // 3x1 CV_32F
     cv::Mat mDescriptor;  // 1x32 CV_8U
@@ -249,6 +251,24 @@ public:
     // members host/GlobalBA.cc writes when the adjustment belongs to a loop (include/KeyFrame.h: mTcwGBA, mnBAGlobalForKF)
     cv::Mat mTcwGBA;
     long unsigned int mnBAGlobalForKF = 0;
+    // members host/EssentialGraph.cc reads (include/KeyFrame.h:82-96; src/KeyFrame.cc:331-364): the spanning tree, the loop edges and
+    // the camera-1 covisibility weights are plain containers the caller fills (mvOrderedWeights_cam1 descending, beside
+    // mvpOrderedConnectedKeyFrames_cam1)
+    KeyFrame* GetParent() { return mpParent; }
+    bool hasChild(KeyFrame* pKF) { return mspChildrens.count(pKF) != 0; }
+    std::set<KeyFrame*> GetLoopEdges() { return mspLoopEdges; }
+    int GetWeight_cam1(KeyFrame* pKF) { auto it = mConnectedKeyFrameWeights_cam1.find(pKF); return it != mConnectedKeyFrameWeights_cam1.end() ? it->second : 0; }
+    std::vector<KeyFrame*> GetCovisiblesByWeight_cam1(const int& w) {
+        if (mvpOrderedConnectedKeyFrames_cam1.empty()) return std::vector<KeyFrame*>();
+        size_t n = 0;                                     // upper_bound(..., w, weightComp): the first weight with w > weight
+        while (n < mvOrderedWeights_cam1.size() && !(w > mvOrderedWeights_cam1[n])) ++n;
+        if (n == mvOrderedWeights_cam1.size()) return std::vector<KeyFrame*>();
+        return std::vector<KeyFrame*>(mvpOrderedConnectedKeyFrames_cam1.begin(), mvpOrderedConnectedKeyFrames_cam1.begin() + n);
+    }
+    KeyFrame* mpParent = nullptr;
+    std::set<KeyFrame*> mspChildrens, mspLoopEdges;
+    std::map<KeyFrame*, int> mConnectedKeyFrameWeights_cam1;
+    std::vector<int> mvOrderedWeights_cam1;
     static std::vector<KeyFrame*> FirstN(const std::vector<KeyFrame*>& v, int N) {   // src/KeyFrame.cc GetBestCovisibilityKeyFrames
         return (int)v.size() < N ? v : std::vector<KeyFrame*>(v.begin(), v.begin() + N);
     }
@@ -271,6 +291,9 @@ public:
     std::vector<MapPoint*> GetAllMapPoints() { return mvpMapPoints; }
     std::vector<KeyFrame*> mvpKeyFrames;
     std::vector<MapPoint*> mvpMapPoints;
+    // what host/EssentialGraph.cc takes of it (include/Map.h:58)
+    long unsigned int GetMaxKFid() { return mnMaxKFid; }
+    long unsigned int mnMaxKFid = 0;
 };
 
 }  // namespace ORB_SLAM2

@@ -551,6 +551,94 @@ def bundle_adjust_host(problem, iterations, robust, order=POSE_ORDER_INDEX, stop
     return res.take(R)
 
 
+class EssentialGraphProblem:
+    """One Optimizer::OptimizeEssentialGraph from its graph on (orbm_eg_problem): vertex n_vertices x 8 double (quaternion x y z w,
+    translation, scale; the free ones first, n_free of them, in ascending mnId), measurement n_edges x 8 (Sji), edge_v0 / edge_v1 (the
+    vertices of Siw and Sjw; the edge position is the active-edge order), points n_points x 3 float, point_ref per point the vertex of
+    its reference keyframe or -1, fix_scale."""
+
+    def __init__(self, n_free, vertex, measurement, edge_v0, edge_v1, points=None, point_ref=None, fix_scale=False):
+        self.vertex = np.ascontiguousarray(vertex, np.float64).reshape(-1, 8)
+        self.measurement = np.ascontiguousarray(measurement, np.float64).reshape(-1, 8)
+        self.edge_v0 = np.ascontiguousarray(edge_v0, np.int32).reshape(-1); self.edge_v1 = np.ascontiguousarray(edge_v1, np.int32).reshape(-1)
+        self.points = np.ascontiguousarray(np.zeros((0, 3)) if points is None else points, np.float32).reshape(-1, 3)
+        self.point_ref = np.ascontiguousarray(np.zeros(0) if point_ref is None else point_ref, np.int32).reshape(-1)
+        self.n_free = int(n_free); self.n_vertices = len(self.vertex); self.n_edges = len(self.measurement); self.n_points = len(self.points)
+        self.fix_scale = bool(fix_scale)
+        assert len(self.edge_v0) == len(self.edge_v1) == self.n_edges and len(self.point_ref) == self.n_points
+        assert 0 <= self.n_free <= self.n_vertices
+
+    def native(self):
+        P = _lib.EgProblem()
+        P.n_free, P.n_vertices, P.n_edges, P.n_points, P.fix_scale = self.n_free, self.n_vertices, self.n_edges, self.n_points, int(self.fix_scale)
+        for k in ("vertex", "measurement", "edge_v0", "edge_v1", "points", "point_ref"):
+            a = getattr(self, k)
+            setattr(P, k, a.ctypes.data if a.size else None)
+        return P
+
+
+class EssentialGraphResult:
+    """orbm_eg_result: estimate n_vertices x 8 (q x y z w, t, s), Tiw n_vertices x 16 (what SetPose receives), point_f n_points x 3 (what
+    SetWorldPos receives), round (iterations, trials, chi2, lambda) of the one optimize(), optimised, active_vertices / active_edges of
+    its initializeOptimization()."""
+    FIELDS = ("estimate", "Tiw", "point_f", "round", "optimised", "active_vertices", "active_edges")
+
+    def __init__(self, problem):
+        self.estimate = np.zeros((problem.n_vertices, 8)); self.Tiw = np.zeros((problem.n_vertices, 16), np.float32)
+        self.point_f = np.zeros((problem.n_points, 3), np.float32)
+        self._pad = [np.zeros(1, a.dtype) if a.size == 0 else a for a in (self.estimate, self.Tiw, self.point_f)]
+
+    def native(self):
+        R = _lib.EgResult()
+        R.estimate, R.Tiw, R.point_f = [a.ctypes.data for a in self._pad]
+        return R
+
+    def take(self, R):
+        self.round = np.zeros(1, _lib.POSE_ROUND_DTYPE)
+        self.round[0] = (R.round.iterations, R.round.trials, R.round.chi2, R.round.lambda_)
+        for k in ("optimised", "active_vertices", "active_edges"):
+            setattr(self, k, int(getattr(R, k)))
+        return self
+
+    same_bytes = LocalBAResult.same_bytes
+
+
+def essential_graph_host(problem, iterations=20, order=POSE_ORDER_INDEX):
+    """orbm_essential_graph_host: Optimizer::OptimizeEssentialGraph from its graph on, entirely on the host (no device needed), in
+    either order -> EssentialGraphResult."""
+    res = EssentialGraphResult(problem); P = problem.native(); R = res.native()
+    check(_lib.lib().orbm_essential_graph_host(C.byref(P), int(iterations), int(order), C.byref(R)))
+    return res.take(R)
+
+
+def eg_edge_eval(measurement, v0, v1, fix_scale=False, order=POSE_ORDER_INDEX):
+    """One edge of the essential graph at two estimates, 8 doubles each (orbm_eg_edge_eval) -> (error 7, chi2, Jacobian by vertex 0
+    7 x 7, by vertex 1 7 x 7; row: the error, column: the dimension)."""
+    M = np.ascontiguousarray(measurement, np.float64).reshape(8); a = np.ascontiguousarray(v0, np.float64).reshape(8)
+    b = np.ascontiguousarray(v1, np.float64).reshape(8); out = np.zeros(106)
+    check(_lib.lib().orbm_eg_edge_eval(ptr(M), ptr(a), ptr(b), 1 if fix_scale else 0, int(order), ptr(out)))
+    return out[:7].copy(), float(out[7]), out[8:57].reshape(7, 7).copy(), out[57:106].reshape(7, 7).copy()
+
+
+def sim3_log_eval(sim3, order=POSE_ORDER_INDEX):
+    """g2o's Sim3::log() of (q x y z w, t, s) (orbm_sim3_log_eval) -> (omega, upsilon, sigma as 7 doubles, the branch taken)."""
+    T = np.ascontiguousarray(sim3, np.float64).reshape(8); out = np.zeros(7)
+    rc = _lib.lib().orbm_sim3_log_eval(ptr(T), int(order), ptr(out))
+    if rc < 0:
+        check(rc)
+    return out, int(rc)
+
+
+def pose_acos(d):
+    """The arc cosine of the device order (orbm_pose_acos): d in [-1, 1]."""
+    return float(_lib.lib().orbm_pose_acos(float(d)))
+
+
+def pose_log(x):
+    """The natural logarithm of the device order (orbm_pose_log)."""
+    return float(_lib.lib().orbm_pose_log(float(x)))
+
+
 def ba_ldlt(H, b):
     """The solver of the global BA's reduced system on the host (orbm_ba_ldlt: the local BA's factorisation, the backward substitution
     in descending order) -> x, or None on a zero or non-finite pivot."""
@@ -1014,6 +1102,21 @@ class Matcher:
         out = (C.c_int * 8)()
         check(_lib.lib().orbm_debug_last_bundle_adjust(self._h, out))
         return tuple(out)
+
+    def essential_graph(self, problem, iterations=20):
+        """Optimizer::OptimizeEssentialGraph (reference src/Optimizer.cc:1373-1677) from its graph on, on the device
+        (orbm_essential_graph): the Levenberg loop is driven from the host, one synchronisation per trial -> EssentialGraphResult."""
+        res = EssentialGraphResult(problem); P = problem.native(); R = res.native()
+        check(_lib.lib().orbm_essential_graph(self._h, C.byref(P), int(iterations), C.byref(R)))
+        return res.take(R)
+
+    def last_essential_graph(self):
+        """What the last essential_graph did: (path: 0 the device, 1 the host routine because a cap EG_MAX_* is exceeded, 2 the host
+        routine because no free vertex is active; kernel launches; stream synchronisations; 0; block pairs computed; block pairs
+        possible; panels of the blocked LDL^T; 0) (orbm_debug_last_essential_graph)."""
+        out = (C.c_int * 8)()
+        check(_lib.lib().orbm_debug_last_essential_graph(self._h, out))
+        return tuple(int(v) for v in out)
 
     def ba_ldlt_device(self, H, b):
         """The device solver of the reduced system alone (orbm_ba_ldlt_device) -> x, or None on a zero or non-finite pivot."""
