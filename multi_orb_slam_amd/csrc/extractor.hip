@@ -2536,6 +2536,13 @@ int orbx_peek_status(const orbx_extractor* ex) {
     const unsigned oldest = (ex->run_seq - (unsigned)ex->inflight) & 1u;
     return ex->h_oct[oldest * (ex->n_cams + 1) + ex->n_cams];
 }
+// Keypoint count of camera `cam` in the OLDEST run in flight, as orbx_finish will adopt it; meaningful under the same condition and
+// only while orbx_peek_status says 0.  -1: nothing in flight.
+int orbx_peek_count(const orbx_extractor* ex, int cam) {
+    if (!ex || ex->inflight == 0 || cam < 0 || cam >= ex->n_cams) return -1;
+    const unsigned oldest = (ex->run_seq - (unsigned)ex->inflight) & 1u;
+    return ex->h_oct[oldest * (ex->n_cams + 1) + cam];
+}
 void* orbx_done_event(const orbx_extractor* ex) { return ex ? (void*)ex->ev_done[(ex->run_seq - 1u) & 1u] : nullptr; }
 
 // the {pointer, pitch} table of level 0 the kernels are handed: the handle's table while the geometry reads level 0 in place

@@ -29,6 +29,7 @@ extern "C" int orbx_set_frame_sink(orbx_extractor* ex, const FrameSink* sink);
 // completion event of the most recently enqueued asynchronous run (valid while it is in flight)
 extern "C" void* orbx_done_event(const orbx_extractor* ex);
 extern "C" int orbx_peek_status(const orbx_extractor* ex);  // status of the oldest run in flight (valid once it completed)
+extern "C" int orbx_peek_count(const orbx_extractor* ex, int cam);  // ... and its count of camera `cam` (while that status is 0)
 
 // Launches a caller wants at the very end of the extractor's launch chain, on its stream (orbf: the frame grid and the
 // camera-pair top-2).  They are issued from inside orbx_run_async, so they become part of the captured chain graph; `tag`

@@ -155,6 +155,16 @@ struct orbf_frontend {
     // previous step (for orbf_step_motion)
     int prev_n = 0;
     std::vector<int32_t> prev_cam_of;
+    // What the end of a step computes from the extraction's counts alone, prepared in front of the wait for the search (the host idles
+    // there; behind the wait every microsecond is on the step's period): the camera of every feature (the next prev_cam_of) and, for
+    // a caller that asked (orbf_step_motion_ahead, orbf_run_stream), the accepted camera-pair matches.  Only for a step whose
+    // extraction chain -- the camera-pair top-2 in it -- was known complete at begin; every other step keeps the order it had.
+    struct Early {
+        bool valid = false;                      // counts / cam_of describe the pending step
+        std::vector<int32_t> counts, cam_of;
+        bool want_cross = false; int th_low = 0; float ratio = 0.f;   // the caller's acceptance test
+        const int32_t* cross_best = nullptr; int cross_n = 0, n_cross = 0;   // cross_best != NULL: n_cross counts cross_n entries of that array
+    } early;
     std::vector<float> scale_factors;
     std::chrono::steady_clock::time_point t_entry;
 };
@@ -688,6 +698,22 @@ static int queries_from_previous_step(orbf_frontend* f, const orbf_motion* motio
                                     R.unx.p, R.uny.p);  // (mvKeysUn: equal to the keypoint positions without a calibration)
 }
 
+// orbf_step_motion for a caller that counts the accepted camera-pair matches of the step (best <= th_low, best < ratio * second; `none`
+// when the step has no camera-pair results): counted in front of the step's wait where that is possible (orbf_frontend::Early), behind
+// the step as ever otherwise.  < -1: an error code.
+static int step_motion_counting(orbf_frontend* f, const orbf_image* images, const orbf_motion* motion, int flags, int th_low, float ratio,
+                                int none, orbf_result* out, int* n_cross) {
+    orbf_frontend::Early& E = f->early;
+    E.want_cross = true; E.th_low = th_low; E.ratio = ratio;
+    const int rc = orbf_step_motion(f, images, motion, flags, out);
+    E.want_cross = false;
+    if (rc) return rc;
+    if (!out->cross_best_dist) *n_cross = none;
+    else if (E.cross_best == out->cross_best_dist && E.cross_n == out->n_total) *n_cross = E.n_cross;
+    else *n_cross = orbm_count_ratio_accepted(out->cross_best_dist, out->cross_second_dist, out->n_total, th_low, ratio);
+    return ORB_OK;
+}
+
 int orbf_run_stream(orbf_frontend* f, const orbf_image* ring, int ring_len, int t0, int steps, int ahead, int* announced_upto,
                     const orbf_motion* motion, int th_low, float ratio, orbf_stream_stats* out) {
     MORB_ARG(f && ring && ring_len >= 1 && t0 >= 0 && steps >= 0 && ahead >= 0 && announced_upto && motion && out);
@@ -705,10 +731,10 @@ int orbf_run_stream(orbf_frontend* f, const orbf_image* ring, int ring_len, int 
             if (rc) return rc;
             *announced_upto = a;
         }
-        int rc = orbf_step_motion(f, images_of(t), motion, ORBF_NO_QUERY_RECORDS, &r);   // (the loop never reads orbf_result::queries)
+        int nx = 0;
+        int rc = step_motion_counting(f, images_of(t), motion, ORBF_NO_QUERY_RECORDS, th_low, ratio, 0, &r, &nx);   // (the loop never reads orbf_result::queries)
         if (rc) return rc;
         if (*announced_upto < t) *announced_upto = t;
-        const int nx = r.cross_best_dist ? orbm_count_ratio_accepted(r.cross_best_dist, r.cross_second_dist, r.n_total, th_low, ratio) : 0;
         if (nx < 0) return nx;
         out->features += r.n_total; out->temporal_matches += r.nmatches; out->cross_accepted += nx;
         uint64_t h = out->digest ^ ((uint64_t)(uint32_t)r.n_total << 40) ^ ((uint64_t)(uint32_t)r.nmatches << 20) ^ (uint64_t)(uint32_t)nx;
@@ -730,8 +756,7 @@ int orbf_step_motion_ahead(orbf_frontend* f, const orbf_image* images, const orb
     MORB_ARG(f && images && motion && out && n_cross);
     int rc;
     if (next_images && (rc = orbf_prefetch(f, next_images))) return rc;
-    if ((rc = orbf_step_motion(f, images, motion, flags, out))) return rc;
-    *n_cross = out->cross_best_dist ? orbm_count_ratio_accepted(out->cross_best_dist, out->cross_second_dist, out->n_total, th_low, ratio) : -1;
+    if ((rc = step_motion_counting(f, images, motion, flags, th_low, ratio, -1, out, n_cross))) return rc;
     return *n_cross < -1 ? *n_cross : ORB_OK;
 }
 
@@ -1273,6 +1298,23 @@ static int orbf_step_end_impl(orbf_frontend* f, orbf_result* out) {
         if (hipEventQuery(f->ev_ready[f->inflight.front().set]) == hipSuccess) f->inflight.front().done = true;
         else (void)hipGetLastError();
     }
+    // what needs only the extraction's counts (orbf_frontend::Early), while the search runs: the run is this extractor's oldest, known
+    // complete and clean at begin, so the counts orbx_finish will adopt below can be read now
+    orbf_frontend::Early& E = f->early;
+    E.valid = false; E.cross_best = nullptr;
+    if (P.async_path && !P.inline_match && P.ext_done && orbx_peek_status(ex) == 0) {
+        E.counts.resize(f->n_cams);
+        int n_early = 0;
+        for (int c = 0; c < f->n_cams; ++c) { E.counts[c] = std::max(orbx_peek_count(ex, c), 0); n_early += E.counts[c]; }
+        E.cam_of.resize(n_early);
+        for (int c = 0, g = 0; c < f->n_cams; ++c)
+            for (int k = 0; k < E.counts[c]; ++k) E.cam_of[g++] = c;
+        E.valid = true;
+        if (E.want_cross && P.cross_from_set && !f->cross_pending[P.set] && !(P.flags & ORBF_SKIP_CROSS) && !f->xcomm && n_early > 0) {
+            E.n_cross = orbm_count_ratio_accepted(R.cross.b.p, R.cross.s.p, n_early, E.th_low, E.ratio);
+            E.cross_best = R.cross.b.p; E.cross_n = n_early;
+        }
+    }
     for (int attempt = 0; attempt < 2; ++attempt) {
         if (attempt == 1 && (rc = step_enqueue(f, P, false))) return rc;
         const auto t0 = std::chrono::steady_clock::now();
@@ -1341,9 +1383,12 @@ static int orbf_step_end_impl(orbf_frontend* f, orbf_result* out) {
     f->last_frame = P.fr; f->last_frame_owned = !P.fr_persistent;  // (returned to the pool when the next step starts)
     f->cur = P.set;
     f->prev_n = n;
-    f->prev_cam_of.resize(n);
-    for (int c = 0, g = 0; c < f->n_cams; ++c)
-        for (int k = 0; k < f->counts[c]; ++k) f->prev_cam_of[g++] = c;
+    if (E.valid && P.async_path && E.counts == f->counts && (int)E.cam_of.size() == n) f->prev_cam_of.swap(E.cam_of);   // (prepared in front of the wait)
+    else {
+        f->prev_cam_of.resize(n);
+        for (int c = 0, g = 0; c < f->n_cams; ++c)
+            for (int k = 0; k < f->counts[c]; ++k) f->prev_cam_of[g++] = c;
+    }
     out->n_queries = nq;
     if (P.use_ms && (P.flags & ORBF_NO_QUERY_RECORDS)) have_records = P.J.q_fill == nullptr;   // (a host fallback may have written them)
     out->queries = !P.use_ms ? reinterpret_cast<const orbm_query*>(f->h_queries.p) : (have_records && nq > 0 ? f->q_host.data() : nullptr);

@@ -887,6 +887,7 @@ __global__ __launch_bounds__(64 * MM_WAVES) MORB_MFMA_IN_VGPRS void k_project_si
                              X.p_second, X.d_range, bx, by);
     } else if (b < X.n_cross + X.n_project) {
         const int qi = __builtin_amdgcn_readfirstlane((b - X.n_cross) * 4 + (int)(threadIdx.x >> 6));
+        morb::project_args_batch(P);
         if (qi < P.nq) morb::project_wave(P, qi, threadIdx.x & 63);
     } else if (X.with_mirror) {
         const int nb = (int)gridDim.x - X.n_cross - X.n_project;

@@ -183,6 +183,10 @@ struct MotionSrc {
     float du, dv, th, mbf;
     orbm_query* rec_out;   // non-NULL: {blocks, angle} of every query into these records (the multi-workgroup resolve reads them)
 };
+// Which lane of the projection wave fetches which word of its query (project_wave: one load, one trip): lanes 0-7 the descriptor,
+// then the scalars, and from MOTION_LANE_CAM on cam_start[1 .. n_cams) -- room for rigs of up to 49 cameras, larger ones loop.
+constexpr int MOTION_LANE_X = 8, MOTION_LANE_Y = 9, MOTION_LANE_DEPTH = 10, MOTION_LANE_ANGLE = 11, MOTION_LANE_OCTAVE = 12,
+              MOTION_LANE_CAM = 16;
 
 // k_project + k_resolve on the device, one D2H of {status, matches}; falls back to host_resolve when the sweep limit is
 // hit, retries with a larger capacity when a candidate list overflowed.  Split in two so that a caller can enqueue

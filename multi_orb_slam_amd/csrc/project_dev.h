@@ -15,6 +15,16 @@ struct ProjectArgs {
     int from_motion = 0; MotionSrc ms;   // from_motion != 0: `q` is unused, the queries come from `ms`
 };
 
+// The kernel arguments the wave needs before its first trip to memory, asked for in ONE batch ahead of the first wait (call it in
+// front of the `qi < nq` test): left alone, the compiler fetches them where they are first used and waits for each group in turn
+// -- the query count, then from_motion, then the motion source's pointers.  Values only: nothing is dereferenced here.  (One
+// statement, kept alive by the query count it hands back: not volatile, so it is no barrier to the scalar loads behind it.  The
+// pointers only pass by: one that came out of the statement would no longer be known to point to global memory.)
+__device__ __forceinline__ void project_args_batch(ProjectArgs& A) {
+    asm("" : "+s"(A.nq), "+s"(A.from_motion), "+s"(A.ms.n_cams)
+        : "s"(A.ms.x), "s"(A.ms.y), "s"(A.ms.depth), "s"(A.ms.angle), "s"(A.ms.octave), "s"(A.ms.desc), "s"(A.ms.cam_start));
+}
+
 // One wave per query.  The window's grid cells are enumerated ix (outer) / iy (inner) -- the reference's visiting
 // order, App. A-8 -- 64 cells at a time, one per lane: every lane fetches its cell's [start, end) in parallel, a wave
 // prefix sum turns the counts into ordered item positions, then the items are tested 64 at a time and the survivors
@@ -37,18 +47,46 @@ __device__ __forceinline__ void project_wave(const ProjectArgs& A, const int qi,
     int minLevel, maxLevel, cam, q_cam, q_blocks;
     uint4 q0, q1;
     if (A.from_motion) {
+        // Everything the wave needs of its query arrives in ONE trip: a single vector load in which every lane asks for another
+        // word (MOTION_LANE_*), handed round by readlane afterwards.  Written field by field, the loads are wave-uniform and become
+        // scalar loads, which return out of order: every use drains all of them, and the octave -> level scale and the camera
+        // starts came as three more dependent trips behind the first (profiles/r23/notes_search_trips.md has the listings).
         const MotionSrc& M = A.ms;
-        const int oct = M.octave[qi];
-        const float dep = M.depth[qi];
-        q0 = M.desc[2 * qi]; q1 = M.desc[2 * qi + 1];
-        q_angle = M.angle[qi];
-        x = M.x[qi] + M.du; y = M.y[qi] + M.dv;
-        r = M.scale[oct] * M.th;
+        const int n_starts = M.n_cams - 1;   // cam_start[1 .. n_cams): the camera of query qi = how many of them are <= qi
+        const bool starts_in_lanes = n_starts <= 64 - MOTION_LANE_CAM;
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(M.octave + qi);   // (idle lanes: any word that is there)
+        if (lane < 8) src = reinterpret_cast<const uint32_t*>(M.desc + 2 * qi) + lane;
+        if (lane == MOTION_LANE_X) src = reinterpret_cast<const uint32_t*>(M.x + qi);
+        if (lane == MOTION_LANE_Y) src = reinterpret_cast<const uint32_t*>(M.y + qi);
+        if (lane == MOTION_LANE_DEPTH) src = reinterpret_cast<const uint32_t*>(M.depth + qi);
+        if (lane == MOTION_LANE_ANGLE) src = reinterpret_cast<const uint32_t*>(M.angle + qi);
+        const bool holds_start = starts_in_lanes && lane >= MOTION_LANE_CAM && lane < MOTION_LANE_CAM + n_starts;
+        if (holds_start) src = reinterpret_cast<const uint32_t*>(M.cam_start + 1 + (lane - MOTION_LANE_CAM));
+        // the level scale without memory: lane l keeps scale l (built while the load is under way), one readlane picks the query's.
+        // (The by-value scales are scalar registers once the kernel arguments are in; left to itself the compiler selects an
+        //  OFFSET into the argument block by the octave and loads from there -- the opaque moves keep them in registers.)
+        float lane_scale = 0.0f;
+#pragma unroll
+        for (int l = 0; l < 16; ++l) {
+            float s = M.scale[l];
+            asm("" : "+s"(s));
+            lane_scale = lane == l ? s : lane_scale;
+        }
+        const int w = (int)*src;
+        auto word = [&](int l) { return __builtin_amdgcn_readlane(w, l); };
+        const int oct = word(MOTION_LANE_OCTAVE);
+        const float dep = __int_as_float(word(MOTION_LANE_DEPTH));
+        q0 = make_uint4((uint32_t)word(0), (uint32_t)word(1), (uint32_t)word(2), (uint32_t)word(3));
+        q1 = make_uint4((uint32_t)word(4), (uint32_t)word(5), (uint32_t)word(6), (uint32_t)word(7));
+        q_angle = __int_as_float(word(MOTION_LANE_ANGLE));
+        x = __int_as_float(word(MOTION_LANE_X)) + M.du; y = __int_as_float(word(MOTION_LANE_Y)) + M.dv;
+        r = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lane_scale), oct)) * M.th;
         const float inv = dep > 0 ? 1.0f / dep : 0.0f;
         ur = x - M.mbf * inv;
         minLevel = oct - 1; maxLevel = oct + 1;
-        cam = 0;
-        for (int c = 1; c < M.n_cams; ++c) cam += (M.cam_start[c] <= qi) ? 1 : 0;
+        cam = __popcll(__ballot(holds_start && w <= qi));
+        if (!starts_in_lanes)   // (more cameras than lanes for their starts: the loop of loads)
+            for (int c = 1; c < M.n_cams; ++c) cam += (M.cam_start[c] <= qi) ? 1 : 0;
         q_blocks = 1;
     } else {
         const orbm_query* Q = q + qi;

@@ -32,6 +32,7 @@ namespace {
 __global__ __launch_bounds__(256) void k_project(ProjectArgs A) {
     MORB_LATENCY_KERNEL_WIDE();
     const int qi = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    project_args_batch(A);
     if (qi >= A.nq) return;
     project_wave(A, qi, threadIdx.x & 63);
 }
@@ -463,49 +464,86 @@ __global__ __launch_bounds__(1024) void k_resolve_mono(FrameDev F, const int2* _
     float* l_fang = lds_at<float>(s_claim, L.fang());
     unsigned short* l_wl = lds_at<unsigned short>(s_claim, L.wl());   // worklist of displaced queries (nq2 entries)
     __shared__ int s_wl_n[2];
-    if (tid == 0) s_red = 0;
-    if (tid < ORBM_HISTO_LENGTH) s_hist[tid] = 0;
-    for (int g = tid; g < F.n_total; g += T) {
-        s_claim[g] = 0x7fffffff; s_owner[g] = -1;
-        if (ANG && check_ori) l_fang[g] = f_angle[g];
-    }
-    __syncthreads();   // (the claims of round 0 go into the table right below)
     // per query of this thread (two in registers; more only beyond 2048 queries, re-read from LDS every round): the shortlist
     // (feature indices, 0xffff = none: every entry k_project put there is acceptable -- not occupied, distance <= th_high --, so the
     // distances stay behind), the cursor, the pick under it (a rescanned pick is not on the shortlist)
     constexpr int K = RESOLVE_K;
     int sl[RQ][K], cur[RQ], pos[RQ], flr[RQ];
     int mx = 0;
-    // set-up of one query: every load is independent of every other -- one trip to HBM for the whole pass.  Round 0 rides along:
-    // without any claim a query takes the head of its shortlist (every entry there is acceptable: not occupied, distance <=
-    // th_high) and, if it blocks, claims it
-    auto setup = [&](const int i, int (&e)[K], int& c, int& fl) {
-        const int cnt_i = cand_count[i];
-        mx = max(mx, cnt_i);
-        l_cnt[i] = (unsigned short)min(cnt_i, 65535);
-        const int2 qm = qmeta[i];
-        fl = (qm.x & 1) | (topk[(2 * K) * nq + i] > K ? 2 : 0);
+    // What set-up reads of one query: every load is independent of every other.  The lines were written by k_project from other XCDs a
+    // moment ago, so every trip is a trip to memory: ALL of a thread's loads -- its RQ register slots and its first feature angles --
+    // are issued in straight-line code with clamped indices before anything waits, stores to LDS or meets the barrier (a load under
+    // an `i < nq` branch is drained at the branch's end, a load in the initialisation loop at every iteration: four trips for one).
+    struct QueryWords { int cnt, elig; int2 qm; int tk[K]; };
+    auto load_query = [&](const int i, QueryWords& w) {
+        w.cnt = cand_count[i];
+        w.qm = qmeta[i];
+        w.elig = topk[(2 * K) * nq + i];
+#pragma unroll
+        for (int k = 0; k < K; ++k) w.tk[k] = tk_g[k * nq + i];
+    };
+    // ... and what it makes of them, in LDS and in the caller's registers.  Round 0 rides along: without any claim a query takes the
+    // head of its shortlist (every entry there is acceptable: not occupied, distance <= th_high); if it blocks, the caller claims it
+    // (claim_head) once the table has been initialised
+    auto store_query = [&](const int i, const QueryWords& w, int (&e)[K], int& c, int& fl) {
+        mx = max(mx, w.cnt);
+        l_cnt[i] = (unsigned short)min(w.cnt, 65535);
+        fl = (w.qm.x & 1) | (w.elig > K ? 2 : 0);
         l_fl[i] = (unsigned char)fl;
-        if (ANG) l_ang[i] = __int_as_float(qm.y);
+        if (ANG) l_ang[i] = __int_as_float(w.qm.y);
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            e[k] = tk_g[k * nq + i] & 0xffff;
+            e[k] = w.tk[k] & 0xffff;
             l_gd[k * nq2 + i] = (unsigned short)e[k];
         }
         const bool has = e[0] != 0xffff;
         c = has ? e[0] : -1;
         l_choice[i] = (unsigned short)(has ? e[0] : 0xffff);
-        if (has && (fl & 1)) atomicMin(&s_claim[e[0]], i);
     };
+    auto claim_head = [&](const int i, const int c, const int fl) {
+        if (c >= 0 && (fl & 1)) atomicMin(&s_claim[c], i);
+    };
+    constexpr int FA = 2;   // feature angles of a thread fetched with the queries (frames of up to FA * T features: no later trip)
+    const bool want_fang = ANG && check_ori;
+    QueryWords qw[RQ];
+    float fa[FA];
+    const int i_last = max(nq - 1, 0), g_last = max(F.n_total - 1, 0);   // (a clamped load reads a neighbour's words: never used)
+#pragma unroll
+    for (int b = 0; b < RQ; ++b) load_query(min(b * T + tid, i_last), qw[b]);
+#pragma unroll
+    for (int a = 0; a < FA; ++a) fa[a] = ANG ? f_angle[min(a * T + tid, g_last)] : 0.0f;
+    // (these two stand BEHIND the loads on purpose: a load whose one use sits in the branch right behind it is moved into that branch)
+    if (tid == 0) s_red = 0;
+    if (tid < ORBM_HISTO_LENGTH) s_hist[tid] = 0;
+#pragma unroll
+    for (int a = 0; a < FA; ++a) {
+        const int g = a * T + tid;
+        if (g < F.n_total) {
+            s_claim[g] = 0x7fffffff; s_owner[g] = -1;
+            if (want_fang) l_fang[g] = fa[a];
+        }
+    }
+    for (int g = FA * T + tid; g < F.n_total; g += T) {
+        s_claim[g] = 0x7fffffff; s_owner[g] = -1;
+        if (want_fang) l_fang[g] = f_angle[g];
+    }
 #pragma unroll
     for (int b = 0; b < RQ; ++b) {
         const int i = b * T + tid;
         cur[b] = -1; pos[b] = 0; flr[b] = 0;
 #pragma unroll
         for (int k = 0; k < K; ++k) sl[b][k] = 0xffff;
-        if (i < nq) setup(i, sl[b], cur[b], flr[b]);
+        if (i < nq) store_query(i, qw[b], sl[b], cur[b], flr[b]);
     }
-    for (int i = RQ * T + tid; i < nq; i += T) { int e[K], c, fl; setup(i, e, c, fl); }
+    __syncthreads();   // (the claims of round 0 go into the table right below)
+#pragma unroll
+    for (int b = 0; b < RQ; ++b) claim_head(b * T + tid, cur[b], flr[b]);   // (no query in the slot: cur < 0)
+    for (int i = RQ * T + tid; i < nq; i += T) {
+        QueryWords w; int e[K], c, fl;
+        load_query(i, w);
+        store_query(i, w, e, c, fl);
+        claim_head(i, c, fl);
+    }
     mx = (int)(0x7fffffffu - wave_min_u32(0x7fffffffu - (unsigned)mx));
     if (lane == 0) atomicMax(&s_red, mx);
     __syncthreads();
