@@ -74,6 +74,10 @@ int orbm_debug_last_bundle_adjust(const orbm_matcher* m, int* out8);
  * host routine because no free vertex is active), kernel launches, stream synchronisations, 0, block pairs computed (the diagonal
  * blocks included), block pairs possible (na (na + 1) / 2), panels of the blocked LDL^T, 0} (inspection only) */
 int orbm_debug_last_essential_graph(const orbm_matcher* m, int* out8);
+/* What the last orbm_map_vote / orbm_map_local_points on the map did: {1 if the last call ran on the device (0: MORB_HOST_RESOLVE=1,
+ * the host routines over the mirror), observation records scanned by the last vote, candidates of the last point list (the sum of the
+ * listed keyframes' feature counts), points it kept} (inspection only) */
+int orbm_debug_last_local_map(const orbm_map* map, int* out4);
 /* Where the work of the last orbm_pnp_ransac went: {problems on the device, problems through the host routine because they have more
  * than ORBM_PNP_CAP correspondences, records refined on the device, records refined by the host routine because they lie beyond
  * ORBM_PNP_MAX_RECORDS of a device problem} (inspection only) */

@@ -15,6 +15,8 @@
  *   ORBmatcher::ComputeThreeMaxima   reference src/ORBmatcher.cc:3948-3989             -> orbm_three_maxima
  *   Tracking::SearchLocalPoints from its second loop on: Frame::isInFrustum + that SearchByProjection
  *        reference src/Tracking.cc:1730-1768, src/Frame.cc:443-499                    -> orbm_points_*, orbm_search_local_points
+ *   Tracking::UpdateLocalKeyFrames' votes, Tracking::UpdateLocalPoints and that search over a map resident under stable slots
+ *        reference src/Tracking.cc:1838-1855, :1794-1824                              -> orbm_map_*, orbm_local_map_*_host
  *   MapPoint::ComputeDistinctiveDescriptors + MapPoint::UpdateNormalAndDepth, batched over the points of a keyframe
  *        reference src/MapPoint.cc:325-438, :480-528                                  -> orbm_refresh_points[_host]
  *
@@ -310,6 +312,69 @@ int orbm_level_thresholds(float log_scale_factor, int n_levels, float* out);
  * q[i] is the query of point i, with cam = -1 (no window) where the point is not in view. */
 int orbm_frustum_host(const orbm_point* pts, int n, const orbm_view* view, const uint8_t* skip, orbm_track* track,
                       orbm_query* q, int* n_to_match);
+
+/* -- the local map on the device: Tracking::UpdateLocalMap over a resident map ----------------------------------
+ * A map that stays in HBM under stable slots -- one per map point, one per keyframe, one per observation -- and the three calls
+ * of Tracking::TrackLocalMap's first half over it (reference src/Tracking.cc:1794-1949, :1730-1768):
+ *   orbm_map_vote                 the keyframe votes of UpdateLocalKeyFrames (:1838-1855): one stream over the observation records
+ *   orbm_map_local_points         UpdateLocalPoints (:1794-1824): a gather over the local keyframes' rows, de-duplicated in order
+ *   orbm_map_search_local_points  orbm_search_local_points over the list the call before left on the device
+ * What is sequential pointer logic (K1 in std::map order, the K2 walk with its marks) stays with the caller, where the graph
+ * lives.  A point's row is sent when the point changes (orbm_map_write_points), never because its place in a list moved.
+ * The object keeps a host mirror of everything it holds; every call runs on the handle's stream and synchronises it once. */
+typedef struct orbm_map orbm_map;
+typedef struct { int32_t point, keyframe; } orbm_obs;   /* one observation; point == -1: a free record */
+enum { ORBM_MAP_MAX_KEYFRAMES = 16384, ORBM_MAP_MAX_FEATURES = 8192, ORBM_MAP_MAX_LOCAL = 4096 };
+enum { ORBM_POINT_BAD = 1 };   /* bit 0 of a point's flag byte: MapPoint::isBad() */
+
+/* kf_capacity 1 .. ORBM_MAP_MAX_KEYFRAMES, features_per_keyframe 1 .. ORBM_MAP_MAX_FEATURES (the stride of a keyframe's row);
+ * point_capacity and obs_capacity >= 0, bounded by memory alone.  Everything starts empty: rows of zeros that are not bad, free
+ * records, keyframes without points. */
+int orbm_map_create(orbm_matcher* m, int kf_capacity, int point_capacity, int obs_capacity, int features_per_keyframe, orbm_map** out);
+void orbm_map_destroy(orbm_map* map);
+/* Point slots slots[0 .. n): row rows[i] and flag byte flags[i] (flags == NULL: 0) into slot slots[i].  A slot named twice takes
+ * its last entry.  One synchronisation; returns when the rows are in HBM.  A slot outside the capacity: ORB_E_CAPACITY, nothing written. */
+int orbm_map_write_points(orbm_matcher* m, orbm_map* map, const int32_t* slots, int n, const orbm_point* rows, const uint8_t* flags);
+/* Record slots slots[0 .. n).  records[i].point is a point slot or -1 (free), .keyframe a keyframe slot (ignored in a free
+ * record).  AT MOST ONE LIVE RECORD PER (point, keyframe), as std::map<KeyFrame*, size_t> guarantees: this is the caller's to
+ * keep and is not checked -- a pair held twice votes twice.  The keyframe high-water mark covers every keyframe a record names. */
+int orbm_map_write_observations(orbm_matcher* m, orbm_map* map, const int32_t* slots, int n, const orbm_obs* records);
+/* Keyframe slot kf: mvpMapPoints as point slots (-1 = none), n_features <= features_per_keyframe entries, and isBad(). */
+int orbm_map_write_keyframe(orbm_matcher* m, orbm_map* map, int kf, const int32_t* point_of_feature, int n_features, int bad);
+int orbm_map_set_keyframe_bad(orbm_matcher* m, orbm_map* map, int kf, int bad);   /* the flag alone (host mirror: no kernel reads it) */
+int orbm_map_keyframes(const orbm_map* map);   /* keyframe high-water mark: one past the last keyframe slot written or named by a record */
+int orbm_map_keyframe_bad(const orbm_map* map, int kf);
+
+/* votes[k], k < orbm_map_keyframes(map): the sum over the features f with frame_points[f] >= 0 and the point not bad of
+ * [a live record (frame_points[f], k) exists] -- keyframeCounter of :1838-1855; a point that sits at two features votes twice.  Bad
+ * keyframes are counted; the caller drops them (:1875).  frame_points[f] is a point slot or negative. */
+int orbm_map_vote(orbm_matcher* m, orbm_map* map, const int32_t* frame_points, int n_features, int32_t* votes);
+/* The candidates are the entries of the rows of local_kfs[0 .. n_local), n_local <= ORBM_MAP_MAX_LOCAL, in the order (position in
+ * local_kfs, feature index).  A candidate is kept if its slot is not negative, the point is not bad and no earlier candidate
+ * holds the same point.  list (room for ORBM_MAX_POINTS entries) receives the kept slots in order, *n_list their number; the list
+ * also stays on the device for orbm_map_search_local_points.  More than ORBM_MAX_POINTS kept points: ORB_E_CAPACITY, and no
+ * list is left.
+ * One deviation from the reference: its mark mnTrackReferenceForFrame survives between calls, so a second UpdateLocalPoints for the
+ * same frame id yields an empty list there.  Here every call starts unmarked. */
+int orbm_map_local_points(orbm_matcher* m, orbm_map* map, const int32_t* local_kfs, int n_local, int32_t* list, int* n_list);
+/* orbm_search_local_points over the list of the last orbm_map_local_points: point i of the search is the point in slot list[i];
+ * track (n_list entries, may be NULL) and match_of_feature index the LIST.  The skip flag is built on the device: a point is
+ * skipped if it is bad, if it is one of frame_points[0 .. n_features) whose point is not bad (the frame's own points, Tracking.cc
+ * :1735-1750) or if it is one of seen[0 .. n_seen) (mnLastFrameSeen as TrackWithMotionModel sets it at :1310).  Everything else as
+ * in orbm_search_local_points, the deviation included. */
+int orbm_map_search_local_points(orbm_matcher* m, const orbm_frame* cur, orbm_map* map, const orbm_view* view,
+                                 const int32_t* frame_points, int n_features, const int32_t* seen, int n_seen,
+                                 const uint8_t* occupied, float nnratio, int th_high, orbm_track* track, int32_t* match_of_feature,
+                                 int* n_to_match, int* nmatches);
+/* Host, on plain arrays, no device and no handle: the fallback and the cross-check of the two calls above.
+ * obs[0 .. n_obs) records (free ones included), point_flags[0 .. n_points), votes[0 .. n_kfs).  A record whose point or keyframe
+ * lies outside those counts: ORB_E_ARG. */
+int orbm_local_map_vote_host(const orbm_obs* obs, int n_obs, const uint8_t* point_flags, int n_points, const int32_t* frame_points,
+                             int n_features, int n_kfs, int32_t* votes);
+/* kf_rows[k * stride + f], f < kf_count[k], the rows of n_kfs keyframes; list has room for list_cap entries; *n_list is the number
+ * kept even when it exceeds list_cap (ORB_E_CAPACITY then, the first list_cap entries written). */
+int orbm_local_map_points_host(const int32_t* kf_rows, const int32_t* kf_count, int n_kfs, int stride, const uint8_t* point_flags,
+                               int n_points, const int32_t* local_kfs, int n_local, int32_t* list, int list_cap, int* n_list);
 
 /* -- map-point refresh: distinctive descriptor, normal, depth --------------------------------------------------
  * The producer of what an orbm_point row holds beyond the position: MapPoint::ComputeDistinctiveDescriptors (reference

@@ -9,6 +9,8 @@ from ._lib import lib, build, LIB_PATH, OrbError, KP_DTYPE, QUERY_DTYPE, POINT_D
 from .extractor import Extractor, ExtractorParams, tables  # noqa: F401
 from .matcher import Matcher, FrameData, LocalPoints, View, descriptor_distance, three_maxima  # noqa: F401
 from .matcher import frustum_host, level_thresholds, RefreshBatch, refresh_points_host  # noqa: F401
+from .matcher import ResidentMap, local_map_vote_host, local_map_points_host  # noqa: F401
+from ._lib import OBS_DTYPE, MAX_POINTS, MAP_MAX_KEYFRAMES, MAP_MAX_FEATURES, MAP_MAX_LOCAL, POINT_BAD  # noqa: F401
 from .matcher import PoseProblem, pose_optimize_host, pose_sincos  # noqa: F401
 from ._lib import POSE_PROBLEM_DTYPE, POSE_RESULT_DTYPE, POSE_CAM0, POSE_ALL_CAMS, POSE_ORDER_INDEX, POSE_ORDER_DEVICE, POSE_CAP  # noqa: F401
 from .matcher import Sim3Problem, sim3_ransac_host, sim3_walk, sim3_iterations, sim3_atan2  # noqa: F401

@@ -25,6 +25,9 @@ REFRESH_DTYPE = np.dtype([("desc", "u1", (32,)), ("normal", "<f4", (3,)), ("min_
                           ("best_obs", "<i4"), ("best_median", "<i4")])   # orbm_refresh_out
 assert REFRESH_DTYPE.itemsize == 60
 REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH, REFRESH_CAP = 1, 2, 256
+OBS_DTYPE = np.dtype([("point", "<i4"), ("keyframe", "<i4")])   # orbm_obs
+assert OBS_DTYPE.itemsize == 8
+MAX_POINTS, MAP_MAX_KEYFRAMES, MAP_MAX_FEATURES, MAP_MAX_LOCAL, POINT_BAD = 65535, 16384, 8192, 4096, 1
 POSE_PROBLEM_DTYPE = np.dtype([("Tcw", "<f4", (16,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("bf", "<f4"),
                                ("Rcam12", "<f4", (9,)), ("tcam12", "<f4", (3,)), ("inv_level_sigma2", "<f4", (32,)),
                                ("n_levels", "<i4"), ("mode", "<i4"), ("n_cam0", "<i4")])   # orbm_pose_problem
@@ -326,6 +329,20 @@ def lib():
     L.orbm_search_local_points.argtypes = [vp, vp, vp, i32, vp, vp, vp, f32, i32, vp, vp, vp, vp]
     L.orbm_level_thresholds.argtypes = [f32, i32, vp]
     L.orbm_frustum_host.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.orbm_map_create.argtypes = [vp, i32, i32, i32, i32, vp]
+    L.orbm_map_destroy.argtypes = [vp]; L.orbm_map_destroy.restype = None
+    L.orbm_map_write_points.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.orbm_map_write_observations.argtypes = [vp, vp, vp, i32, vp]
+    L.orbm_map_write_keyframe.argtypes = [vp, vp, i32, vp, i32, i32]
+    L.orbm_map_set_keyframe_bad.argtypes = [vp, vp, i32, i32]
+    L.orbm_map_keyframes.argtypes = [vp]
+    L.orbm_map_keyframe_bad.argtypes = [vp, i32]
+    L.orbm_map_vote.argtypes = [vp, vp, vp, i32, vp]
+    L.orbm_map_local_points.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.orbm_map_search_local_points.argtypes = [vp, vp, vp, vp, vp, i32, vp, i32, vp, f32, i32, vp, vp, vp, vp]
+    L.orbm_local_map_vote_host.argtypes = [vp, i32, vp, i32, vp, i32, i32, vp]
+    L.orbm_local_map_points_host.argtypes = [vp, vp, i32, i32, vp, i32, vp, i32, vp, i32, vp]
+    L.orbm_debug_last_local_map.argtypes = [vp, vp]
     L.orbm_refresh_points.argtypes = [vp, vp, vp]
     L.orbm_refresh_points_host.argtypes = [vp, vp]
     L.orbm_debug_last_refresh.argtypes = [vp, vp]

@@ -85,15 +85,28 @@ __host__ __device__ inline void frustum_records(const FrustumView& V, const orbm
     }
 }
 
-// One lane per table row.  A few dozen flops and 160 bytes per point: the launch is what it costs.  `track` is mapped pinned
+// One lane per point.  A few dozen flops and 160 bytes per point: the launch is what it costs.  `track` is mapped pinned
 // host memory (the caller reads it after the stream has been synchronised), `q` the matcher's query buffer in HBM.
+// INDEXED (the resident map, localmap.hip): point i is row index[i], and it is skipped if its flag byte says bad or its mark is the
+// call's epoch (k_map_mark); otherwise point i is row i and skip[i] decides.
+struct FrustumIndex { const int32_t* index; const uint32_t* mark; const uint8_t* flags; uint32_t epoch; };
+
+template <bool INDEXED>
 __global__ __launch_bounds__(256) void k_frustum(FrustumView V, const orbm_point* __restrict__ pts, const uint8_t* __restrict__ skip, int n,
-                                                 orbm_query* __restrict__ q, orbm_track* __restrict__ track) {
+                                                 orbm_query* __restrict__ q, orbm_track* __restrict__ track, FrustumIndex X) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const orbm_point pt = pts[i];
+    int row = i;
+    bool skipped;
+    if (INDEXED) {
+        row = X.index[i];
+        skipped = (X.flags[row] & ORBM_POINT_BAD) != 0 || X.mark[row] == X.epoch;
+    } else {
+        skipped = skip && skip[i] != 0;
+    }
+    const orbm_point pt = pts[row];
     orbm_query Q; orbm_track T;
-    frustum_records(V, pt, skip && skip[i] != 0, Q, T);
+    frustum_records(V, pt, skipped, Q, T);
     q[i] = Q;
     track[i] = T;
 }
@@ -138,16 +151,42 @@ int make_view(const orbm_view* v, const float* thr, FrustumView& V) {
     return ORB_OK;
 }
 
-void frustum_host(const FrustumView& V, const orbm_point* pts, int n, const uint8_t* skip, orbm_track* track, orbm_query* q, int* n_in) {
+void frustum_host(const FrustumView& V, const orbm_point* pts, const int32_t* index, int n, const uint8_t* skip, orbm_track* track,
+                  orbm_query* q, int* n_in) {
     int cnt = 0;
     for (int i = 0; i < n; ++i) {
         orbm_query Q; orbm_track T;
-        frustum_records(V, pts[i], skip && skip[i] != 0, Q, T);
+        frustum_records(V, pts[index ? index[i] : i], skip && skip[i] != 0, Q, T);
         cnt += T.in_view;
         if (q) q[i] = Q;
         if (track) track[i] = T;
     }
     if (n_in) *n_in = cnt;
+}
+
+int thresholds_of(FrustumScratch& p, const orbm_view* v) {
+    if (p.thr_levels == v->n_levels && memcmp(&p.thr_lsf, &v->log_scale_factor, 4) == 0) return ORB_OK;
+    p.thr_levels = 0;
+    int rc = build_thresholds(v->log_scale_factor, v->n_levels, p.thr);
+    if (rc) return rc;
+    p.thr_lsf = v->log_scale_factor; p.thr_levels = v->n_levels;
+    return ORB_OK;
+}
+
+// the skip flags of a source on the host: the caller's, or (resident map) the ones its routine writes into `store`
+const uint8_t* host_skip_of(const LocalPointSource& S, int n, std::vector<uint8_t>& store) {
+    if (!S.host_skip) return S.skip;
+    store.assign((size_t)n, 0);
+    S.host_skip(S.host_skip_ctx, store.data());
+    return store.data();
+}
+
+struct FillCtx { const FrustumView* V; const LocalPointSource* S; int n; orbm_query* q; };
+void fill_queries(void* c) {
+    const FillCtx* F = (const FillCtx*)c;
+    std::vector<uint8_t> store;
+    const uint8_t* skip = host_skip_of(*F->S, F->n, store);
+    frustum_host(*F->V, F->S->h_rows, F->S->h_index, F->n, skip, nullptr, F->q, nullptr);
 }
 
 }  // namespace
@@ -158,19 +197,8 @@ struct orbm_points {
     int capacity = 0, count = 0;
     DevBuf<orbm_point> d;            // the table
     std::vector<orbm_point> h;       // its host mirror: the exact host fallback of the search rebuilds the queries from it
-    PinnedBuf<orbm_track> h_track;   // written by k_frustum
-    std::vector<orbm_query> hq;      // host queries (fallback / MORB_HOST_RESOLVE=1 only)
-    float thr_lsf = 0; int thr_levels = 0; float thr[ORBM_MAX_LEVELS - 1];   // level thresholds of the last (log_scale_factor, n_levels)
+    FrustumScratch s;                // what a search keeps between calls: the records k_frustum writes, host queries, level thresholds
 };
-
-static int thresholds_of(orbm_points* p, const orbm_view* v) {
-    if (p->thr_levels == v->n_levels && memcmp(&p->thr_lsf, &v->log_scale_factor, 4) == 0) return ORB_OK;
-    p->thr_levels = 0;
-    int rc = build_thresholds(v->log_scale_factor, v->n_levels, p->thr);
-    if (rc) return rc;
-    p->thr_lsf = v->log_scale_factor; p->thr_levels = v->n_levels;
-    return ORB_OK;
-}
 
 int orbm_level_thresholds(float log_scale_factor, int n_levels, float* out) {
     MORB_ARG(n_levels >= 1 && n_levels <= ORBM_MAX_LEVELS && (n_levels == 1 || out));
@@ -190,7 +218,7 @@ int orbm_frustum_host(const orbm_point* pts, int n, const orbm_view* view, const
     }
     FrustumView V;
     make_view(view, cache.thr, V);
-    frustum_host(V, pts, n, skip, track, q, n_to_match);
+    frustum_host(V, pts, nullptr, n, skip, track, q, n_to_match);
     return ORB_OK;
 }
 
@@ -201,8 +229,8 @@ int orbm_points_create(orbm_matcher* m, int capacity, orbm_points** out) {
     orbm_points* p = new orbm_points;
     p->owner = m; p->device = m->device; p->capacity = capacity;
     int rc;
-    if ((rc = p->d.reserve((size_t)std::max(capacity, 1))) || (rc = p->h_track.reserve((size_t)std::max(capacity, 1)))) {
-        p->d.release(); p->h_track.release(); delete p;
+    if ((rc = p->d.reserve((size_t)std::max(capacity, 1))) || (rc = p->s.h_track.reserve((size_t)std::max(capacity, 1)))) {
+        p->d.release(); p->s.h_track.release(); delete p;
         return rc;
     }
     p->h.resize((size_t)capacity);
@@ -211,7 +239,7 @@ int orbm_points_create(orbm_matcher* m, int capacity, orbm_points** out) {
     if (hipMemsetAsync(p->d.p, 0, (size_t)std::max(capacity, 1) * sizeof(orbm_point), m->stream) != hipSuccess ||
         hipStreamSynchronize(m->stream) != hipSuccess) {
         morb::set_error("clearing the point table failed");
-        p->d.release(); p->h_track.release(); delete p;
+        p->d.release(); p->s.h_track.release(); delete p;
         return ORB_E_HIP;
     }
     *out = p;
@@ -221,7 +249,7 @@ int orbm_points_create(orbm_matcher* m, int capacity, orbm_points** out) {
 void orbm_points_destroy(orbm_points* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
-    p->d.release(); p->h_track.release();
+    p->d.release(); p->s.h_track.release();
     delete p;
 }
 
@@ -247,13 +275,60 @@ int orbm_points_write(orbm_matcher* m, orbm_points* p, int first, int n, const o
     return ORB_OK;
 }
 
-namespace {
-struct FillCtx { const FrustumView* V; const orbm_points* p; int n; const uint8_t* skip; orbm_query* q; };
-void fill_queries(void* c) {
-    const FillCtx* F = (const FillCtx*)c;
-    frustum_host(*F->V, F->p->h.data(), F->n, F->skip, nullptr, F->q, nullptr);
+// The body both entries of the local-point search share: thresholds, k_frustum into the matcher's query buffer, project + resolve
+// behind it, one synchronisation, the exact host route when the matcher asks for it or the resolve falls back.
+int morb::search_local_points_body(orbm_matcher* m, const orbm_frame* cur, FrustumScratch& scr, const LocalPointSource& S, int n,
+                                   const orbm_view* view, const uint8_t* occupied, float nnratio, int th_high, orbm_track* track,
+                                   int32_t* match_of_feature, int* n_to_match, int* nmatches) {
+    MORB_HIP(hipSetDevice(m->device));
+    int rc;
+    if ((rc = thresholds_of(scr, view))) return rc;
+    FrustumView V;
+    make_view(view, scr.thr, V);
+    *n_to_match = 0; *nmatches = 0;
+    const int nf = cur->n_total;
+    if (n == 0) { for (int g = 0; g < nf; ++g) match_of_feature[g] = -1; return ORB_OK; }
+
+    if ((rc = scr.h_track.reserve((size_t)n))) return rc;
+    scr.hq.resize((size_t)n);
+    FillCtx ctx{&V, &S, n, scr.hq.data()};
+    // J.q: host records.  On the device path they are NOT written here -- nothing reads them unless the resolve falls back, and then
+    // q_fill (below) writes them first.  Until then the buffer may hold an earlier call's records: do not read it here.
+    SearchJob J{cur, scr.hq.data(), n, occupied, true, nnratio, th_high, 0, 64, false};
+    if (m->host_resolve) {   // MORB_HOST_RESOLVE=1: everything from the host restatement, the search through host_resolve
+        int cnt = 0;
+        std::vector<uint8_t> store;
+        const uint8_t* skip = host_skip_of(S, n, store);
+        frustum_host(V, S.h_rows, S.h_index, n, skip, track, scr.hq.data(), &cnt);
+        *n_to_match = cnt;
+        if ((rc = search_enqueue(m, J))) return rc;
+        return search_finish(m, J, match_of_feature, nmatches);
+    }
+    // skip flags and occupied flags through the host-written staging, read in place by the kernels
+    const size_t sbytes = ((size_t)n + 255) & ~(size_t)255, obytes = occupied ? (size_t)nf : 0;
+    if ((rc = m->stage_q.reserve(sbytes + obytes + 16)) || (rc = m->d_queries.reserve((size_t)n * sizeof(orbm_query)))) return rc;
+    if (S.skip) memcpy(m->stage_q.p, S.skip, (size_t)n);
+    if (occupied) memcpy(m->stage_q.p + sbytes, occupied, obytes);
+    m->stage_q.publish();
+    J.occ_dev = occupied ? m->stage_q.dp + sbytes : nullptr;
+    J.q_fill = fill_queries; J.q_fill_ctx = &ctx;   // host records only if the resolve falls back
+    const FrustumIndex X{S.d_index, S.d_mark, S.d_flags, S.epoch};
+    if (S.d_index)
+        hipLaunchKernelGGL(k_frustum<true>, dim3((n + 255) / 256), dim3(256), 0, m->stream, V, S.d_rows, (const uint8_t*)nullptr, n,
+                           (orbm_query*)m->d_queries.p, scr.h_track.dp, X);
+    else
+        hipLaunchKernelGGL(k_frustum<false>, dim3((n + 255) / 256), dim3(256), 0, m->stream, V, S.d_rows,
+                           S.skip ? (const uint8_t*)m->stage_q.dp : (const uint8_t*)nullptr, n, (orbm_query*)m->d_queries.p, scr.h_track.dp, X);
+    MORB_HIP(hipGetLastError());
+    if ((rc = search_enqueue(m, J, /*queries_already_on_device=*/true))) return rc;
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    int cnt = 0;
+    const orbm_track* T = scr.h_track.p;
+    for (int i = 0; i < n; ++i) cnt += T[i].in_view;
+    *n_to_match = cnt;
+    if (track) memcpy(track, T, (size_t)n * sizeof(orbm_track));
+    return search_finish(m, J, match_of_feature, nmatches);
 }
-}  // namespace
 
 int orbm_search_local_points(orbm_matcher* m, const orbm_frame* cur, const orbm_points* pts_c, int n, const orbm_view* view,
                              const uint8_t* skip, const uint8_t* occupied, float nnratio, int th_high, orbm_track* track,
@@ -264,44 +339,7 @@ int orbm_search_local_points(orbm_matcher* m, const orbm_frame* cur, const orbm_
     MORB_ARG(view->n_levels >= 1 && view->n_levels <= ORBM_MAX_LEVELS && view->scale_factors);
     if (n > pts->count) { morb::set_error("%d points asked for, %d written to the table", n, pts->count); return ORB_E_CAPACITY; }
     if (n > ORBM_MAX_POINTS) { morb::set_error("%d points are more than a search takes (%d)", n, (int)ORBM_MAX_POINTS); return ORB_E_CAPACITY; }
-    MORB_HIP(hipSetDevice(m->device));
-    int rc;
-    if ((rc = thresholds_of(pts, view))) return rc;
-    FrustumView V;
-    make_view(view, pts->thr, V);
-    *n_to_match = 0; *nmatches = 0;
-    const int nf = cur->n_total;
-    if (n == 0) { for (int g = 0; g < nf; ++g) match_of_feature[g] = -1; return ORB_OK; }
-
-    pts->hq.resize((size_t)n);
-    FillCtx ctx{&V, pts, n, skip, pts->hq.data()};
-    // J.q: host records.  On the device path they are NOT written here -- nothing reads them unless the resolve falls back, and then
-    // q_fill (below) writes them first.  Until then the buffer may hold an earlier call's records: do not read it here.
-    SearchJob J{cur, pts->hq.data(), n, occupied, true, nnratio, th_high, 0, 64, false};
-    if (m->host_resolve) {   // MORB_HOST_RESOLVE=1: everything from the host restatement, the search through host_resolve
-        int cnt = 0;
-        frustum_host(V, pts->h.data(), n, skip, track, pts->hq.data(), &cnt);
-        *n_to_match = cnt;
-        if ((rc = search_enqueue(m, J))) return rc;
-        return search_finish(m, J, match_of_feature, nmatches);
-    }
-    // skip flags and occupied flags through the host-written staging, read in place by the kernels
-    const size_t sbytes = ((size_t)n + 255) & ~(size_t)255, obytes = occupied ? (size_t)nf : 0;
-    if ((rc = m->stage_q.reserve(sbytes + obytes + 16)) || (rc = m->d_queries.reserve((size_t)n * sizeof(orbm_query)))) return rc;
-    if (skip) memcpy(m->stage_q.p, skip, (size_t)n);
-    if (occupied) memcpy(m->stage_q.p + sbytes, occupied, obytes);
-    m->stage_q.publish();
-    J.occ_dev = occupied ? m->stage_q.dp + sbytes : nullptr;
-    J.q_fill = fill_queries; J.q_fill_ctx = &ctx;   // host records only if the resolve falls back
-    hipLaunchKernelGGL(k_frustum, dim3((n + 255) / 256), dim3(256), 0, m->stream, V, (const orbm_point*)pts->d.p,
-                       skip ? (const uint8_t*)m->stage_q.dp : (const uint8_t*)nullptr, n, (orbm_query*)m->d_queries.p, pts->h_track.dp);
-    MORB_HIP(hipGetLastError());
-    if ((rc = search_enqueue(m, J, /*queries_already_on_device=*/true))) return rc;
-    MORB_HIP(hipStreamSynchronize(m->stream));
-    int cnt = 0;
-    const orbm_track* T = pts->h_track.p;
-    for (int i = 0; i < n; ++i) cnt += T[i].in_view;
-    *n_to_match = cnt;
-    if (track) memcpy(track, T, (size_t)n * sizeof(orbm_track));
-    return search_finish(m, J, match_of_feature, nmatches);
+    LocalPointSource S{};
+    S.d_rows = pts->d.p; S.h_rows = pts->h.data(); S.skip = skip;
+    return morb::search_local_points_body(m, cur, pts->s, S, n, view, occupied, nnratio, th_high, track, match_of_feature, n_to_match, nmatches);
 }

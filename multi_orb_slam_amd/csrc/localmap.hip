@@ -1,0 +1,405 @@
+// localmap.hip -- the local map on the device (include/orbm.h, "the local map on the device"): a map resident in HBM under stable
+// slots (one per map point, one per keyframe, one per observation) and Tracking::UpdateLocalMap's data-parallel parts over it
+// (reference src/Tracking.cc:1794-1949):
+//   orbm_map_vote                 keyframeCounter of UpdateLocalKeyFrames (:1838-1855): k_map_mult, k_map_vote, k_map_vote_out
+//   orbm_map_local_points         UpdateLocalPoints (:1794-1824): k_map_first, k_map_count, k_map_scan, k_map_scatter
+//   orbm_map_search_local_points  k_map_mark, then the body orbm_search_local_points runs (frustum.hip), reading rows[list[i]]
+// The kernels are in localmap_dev.h.  The two host routines (orbm_local_map_vote_host, orbm_local_map_points_host) are the
+// reference's loops on plain arrays: the fallback under MORB_HOST_RESOLVE=1, over the mirror, and the cross-check of the tests.
+// K1, K2 and the marks are pointer logic over the covisibility graph and stay with the caller (host/LocalMap.cc).
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "../../include/orbm.h"
+#include "../../include/orb_debug.h"
+#include "orb_common.h"
+#include "matcher_internal.h"
+#include "localmap_dev.h"
+
+using namespace morb;
+
+struct orbm_map {
+    orbm_matcher* owner = nullptr;   // compared, never dereferenced after creation
+    int device = 0;
+    int kf_cap = 0, pt_cap = 0, obs_cap = 0, stride = 0;
+    int kf_hw = 0, obs_hw = 0;       // high-water marks: one past the last keyframe / record slot in use
+    // the map in HBM ...
+    DevBuf<orbm_point> d_rows; DevBuf<uint8_t> d_flags; DevBuf<orbm_obs> d_obs; DevBuf<int32_t> d_kf_rows, d_kf_count;
+    // ... and its host mirror
+    std::vector<orbm_point> h_rows; std::vector<uint8_t> h_flags; std::vector<orbm_obs> h_obs;
+    std::vector<int32_t> h_kf_rows, h_kf_count; std::vector<uint8_t> h_kf_bad;
+    // per-point scratch that stays clean between calls: the frame's multiplicity (zero), the least candidate key and the skip mark
+    // (both carry the epoch of the call that wrote them)
+    DevBuf<int32_t> d_mult; DevBuf<unsigned long long> d_first; DevBuf<uint32_t> d_mark;
+    std::vector<uint32_t> h_mark;    // host twin of d_mark (fallback only)
+    uint32_t epoch = 0;
+    DevBuf<int32_t> d_votes, d_block, d_list, d_total;
+    PinnedBuf<int32_t> h_votes, h_list, h_total;   // what the kernels write for the host: mapped pinned
+    StageBuf stage;                  // the host-written inputs of a call
+    std::vector<int32_t> list;       // the last point list (host copy; the search's fallback reads it)
+    int list_n = -1;                 // -1: no list
+    FrustumScratch scr;
+    int last[4] = {0, 0, 0, 0};
+};
+
+namespace {
+
+void release_all(orbm_map* p) {
+    p->d_rows.release(); p->d_flags.release(); p->d_obs.release(); p->d_kf_rows.release(); p->d_kf_count.release();
+    p->d_mult.release(); p->d_first.release(); p->d_mark.release(); p->d_votes.release(); p->d_block.release(); p->d_list.release();
+    p->d_total.release(); p->h_votes.release(); p->h_list.release(); p->h_total.release(); p->stage.release(); p->scr.h_track.release();
+}
+
+// A new epoch for the keys of k_map_first and the marks of k_map_mark; the arrays are cleared when the counter would wrap.
+int next_epoch(orbm_matcher* m, orbm_map* p) {
+    if (p->epoch >= 0xfffffff0u) {
+        MORB_HIP(hipMemsetAsync(p->d_first.p, 0xff, (size_t)std::max(p->pt_cap, 1) * sizeof(unsigned long long), m->stream));
+        MORB_HIP(hipMemsetAsync(p->d_mark.p, 0, (size_t)std::max(p->pt_cap, 1) * sizeof(uint32_t), m->stream));
+        std::fill(p->h_mark.begin(), p->h_mark.end(), 0u);
+        p->epoch = 0;
+    }
+    ++p->epoch;
+    return ORB_OK;
+}
+
+int check_slots(const int32_t* s, int n, int lo, int cap, const char* what) {
+    for (int i = 0; i < n; ++i)
+        if (s[i] < lo || s[i] >= cap) { morb::set_error("%s %d (entry %d) is outside [%d, %d)", what, s[i], i, lo, cap); return s[i] < lo ? ORB_E_ARG : ORB_E_CAPACITY; }
+    return ORB_OK;
+}
+
+inline unsigned blocks_of(long long n) { return (unsigned)((n + MAP_BLOCK - 1) / MAP_BLOCK); }
+
+}  // namespace
+
+int orbm_local_map_vote_host(const orbm_obs* obs, int n_obs, const uint8_t* point_flags, int n_points, const int32_t* frame_points,
+                             int n_features, int n_kfs, int32_t* votes) {
+    MORB_ARG(n_obs >= 0 && (n_obs == 0 || obs) && n_points >= 0 && (n_points == 0 || point_flags) && n_features >= 0 &&
+             (n_features == 0 || frame_points) && n_kfs >= 0 && (n_kfs == 0 || votes));
+    std::vector<int32_t> mult((size_t)n_points, 0);
+    for (int f = 0; f < n_features; ++f) {
+        const int p = frame_points[f];
+        if (p < 0) continue;
+        MORB_ARG(p < n_points);
+        if (!(point_flags[p] & ORBM_POINT_BAD)) ++mult[p];
+    }
+    for (int k = 0; k < n_kfs; ++k) votes[k] = 0;
+    for (int i = 0; i < n_obs; ++i) {
+        if (obs[i].point < 0) continue;
+        MORB_ARG(obs[i].point < n_points && obs[i].keyframe >= 0 && obs[i].keyframe < n_kfs);
+        votes[obs[i].keyframe] += mult[obs[i].point];
+    }
+    return ORB_OK;
+}
+
+int orbm_local_map_points_host(const int32_t* kf_rows, const int32_t* kf_count, int n_kfs, int stride, const uint8_t* point_flags,
+                               int n_points, const int32_t* local_kfs, int n_local, int32_t* list, int list_cap, int* n_list) {
+    MORB_ARG(n_kfs >= 0 && stride >= 1 && (n_kfs == 0 || (kf_rows && kf_count)) && n_points >= 0 && (n_points == 0 || point_flags) &&
+             n_local >= 0 && (n_local == 0 || local_kfs) && list_cap >= 0 && (list_cap == 0 || list) && n_list);
+    std::vector<uint8_t> marked((size_t)n_points, 0);   // mnTrackReferenceForFrame == mCurrentFrame.mnId
+    int n = 0;
+    for (int j = 0; j < n_local; ++j) {
+        const int kf = local_kfs[j];
+        MORB_ARG(kf >= 0 && kf < n_kfs && kf_count[kf] >= 0 && kf_count[kf] <= stride);
+        for (int f = 0; f < kf_count[kf]; ++f) {
+            const int s = kf_rows[(size_t)kf * stride + f];
+            if (s < 0) continue;
+            MORB_ARG(s < n_points);
+            if (marked[s]) continue;
+            if (point_flags[s] & ORBM_POINT_BAD) continue;
+            if (n < list_cap) list[n] = s;
+            ++n;
+            marked[s] = 1;
+        }
+    }
+    *n_list = n;
+    if (n > list_cap) { morb::set_error("%d local points are more than the list takes (%d)", n, list_cap); return ORB_E_CAPACITY; }
+    return ORB_OK;
+}
+
+int orbm_map_create(orbm_matcher* m, int kf_capacity, int point_capacity, int obs_capacity, int features_per_keyframe, orbm_map** out) {
+    MORB_ARG(m && out && kf_capacity >= 1 && point_capacity >= 0 && obs_capacity >= 0 && features_per_keyframe >= 1);
+    if (kf_capacity > ORBM_MAP_MAX_KEYFRAMES || features_per_keyframe > ORBM_MAP_MAX_FEATURES) {
+        morb::set_error("a resident map holds at most %d keyframes of %d features (asked for %d of %d)", (int)ORBM_MAP_MAX_KEYFRAMES,
+                        (int)ORBM_MAP_MAX_FEATURES, kf_capacity, features_per_keyframe);
+        return ORB_E_CAPACITY;
+    }
+    MORB_HIP(hipSetDevice(m->device));
+    orbm_map* p = new orbm_map;
+    p->owner = m; p->device = m->device;
+    p->kf_cap = kf_capacity; p->pt_cap = point_capacity; p->obs_cap = obs_capacity; p->stride = features_per_keyframe;
+    const size_t np = (size_t)std::max(point_capacity, 1), no = (size_t)std::max(obs_capacity, 1);
+    const size_t nk = (size_t)kf_capacity, nr = nk * (size_t)features_per_keyframe;
+    int rc;
+    if ((rc = p->d_rows.reserve(np)) || (rc = p->d_flags.reserve(np)) || (rc = p->d_obs.reserve(no)) || (rc = p->d_kf_rows.reserve(nr)) ||
+        (rc = p->d_kf_count.reserve(nk)) || (rc = p->d_mult.reserve(np)) || (rc = p->d_first.reserve(np)) || (rc = p->d_mark.reserve(np)) ||
+        (rc = p->d_votes.reserve(nk)) || (rc = p->d_list.reserve(ORBM_MAX_POINTS)) || (rc = p->d_total.reserve(4)) ||
+        (rc = p->h_votes.reserve(nk)) || (rc = p->h_list.reserve(ORBM_MAX_POINTS)) || (rc = p->h_total.reserve(4))) {
+        release_all(p); delete p;
+        return rc;
+    }
+    // empty on both sides: rows of zeros that are not bad, free records, keyframes without points, clean scratch
+    hipStream_t st = m->stream;
+    if (hipMemsetAsync(p->d_rows.p, 0, np * sizeof(orbm_point), st) != hipSuccess || hipMemsetAsync(p->d_flags.p, 0, np, st) != hipSuccess ||
+        hipMemsetAsync(p->d_obs.p, 0xff, no * sizeof(orbm_obs), st) != hipSuccess ||
+        hipMemsetAsync(p->d_kf_rows.p, 0xff, nr * sizeof(int32_t), st) != hipSuccess ||
+        hipMemsetAsync(p->d_kf_count.p, 0, nk * sizeof(int32_t), st) != hipSuccess ||
+        hipMemsetAsync(p->d_mult.p, 0, np * sizeof(int32_t), st) != hipSuccess ||
+        hipMemsetAsync(p->d_first.p, 0xff, np * sizeof(unsigned long long), st) != hipSuccess ||
+        hipMemsetAsync(p->d_mark.p, 0, np * sizeof(uint32_t), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        morb::set_error("clearing the resident map failed");
+        release_all(p); delete p;
+        return ORB_E_HIP;
+    }
+    orbm_point zero; memset(&zero, 0, sizeof(zero));
+    p->h_rows.assign((size_t)point_capacity, zero); p->h_flags.assign((size_t)point_capacity, 0);
+    p->h_obs.assign((size_t)obs_capacity, orbm_obs{-1, -1});
+    p->h_kf_rows.assign(nr, -1); p->h_kf_count.assign(nk, 0); p->h_kf_bad.assign(nk, 0);
+    p->h_mark.assign((size_t)point_capacity, 0u);
+    *out = p;
+    return ORB_OK;
+}
+
+void orbm_map_destroy(orbm_map* p) {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    release_all(p);
+    delete p;
+}
+
+int orbm_map_keyframes(const orbm_map* p) { return p ? p->kf_hw : ORB_E_ARG; }
+
+int orbm_map_keyframe_bad(const orbm_map* p, int kf) {
+    MORB_ARG(p && kf >= 0 && kf < p->kf_cap);
+    return p->h_kf_bad[(size_t)kf];
+}
+
+int orbm_debug_last_local_map(const orbm_map* p, int* out4) {
+    MORB_ARG(p && out4);
+    for (int k = 0; k < 4; ++k) out4[k] = p->last[k];
+    return ORB_OK;
+}
+
+int orbm_map_write_points(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n, const orbm_point* rows, const uint8_t* flags) {
+    MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || (slots && rows)));
+    int rc;
+    if ((rc = check_slots(slots, n, 0, p->pt_cap, "point slot"))) return rc;
+    if (n == 0) return ORB_OK;
+    MORB_HIP(hipSetDevice(m->device));
+    static_assert(sizeof(orbm_point) == 68, "orbm_point is 17 words");
+    const size_t off_rows = (size_t)n * 4, off_flags = off_rows + (size_t)n * sizeof(orbm_point);
+    if ((rc = p->stage.reserve(off_flags + (size_t)n + 16))) return rc;
+    for (int i = 0; i < n; ++i) { p->h_rows[(size_t)slots[i]] = rows[i]; p->h_flags[(size_t)slots[i]] = flags ? flags[i] : 0; }
+    // staged from the mirror: a slot named twice is staged twice with its last entry, so the order of the lanes does not matter
+    memcpy(p->stage.p, slots, (size_t)n * 4);
+    for (int i = 0; i < n; ++i) {
+        memcpy(p->stage.p + off_rows + (size_t)i * sizeof(orbm_point), &p->h_rows[(size_t)slots[i]], sizeof(orbm_point));
+        p->stage.p[off_flags + (size_t)i] = p->h_flags[(size_t)slots[i]];
+    }
+    p->stage.publish();
+    const int words = (int)(sizeof(orbm_point) / 4);
+    hipLaunchKernelGGL(k_map_put_words, dim3(blocks_of((long long)n * words)), dim3(MAP_BLOCK), 0, m->stream,
+                       (const uint32_t*)(p->stage.dp + off_rows), (const int32_t*)p->stage.dp, n, words, (uint32_t*)p->d_rows.p);
+    hipLaunchKernelGGL(k_map_put_flags, dim3(blocks_of(n)), dim3(MAP_BLOCK), 0, m->stream, (const uint8_t*)(p->stage.dp + off_flags),
+                       (const int32_t*)p->stage.dp, n, p->d_flags.p);
+    MORB_HIP(hipGetLastError());
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    return ORB_OK;
+}
+
+int orbm_map_write_observations(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n, const orbm_obs* records) {
+    MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || (slots && records)));
+    int rc;
+    if ((rc = check_slots(slots, n, 0, p->obs_cap, "record slot"))) return rc;
+    for (int i = 0; i < n; ++i) {
+        if (records[i].point < 0) continue;
+        if (records[i].point >= p->pt_cap || records[i].keyframe < 0 || records[i].keyframe >= p->kf_cap) {
+            morb::set_error("record %d names point %d, keyframe %d: outside the map (%d points, %d keyframes)", i, records[i].point,
+                            records[i].keyframe, p->pt_cap, p->kf_cap);
+            return ORB_E_CAPACITY;
+        }
+    }
+    if (n == 0) return ORB_OK;
+    MORB_HIP(hipSetDevice(m->device));
+    const size_t off_rec = (size_t)n * 4;
+    if ((rc = p->stage.reserve(off_rec + (size_t)n * sizeof(orbm_obs) + 16))) return rc;
+    for (int i = 0; i < n; ++i) {
+        orbm_obs r = records[i];
+        if (r.point < 0) { r.point = -1; r.keyframe = -1; }   // one form of a free record
+        else p->kf_hw = std::max(p->kf_hw, r.keyframe + 1);
+        p->h_obs[(size_t)slots[i]] = r;
+        p->obs_hw = std::max(p->obs_hw, slots[i] + 1);
+    }
+    memcpy(p->stage.p, slots, (size_t)n * 4);
+    for (int i = 0; i < n; ++i) memcpy(p->stage.p + off_rec + (size_t)i * sizeof(orbm_obs), &p->h_obs[(size_t)slots[i]], sizeof(orbm_obs));
+    p->stage.publish();
+    hipLaunchKernelGGL(k_map_put_words, dim3(blocks_of((long long)n * 2)), dim3(MAP_BLOCK), 0, m->stream,
+                       (const uint32_t*)(p->stage.dp + off_rec), (const int32_t*)p->stage.dp, n, 2, (uint32_t*)p->d_obs.p);
+    MORB_HIP(hipGetLastError());
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    return ORB_OK;
+}
+
+int orbm_map_write_keyframe(orbm_matcher* m, orbm_map* p, int kf, const int32_t* point_of_feature, int n_features, int bad) {
+    MORB_ARG(m && p && p->owner == m && n_features >= 0 && (n_features == 0 || point_of_feature));
+    if (kf < 0 || kf >= p->kf_cap || n_features > p->stride) {
+        morb::set_error("keyframe slot %d with %d features does not fit a map of %d keyframes of %d", kf, n_features, p->kf_cap, p->stride);
+        return kf < 0 ? ORB_E_ARG : ORB_E_CAPACITY;
+    }
+    for (int f = 0; f < n_features; ++f)
+        if (point_of_feature[f] >= p->pt_cap) { morb::set_error("feature %d holds point slot %d of %d", f, point_of_feature[f], p->pt_cap); return ORB_E_CAPACITY; }
+    MORB_HIP(hipSetDevice(m->device));
+    int32_t* row = p->h_kf_rows.data() + (size_t)kf * p->stride;
+    for (int f = 0; f < n_features; ++f) row[f] = point_of_feature[f] < 0 ? -1 : point_of_feature[f];
+    for (int f = n_features; f < p->stride; ++f) row[f] = -1;
+    // the old row's tail is dead once the count says so: send what the new count covers, and the count
+    const int n_send = std::max(n_features, 1);
+    p->h_kf_count[(size_t)kf] = n_features; p->h_kf_bad[(size_t)kf] = bad ? 1 : 0;
+    p->kf_hw = std::max(p->kf_hw, kf + 1);
+    MORB_HIP(hipMemcpyAsync(p->d_kf_rows.p + (size_t)kf * p->stride, row, (size_t)n_send * 4, hipMemcpyHostToDevice, m->stream));
+    MORB_HIP(hipMemcpyAsync(p->d_kf_count.p + kf, &p->h_kf_count[(size_t)kf], 4, hipMemcpyHostToDevice, m->stream));
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    return ORB_OK;
+}
+
+int orbm_map_set_keyframe_bad(orbm_matcher* m, orbm_map* p, int kf, int bad) {
+    MORB_ARG(m && p && p->owner == m && kf >= 0 && kf < p->kf_cap);
+    p->h_kf_bad[(size_t)kf] = bad ? 1 : 0;
+    p->kf_hw = std::max(p->kf_hw, kf + 1);
+    return ORB_OK;
+}
+
+int orbm_map_vote(orbm_matcher* m, orbm_map* p, const int32_t* frame_points, int n_features, int32_t* votes) {
+    MORB_ARG(m && p && p->owner == m && n_features >= 0 && (n_features == 0 || frame_points) && (p->kf_hw == 0 || votes));
+    for (int f = 0; f < n_features; ++f)
+        if (frame_points[f] >= p->pt_cap) { morb::set_error("feature %d holds point slot %d of %d", f, frame_points[f], p->pt_cap); return ORB_E_ARG; }
+    const int nk = p->kf_hw;
+    p->last[1] = p->obs_hw;
+    if (m->host_resolve) {   // MORB_HOST_RESOLVE=1: the host routine over the mirror
+        p->last[0] = 0;
+        return orbm_local_map_vote_host(p->h_obs.data(), p->obs_hw, p->h_flags.data(), p->pt_cap, frame_points, n_features, nk, votes);
+    }
+    p->last[0] = 1;
+    if (nk == 0) return ORB_OK;
+    if (n_features == 0 || p->obs_hw == 0) { for (int k = 0; k < nk; ++k) votes[k] = 0; return ORB_OK; }
+    MORB_HIP(hipSetDevice(m->device));
+    int rc;
+    if ((rc = p->stage.reserve((size_t)n_features * 4 + 16))) return rc;
+    memcpy(p->stage.p, frame_points, (size_t)n_features * 4);
+    p->stage.publish();
+    const int32_t* d_fp = (const int32_t*)p->stage.dp;
+    const unsigned g = blocks_of(std::max(n_features, nk));
+    hipLaunchKernelGGL(k_map_mult, dim3(g), dim3(MAP_BLOCK), 0, m->stream, d_fp, n_features, (const uint8_t*)p->d_flags.p, p->d_mult.p,
+                       p->d_votes.p, nk);
+    const long long per_block = (long long)MAP_BLOCK * MAP_VOTE_PER_LANE;
+    const unsigned gv = (unsigned)std::min<long long>(MAP_VOTE_MAX_BLOCKS, (p->obs_hw + per_block - 1) / per_block);
+    hipLaunchKernelGGL(k_map_vote, dim3(gv), dim3(MAP_BLOCK), (size_t)nk * sizeof(int32_t), m->stream, (const orbm_obs*)p->d_obs.p, p->obs_hw,
+                       (const int32_t*)p->d_mult.p, p->d_votes.p, nk);
+    hipLaunchKernelGGL(k_map_vote_out, dim3(g), dim3(MAP_BLOCK), 0, m->stream, d_fp, n_features, p->d_mult.p, (const int32_t*)p->d_votes.p, nk,
+                       p->h_votes.dp);
+    MORB_HIP(hipGetLastError());
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    memcpy(votes, p->h_votes.p, (size_t)nk * sizeof(int32_t));
+    return ORB_OK;
+}
+
+int orbm_map_local_points(orbm_matcher* m, orbm_map* p, const int32_t* local_kfs, int n_local, int32_t* list, int* n_list) {
+    MORB_ARG(m && p && p->owner == m && n_local >= 0 && (n_local == 0 || local_kfs) && list && n_list);
+    if (n_local > ORBM_MAP_MAX_LOCAL) { morb::set_error("%d local keyframes are more than a call takes (%d)", n_local, (int)ORBM_MAP_MAX_LOCAL); return ORB_E_CAPACITY; }
+    int rc;
+    if (check_slots(local_kfs, n_local, 0, p->kf_hw, "local keyframe")) return ORB_E_ARG;
+    p->list_n = -1; *n_list = 0;
+    long long cand = 0; int fmax = 0;
+    for (int j = 0; j < n_local; ++j) { const int c = p->h_kf_count[(size_t)local_kfs[j]]; cand += c; fmax = std::max(fmax, c); }
+    p->last[2] = (int)std::min<long long>(cand, 0x7fffffff); p->last[3] = 0;
+    p->list.resize(ORBM_MAX_POINTS);
+    int n = 0;
+    if (m->host_resolve) {   // MORB_HOST_RESOLVE=1: the host routine over the mirror (the list still goes to HBM for the search's kernels)
+        p->last[0] = 0;
+        rc = orbm_local_map_points_host(p->h_kf_rows.data(), p->h_kf_count.data(), p->kf_hw, p->stride, p->h_flags.data(), p->pt_cap,
+                                        local_kfs, n_local, p->list.data(), ORBM_MAX_POINTS, &n);
+        if (rc) return rc;
+    } else {
+        p->last[0] = 1;
+        if (fmax > 0) {
+            MORB_HIP(hipSetDevice(m->device));
+            const int bpk = (fmax + MAP_BLOCK - 1) / MAP_BLOCK, nb = n_local * bpk;
+            if ((rc = p->stage.reserve((size_t)n_local * 4 + 16)) || (rc = p->d_block.reserve((size_t)nb)) || (rc = next_epoch(m, p))) return rc;
+            memcpy(p->stage.p, local_kfs, (size_t)n_local * 4);
+            p->stage.publish();
+            const int32_t* d_kfs = (const int32_t*)p->stage.dp;
+            const int32_t *rows = p->d_kf_rows.p, *cnt = p->d_kf_count.p;
+            const uint8_t* fl = p->d_flags.p;
+            hipLaunchKernelGGL(k_map_first, dim3(nb), dim3(MAP_BLOCK), 0, m->stream, rows, cnt, d_kfs, p->stride, bpk, fl, p->d_first.p, p->epoch);
+            hipLaunchKernelGGL(k_map_count, dim3(nb), dim3(MAP_BLOCK), 0, m->stream, rows, cnt, d_kfs, p->stride, bpk, fl,
+                               (const unsigned long long*)p->d_first.p, p->epoch, p->d_block.p);
+            hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(MAP_SCAN_LANES), 0, m->stream, p->d_block.p, nb, p->d_total.p, p->h_total.dp);
+            hipLaunchKernelGGL(k_map_scatter, dim3(nb), dim3(MAP_BLOCK), 0, m->stream, rows, cnt, d_kfs, p->stride, bpk, fl,
+                               (const unsigned long long*)p->d_first.p, p->epoch, (const int32_t*)p->d_block.p, p->d_list.p, p->h_list.dp,
+                               (int)ORBM_MAX_POINTS);
+            MORB_HIP(hipGetLastError());
+            MORB_HIP(hipStreamSynchronize(m->stream));
+            n = p->h_total.p[0];
+            if (n > ORBM_MAX_POINTS) { morb::set_error("%d local points are more than a search takes (%d)", n, (int)ORBM_MAX_POINTS); return ORB_E_CAPACITY; }
+            memcpy(p->list.data(), p->h_list.p, (size_t)n * sizeof(int32_t));
+        }
+    }
+    if (m->host_resolve && n > 0) {
+        MORB_HIP(hipSetDevice(m->device));
+        MORB_HIP(hipMemcpyAsync(p->d_list.p, p->list.data(), (size_t)n * 4, hipMemcpyHostToDevice, m->stream));
+        MORB_HIP(hipStreamSynchronize(m->stream));
+    }
+    memcpy(list, p->list.data(), (size_t)n * sizeof(int32_t));
+    p->list_n = n; *n_list = n; p->last[3] = n;
+    return ORB_OK;
+}
+
+namespace {
+struct SkipCtx { orbm_map* p; const int32_t* frame_points; int n_features; const int32_t* seen; int n_seen; };
+void host_skip(void* c, uint8_t* out) {   // what k_map_mark + k_frustum<true> decide, from the mirror
+    const SkipCtx* S = (const SkipCtx*)c;
+    orbm_map* p = S->p;
+    for (int f = 0; f < S->n_features; ++f) {
+        const int s = S->frame_points[f];
+        if (s >= 0 && !(p->h_flags[(size_t)s] & ORBM_POINT_BAD)) p->h_mark[(size_t)s] = p->epoch;
+    }
+    for (int i = 0; i < S->n_seen; ++i)
+        if (S->seen[i] >= 0) p->h_mark[(size_t)S->seen[i]] = p->epoch;
+    for (int i = 0; i < p->list_n; ++i) {
+        const size_t s = (size_t)p->list[(size_t)i];
+        out[i] = ((p->h_flags[s] & ORBM_POINT_BAD) || p->h_mark[s] == p->epoch) ? 1 : 0;
+    }
+}
+}  // namespace
+
+int orbm_map_search_local_points(orbm_matcher* m, const orbm_frame* cur, orbm_map* p, const orbm_view* view, const int32_t* frame_points,
+                                 int n_features, const int32_t* seen, int n_seen, const uint8_t* occupied, float nnratio, int th_high,
+                                 orbm_track* track, int32_t* match_of_feature, int* n_to_match, int* nmatches) {
+    MORB_ARG(m && cur && p && p->owner == m && cur->owner == m && view && n_to_match && nmatches && (cur->n_total == 0 || match_of_feature));
+    MORB_ARG(n_features >= 0 && (n_features == 0 || frame_points) && n_seen >= 0 && (n_seen == 0 || seen));
+    MORB_ARG(view->n_levels >= 1 && view->n_levels <= ORBM_MAX_LEVELS && view->scale_factors);
+    if (p->list_n < 0) { morb::set_error("no point list on the map: orbm_map_local_points comes first"); return ORB_E_ARG; }
+    for (int f = 0; f < n_features; ++f) MORB_ARG(frame_points[f] < p->pt_cap);
+    for (int i = 0; i < n_seen; ++i) MORB_ARG(seen[i] < p->pt_cap);
+    const int n = p->list_n;
+    int rc;
+    MORB_HIP(hipSetDevice(m->device));
+    if ((rc = next_epoch(m, p))) return rc;
+    SkipCtx sc{p, frame_points, n_features, seen, n_seen};
+    LocalPointSource S{};
+    S.d_rows = p->d_rows.p; S.h_rows = p->h_rows.data(); S.d_index = p->d_list.p; S.h_index = p->list.data();
+    S.d_mark = p->d_mark.p; S.d_flags = p->d_flags.p; S.epoch = p->epoch; S.host_skip = host_skip; S.host_skip_ctx = &sc;
+    if (!m->host_resolve && n > 0 && n_features + n_seen > 0) {
+        const size_t off_seen = (size_t)n_features * 4;
+        if ((rc = p->stage.reserve(off_seen + (size_t)n_seen * 4 + 16))) return rc;
+        if (n_features) memcpy(p->stage.p, frame_points, (size_t)n_features * 4);
+        if (n_seen) memcpy(p->stage.p + off_seen, seen, (size_t)n_seen * 4);
+        p->stage.publish();
+        hipLaunchKernelGGL(k_map_mark, dim3(blocks_of((long long)n_features + n_seen)), dim3(MAP_BLOCK), 0, m->stream,
+                           (const int32_t*)p->stage.dp, n_features, (const int32_t*)(p->stage.dp + off_seen), n_seen,
+                           (const uint8_t*)p->d_flags.p, p->d_mark.p, p->epoch);
+        MORB_HIP(hipGetLastError());
+    }
+    return morb::search_local_points_body(m, cur, p->scr, S, n, view, occupied, nnratio, th_high, track, match_of_feature, n_to_match, nmatches);
+}

@@ -1,0 +1,182 @@
+// localmap_dev.h -- the kernels of the resident map (localmap.hip; include/orbm.h, "the local map on the device").
+// Every sum here is an integer: the atomics are integer adds and unsigned minima, so any arrival order leaves the same bits.
+//   vote:        k_map_mult      one lane per frame feature: multiplicity of the frame per point slot (and the vote bins cleared)
+//                k_map_vote      one lane per observation record, grid-stride: the histogram private to the workgroup in LDS, one
+//                                merge per non-zero bin
+//                k_map_vote_out  the bins into the mapped result, the multiplicities back to zero
+//   point list:  k_map_first     one lane per candidate: the least position per point (64-bit minimum, the call's epoch on top)
+//                k_map_count     kept candidates per block of 256
+//                k_map_scan      one workgroup: exclusive prefix sum over the block counts, the total
+//                k_map_scatter   the kept slots to their places
+//   search:      k_map_mark      the frame's own points and the `seen` list stamped with the call's epoch (k_frustum<true> reads it)
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/orbm.h"
+
+namespace morb {
+
+constexpr int MAP_BLOCK = 256;         // lanes per workgroup of every kernel here but the scan; the compaction's block size
+constexpr int MAP_SCAN_LANES = 1024;   // the one workgroup of k_map_scan
+constexpr int MAP_VOTE_PER_LANE = 16;  // records per lane k_map_vote's grid is sized for (a workgroup pays kf bins to clear and merge)
+constexpr int MAP_VOTE_MAX_BLOCKS = 512;
+
+// A candidate's key: the call's epoch, inverted, above its position.  A later call's keys are all smaller than an earlier call's, so the
+// minimum needs no clearing between calls: whatever an older call left loses to the first candidate of this one.
+__host__ __device__ inline unsigned long long map_key(uint32_t epoch, uint32_t pos) {
+    return ((unsigned long long)(0xffffffffu - epoch) << 32) | pos;
+}
+
+__global__ __launch_bounds__(MAP_BLOCK) void k_map_mult(const int32_t* __restrict__ frame_points, int n_features,
+                                                        const uint8_t* __restrict__ flags, int32_t* __restrict__ mult,
+                                                        int32_t* __restrict__ votes, int n_kfs) {
+    const int i = blockIdx.x * MAP_BLOCK + threadIdx.x;
+    if (i < n_kfs) votes[i] = 0;
+    if (i >= n_features) return;
+    const int p = frame_points[i];   // (validated on the host: negative or a slot inside the capacity)
+    if (p >= 0 && !(flags[p] & ORBM_POINT_BAD)) atomicAdd(&mult[p], 1);
+}
+
+// Adds from every lane into a few global bins serialise at the memory side; here a lane adds into its workgroup's LDS copy of the bins
+// and the workgroup merges each bin it touched with one global add.  Dynamic LDS: n_kfs ints (at most 64 KiB).
+__global__ __launch_bounds__(MAP_BLOCK) void k_map_vote(const orbm_obs* __restrict__ obs, int n_obs, const int32_t* __restrict__ mult,
+                                                        int32_t* __restrict__ votes, int n_kfs) {
+    extern __shared__ int32_t bins[];
+    for (int k = threadIdx.x; k < n_kfs; k += MAP_BLOCK) bins[k] = 0;
+    __syncthreads();
+    for (long long i = (long long)blockIdx.x * MAP_BLOCK + threadIdx.x; i < n_obs; i += (long long)gridDim.x * MAP_BLOCK) {
+        const orbm_obs r = obs[i];
+        if (r.point < 0) continue;   // a free record
+        const int w = mult[r.point];
+        if (w) atomicAdd(&bins[r.keyframe], w);   // (keyframe < n_kfs: the high-water mark covers every record's)
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < n_kfs; k += MAP_BLOCK) {
+        const int v = bins[k];
+        if (v) atomicAdd(&votes[k], v);
+    }
+}
+
+__global__ __launch_bounds__(MAP_BLOCK) void k_map_vote_out(const int32_t* __restrict__ frame_points, int n_features,
+                                                            int32_t* __restrict__ mult, const int32_t* __restrict__ votes, int n_kfs,
+                                                            int32_t* __restrict__ out) {
+    const int i = blockIdx.x * MAP_BLOCK + threadIdx.x;
+    if (i < n_kfs) out[i] = votes[i];
+    if (i >= n_features) return;
+    const int p = frame_points[i];
+    if (p >= 0) mult[p] = 0;
+}
+
+// The candidates of a point list: block b covers the features [256 (b % bpk), +256) of local keyframe b / bpk; a candidate's
+// position is keyframe position * stride + feature, ascending in the reference's order.
+struct MapCand { int slot; uint32_t pos; };
+
+__device__ inline MapCand map_candidate(const int32_t* __restrict__ kf_rows, const int32_t* __restrict__ kf_count,
+                                        const int32_t* __restrict__ local_kfs, int stride, int bpk, const uint8_t* __restrict__ flags) {
+    const int j = blockIdx.x / bpk, f = (blockIdx.x % bpk) * MAP_BLOCK + threadIdx.x;
+    const int kf = local_kfs[j];
+    MapCand c; c.slot = -1; c.pos = (uint32_t)j * (uint32_t)stride + (uint32_t)f;
+    if (f < kf_count[kf]) {
+        const int s = kf_rows[(size_t)kf * stride + f];
+        if (s >= 0 && !(flags[s] & ORBM_POINT_BAD)) c.slot = s;
+    }
+    return c;
+}
+
+__global__ __launch_bounds__(MAP_BLOCK) void k_map_first(const int32_t* __restrict__ kf_rows, const int32_t* __restrict__ kf_count,
+                                                         const int32_t* __restrict__ local_kfs, int stride, int bpk,
+                                                         const uint8_t* __restrict__ flags, unsigned long long* __restrict__ first,
+                                                         uint32_t epoch) {
+    const MapCand c = map_candidate(kf_rows, kf_count, local_kfs, stride, bpk, flags);
+    if (c.slot >= 0) atomicMin(&first[c.slot], map_key(epoch, c.pos));
+}
+
+__global__ __launch_bounds__(MAP_BLOCK) void k_map_count(const int32_t* __restrict__ kf_rows, const int32_t* __restrict__ kf_count,
+                                                         const int32_t* __restrict__ local_kfs, int stride, int bpk,
+                                                         const uint8_t* __restrict__ flags, const unsigned long long* __restrict__ first,
+                                                         uint32_t epoch, int32_t* __restrict__ block_count) {
+    __shared__ int wave_n[MAP_BLOCK / 64];
+    const MapCand c = map_candidate(kf_rows, kf_count, local_kfs, stride, bpk, flags);
+    const bool keep = c.slot >= 0 && first[c.slot] == map_key(epoch, c.pos);
+    const unsigned long long b = __ballot(keep);
+    if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = __popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+        for (int w = 0; w < MAP_BLOCK / 64; ++w) s += wave_n[w];
+        block_count[blockIdx.x] = s;
+    }
+}
+
+// One workgroup: block_count[0 .. nb) becomes its exclusive prefix sum, *total and *total_out (mapped) the sum.  A lane owns a
+// contiguous run of blocks; the runs' sums are scanned through LDS.
+__global__ __launch_bounds__(MAP_SCAN_LANES) void k_map_scan(int32_t* __restrict__ block_count, int nb, int32_t* __restrict__ total,
+                                                             int32_t* __restrict__ total_out) {
+    __shared__ int run_sum[MAP_SCAN_LANES];
+    const int per = (nb + MAP_SCAN_LANES - 1) / MAP_SCAN_LANES;
+    const int lo = min(nb, (int)threadIdx.x * per), hi = min(nb, lo + per);
+    int s = 0;
+    for (int i = lo; i < hi; ++i) s += block_count[i];
+    run_sum[threadIdx.x] = s;
+    __syncthreads();
+    for (int d = 1; d < MAP_SCAN_LANES; d <<= 1) {   // Hillis-Steele, inclusive
+        const int v = threadIdx.x >= (unsigned)d ? run_sum[threadIdx.x - d] : 0;
+        __syncthreads();
+        run_sum[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int off = run_sum[threadIdx.x] - s;
+    for (int i = lo; i < hi; ++i) { const int c = block_count[i]; block_count[i] = off; off += c; }
+    if (threadIdx.x == MAP_SCAN_LANES - 1) { *total = run_sum[threadIdx.x]; *total_out = run_sum[threadIdx.x]; }
+}
+
+// list and list_out (mapped) have room for list_cap entries; a place beyond it is not written (the caller reports the overflow).
+__global__ __launch_bounds__(MAP_BLOCK) void k_map_scatter(const int32_t* __restrict__ kf_rows, const int32_t* __restrict__ kf_count,
+                                                           const int32_t* __restrict__ local_kfs, int stride, int bpk,
+                                                           const uint8_t* __restrict__ flags, const unsigned long long* __restrict__ first,
+                                                           uint32_t epoch, const int32_t* __restrict__ block_off, int32_t* __restrict__ list,
+                                                           int32_t* __restrict__ list_out, int list_cap) {
+    __shared__ int wave_n[MAP_BLOCK / 64];
+    const MapCand c = map_candidate(kf_rows, kf_count, local_kfs, stride, bpk, flags);
+    const bool keep = c.slot >= 0 && first[c.slot] == map_key(epoch, c.pos);
+    const unsigned long long b = __ballot(keep);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_n[wave] = __popcll(b);
+    __syncthreads();
+    if (!keep) return;
+    int at = block_off[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) at += wave_n[w];
+    if (at < list_cap) { list[at] = c.slot; list_out[at] = c.slot; }
+}
+
+// Scattered writes of orbm_map_write_points / _observations: entry r of the staged block, `words` 32-bit words long, into slot
+// slots[r]; one lane per word.  (A slot named twice was staged twice with the same bytes.)
+__global__ __launch_bounds__(MAP_BLOCK) void k_map_put_words(const uint32_t* __restrict__ src, const int32_t* __restrict__ slots, int n,
+                                                             int words, uint32_t* __restrict__ dst) {
+    const long long i = (long long)blockIdx.x * MAP_BLOCK + threadIdx.x;
+    if (i >= (long long)n * words) return;
+    const int r = (int)(i / words), w = (int)(i % words);
+    dst[(size_t)slots[r] * words + w] = src[i];
+}
+
+__global__ __launch_bounds__(MAP_BLOCK) void k_map_put_flags(const uint8_t* __restrict__ src, const int32_t* __restrict__ slots, int n,
+                                                             uint8_t* __restrict__ dst) {
+    const int r = blockIdx.x * MAP_BLOCK + threadIdx.x;
+    if (r < n) dst[slots[r]] = src[r];
+}
+
+// The skip marks of a search: the frame's own points that are not bad, and the points of `seen`.  Every lane stores the same value.
+__global__ __launch_bounds__(MAP_BLOCK) void k_map_mark(const int32_t* __restrict__ frame_points, int n_features,
+                                                        const int32_t* __restrict__ seen, int n_seen, const uint8_t* __restrict__ flags,
+                                                        uint32_t* __restrict__ mark, uint32_t epoch) {
+    const int i = blockIdx.x * MAP_BLOCK + threadIdx.x;
+    if (i < n_features) {
+        const int p = frame_points[i];
+        if (p >= 0 && !(flags[p] & ORBM_POINT_BAD)) mark[p] = epoch;
+    } else if (i < n_features + n_seen) {
+        const int p = seen[i - n_features];
+        if (p >= 0) mark[p] = epoch;
+    }
+}
+
+}  // namespace morb

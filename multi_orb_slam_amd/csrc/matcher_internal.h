@@ -233,6 +233,21 @@ struct CrossOut {
     void release() { i.release(); b.release(); s.release(); scratch.release(); }
 };
 
+// ---- the local-point search (frustum.hip), shared by its two entries: orbm_search_local_points over a point table and
+// orbm_map_search_local_points over a resident map (localmap.hip)
+struct FrustumScratch {              // what a search keeps between calls; one per table / map
+    PinnedBuf<orbm_track> h_track;   // written by k_frustum
+    std::vector<orbm_query> hq;      // host queries (fallback / MORB_HOST_RESOLVE=1 only)
+    float thr_lsf = 0; int thr_levels = 0; float thr[ORBM_MAX_LEVELS - 1];   // level thresholds of the last (log_scale_factor, n_levels)
+};
+struct LocalPointSource {            // where the n points of a search come from
+    const orbm_point* d_rows; const orbm_point* h_rows;   // rows in HBM and their host mirror
+    const int32_t* d_index; const int32_t* h_index;       // point i is row index[i]; NULL: row i
+    const uint8_t* skip;                                  // host skip flags per point (NULL: none); not with d_index
+    const uint32_t* d_mark; const uint8_t* d_flags; uint32_t epoch;   // with d_index: row r is skipped if d_flags[r] & 1 or d_mark[r] == epoch
+    void (*host_skip)(void* ctx, uint8_t* out); void* host_skip_ctx;  // ... and this writes the same flags per point on the host (fallback only)
+};
+
 namespace morb {
 // ---- frame.hip
 FrameBufs* take_bufs(orbm_matcher* m);
@@ -262,6 +277,9 @@ int phases_frame_build(unsigned long long* out64);
 // ---- frustum.hip
 // the device rows and the host mirror of a point table (orbm_pose_optimize_resident reads positions by row)
 int points_view(const orbm_points* p, const orbm_matcher* m, const orbm_point** d_rows, const orbm_point** h_rows, int* count);
+int search_local_points_body(orbm_matcher* m, const orbm_frame* cur, FrustumScratch& scr, const LocalPointSource& S, int n,
+                             const orbm_view* view, const uint8_t* occupied, float nnratio, int th_high, orbm_track* track,
+                             int32_t* match_of_feature, int* n_to_match, int* nmatches);
 // ---- search.hip
 int search_raise_lds_limits();  // per device, from orbm_create
 int search_enqueue(orbm_matcher* m, SearchJob& J, bool queries_already_on_device = false);

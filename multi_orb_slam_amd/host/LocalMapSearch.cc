@@ -5,21 +5,11 @@
 #include <cstdio>
 #include <cstring>
 #include "../../include/orbm.h"
+#include "point_row.h"
 
 namespace ORB_SLAM2 {
 
 namespace {
-
-// The raw distance bounds of a MapPoint.  They are protected in the reference's class (include/MapPoint.h:152-153), whose
-// accessors hand out 0.8f * min and 1.2f * max only; a build against the reference's headers adds the two accessors named
-// here to MapPoint.
-#ifdef MORB_USE_REFERENCE_TYPES
-inline float raw_min_distance(MapPoint* p) { return p->GetMinDistance(); }
-inline float raw_max_distance(MapPoint* p) { return p->GetMaxDistance(); }
-#else
-inline float raw_min_distance(MapPoint* p) { return p->mfMinDistance; }
-inline float raw_max_distance(MapPoint* p) { return p->mfMaxDistance; }
-#endif
 
 // The point table belongs to the calling THREAD, like the matcher handle it was created on (ORBmatcher.cc: ThreadState).  `rows`
 // is what the table holds, byte for byte: a row is sent again only if its 68 packed bytes differ -- compared, not inferred from
@@ -40,15 +30,6 @@ thread_local LocalTable tls_table;
 int report(const char* what, int rc) {
     std::fprintf(stderr, "SearchLocalPoints: %s failed (%d): %s -- search reports 0 matches\n", what, rc, orb_last_error());
     return 0;
-}
-
-inline void pack(MapPoint* pMP, orbm_point& r) {
-    std::memset(&r, 0, sizeof(r));
-    const cv::Mat P = pMP->GetWorldPos(), Pn = pMP->GetNormal(), d = pMP->GetDescriptor();
-    for (int k = 0; k < 3; ++k) { r.pos[k] = P.at<float>(k); r.normal[k] = Pn.at<float>(k); }
-    r.min_dist = raw_min_distance(pMP); r.max_dist = raw_max_distance(pMP);
-    r.blocks = pMP->Observations() > 0 ? 1 : 0;
-    std::memcpy(r.desc, d.ptr(0), 32);
 }
 
 }  // namespace
@@ -89,7 +70,7 @@ int SearchLocalPoints(ORBmatcher& matcher, Frame& F, std::vector<MapPoint*>& vpL
     for (int i = 0; i < n; ++i) {
         MapPoint* pMP = vpLocalMapPoints[i];
         T.skip[i] = (pMP->mnLastFrameSeen == F.mnId || pMP->isBad()) ? 1 : 0;
-        pack(pMP, T.fresh[i]);
+        pack_point_row(pMP, T.fresh[i]);
     }
     // send the runs of rows that changed (runs less than 32 unchanged rows apart go out as one)
     const int known = (int)T.rows.size();

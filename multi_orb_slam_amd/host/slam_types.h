@@ -46,6 +46,8 @@ public:
     float mTrackViewCos = 1.f;
     // bookkeeping of Tracking::SearchLocalPoints (src/Tracking.cc:1702-1770; include/MapPoint.h, src/MapPoint.cc:IncreaseVisible)
     long unsigned int mnLastFrameSeen = 0;
+    // the mark of Tracking::UpdateLocalPoints (src/Tracking.cc:1812-1817; include/MapPoint.h:106), read and written by host/LocalMap.cc
+    long unsigned int mnTrackReferenceForFrame = 0;
     void IncreaseVisible(int n = 1) { mnVisible += n; }
     int mnVisible = 1;
 
@@ -130,6 +132,7 @@ public:
     // members host/Optimizer.cc reads (include/Frame.h:226-227, :243)
     std::vector<float> mvInvLevelSigma2, mvLevelSigma2;   // (mvLevelSigma2: include/Frame.h:242, read by host/PnPsolver.cc)
     cv::Mat mRcam12, mtcam12;                 // 3x3, 3x1 CV_32F
+    KeyFrame* mpReferenceKF = nullptr;        // include/Frame.h:234, written by Tracking::UpdateLocalKeyFrames (src/Tracking.cc:1947)
 
     // pose members (include/Frame.h:82-99, src/Frame.cc:420-499)
     void SetPose(cv::Mat Tcw) { mTcw = Tcw.clone(); UpdatePoseMatrices(); }
@@ -255,6 +258,9 @@ public:
     // the camera-1 covisibility weights are plain containers the caller fills (mvOrderedWeights_cam1 descending, beside
     // mvpOrderedConnectedKeyFrames_cam1)
     KeyFrame* GetParent() { return mpParent; }
+    std::set<KeyFrame*> GetChilds() { return mspChildrens; }
+    // the mark of Tracking::UpdateLocalKeyFrames (src/Tracking.cc:1885-1937; include/KeyFrame.h:164), read and written by host/LocalMap.cc
+    long unsigned int mnTrackReferenceForFrame = 0;
     bool hasChild(KeyFrame* pKF) { return mspChildrens.count(pKF) != 0; }
     std::set<KeyFrame*> GetLoopEdges() { return mspLoopEdges; }
     int GetWeight_cam1(KeyFrame* pKF) { auto it = mConnectedKeyFrameWeights_cam1.find(pKF); return it != mConnectedKeyFrameWeights_cam1.end() ? it->second : 0; }

@@ -4,6 +4,7 @@ import weakref
 import numpy as np
 from . import _lib
 from ._lib import KP_DTYPE, QUERY_DTYPE, POINT_DTYPE, TRACK_DTYPE, REFRESH_DTYPE, CamFeatures, FrameDesc, check, ptr
+from ._lib import OBS_DTYPE, MAX_POINTS  # noqa: F401
 from ._lib import POSE_PROBLEM_DTYPE, POSE_RESULT_DTYPE, POSE_CAM0, POSE_ALL_CAMS, POSE_ORDER_INDEX, POSE_ORDER_DEVICE  # noqa: F401
 from ._lib import SIM3_PROBLEM_DTYPE, SIM3_HYP_DTYPE, SIM3_WALK_DTYPE, SIM3_MATH_LIBM, SIM3_MATH_DEVICE  # noqa: F401
 from ._lib import SIM3OPT_PROBLEM_DTYPE, SIM3OPT_RESULT_DTYPE  # noqa: F401
@@ -714,6 +715,128 @@ class LocalPoints:
         return False
 
 
+def _i32(a):
+    return np.ascontiguousarray(a, np.int32).reshape(-1)
+
+
+def local_map_vote_host(obs, point_flags, frame_points, n_kfs):
+    """orbm_local_map_vote_host: keyframeCounter of UpdateLocalKeyFrames (reference src/Tracking.cc:1838-1855) on plain arrays: obs
+    OBS_DTYPE records (point -1 = free), point_flags one byte per point slot (bit 0 = bad), frame_points the point slot of every
+    feature of the frame or -1 -> votes[n_kfs]."""
+    obs = np.ascontiguousarray(obs, OBS_DTYPE); fl = np.ascontiguousarray(point_flags, np.uint8); fp = _i32(frame_points)
+    votes = np.zeros(max(int(n_kfs), 1), np.int32)
+    check(_lib.lib().orbm_local_map_vote_host(ptr(obs), len(obs), ptr(fl), len(fl), ptr(fp), len(fp), int(n_kfs), ptr(votes)))
+    return votes[:int(n_kfs)]
+
+
+def local_map_points_host(kf_rows, kf_count, point_flags, local_kfs, list_cap=MAX_POINTS):
+    """orbm_local_map_points_host: UpdateLocalPoints (reference src/Tracking.cc:1794-1824) on plain arrays: kf_rows n_kfs x stride point
+    slots (-1 = none), kf_count the features of every keyframe, local_kfs the local keyframes in order -> the kept slots in order."""
+    rows = np.ascontiguousarray(kf_rows, np.int32); assert rows.ndim == 2
+    cnt = _i32(kf_count); fl = np.ascontiguousarray(point_flags, np.uint8); lk = _i32(local_kfs)
+    assert len(cnt) == rows.shape[0]
+    out = np.zeros(max(int(list_cap), 1), np.int32); n = C.c_int()
+    check(_lib.lib().orbm_local_map_points_host(ptr(rows), ptr(cnt), rows.shape[0], max(rows.shape[1], 1), ptr(fl), len(fl), ptr(lk),
+                                                len(lk), ptr(out), int(list_cap), C.byref(n)))
+    return out[:n.value].copy()
+
+
+class ResidentMap:
+    """A map resident in HBM under stable slots (orbm_map): one slot per map point (a POINT_DTYPE row + a flag byte, bit 0 = bad),
+    per keyframe (mvpMapPoints as point slots) and per observation (OBS_DTYPE), and Tracking::UpdateLocalMap's data-parallel parts
+    over it: vote, local_points, search."""
+
+    def __init__(self, matcher, kf_capacity, point_capacity, obs_capacity, features_per_keyframe):
+        self._m = matcher; self._h = C.c_void_p()
+        self.kf_capacity, self.point_capacity, self.obs_capacity = int(kf_capacity), int(point_capacity), int(obs_capacity)
+        self.features_per_keyframe = int(features_per_keyframe)
+        check(_lib.lib().orbm_map_create(matcher._h, self.kf_capacity, self.point_capacity, self.obs_capacity,
+                                         self.features_per_keyframe, C.byref(self._h)))
+
+    def write_points(self, slots, rows, flags=None):
+        """Rows (POINT_DTYPE) and flag bytes into the listed point slots, one call (orbm_map_write_points)."""
+        slots = _i32(slots); rows = np.ascontiguousarray(rows, POINT_DTYPE)
+        fl = None if flags is None else np.ascontiguousarray(flags, np.uint8)
+        assert len(rows) == len(slots) and (fl is None or len(fl) == len(slots))
+        check(_lib.lib().orbm_map_write_points(self._m._h, self._h, ptr(slots), len(slots), ptr(rows), None if fl is None else ptr(fl)))
+
+    def write_observations(self, slots, records):
+        """Records (OBS_DTYPE; point -1 frees the slot) into the listed record slots (orbm_map_write_observations)."""
+        slots = _i32(slots); rec = np.ascontiguousarray(records, OBS_DTYPE)
+        assert len(rec) == len(slots)
+        check(_lib.lib().orbm_map_write_observations(self._m._h, self._h, ptr(slots), len(slots), ptr(rec)))
+
+    def write_keyframe(self, kf, point_of_feature, bad=False):
+        pof = _i32(point_of_feature)
+        check(_lib.lib().orbm_map_write_keyframe(self._m._h, self._h, int(kf), ptr(pof), len(pof), int(bool(bad))))
+
+    def set_keyframe_bad(self, kf, bad=True):
+        check(_lib.lib().orbm_map_set_keyframe_bad(self._m._h, self._h, int(kf), int(bool(bad))))
+
+    @property
+    def keyframes(self):
+        """Keyframe high-water mark (orbm_map_keyframes)."""
+        n = int(_lib.lib().orbm_map_keyframes(self._h))
+        if n < 0:
+            raise _lib.OrbError(n, "orbm_map_keyframes on a closed map")
+        return n
+
+    def keyframe_bad(self, kf):
+        r = int(_lib.lib().orbm_map_keyframe_bad(self._h, int(kf)))
+        check(min(r, 0))
+        return bool(r)
+
+    def vote(self, frame_points):
+        """orbm_map_vote -> votes[keyframes]."""
+        fp = _i32(frame_points); votes = np.zeros(max(self.kf_capacity, 1), np.int32)
+        check(_lib.lib().orbm_map_vote(self._m._h, self._h, ptr(fp), len(fp), ptr(votes)))
+        return votes[:self.keyframes]
+
+    def local_points(self, local_kfs):
+        """orbm_map_local_points -> the kept point slots in order; the list stays on the device for search()."""
+        lk = _i32(local_kfs); out = np.zeros(MAX_POINTS, np.int32); n = C.c_int()
+        check(_lib.lib().orbm_map_local_points(self._m._h, self._h, ptr(lk), len(lk), ptr(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def search(self, frame, view, frame_points=(), seen=(), occupied=None, th_high=TH_HIGH, n_list=None, want_track=True):
+        """orbm_map_search_local_points over the list of the last local_points() -> (n_to_match, nmatches, match_of_feature, track);
+        match_of_feature and track index the LIST.  n_list: the length of that list (sizes `track`; default the largest a list has)."""
+        fp = _i32(frame_points); sn = _i32(seen)
+        occ = None if occupied is None else np.ascontiguousarray(occupied, np.uint8)
+        assert occ is None or len(occ) >= frame.data.n_total
+        n = MAX_POINTS if n_list is None else int(n_list)
+        mo = np.zeros(max(frame.data.n_total, 1), np.int32); nm = C.c_int(); nt = C.c_int()
+        track = np.zeros(max(n, 1), TRACK_DTYPE) if want_track else None
+        check(_lib.lib().orbm_map_search_local_points(self._m._h, frame._h, self._h, C.byref(view.c), ptr(fp), len(fp), ptr(sn), len(sn),
+                                                      None if occ is None else ptr(occ), self._m.nnratio, th_high,
+                                                      None if track is None else ptr(track), ptr(mo), C.byref(nt), C.byref(nm)))
+        return nt.value, nm.value, mo[:frame.data.n_total], (None if track is None else track[:n])
+
+    def last_local_map(self):
+        """(1 if the last vote / point list ran on the device, records scanned by the last vote, candidates of the last point list,
+        points it kept) (orbm_debug_last_local_map)."""
+        out = (C.c_int * 4)()
+        check(_lib.lib().orbm_debug_last_local_map(self._h, out))
+        return tuple(out)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            try:
+                _lib.lib().orbm_map_destroy(self._h)
+            except Exception:
+                pass
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 class FrameData:
     """Flat arrays of the Frame members the matcher reads (reference src/Frame.cc:191-288): cam-major global index."""
 
@@ -1175,6 +1298,11 @@ class Matcher:
         out = (C.c_int * 5)()
         check(_lib.lib().orbm_debug_last_refresh(self._h, out))
         return tuple(out)
+
+    def last_local_map(self, resident_map):
+        """What the last vote / point list on a ResidentMap did: (device path ran, observation records scanned, candidates, points
+        kept) (orbm_debug_last_local_map)."""
+        return resident_map.last_local_map()
 
     def SearchLocalPoints(self, frame, points, view, skip=None, occupied=None, th_high=TH_HIGH, n=None, want_track=True):
         """Tracking::SearchLocalPoints from its second loop on (reference src/Tracking.cc:1730-1768) over the first n rows
