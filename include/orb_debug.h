@@ -78,6 +78,10 @@ int orbm_debug_last_essential_graph(const orbm_matcher* m, int* out8);
  * the host routines over the mirror), observation records scanned by the last vote, candidates of the last point list (the sum of the
  * listed keyframes' feature counts), points it kept} (inspection only) */
 int orbm_debug_last_local_map(const orbm_map* map, int* out4);
+/* What the last orbm_map_covisibility / orbm_map_culling_counts on the map did: {1 if it ran on the device (0: MORB_HOST_RESOLVE=1, the
+ * host routines over the mirror), 1 if this call rebuilt the point -> records index (only after an orbm_map_write_observations),
+ * records indexed (the record high-water mark), keyframes processed} (inspection only) */
+int orbm_debug_last_covisibility(const orbm_map* map, int* out4);
 /* Where the work of the last orbm_pnp_ransac went: {problems on the device, problems through the host routine because they have more
  * than ORBM_PNP_CAP correspondences, records refined on the device, records refined by the host routine because they lie beyond
  * ORBM_PNP_MAX_RECORDS of a device problem} (inspection only) */

@@ -17,6 +17,8 @@
  *        reference src/Tracking.cc:1730-1768, src/Frame.cc:443-499                    -> orbm_points_*, orbm_search_local_points
  *   Tracking::UpdateLocalKeyFrames' votes, Tracking::UpdateLocalPoints and that search over a map resident under stable slots
  *        reference src/Tracking.cc:1838-1855, :1794-1824                              -> orbm_map_*, orbm_local_map_*_host
+ *   KeyFrame::UpdateConnections' two counters and LocalMapping::KeyFrameCulling's counts over the same map
+ *        reference src/KeyFrame.cc:512-552, src/LocalMapping.cc:990-1032              -> orbm_map_covisibility, orbm_map_culling_counts
  *   MapPoint::ComputeDistinctiveDescriptors + MapPoint::UpdateNormalAndDepth, batched over the points of a keyframe
  *        reference src/MapPoint.cc:325-438, :480-528                                  -> orbm_refresh_points[_host]
  *
@@ -375,6 +377,56 @@ int orbm_local_map_vote_host(const orbm_obs* obs, int n_obs, const uint8_t* poin
  * kept even when it exceeds list_cap (ORB_E_CAPACITY then, the first list_cap entries written). */
 int orbm_local_map_points_host(const int32_t* kf_rows, const int32_t* kf_count, int n_kfs, int stride, const uint8_t* point_flags,
                                int n_points, const int32_t* local_kfs, int n_local, int32_t* list, int list_cap, int* n_list);
+
+/* -- covisibility on the device: KeyFrame::UpdateConnections' counters and LocalMapping::KeyFrameCulling's counts ----------
+ * The two routines of the LocalMapping and LoopClosing threads that walk keyframe -> map points -> observations and count
+ * (reference src/KeyFrame.cc:512-552, src/LocalMapping.cc:990-1032), over the same resident map.  The map learns four more facts,
+ * all additive: what the calls above read and return is untouched by them.
+ *   per record    the feature index of the observation in its keyframe (mObservations[pKF]); a record never written holds 0
+ *   per keyframe  one byte per feature -- bits 0-4 mvKeysUn_total[i].octave, bit 7 (ORBM_FEATURE_FAR) the HOST's float evaluation
+ *                 of `mvDepth_total[i] > mThDepth || mvDepth_total[i] < 0` -- and N, the camera-1 feature count; never written: zeros
+ *   per point     n_obs, what MapPoint::Observations() returns (mirrored as a value, not recomputed); never written: 0
+ *   an index      from a point to its live records: a chain head[point], next[record], built on the device by the first counting
+ *                 call after any orbm_map_write_observations.  A record's place in its chain is arbitrary from build to build:
+ *                 NOTHING THAT DEPENDS ON CHAIN ORDER IS EVER READ OUT OF IT -- both calls below only count.
+ * Integer counting only: the device's results are exact whatever order the lanes arrive in. */
+enum { ORBM_FEATURE_LEVEL_MASK = 0x1f, ORBM_FEATURE_FAR = 0x80 };
+typedef struct { int32_t keyframe, all, cam1; } orbm_covis_entry;
+/* feature[i], in 0 .. features_per_keyframe-1, into record slot slots[i].  Outside: ORB_E_ARG / ORB_E_CAPACITY, nothing written. */
+int orbm_map_write_observation_features(orbm_matcher* m, orbm_map* map, const int32_t* slots, int n, const int32_t* feature);
+/* Keyframe slot kf: feature_bytes[0 .. n_features) (the rest of the row becomes 0) and n_cam1 in 0 .. features_per_keyframe. */
+int orbm_map_write_keyframe_features(orbm_matcher* m, orbm_map* map, int kf, const uint8_t* feature_bytes, int n_features, int n_cam1);
+int orbm_map_write_point_nobs(orbm_matcher* m, orbm_map* map, const int32_t* slots, int n, const int32_t* n_obs);
+/* For keyframe k = kfs[j], j < n <= ORBM_MAP_MAX_LOCAL (src/KeyFrame.cc:512-552):
+ *   for i in 0 .. kf_count[k]-1:  p = row[k][i];  skip p < 0;  skip bad(p)
+ *     for every live record r of p with r.keyframe != k:
+ *       all[r.keyframe] += 1
+ *       if i < n_cam1[k] and feature(r) < n_cam1[r.keyframe]:  cam1[r.keyframe] += 1
+ * The entries with all > 0, in ascending keyframe slot, are entries[first_out[j] .. first_out[j+1]-1]; first_out has n + 1 entries.
+ * A point at two features of k counts twice; bad keyframes are counted; a keyframe named twice gets two equal lists.  The device
+ * keeps both counters of a keyframe in one 32-bit bin, which holds as long as a count stays below 65 536: it cannot exceed the
+ * length of a row while the map keeps to one live record per (point, keyframe) (orbm_map_write_observations).  More entries
+ * than entries_cap: ORB_E_CAPACITY, first_out[n] (and the error text) the number needed, first_out[0 .. n) zero, no list. */
+int orbm_map_covisibility(orbm_matcher* m, orbm_map* map, const int32_t* kfs, int n, int32_t* first_out, orbm_covis_entry* entries,
+                          int entries_cap);
+/* counts_out[2 j], counts_out[2 j + 1] = nMPs, nRedundantObservations of keyframe kfs[j] (src/LocalMapping.cc:990-1032):
+ *   for i in 0 .. kf_count[k]-1:  p = row[k][i];  skip p < 0;  skip bad(p);  skip far(k, i) unless mono
+ *     nMPs += 1
+ *     if n_obs[p] > 3:
+ *       c = #{ live records r of p : r.keyframe != k  and  level(r.keyframe, feature(r)) <= level(k, i) + 1 }
+ *       if c >= 3: nRedundant += 1
+ * (the reference's break at the third hit is an early exit only: c >= 3 does not depend on the order of the observations.) */
+int orbm_map_culling_counts(orbm_matcher* m, orbm_map* map, const int32_t* kfs, int n, int mono, int32_t* counts_out);
+/* Host, on plain arrays: the fallback (MORB_HOST_RESOLVE=1, over the mirror), the route of a map without a device and the
+ * cross-check of the two calls above.  obs_feature[i] belongs to obs[i]; kf_feature_bytes[k * stride + f]; a record or a row entry
+ * outside the counts given: ORB_E_ARG.  The covisibility routine writes the first entries_cap entries when there are more. */
+int orbm_local_map_covisibility_host(const orbm_obs* obs, const int32_t* obs_feature, int n_obs, const uint8_t* point_flags, int n_points,
+                                     const int32_t* kf_rows, const int32_t* kf_count, const int32_t* kf_n_cam1, int n_kfs, int stride,
+                                     const int32_t* kfs, int n, int32_t* first_out, orbm_covis_entry* entries, int entries_cap);
+int orbm_local_map_culling_host(const orbm_obs* obs, const int32_t* obs_feature, int n_obs, const uint8_t* point_flags,
+                                const int32_t* point_n_obs, int n_points, const int32_t* kf_rows, const int32_t* kf_count,
+                                const uint8_t* kf_feature_bytes, int n_kfs, int stride, const int32_t* kfs, int n, int mono,
+                                int32_t* counts_out);
 
 /* -- map-point refresh: distinctive descriptor, normal, depth --------------------------------------------------
  * The producer of what an orbm_point row holds beyond the position: MapPoint::ComputeDistinctiveDescriptors (reference

@@ -28,6 +28,9 @@ REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH, REFRESH_CAP = 1, 2, 256
 OBS_DTYPE = np.dtype([("point", "<i4"), ("keyframe", "<i4")])   # orbm_obs
 assert OBS_DTYPE.itemsize == 8
 MAX_POINTS, MAP_MAX_KEYFRAMES, MAP_MAX_FEATURES, MAP_MAX_LOCAL, POINT_BAD = 65535, 16384, 8192, 4096, 1
+COVIS_DTYPE = np.dtype([("keyframe", "<i4"), ("all", "<i4"), ("cam1", "<i4")])   # orbm_covis_entry
+assert COVIS_DTYPE.itemsize == 12
+FEATURE_LEVEL_MASK, FEATURE_FAR = 0x1f, 0x80
 POSE_PROBLEM_DTYPE = np.dtype([("Tcw", "<f4", (16,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("bf", "<f4"),
                                ("Rcam12", "<f4", (9,)), ("tcam12", "<f4", (3,)), ("inv_level_sigma2", "<f4", (32,)),
                                ("n_levels", "<i4"), ("mode", "<i4"), ("n_cam0", "<i4")])   # orbm_pose_problem
@@ -343,6 +346,14 @@ def lib():
     L.orbm_local_map_vote_host.argtypes = [vp, i32, vp, i32, vp, i32, i32, vp]
     L.orbm_local_map_points_host.argtypes = [vp, vp, i32, i32, vp, i32, vp, i32, vp, i32, vp]
     L.orbm_debug_last_local_map.argtypes = [vp, vp]
+    L.orbm_map_write_observation_features.argtypes = [vp, vp, vp, i32, vp]
+    L.orbm_map_write_keyframe_features.argtypes = [vp, vp, i32, vp, i32, i32]
+    L.orbm_map_write_point_nobs.argtypes = [vp, vp, vp, i32, vp]
+    L.orbm_map_covisibility.argtypes = [vp, vp, vp, i32, vp, vp, i32]
+    L.orbm_map_culling_counts.argtypes = [vp, vp, vp, i32, i32, vp]
+    L.orbm_local_map_covisibility_host.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, i32]
+    L.orbm_local_map_culling_host.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, i32, vp]
+    L.orbm_debug_last_covisibility.argtypes = [vp, vp]
     L.orbm_refresh_points.argtypes = [vp, vp, vp]
     L.orbm_refresh_points_host.argtypes = [vp, vp]
     L.orbm_debug_last_refresh.argtypes = [vp, vp]

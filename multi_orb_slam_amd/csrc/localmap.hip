@@ -4,6 +4,10 @@
 //   orbm_map_vote                 keyframeCounter of UpdateLocalKeyFrames (:1838-1855): k_map_mult, k_map_vote, k_map_vote_out
 //   orbm_map_local_points         UpdateLocalPoints (:1794-1824): k_map_first, k_map_count, k_map_scan, k_map_scatter
 //   orbm_map_search_local_points  k_map_mark, then the body orbm_search_local_points runs (frustum.hip), reading rows[list[i]]
+// and the two counting routines of the LocalMapping / LoopClosing threads over the same map:
+//   orbm_map_covisibility         KFcounter / KFcounter_cam1 of KeyFrame::UpdateConnections (src/KeyFrame.cc:512-552): k_map_covis
+//   orbm_map_culling_counts       nMPs / nRedundantObservations of LocalMapping::KeyFrameCulling (src/LocalMapping.cc:990-1032): k_map_cull
+//   both read the chain from a point to its live records, which k_map_chain builds when a record write has made it stale
 // The kernels are in localmap_dev.h.  The two host routines (orbm_local_map_vote_host, orbm_local_map_points_host) are the
 // reference's loops on plain arrays: the fallback under MORB_HOST_RESOLVE=1, over the mirror, and the cross-check of the tests.
 // K1, K2 and the marks are pointer logic over the covisibility graph and stay with the caller (host/LocalMap.cc).
@@ -41,6 +45,14 @@ struct orbm_map {
     int list_n = -1;                 // -1: no list
     FrustumScratch scr;
     int last[4] = {0, 0, 0, 0};
+    // covisibility and culling: the record's feature, the feature bytes and camera-1 count of a keyframe, the point's n_obs ...
+    DevBuf<int32_t> d_obs_feat, d_nobs, d_kf_ncam1; DevBuf<uint8_t> d_kf_feat;
+    std::vector<int32_t> h_obs_feat, h_nobs, h_kf_ncam1; std::vector<uint8_t> h_kf_feat;
+    // ... and the chain from a point to its live records, stale after any record write
+    DevBuf<int32_t> d_head, d_next, d_cursor;
+    bool index_dirty = false;
+    PinnedBuf<int32_t> h_span, h_counts; PinnedBuf<orbm_covis_entry> h_entries;
+    int last_cov[4] = {0, 0, 0, 0};
 };
 
 namespace {
@@ -48,6 +60,8 @@ namespace {
 void release_all(orbm_map* p) {
     p->d_rows.release(); p->d_flags.release(); p->d_obs.release(); p->d_kf_rows.release(); p->d_kf_count.release();
     p->d_mult.release(); p->d_first.release(); p->d_mark.release(); p->d_votes.release(); p->d_block.release(); p->d_list.release();
+    p->d_obs_feat.release(); p->d_nobs.release(); p->d_kf_ncam1.release(); p->d_kf_feat.release(); p->d_head.release(); p->d_next.release();
+    p->d_cursor.release(); p->h_span.release(); p->h_counts.release(); p->h_entries.release();
     p->d_total.release(); p->h_votes.release(); p->h_list.release(); p->h_total.release(); p->stage.release(); p->scr.h_track.release();
 }
 
@@ -135,7 +149,9 @@ int orbm_map_create(orbm_matcher* m, int kf_capacity, int point_capacity, int ob
     if ((rc = p->d_rows.reserve(np)) || (rc = p->d_flags.reserve(np)) || (rc = p->d_obs.reserve(no)) || (rc = p->d_kf_rows.reserve(nr)) ||
         (rc = p->d_kf_count.reserve(nk)) || (rc = p->d_mult.reserve(np)) || (rc = p->d_first.reserve(np)) || (rc = p->d_mark.reserve(np)) ||
         (rc = p->d_votes.reserve(nk)) || (rc = p->d_list.reserve(ORBM_MAX_POINTS)) || (rc = p->d_total.reserve(4)) ||
-        (rc = p->h_votes.reserve(nk)) || (rc = p->h_list.reserve(ORBM_MAX_POINTS)) || (rc = p->h_total.reserve(4))) {
+        (rc = p->h_votes.reserve(nk)) || (rc = p->h_list.reserve(ORBM_MAX_POINTS)) || (rc = p->h_total.reserve(4)) ||
+        (rc = p->d_obs_feat.reserve(no)) || (rc = p->d_nobs.reserve(np)) || (rc = p->d_kf_ncam1.reserve(nk)) || (rc = p->d_kf_feat.reserve(nr)) ||
+        (rc = p->d_head.reserve(np)) || (rc = p->d_next.reserve(no)) || (rc = p->d_cursor.reserve(1))) {
         release_all(p); delete p;
         return rc;
     }
@@ -147,7 +163,11 @@ int orbm_map_create(orbm_matcher* m, int kf_capacity, int point_capacity, int ob
         hipMemsetAsync(p->d_kf_count.p, 0, nk * sizeof(int32_t), st) != hipSuccess ||
         hipMemsetAsync(p->d_mult.p, 0, np * sizeof(int32_t), st) != hipSuccess ||
         hipMemsetAsync(p->d_first.p, 0xff, np * sizeof(unsigned long long), st) != hipSuccess ||
-        hipMemsetAsync(p->d_mark.p, 0, np * sizeof(uint32_t), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        hipMemsetAsync(p->d_mark.p, 0, np * sizeof(uint32_t), st) != hipSuccess ||
+        hipMemsetAsync(p->d_obs_feat.p, 0, no * sizeof(int32_t), st) != hipSuccess || hipMemsetAsync(p->d_nobs.p, 0, np * sizeof(int32_t), st) != hipSuccess ||
+        hipMemsetAsync(p->d_kf_ncam1.p, 0, nk * sizeof(int32_t), st) != hipSuccess || hipMemsetAsync(p->d_kf_feat.p, 0, nr, st) != hipSuccess ||
+        hipMemsetAsync(p->d_head.p, 0xff, np * sizeof(int32_t), st) != hipSuccess ||
+        hipMemsetAsync(p->d_next.p, 0xff, no * sizeof(int32_t), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
         morb::set_error("clearing the resident map failed");
         release_all(p); delete p;
         return ORB_E_HIP;
@@ -157,6 +177,7 @@ int orbm_map_create(orbm_matcher* m, int kf_capacity, int point_capacity, int ob
     p->h_obs.assign((size_t)obs_capacity, orbm_obs{-1, -1});
     p->h_kf_rows.assign(nr, -1); p->h_kf_count.assign(nk, 0); p->h_kf_bad.assign(nk, 0);
     p->h_mark.assign((size_t)point_capacity, 0u);
+    p->h_obs_feat.assign((size_t)obs_capacity, 0); p->h_nobs.assign((size_t)point_capacity, 0); p->h_kf_ncam1.assign(nk, 0); p->h_kf_feat.assign(nr, 0);
     *out = p;
     return ORB_OK;
 }
@@ -231,6 +252,7 @@ int orbm_map_write_observations(orbm_matcher* m, orbm_map* p, const int32_t* slo
         p->h_obs[(size_t)slots[i]] = r;
         p->obs_hw = std::max(p->obs_hw, slots[i] + 1);
     }
+    p->index_dirty = true;   // the chain from a point to its records is rebuilt by the next counting call
     memcpy(p->stage.p, slots, (size_t)n * 4);
     for (int i = 0; i < n; ++i) memcpy(p->stage.p + off_rec + (size_t)i * sizeof(orbm_obs), &p->h_obs[(size_t)slots[i]], sizeof(orbm_obs));
     p->stage.publish();
@@ -402,4 +424,270 @@ int orbm_map_search_local_points(orbm_matcher* m, const orbm_frame* cur, orbm_ma
         MORB_HIP(hipGetLastError());
     }
     return morb::search_local_points_body(m, cur, p->scr, S, n, view, occupied, nnratio, th_high, track, match_of_feature, n_to_match, nmatches);
+}
+
+// ---- covisibility and culling counts
+
+namespace {
+
+// The live records of every point as a CSR list, for the host routines: first[p] .. first[p+1]-1 index `recs`, in record order.
+int records_by_point(const orbm_obs* obs, const int32_t* obs_feature, int n_obs, int n_points, int n_kfs, int stride,
+                     std::vector<int32_t>& first, std::vector<int32_t>& recs) {
+    first.assign((size_t)n_points + 1, 0);
+    for (int r = 0; r < n_obs; ++r) {
+        if (obs[r].point < 0) continue;
+        MORB_ARG(obs[r].point < n_points && obs[r].keyframe >= 0 && obs[r].keyframe < n_kfs && obs_feature[r] >= 0 && obs_feature[r] < stride);
+        ++first[(size_t)obs[r].point + 1];
+    }
+    for (int p = 0; p < n_points; ++p) first[(size_t)p + 1] += first[(size_t)p];
+    recs.resize((size_t)first[(size_t)n_points]);
+    std::vector<int32_t> at(first.begin(), first.end() - 1);
+    for (int r = 0; r < n_obs; ++r)
+        if (obs[r].point >= 0) recs[(size_t)at[(size_t)obs[r].point]++] = r;
+    return ORB_OK;
+}
+
+int check_rows(const int32_t* kf_rows, const int32_t* kf_count, int n_kfs, int stride, int n_points, const int32_t* kfs, int n) {
+    for (int j = 0; j < n; ++j) {
+        MORB_ARG(kfs[j] >= 0 && kfs[j] < n_kfs && kf_count[kfs[j]] >= 0 && kf_count[kfs[j]] <= stride);
+        for (int i = 0; i < kf_count[kfs[j]]; ++i) MORB_ARG(kf_rows[(size_t)kfs[j] * stride + i] < n_points);
+    }
+    return ORB_OK;
+}
+
+// Clears the heads and links every live record below the high-water mark, when a record write has made the chains stale.
+int build_index_if_dirty(orbm_matcher* m, orbm_map* p) {
+    p->last_cov[1] = 0; p->last_cov[2] = p->obs_hw;
+    if (!p->index_dirty) return ORB_OK;
+    MORB_HIP(hipMemsetAsync(p->d_head.p, 0xff, (size_t)std::max(p->pt_cap, 1) * sizeof(int32_t), m->stream));
+    if (p->obs_hw > 0)
+        hipLaunchKernelGGL(k_map_chain, dim3(blocks_of(p->obs_hw)), dim3(MAP_BLOCK), 0, m->stream, (const orbm_obs*)p->d_obs.p, p->obs_hw,
+                           p->d_head.p, p->d_next.p);
+    MORB_HIP(hipGetLastError());
+    p->index_dirty = false; p->last_cov[1] = 1;
+    return ORB_OK;
+}
+
+int check_listed(const orbm_map* p, const int32_t* kfs, int n) {
+    if (n > ORBM_MAP_MAX_LOCAL) { morb::set_error("%d keyframes are more than a call takes (%d)", n, (int)ORBM_MAP_MAX_LOCAL); return ORB_E_CAPACITY; }
+    return check_slots(kfs, n, 0, p->kf_hw, "keyframe") ? ORB_E_ARG : ORB_OK;
+}
+
+}  // namespace
+
+int orbm_local_map_covisibility_host(const orbm_obs* obs, const int32_t* obs_feature, int n_obs, const uint8_t* point_flags, int n_points,
+                                     const int32_t* kf_rows, const int32_t* kf_count, const int32_t* kf_n_cam1, int n_kfs, int stride,
+                                     const int32_t* kfs, int n, int32_t* first_out, orbm_covis_entry* entries, int entries_cap) {
+    MORB_ARG(n_obs >= 0 && (n_obs == 0 || (obs && obs_feature)) && n_points >= 0 && (n_points == 0 || point_flags) && n_kfs >= 0 && stride >= 1 &&
+             (n_kfs == 0 || (kf_rows && kf_count && kf_n_cam1)) && n >= 0 && (n == 0 || kfs) && first_out && entries_cap >= 0 &&
+             (entries_cap == 0 || entries));
+    int rc;
+    if ((rc = check_rows(kf_rows, kf_count, n_kfs, stride, n_points, kfs, n))) return rc;
+    std::vector<int32_t> first, recs;
+    if ((rc = records_by_point(obs, obs_feature, n_obs, n_points, n_kfs, stride, first, recs))) return rc;
+    std::vector<int32_t> all((size_t)n_kfs, 0), cam1((size_t)n_kfs, 0), touched;
+    long long total = 0;
+    first_out[0] = 0;
+    for (int j = 0; j < n; ++j) {
+        const int k = kfs[j];
+        touched.clear();
+        for (int i = 0; i < kf_count[k]; ++i) {
+            const int p = kf_rows[(size_t)k * stride + i];
+            if (p < 0) continue;
+            if (point_flags[p] & ORBM_POINT_BAD) continue;
+            for (int a = first[(size_t)p]; a < first[(size_t)p + 1]; ++a) {
+                const int r = recs[(size_t)a], kf = obs[r].keyframe;
+                if (kf == k) continue;
+                if (all[(size_t)kf]++ == 0) touched.push_back(kf);
+                if (i < kf_n_cam1[k] && obs_feature[r] < kf_n_cam1[kf]) ++cam1[(size_t)kf];
+            }
+        }
+        std::sort(touched.begin(), touched.end());
+        for (int kf : touched) {
+            if (total < entries_cap) entries[total] = orbm_covis_entry{kf, all[(size_t)kf], cam1[(size_t)kf]};
+            ++total;
+            all[(size_t)kf] = 0; cam1[(size_t)kf] = 0;
+        }
+        first_out[j + 1] = (int32_t)std::min<long long>(total, 0x7fffffff);
+    }
+    if (total > entries_cap) { morb::set_error("%lld covisibility entries are more than the list takes (%d)", total, entries_cap); return ORB_E_CAPACITY; }
+    return ORB_OK;
+}
+
+int orbm_local_map_culling_host(const orbm_obs* obs, const int32_t* obs_feature, int n_obs, const uint8_t* point_flags,
+                                const int32_t* point_n_obs, int n_points, const int32_t* kf_rows, const int32_t* kf_count,
+                                const uint8_t* kf_feature_bytes, int n_kfs, int stride, const int32_t* kfs, int n, int mono,
+                                int32_t* counts_out) {
+    MORB_ARG(n_obs >= 0 && (n_obs == 0 || (obs && obs_feature)) && n_points >= 0 && (n_points == 0 || (point_flags && point_n_obs)) &&
+             n_kfs >= 0 && stride >= 1 && (n_kfs == 0 || (kf_rows && kf_count && kf_feature_bytes)) && n >= 0 && (n == 0 || (kfs && counts_out)));
+    int rc;
+    if ((rc = check_rows(kf_rows, kf_count, n_kfs, stride, n_points, kfs, n))) return rc;
+    std::vector<int32_t> first, recs;
+    if ((rc = records_by_point(obs, obs_feature, n_obs, n_points, n_kfs, stride, first, recs))) return rc;
+    for (int j = 0; j < n; ++j) {
+        const int k = kfs[j];
+        const uint8_t* feat = kf_feature_bytes + (size_t)k * stride;
+        int nMPs = 0, nRedundant = 0;
+        for (int i = 0; i < kf_count[k]; ++i) {
+            const int p = kf_rows[(size_t)k * stride + i];
+            if (p < 0) continue;
+            if (point_flags[p] & ORBM_POINT_BAD) continue;
+            if (!mono && (feat[i] & ORBM_FEATURE_FAR)) continue;
+            ++nMPs;
+            if (point_n_obs[p] > 3) {
+                const int level = feat[i] & ORBM_FEATURE_LEVEL_MASK;
+                int c = 0;
+                for (int a = first[(size_t)p]; a < first[(size_t)p + 1]; ++a) {
+                    const int r = recs[(size_t)a], kf = obs[r].keyframe;
+                    if (kf == k) continue;
+                    if ((kf_feature_bytes[(size_t)kf * stride + obs_feature[r]] & ORBM_FEATURE_LEVEL_MASK) <= level + 1) ++c;
+                }
+                if (c >= 3) ++nRedundant;
+            }
+        }
+        counts_out[2 * j] = nMPs; counts_out[2 * j + 1] = nRedundant;
+    }
+    return ORB_OK;
+}
+
+int orbm_debug_last_covisibility(const orbm_map* p, int* out4) {
+    MORB_ARG(p && out4);
+    for (int k = 0; k < 4; ++k) out4[k] = p->last_cov[k];
+    return ORB_OK;
+}
+
+int orbm_map_write_observation_features(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n, const int32_t* feature) {
+    MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || (slots && feature)));
+    int rc;
+    if ((rc = check_slots(slots, n, 0, p->obs_cap, "record slot")) || (rc = check_slots(feature, n, 0, p->stride, "feature index"))) return rc;
+    if (n == 0) return ORB_OK;
+    MORB_HIP(hipSetDevice(m->device));
+    const size_t off_val = (size_t)n * 4;
+    if ((rc = p->stage.reserve(off_val + (size_t)n * 4 + 16))) return rc;
+    for (int i = 0; i < n; ++i) p->h_obs_feat[(size_t)slots[i]] = feature[i];
+    memcpy(p->stage.p, slots, (size_t)n * 4);   // (staged from the mirror, as the records are: a slot named twice takes its last entry)
+    for (int i = 0; i < n; ++i) memcpy(p->stage.p + off_val + (size_t)i * 4, &p->h_obs_feat[(size_t)slots[i]], 4);
+    p->stage.publish();
+    hipLaunchKernelGGL(k_map_put_words, dim3(blocks_of(n)), dim3(MAP_BLOCK), 0, m->stream, (const uint32_t*)(p->stage.dp + off_val),
+                       (const int32_t*)p->stage.dp, n, 1, (uint32_t*)p->d_obs_feat.p);
+    MORB_HIP(hipGetLastError());
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    return ORB_OK;
+}
+
+int orbm_map_write_point_nobs(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n, const int32_t* n_obs) {
+    MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || (slots && n_obs)));
+    int rc;
+    if ((rc = check_slots(slots, n, 0, p->pt_cap, "point slot"))) return rc;
+    if (n == 0) return ORB_OK;
+    MORB_HIP(hipSetDevice(m->device));
+    const size_t off_val = (size_t)n * 4;
+    if ((rc = p->stage.reserve(off_val + (size_t)n * 4 + 16))) return rc;
+    for (int i = 0; i < n; ++i) p->h_nobs[(size_t)slots[i]] = n_obs[i];
+    memcpy(p->stage.p, slots, (size_t)n * 4);
+    for (int i = 0; i < n; ++i) memcpy(p->stage.p + off_val + (size_t)i * 4, &p->h_nobs[(size_t)slots[i]], 4);
+    p->stage.publish();
+    hipLaunchKernelGGL(k_map_put_words, dim3(blocks_of(n)), dim3(MAP_BLOCK), 0, m->stream, (const uint32_t*)(p->stage.dp + off_val),
+                       (const int32_t*)p->stage.dp, n, 1, (uint32_t*)p->d_nobs.p);
+    MORB_HIP(hipGetLastError());
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    return ORB_OK;
+}
+
+int orbm_map_write_keyframe_features(orbm_matcher* m, orbm_map* p, int kf, const uint8_t* feature_bytes, int n_features, int n_cam1) {
+    MORB_ARG(m && p && p->owner == m && n_features >= 0 && (n_features == 0 || feature_bytes) && n_cam1 >= 0);
+    if (kf < 0 || kf >= p->kf_cap || n_features > p->stride || n_cam1 > p->stride) {
+        morb::set_error("keyframe slot %d with %d features, %d of camera 1, does not fit a map of %d keyframes of %d", kf, n_features, n_cam1,
+                        p->kf_cap, p->stride);
+        return kf < 0 ? ORB_E_ARG : ORB_E_CAPACITY;
+    }
+    MORB_HIP(hipSetDevice(m->device));
+    uint8_t* row = p->h_kf_feat.data() + (size_t)kf * p->stride;
+    if (n_features) memcpy(row, feature_bytes, (size_t)n_features);
+    memset(row + n_features, 0, (size_t)(p->stride - n_features));
+    p->h_kf_ncam1[(size_t)kf] = n_cam1;
+    // the whole row travels: a record of another keyframe's point may name any feature of this one
+    MORB_HIP(hipMemcpyAsync(p->d_kf_feat.p + (size_t)kf * p->stride, row, (size_t)p->stride, hipMemcpyHostToDevice, m->stream));
+    MORB_HIP(hipMemcpyAsync(p->d_kf_ncam1.p + kf, &p->h_kf_ncam1[(size_t)kf], 4, hipMemcpyHostToDevice, m->stream));
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    return ORB_OK;
+}
+
+int orbm_map_covisibility(orbm_matcher* m, orbm_map* p, const int32_t* kfs, int n, int32_t* first_out, orbm_covis_entry* entries,
+                          int entries_cap) {
+    MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || kfs) && first_out && entries_cap >= 0 && (entries_cap == 0 || entries));
+    int rc;
+    if ((rc = check_listed(p, kfs, n))) return rc;
+    p->last_cov[3] = n;
+    if (m->host_resolve) {   // MORB_HOST_RESOLVE=1: the host routine over the mirror
+        p->last_cov[0] = 0; p->last_cov[1] = 0; p->last_cov[2] = p->obs_hw;
+        std::vector<orbm_covis_entry> tmp((size_t)std::max(entries_cap, 1));
+        rc = orbm_local_map_covisibility_host(p->h_obs.data(), p->h_obs_feat.data(), p->obs_hw, p->h_flags.data(), p->pt_cap, p->h_kf_rows.data(),
+                                              p->h_kf_count.data(), p->h_kf_ncam1.data(), p->kf_hw, p->stride, kfs, n, first_out, tmp.data(),
+                                              entries_cap);
+        if (rc == ORB_E_CAPACITY) { const int32_t need = first_out[n]; for (int j = 0; j < n; ++j) first_out[j] = 0; first_out[n] = need; }
+        if (rc == ORB_OK && first_out[n] > 0) memcpy(entries, tmp.data(), (size_t)first_out[n] * sizeof(orbm_covis_entry));
+        return rc;
+    }
+    p->last_cov[0] = 1;
+    MORB_HIP(hipSetDevice(m->device));
+    if ((rc = build_index_if_dirty(m, p))) return rc;
+    first_out[0] = 0;
+    if (n == 0) { MORB_HIP(hipStreamSynchronize(m->stream)); return ORB_OK; }
+    if ((rc = p->stage.reserve((size_t)n * 4 + 16)) || (rc = p->h_span.reserve((size_t)n * 2)) ||
+        (rc = p->h_entries.reserve((size_t)std::max(entries_cap, 1)))) return rc;
+    memcpy(p->stage.p, kfs, (size_t)n * 4);
+    p->stage.publish();
+    MORB_HIP(hipMemsetAsync(p->d_cursor.p, 0, sizeof(int32_t), m->stream));
+    const int nk = p->kf_hw;
+    hipLaunchKernelGGL(k_map_covis, dim3(n), dim3(MAP_BLOCK), ((size_t)nk + MAP_BLOCK / 64 + 1) * sizeof(int32_t), m->stream,
+                       (const int32_t*)p->stage.dp, (const int32_t*)p->d_kf_rows.p, (const int32_t*)p->d_kf_count.p,
+                       (const int32_t*)p->d_kf_ncam1.p, p->stride, (const uint8_t*)p->d_flags.p, (const orbm_obs*)p->d_obs.p,
+                       (const int32_t*)p->d_obs_feat.p, (const int32_t*)p->d_head.p, (const int32_t*)p->d_next.p, nk, p->d_cursor.p,
+                       p->h_span.dp, p->h_entries.dp, entries_cap);
+    MORB_HIP(hipGetLastError());
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    long long total = 0;
+    for (int j = 0; j < n; ++j) total += p->h_span.p[2 * j + 1];
+    if (total > entries_cap) {
+        for (int j = 0; j < n; ++j) first_out[j] = 0;
+        first_out[n] = (int32_t)std::min<long long>(total, 0x7fffffff);
+        morb::set_error("%lld covisibility entries are more than the list takes (%d)", total, entries_cap);
+        return ORB_E_CAPACITY;
+    }
+    // the workgroups took their spans in the order they arrived: laid out here in the order of kfs
+    for (int j = 0; j < n; ++j) {
+        const int start = p->h_span.p[2 * j], cnt = p->h_span.p[2 * j + 1];
+        if (cnt) memcpy(entries + first_out[j], p->h_entries.p + start, (size_t)cnt * sizeof(orbm_covis_entry));
+        first_out[j + 1] = first_out[j] + cnt;
+    }
+    return ORB_OK;
+}
+
+int orbm_map_culling_counts(orbm_matcher* m, orbm_map* p, const int32_t* kfs, int n, int mono, int32_t* counts_out) {
+    MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || (kfs && counts_out)));
+    int rc;
+    if ((rc = check_listed(p, kfs, n))) return rc;
+    p->last_cov[3] = n;
+    if (m->host_resolve) {   // MORB_HOST_RESOLVE=1: the host routine over the mirror
+        p->last_cov[0] = 0; p->last_cov[1] = 0; p->last_cov[2] = p->obs_hw;
+        return orbm_local_map_culling_host(p->h_obs.data(), p->h_obs_feat.data(), p->obs_hw, p->h_flags.data(), p->h_nobs.data(), p->pt_cap,
+                                           p->h_kf_rows.data(), p->h_kf_count.data(), p->h_kf_feat.data(), p->kf_hw, p->stride, kfs, n, mono,
+                                           counts_out);
+    }
+    p->last_cov[0] = 1;
+    MORB_HIP(hipSetDevice(m->device));
+    if ((rc = build_index_if_dirty(m, p))) return rc;
+    if (n == 0) { MORB_HIP(hipStreamSynchronize(m->stream)); return ORB_OK; }
+    if ((rc = p->stage.reserve((size_t)n * 4 + 16)) || (rc = p->h_counts.reserve((size_t)n * 2))) return rc;
+    memcpy(p->stage.p, kfs, (size_t)n * 4);
+    p->stage.publish();
+    hipLaunchKernelGGL(k_map_cull, dim3(n), dim3(MAP_BLOCK), 0, m->stream, (const int32_t*)p->stage.dp, (const int32_t*)p->d_kf_rows.p,
+                       (const int32_t*)p->d_kf_count.p, (const uint8_t*)p->d_kf_feat.p, p->stride, (const uint8_t*)p->d_flags.p,
+                       (const int32_t*)p->d_nobs.p, (const orbm_obs*)p->d_obs.p, (const int32_t*)p->d_obs_feat.p, (const int32_t*)p->d_head.p,
+                       (const int32_t*)p->d_next.p, mono ? 1 : 0, p->h_counts.dp);
+    MORB_HIP(hipGetLastError());
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    memcpy(counts_out, p->h_counts.p, (size_t)n * 2 * sizeof(int32_t));
+    return ORB_OK;
 }

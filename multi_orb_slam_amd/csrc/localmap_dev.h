@@ -9,6 +9,9 @@
 //                k_map_scan      one workgroup: exclusive prefix sum over the block counts, the total
 //                k_map_scatter   the kept slots to their places
 //   search:      k_map_mark      the frame's own points and the `seen` list stamped with the call's epoch (k_frustum<true> reads it)
+//   counting:    k_map_chain     one lane per record: the chain from a point to its live records (an exchange on the point's head)
+//                k_map_covis     one workgroup per keyframe: UpdateConnections' two counters in LDS bins, compacted in slot order
+//                k_map_cull      one workgroup per keyframe: KeyFrameCulling's two counts, ballots only
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -176,6 +179,135 @@ __global__ __launch_bounds__(MAP_BLOCK) void k_map_mark(const int32_t* __restric
     } else if (i < n_features + n_seen) {
         const int p = seen[i - n_features];
         if (p >= 0) mark[p] = epoch;
+    }
+}
+
+// ---- covisibility and culling counts (include/orbm.h, "covisibility on the device")
+// The index from a point to its live records: head[point] (cleared to -1 before), next[record]; one lane per record slot below the
+// high-water mark.  The exchange is the only ordering there is: a record's place in its chain is arbitrary, so the readers count
+// and never report a position.
+__global__ __launch_bounds__(MAP_BLOCK) void k_map_chain(const orbm_obs* __restrict__ obs, int n_obs, int32_t* __restrict__ head,
+                                                         int32_t* __restrict__ next) {
+    const int r = blockIdx.x * MAP_BLOCK + threadIdx.x;
+    if (r >= n_obs) return;
+    const int p = obs[r].point;
+    next[r] = p >= 0 ? atomicExch(&head[p], r) : -1;
+}
+
+// One bin holds both counters of a keyframe: `all` in the low half, `cam1` in the high half.  Either is at most the length of a
+// row (ORBM_MAP_MAX_FEATURES = 8192 < 65536: one live record per (point, keyframe), one add per row entry and record), so one walk
+// of the chains fills both and no carry crosses the halves.
+constexpr int COVIS_CAM1_SHIFT = 16;
+static_assert(ORBM_MAP_MAX_FEATURES < (1 << COVIS_CAM1_SHIFT), "a row's count must fit half a bin");
+
+// One workgroup per listed keyframe.  Lanes stride over the row, each lane walks its point's chain and adds into the workgroup's
+// bins in LDS (k_map_vote's idiom); the non-zero bins are then compacted in slot order, 256 at a time.  The workgroup takes its span
+// of the output with one add on *cursor, so no workgroup waits for another; span[j] = {start, count} lets the host lay the lists
+// out in the order of kfs.  An entry beyond entries_cap is not written (the cursor still says how many there were).
+// Dynamic LDS: n_kfs ints and MAP_BLOCK / 64 more.
+__global__ __launch_bounds__(MAP_BLOCK) void k_map_covis(const int32_t* __restrict__ kfs, const int32_t* __restrict__ kf_rows,
+                                                         const int32_t* __restrict__ kf_count, const int32_t* __restrict__ kf_ncam1,
+                                                         int stride, const uint8_t* __restrict__ flags,
+                                                         const orbm_obs* __restrict__ obs, const int32_t* __restrict__ obs_feat,
+                                                         const int32_t* __restrict__ head, const int32_t* __restrict__ next, int n_kfs,
+                                                         int32_t* __restrict__ cursor, int32_t* __restrict__ span,
+                                                         orbm_covis_entry* __restrict__ entries, int entries_cap) {
+    extern __shared__ int32_t bins[];
+    int32_t* wave_n = bins + n_kfs;   // [MAP_BLOCK / 64], then the span's start
+    const int k = kfs[blockIdx.x];
+    for (int b = threadIdx.x; b < n_kfs; b += MAP_BLOCK) bins[b] = 0;
+    __syncthreads();
+    const int cnt = kf_count[k], ncam1 = kf_ncam1[k];
+    const int32_t* row = kf_rows + (size_t)k * stride;
+    for (int i = threadIdx.x; i < cnt; i += MAP_BLOCK) {
+        const int p = row[i];
+        if (p < 0 || (flags[p] & ORBM_POINT_BAD)) continue;
+        for (int r = head[p]; r >= 0; r = next[r]) {
+            const int kf = obs[r].keyframe;
+            if (kf == k) continue;
+            int add = 1;
+            if (i < ncam1 && obs_feat[r] < kf_ncam1[kf]) add |= 1 << COVIS_CAM1_SHIFT;
+            atomicAdd(&bins[kf], add);
+        }
+    }
+    __syncthreads();
+    // the workgroup's total, then its span
+    int mine = 0;
+    for (int b = threadIdx.x; b < n_kfs; b += MAP_BLOCK) mine += bins[b] != 0;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
+    if (lane == 0) wave_n[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int total = 0;
+        for (int w = 0; w < MAP_BLOCK / 64; ++w) total += wave_n[w];
+        const int start = atomicAdd(cursor, total);
+        span[2 * blockIdx.x] = start; span[2 * blockIdx.x + 1] = total;
+        wave_n[MAP_BLOCK / 64] = start;
+    }
+    __syncthreads();
+    int at = wave_n[MAP_BLOCK / 64];
+    __syncthreads();
+    for (int base = 0; base < n_kfs; base += MAP_BLOCK) {   // (uniform trip count: the ballots and barriers see every lane)
+        const int b = base + threadIdx.x;
+        const int v = b < n_kfs ? bins[b] : 0;
+        const unsigned long long bal = __ballot(v != 0);
+        if (lane == 0) wave_n[wave] = __popcll(bal);
+        __syncthreads();
+        int mine_at = at + __popcll(bal & ((1ull << lane) - 1ull)), step = 0;
+        for (int w = 0; w < MAP_BLOCK / 64; ++w) { if (w < wave) mine_at += wave_n[w]; step += wave_n[w]; }
+        if (v != 0 && mine_at < entries_cap) {
+            orbm_covis_entry e; e.keyframe = b; e.all = v & ((1 << COVIS_CAM1_SHIFT) - 1); e.cam1 = v >> COVIS_CAM1_SHIFT;
+            entries[mine_at] = e;
+        }
+        at += step;
+        __syncthreads();
+    }
+}
+
+// One workgroup per listed keyframe; no bins: per lane two predicates, per wave a ballot and a population count.
+// counts[2 j] = nMPs, counts[2 j + 1] = nRedundantObservations.
+__global__ __launch_bounds__(MAP_BLOCK) void k_map_cull(const int32_t* __restrict__ kfs, const int32_t* __restrict__ kf_rows,
+                                                        const int32_t* __restrict__ kf_count, const uint8_t* __restrict__ kf_feat,
+                                                        int stride, const uint8_t* __restrict__ flags, const int32_t* __restrict__ nobs,
+                                                        const orbm_obs* __restrict__ obs, const int32_t* __restrict__ obs_feat,
+                                                        const int32_t* __restrict__ head, const int32_t* __restrict__ next, int mono,
+                                                        int32_t* __restrict__ counts) {
+    __shared__ int wave_mp[MAP_BLOCK / 64], wave_red[MAP_BLOCK / 64];
+    const int k = kfs[blockIdx.x];
+    const int cnt = kf_count[k];
+    const int32_t* row = kf_rows + (size_t)k * stride;
+    const uint8_t* feat = kf_feat + (size_t)k * stride;
+    int n_mp = 0, n_red = 0;   // wave-uniform
+    for (int base = 0; base < cnt; base += MAP_BLOCK) {
+        const int i = base + threadIdx.x;
+        bool counted = false, redundant = false;
+        if (i < cnt) {
+            const int p = row[i];
+            const int fb = feat[i];
+            if (p >= 0 && !(flags[p] & ORBM_POINT_BAD) && (mono || !(fb & ORBM_FEATURE_FAR))) {
+                counted = true;
+                if (nobs[p] > 3) {
+                    const int limit = (fb & ORBM_FEATURE_LEVEL_MASK) + 1;
+                    int c = 0;
+                    for (int r = head[p]; r >= 0; r = next[r]) {
+                        const int kf = obs[r].keyframe;
+                        if (kf == k) continue;
+                        c += (kf_feat[(size_t)kf * stride + obs_feat[r]] & ORBM_FEATURE_LEVEL_MASK) <= limit;
+                    }
+                    redundant = c >= 3;
+                }
+            }
+        }
+        n_mp += __popcll(__ballot(counted));
+        n_red += __popcll(__ballot(redundant));
+    }
+    if ((threadIdx.x & 63) == 0) { wave_mp[threadIdx.x >> 6] = n_mp; wave_red[threadIdx.x >> 6] = n_red; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int a = 0, b = 0;
+        for (int w = 0; w < MAP_BLOCK / 64; ++w) { a += wave_mp[w]; b += wave_red[w]; }
+        counts[2 * blockIdx.x] = a; counts[2 * blockIdx.x + 1] = b;
     }
 }
 

@@ -7,6 +7,7 @@
 #include <functional>
 #include <set>
 #include "../../include/orbm.h"
+#include "../../include/orb_debug.h"
 #include "point_row.h"
 
 namespace ORB_SLAM2 {
@@ -14,6 +15,18 @@ namespace ORB_SLAM2 {
 namespace {
 void report(const char* who, const char* what, int rc) {
     std::fprintf(stderr, "%s: %s failed (%d): %s\n", who, what, rc, orb_last_error());
+}
+
+// out[f], f < stride: the level of feature f in the low five bits, ORBM_FEATURE_FAR where the reference's statement
+// `mvDepth_total[f] > mThDepth || mvDepth_total[f] < 0` holds; zero from the n-th feature on and where the keyframe's vectors end.
+void keyframe_feature_bytes(KeyFrame* pKF, size_t n, int stride, std::vector<uint8_t>& out) {
+    out.assign((size_t)stride, 0);
+    for (size_t f = 0; f < n && f < (size_t)stride; ++f) {
+        uint8_t b = 0;
+        if (f < pKF->mvKeysUn_total.size()) b = (uint8_t)(pKF->mvKeysUn_total[f].octave & ORBM_FEATURE_LEVEL_MASK);
+        if (f < pKF->mvDepth_total.size() && (pKF->mvDepth_total[f] > pKF->mThDepth || pKF->mvDepth_total[f] < 0)) b |= ORBM_FEATURE_FAR;
+        out[f] = b;
+    }
 }
 }  // namespace
 
@@ -46,7 +59,7 @@ int ResidentMap::SlotOf(MapPoint* pMP) {
     if (slot >= mCap.points) { std::fprintf(stderr, "ResidentMap: more than %d map points\n", mCap.points); mbFailed = true; return -1; }
     mvPointOfSlot.push_back(pMP);
     orbm_point zero; std::memset(&zero, 0, sizeof(zero));
-    mvRows.push_back(zero); mvFlags.push_back(0);             // what an unwritten slot holds on the device
+    mvRows.push_back(zero); mvFlags.push_back(0); mvPointNObs.push_back(0);   // what an unwritten slot holds on the device
     mPoints[pMP] = PointEntry{slot, {}};
     return slot;
 }
@@ -58,7 +71,8 @@ int ResidentMap::SlotOf(KeyFrame* pKF) {
     if (slot >= mCap.keyframes) { std::fprintf(stderr, "ResidentMap: more than %d keyframes\n", mCap.keyframes); mbFailed = true; return -1; }
     mvKeyFrameOfSlot.push_back(pKF);
     mvKeyFrameRows.resize((size_t)(slot + 1) * mCap.features_per_keyframe, -1);
-    mvKeyFrameCount.push_back(0); mvKeyFrameBad.push_back(0); mvKeyFrameSent.push_back(0);
+    mvKeyFrameFeatures.resize((size_t)(slot + 1) * mCap.features_per_keyframe, 0);
+    mvKeyFrameCount.push_back(0); mvKeyFrameBad.push_back(0); mvKeyFrameSent.push_back(0); mvKeyFrameNCam1.push_back(0);
     mKeyFrames[pKF] = slot;
     return slot;
 }
@@ -73,7 +87,13 @@ bool ResidentMap::EnsureDevice() {
     return true;
 }
 
+void ResidentMap::LastCovisibility(int out4[4]) const {
+    for (int k = 0; k < 4; ++k) out4[k] = 0;
+    if (mpMap) (void)orbm_debug_last_covisibility(mpMap, out4);
+}
+
 int ResidentMap::Flush() {
+    std::lock_guard<std::recursive_mutex> lock_map(mMutexMap);
     mLastFlush = FlushStats();
     if (mbFailed) return -1;                                   // a map that outgrew its capacity or lost a device call stays loud
     std::vector<MapPoint*> points; std::vector<KeyFrame*> keyframes;
@@ -88,9 +108,12 @@ int ResidentMap::Flush() {
     std::sort(keyframes.begin(), keyframes.end(), std::less<KeyFrame*>()); keyframes.erase(std::unique(keyframes.begin(), keyframes.end()), keyframes.end());
 
     std::vector<int32_t> row_slots, rec_slots; std::vector<orbm_point> rows; std::vector<uint8_t> flags; std::vector<orbm_obs> recs;
+    std::vector<int32_t> nobs_slots, nobs, feat_slots, feats;
     for (MapPoint* pMP : points) {
         const int slot = SlotOf(pMP);
         if (slot < 0) return -1;
+        const int n_obs = pMP->Observations();                 // (the reference's counter, mirrored as a value)
+        if (n_obs != mvPointNObs[(size_t)slot]) { mvPointNObs[(size_t)slot] = n_obs; nobs_slots.push_back(slot); nobs.push_back(n_obs); }
         orbm_point row; pack_point_row(pMP, row);
         const uint8_t flag = pMP->isBad() ? ORBM_POINT_BAD : 0;
         if (std::memcmp(&row, &mvRows[(size_t)slot], sizeof(row)) != 0 || flag != mvFlags[(size_t)slot]) {
@@ -108,7 +131,13 @@ int ResidentMap::Flush() {
             it = held.erase(it);
         }
         for (const auto& ob : now) {
-            if (held.count(ob.first)) continue;
+            // the feature index of the observation in its keyframe, of a record the mirror holds already and of a new one alike
+            const int feature = (int)std::min<size_t>(ob.second, (size_t)mCap.features_per_keyframe - 1);
+            auto h = held.find(ob.first);
+            if (h != held.end()) {
+                if (mvRecordFeature[(size_t)h->second] != feature) { mvRecordFeature[(size_t)h->second] = feature; feat_slots.push_back(h->second); feats.push_back(feature); }
+                continue;
+            }
             const int kf = SlotOf(ob.first);
             if (kf < 0) return -1;
             int rec;
@@ -116,8 +145,9 @@ int ResidentMap::Flush() {
             else {
                 rec = (int)mvRecords.size();
                 if (rec >= mCap.observations) { std::fprintf(stderr, "ResidentMap: more than %d observations\n", mCap.observations); mbFailed = true; return -1; }
-                mvRecords.push_back(orbm_obs{-1, -1});
+                mvRecords.push_back(orbm_obs{-1, -1}); mvRecordFeature.push_back(0);
             }
+            if (mvRecordFeature[(size_t)rec] != feature) { mvRecordFeature[(size_t)rec] = feature; feat_slots.push_back(rec); feats.push_back(feature); }
             mvRecords[(size_t)rec] = orbm_obs{slot, kf};
             // a record slot freed and taken again in this Flush: the later entry is the one both sides keep (orbm_map_write_observations
             // stages from its mirror, which holds the last entry of a slot)
@@ -127,7 +157,9 @@ int ResidentMap::Flush() {
     }
     struct KfSend { int slot, n; };
     std::vector<KfSend> kf_send;
+    std::vector<int> kf_feat_send;
     std::vector<int32_t> row;
+    std::vector<uint8_t> feat_row;
     for (KeyFrame* pKF : keyframes) {
         const int slot = SlotOf(pKF);
         if (slot < 0) return -1;
@@ -135,6 +167,16 @@ int ResidentMap::Flush() {
         if ((int)vpMPs.size() > mCap.features_per_keyframe) {
             std::fprintf(stderr, "ResidentMap: a keyframe of %d features does not fit rows of %d\n", (int)vpMPs.size(), mCap.features_per_keyframe);
             mbFailed = true; return -1;
+        }
+        // a byte per feature: the level, and the far test of LocalMapping::KeyFrameCulling evaluated here, in float, as the reference
+        // states it (src/LocalMapping.cc:999).  A keyframe whose key or depth vector is shorter than its matches: level 0, not far.
+        keyframe_feature_bytes(pKF, vpMPs.size(), mCap.features_per_keyframe, feat_row);
+        const int n_cam1 = std::max(0, std::min(pKF->N, mCap.features_per_keyframe));
+        uint8_t* held_feat = mvKeyFrameFeatures.data() + (size_t)slot * mCap.features_per_keyframe;
+        if (n_cam1 != mvKeyFrameNCam1[(size_t)slot] || std::memcmp(held_feat, feat_row.data(), feat_row.size()) != 0) {
+            std::memcpy(held_feat, feat_row.data(), feat_row.size());
+            mvKeyFrameNCam1[(size_t)slot] = n_cam1;
+            kf_feat_send.push_back(slot);
         }
         row.assign((size_t)mCap.features_per_keyframe, -1);
         for (size_t f = 0; f < vpMPs.size(); ++f)
@@ -149,8 +191,16 @@ int ResidentMap::Flush() {
         kf_send.push_back(KfSend{slot, (int)vpMPs.size()});
     }
     mLastFlush.rows = (int)row_slots.size(); mLastFlush.records = (int)rec_slots.size(); mLastFlush.keyframes = (int)kf_send.size();
+    mLastFlush.record_features = (int)feat_slots.size(); mLastFlush.point_nobs = (int)nobs_slots.size(); mLastFlush.keyframe_features = (int)kf_feat_send.size();
     if (mpMap) {
         int rc;
+        if ((rc = orbm_map_write_point_nobs(mpHandle, mpMap, nobs_slots.data(), (int)nobs_slots.size(), nobs.data()))) { report("ResidentMap::Flush", "orbm_map_write_point_nobs", rc); mbFailed = true; return -1; }
+        if ((rc = orbm_map_write_observation_features(mpHandle, mpMap, feat_slots.data(), (int)feat_slots.size(), feats.data()))) { report("ResidentMap::Flush", "orbm_map_write_observation_features", rc); mbFailed = true; return -1; }
+        for (int slot : kf_feat_send)
+            if ((rc = orbm_map_write_keyframe_features(mpHandle, mpMap, slot, mvKeyFrameFeatures.data() + (size_t)slot * mCap.features_per_keyframe,
+                                                       mCap.features_per_keyframe, mvKeyFrameNCam1[(size_t)slot]))) {
+                report("ResidentMap::Flush", "orbm_map_write_keyframe_features", rc); mbFailed = true; return -1;
+            }
         if ((rc = orbm_map_write_points(mpHandle, mpMap, row_slots.data(), (int)row_slots.size(), rows.data(), flags.data()))) { report("ResidentMap::Flush", "orbm_map_write_points", rc); mbFailed = true; return -1; }
         if ((rc = orbm_map_write_observations(mpHandle, mpMap, rec_slots.data(), (int)rec_slots.size(), recs.data()))) { report("ResidentMap::Flush", "orbm_map_write_observations", rc); mbFailed = true; return -1; }
         for (const KfSend& k : kf_send)
@@ -162,7 +212,9 @@ int ResidentMap::Flush() {
 }
 
 int ResidentMap::Audit(const std::vector<KeyFrame*>& vpKeyFrames, const std::vector<MapPoint*>& vpMapPoints) {
+    std::lock_guard<std::recursive_mutex> lock_map(mMutexMap);
     int differences = 0;
+    std::vector<uint8_t> feat_row;
     for (MapPoint* pMP : vpMapPoints) {
         if (!pMP) continue;
         auto it = mPoints.find(pMP);
@@ -171,13 +223,15 @@ int ResidentMap::Audit(const std::vector<KeyFrame*>& vpKeyFrames, const std::vec
         orbm_point row; pack_point_row(pMP, row);
         if (std::memcmp(&row, &mvRows[(size_t)slot], sizeof(row)) != 0) ++differences;
         if ((pMP->isBad() ? ORBM_POINT_BAD : 0) != mvFlags[(size_t)slot]) ++differences;
+        if (pMP->Observations() != mvPointNObs[(size_t)slot]) ++differences;
         const std::map<KeyFrame*, size_t> now = pMP->GetObservations();
         const std::map<KeyFrame*, int>& held = it->second.records;
         bool same = now.size() == held.size();
         for (auto a = now.begin(); same && a != now.end(); ++a) {
             auto h = held.find(a->first);
             same = h != held.end() && mvRecords[(size_t)h->second].point == slot && mKeyFrames.count(a->first) &&
-                   mvRecords[(size_t)h->second].keyframe == mKeyFrames[a->first];
+                   mvRecords[(size_t)h->second].keyframe == mKeyFrames[a->first] &&
+                   mvRecordFeature[(size_t)h->second] == (int)std::min<size_t>(a->second, (size_t)mCap.features_per_keyframe - 1);
         }
         if (!same) ++differences;
     }
@@ -196,11 +250,15 @@ int ResidentMap::Audit(const std::vector<KeyFrame*>& vpKeyFrames, const std::vec
             same = held[f] == want;
         }
         if (!same) ++differences;
+        keyframe_feature_bytes(pKF, vpMPs.size(), mCap.features_per_keyframe, feat_row);
+        if (std::max(0, std::min(pKF->N, mCap.features_per_keyframe)) != mvKeyFrameNCam1[(size_t)slot] ||
+            std::memcmp(mvKeyFrameFeatures.data() + (size_t)slot * mCap.features_per_keyframe, feat_row.data(), feat_row.size()) != 0) ++differences;
     }
     return differences;
 }
 
 int ResidentMap::Vote(const std::vector<int32_t>& frame_points, std::vector<int32_t>& votes) {
+    std::lock_guard<std::recursive_mutex> lock_map(mMutexMap);
     const int n_kfs = (int)mvKeyFrameOfSlot.size();
     votes.assign((size_t)std::max(n_kfs, 1), 0);
     if (mpMap) {
@@ -215,7 +273,51 @@ int ResidentMap::Vote(const std::vector<int32_t>& frame_points, std::vector<int3
     return rc;
 }
 
+bool ResidentMap::SlotsOfSent(const std::vector<KeyFrame*>& vpKFs, size_t begin, size_t end, std::vector<int32_t>& slots) {
+    slots.clear();
+    bool fresh = false;
+    for (size_t i = begin; i < end; ++i) {
+        const int slot = SlotOf(vpKFs[i]);
+        if (slot < 0) return false;
+        slots.push_back(slot);
+        if (!mvKeyFrameSent[(size_t)slot]) { Touch(vpKFs[i]); fresh = true; }   // (Audit counts such keyframes)
+    }
+    return !fresh || Flush() >= 0;
+}
+
+int ResidentMap::Covisibility(const std::vector<int32_t>& kfs, std::vector<int32_t>& first, std::vector<orbm_covis_entry>& entries) {
+    std::lock_guard<std::recursive_mutex> lock_map(mMutexMap);
+    const int n = (int)kfs.size();
+    first.assign((size_t)n + 1, 0);
+    if (entries.size() < 1024) entries.resize(1024);
+    for (int attempt = 0; attempt < 2; ++attempt) {            // a list too short says how long it must be: asked again once
+        int rc;
+        if (mpMap) rc = orbm_map_covisibility(mpHandle, mpMap, kfs.data(), n, first.data(), entries.data(), (int)entries.size());
+        else rc = orbm_local_map_covisibility_host(mvRecords.data(), mvRecordFeature.data(), (int)mvRecords.size(), mvFlags.data(), (int)mvFlags.size(),
+                                                   mvKeyFrameRows.data(), mvKeyFrameCount.data(), mvKeyFrameNCam1.data(), (int)mvKeyFrameOfSlot.size(),
+                                                   mCap.features_per_keyframe, kfs.data(), n, first.data(), entries.data(), (int)entries.size());
+        if (rc == ORB_E_CAPACITY && attempt == 0 && first[(size_t)n] > (int)entries.size()) { entries.resize((size_t)first[(size_t)n]); continue; }
+        if (rc) report("CovisibilityCounts", mpMap ? "orbm_map_covisibility" : "orbm_local_map_covisibility_host", rc);
+        return rc;
+    }
+    return ORB_E_CAPACITY;
+}
+
+int ResidentMap::CullingCounts(const std::vector<int32_t>& kfs, bool mono, std::vector<int32_t>& counts) {
+    std::lock_guard<std::recursive_mutex> lock_map(mMutexMap);
+    const int n = (int)kfs.size();
+    counts.assign((size_t)std::max(n, 1) * 2, 0);
+    int rc;
+    if (mpMap) rc = orbm_map_culling_counts(mpHandle, mpMap, kfs.data(), n, mono ? 1 : 0, counts.data());
+    else rc = orbm_local_map_culling_host(mvRecords.data(), mvRecordFeature.data(), (int)mvRecords.size(), mvFlags.data(), mvPointNObs.data(),
+                                          (int)mvFlags.size(), mvKeyFrameRows.data(), mvKeyFrameCount.data(), mvKeyFrameFeatures.data(),
+                                          (int)mvKeyFrameOfSlot.size(), mCap.features_per_keyframe, kfs.data(), n, mono ? 1 : 0, counts.data());
+    if (rc) report("KeyFrameCulling", mpMap ? "orbm_map_culling_counts" : "orbm_local_map_culling_host", rc);
+    return rc;
+}
+
 int ResidentMap::LocalPoints(const std::vector<int32_t>& local_kfs, std::vector<int32_t>& list) {
+    std::lock_guard<std::recursive_mutex> lock_map(mMutexMap);
     list.assign(ORBM_MAX_POINTS, 0);
     int n = 0, rc;
     if (mpMap) {
@@ -233,6 +335,7 @@ int ResidentMap::LocalPoints(const std::vector<int32_t>& local_kfs, std::vector<
 
 void UpdateLocalMap(ResidentMap& R, Frame& F, std::vector<KeyFrame*>& vpLocalKeyFrames, std::vector<MapPoint*>& vpLocalMapPoints,
                     KeyFrame*& pReferenceKF) {
+    std::lock_guard<std::recursive_mutex> lock_map(R.mMutexMap);
     const bool flushed = R.Flush() >= 0;
 
     // ---- UpdateLocalKeyFrames (src/Tracking.cc:1832-1949)
@@ -344,6 +447,7 @@ void UpdateLocalMap(ResidentMap& R, Frame& F, std::vector<KeyFrame*>& vpLocalKey
 
 int SearchLocalPoints(ORBmatcher& matcher, ResidentMap& R, Frame& F, std::vector<MapPoint*>& vpLocalMapPoints, float th, int* nToMatch) {
     static const char* who = "SearchLocalPoints";
+    std::lock_guard<std::recursive_mutex> lock_map(R.mMutexMap);
     if (nToMatch) *nToMatch = 0;
     // points the frame already holds are not searched again (src/Tracking.cc:1708-1728)
     for (MapPoint*& pMP : F.mvpMapPoints) {

@@ -51,12 +51,20 @@ public:
 
     bool HostOnly() const { return mpMatcher == nullptr; }
     // inspection (tests / bench): what the last Flush sent
-    struct FlushStats { int rows = 0, records = 0, keyframes = 0; };
+    // (rows, records, keyframes: as ever.  The facts the covisibility and culling counts read beyond them (host/Covisibility.h):
+    // record_features the records whose feature index was sent, point_nobs the points whose Observations() was, keyframe_features
+    // the keyframes whose level / far bytes and camera-1 count were.  Flush's return value stays the sum of the first three.)
+    struct FlushStats { int rows = 0, records = 0, keyframes = 0, record_features = 0, point_nobs = 0, keyframe_features = 0; };
     FlushStats LastFlush() const { return mLastFlush; }
+    // inspection: orbm_debug_last_covisibility of the device map (all zero for a host-only map)
+    void LastCovisibility(int out4[4]) const;
 
 private:
     friend void UpdateLocalMap(ResidentMap&, Frame&, std::vector<KeyFrame*>&, std::vector<MapPoint*>&, KeyFrame*&);
     friend int SearchLocalPoints(ORBmatcher&, ResidentMap&, Frame&, std::vector<MapPoint*>&, float, int*);
+    friend void CovisibilityCounts(ResidentMap&, const std::vector<KeyFrame*>&, std::vector<std::map<KeyFrame*, int> >&,
+                                   std::vector<std::map<KeyFrame*, int> >&);
+    friend void KeyFrameCulling(ResidentMap&, KeyFrame*, bool);
 
     struct PointEntry { int slot; std::map<KeyFrame*, int> records; };   // the record slot of each observation the mirror holds
     int SlotOf(MapPoint* pMP);      // assigned on first sight; -1 when the map is full (reported)
@@ -64,6 +72,14 @@ private:
     bool EnsureDevice();
     int Vote(const std::vector<int32_t>& frame_points, std::vector<int32_t>& votes);
     int LocalPoints(const std::vector<int32_t>& local_kfs, std::vector<int32_t>& list);
+    // the slots of keyframes the map has been told of (one it has not is read now, as a Touch would have it); false after a failure
+    bool SlotsOfSent(const std::vector<KeyFrame*>& vpKFs, size_t begin, size_t end, std::vector<int32_t>& slots);
+    int Covisibility(const std::vector<int32_t>& kfs, std::vector<int32_t>& first, std::vector<orbm_covis_entry>& entries);
+    int CullingCounts(const std::vector<int32_t>& kfs, bool mono, std::vector<int32_t>& counts);
+
+    // Everything that touches the device object or the slot tables runs under this: Flush, Audit, the calls of the tracking thread and
+    // those of the LocalMapping / LoopClosing threads (an orbm_map is bound to one handle, and one call uses it at a time).
+    std::recursive_mutex mMutexMap;
 
     ORBmatcher* mpMatcher;
     Capacity mCap;
@@ -86,6 +102,8 @@ private:
     std::vector<uint8_t> mvFlags, mvKeyFrameBad, mvKeyFrameSent;
     std::vector<orbm_obs> mvRecords;
     std::vector<int32_t> mvKeyFrameRows, mvKeyFrameCount;   // mvKeyFrameRows[slot * features_per_keyframe + f]
+    std::vector<int32_t> mvRecordFeature, mvPointNObs, mvKeyFrameNCam1;   // per record, per point slot, per keyframe slot
+    std::vector<uint8_t> mvKeyFrameFeatures;                // [slot * features_per_keyframe + f]: level | ORBM_FEATURE_FAR
     // the last point list (slots), what SearchLocalPoints searches
     std::vector<int32_t> mvList;
     FlushStats mLastFlush;

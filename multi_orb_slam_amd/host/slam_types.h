@@ -9,6 +9,7 @@
 // that build (-fsyntax-only, reference headers used in place) to zero errors on every CPU run.
 #pragma once
 #ifndef MORB_USE_REFERENCE_TYPES
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <map>
@@ -86,6 +87,13 @@ public:
         mObservations.erase(pKF); nObs--;
         if (mpRefKF == pKF) mpRefKF = mObservations.empty() ? nullptr : mObservations.begin()->first;
     }
+
+    // members host/Covisibility.cc and its driver read (include/MapPoint.h; src/MapPoint.cc:138-209): the camera-1 observations -- here
+    // computed from mObservations by the rule AddObservation files them under (idx < pKF->N) --, and the reference's EraseObservation
+    // as KeyFrame::SetBadFlag needs it: the counter drops by 2 for a stereo feature, and a point left with two observations or fewer
+    // goes bad and lets go of every keyframe that holds it (MapPoint::SetBadFlag).  Both are defined behind KeyFrame.
+    std::map<KeyFrame*, size_t> GetObservations_cam1();
+    void EraseObservationOfBadKeyFrame(KeyFrame* pKF);
 
     // members host/GlobalBA.cc writes when the adjustment belongs to a loop (include/MapPoint.h: mPosGBA, mnBAGlobalForKF)
     cv::Mat mPosGBA;
@@ -278,9 +286,80 @@ public:
     static std::vector<KeyFrame*> FirstN(const std::vector<KeyFrame*>& v, int N) {   // src/KeyFrame.cc GetBestCovisibilityKeyFrames
         return (int)v.size() < N ? v : std::vector<KeyFrame*>(v.begin(), v.begin() + N);
     }
+
+    // members host/Covisibility.cc and its driver read or write (include/KeyFrame.h; src/KeyFrame.cc:176-263, :486-668, :670-700,
+    // :760-886): the weights of the covisibility graph and what keeps them ordered, the rest of UpdateConnections' state, and
+    // SetBadFlag without the re-parenting of the children (the spanning tree is not what the culling reads) and without the map and
+    // the keyframe database.
+    float mThDepth = 0;
+    bool mbFirstConnection = true, mbNotErase = false, mbToBeErased = false;
+    std::map<KeyFrame*, int> mConnectedKeyFrameWeights;
+    std::vector<int> mvOrderedWeights;
+    static void OrderByWeight(const std::map<KeyFrame*, int>& weights, std::vector<KeyFrame*>& kfs, std::vector<int>& ws) {
+        std::vector<std::pair<int, KeyFrame*> > vPairs;   // src/KeyFrame.cc:226-241: ascending sort, then pushed to the front
+        for (const auto& kv : weights) vPairs.push_back(std::make_pair(kv.second, kv.first));
+        std::sort(vPairs.begin(), vPairs.end());
+        kfs.clear(); ws.clear();
+        for (size_t i = vPairs.size(); i-- > 0;) { kfs.push_back(vPairs[i].second); ws.push_back(vPairs[i].first); }
+    }
+    void UpdateBestCovisibles() { OrderByWeight(mConnectedKeyFrameWeights, mvpOrderedConnectedKeyFrames, mvOrderedWeights); }
+    void UpdateBestCovisibles_cam1() { OrderByWeight(mConnectedKeyFrameWeights_cam1, mvpOrderedConnectedKeyFrames_cam1, mvOrderedWeights_cam1); }
+    void AddConnection(KeyFrame* pKF, const int& weight) {
+        LogCall("AddConnection", mnId, pKF->mnId);
+        auto it = mConnectedKeyFrameWeights.find(pKF);
+        if (it != mConnectedKeyFrameWeights.end() && it->second == weight) return;
+        mConnectedKeyFrameWeights[pKF] = weight;
+        UpdateBestCovisibles();
+    }
+    void AddConnection_cam1(KeyFrame* pKF, const int& weight) {
+        LogCall("AddConnection_cam1", mnId, pKF->mnId);
+        auto it = mConnectedKeyFrameWeights_cam1.find(pKF);
+        if (it != mConnectedKeyFrameWeights_cam1.end() && it->second == weight) return;
+        mConnectedKeyFrameWeights_cam1[pKF] = weight;
+        UpdateBestCovisibles_cam1();
+    }
+    void EraseConnection(KeyFrame* pKF) { if (mConnectedKeyFrameWeights.erase(pKF)) UpdateBestCovisibles(); }
+    void AddChild(KeyFrame* pKF) { mspChildrens.insert(pKF); }
+    void EraseChild(KeyFrame* pKF) { mspChildrens.erase(pKF); }
+    void SetNotErase() { mbNotErase = true; }
+    void SetBadFlag() {
+        LogCall("SetBadFlag", mnId);
+        if (mnId == 0) return;
+        if (mbNotErase) { mbToBeErased = true; return; }
+        for (auto& kv : mConnectedKeyFrameWeights) kv.first->EraseConnection(this);
+        for (size_t i = 0; i < mvpMapPoints.size(); i++)
+            if (mvpMapPoints[i]) mvpMapPoints[i]->EraseObservationOfBadKeyFrame(this);
+        mConnectedKeyFrameWeights.clear();
+        mvpOrderedConnectedKeyFrames.clear();
+        mvpOrderedConnectedKeyFrames_cam1.clear();
+        if (mpParent) mpParent->EraseChild(this);
+        mbBad = true;
+    }
 };
 
 inline void MapPoint::EraseObservation(KeyFrame* pKF) { LogCall("EraseObservation", mnId, pKF->mnId); EraseObservationImpl(pKF); }
+
+inline std::map<KeyFrame*, size_t> MapPoint::GetObservations_cam1() {
+    std::map<KeyFrame*, size_t> cam1;
+    for (const auto& ob : mObservations)
+        if ((int)ob.second < ob.first->N) cam1.insert(ob);
+    return cam1;
+}
+
+inline void MapPoint::EraseObservationOfBadKeyFrame(KeyFrame* pKF) {   // src/MapPoint.cc:167-199, then :225-247 when it goes bad
+    auto it = mObservations.find(pKF);
+    if (it == mObservations.end()) return;
+    const size_t idx = it->second;
+    nObs -= (idx < pKF->mvuRight_total.size() && pKF->mvuRight_total[idx] >= 0) ? 2 : 1;
+    mObservations.erase(it);
+    if (mpRefKF == pKF) mpRefKF = mObservations.empty() ? nullptr : mObservations.begin()->first;
+    if (nObs > 2) return;
+    mbBad = true;
+    const std::map<KeyFrame*, size_t> obs = mObservations;
+    mObservations.clear();
+    for (const auto& ob : obs)
+        if (ob.second < ob.first->mvpMapPoints.size()) ob.first->mvpMapPoints[ob.second] = nullptr;   // EraseMapPointMatch(idx)
+}
 
 // Map: what host/LocalBA.cc takes of it (include/Map.h).  The stand-in's mutex is a std::mutex that records when it is taken and given back.
 struct LoggedMutex {

@@ -4,7 +4,7 @@ import weakref
 import numpy as np
 from . import _lib
 from ._lib import KP_DTYPE, QUERY_DTYPE, POINT_DTYPE, TRACK_DTYPE, REFRESH_DTYPE, CamFeatures, FrameDesc, check, ptr
-from ._lib import OBS_DTYPE, MAX_POINTS  # noqa: F401
+from ._lib import OBS_DTYPE, MAX_POINTS, COVIS_DTYPE  # noqa: F401
 from ._lib import POSE_PROBLEM_DTYPE, POSE_RESULT_DTYPE, POSE_CAM0, POSE_ALL_CAMS, POSE_ORDER_INDEX, POSE_ORDER_DEVICE  # noqa: F401
 from ._lib import SIM3_PROBLEM_DTYPE, SIM3_HYP_DTYPE, SIM3_WALK_DTYPE, SIM3_MATH_LIBM, SIM3_MATH_DEVICE  # noqa: F401
 from ._lib import SIM3OPT_PROBLEM_DTYPE, SIM3OPT_RESULT_DTYPE  # noqa: F401
@@ -741,6 +741,41 @@ def local_map_points_host(kf_rows, kf_count, point_flags, local_kfs, list_cap=MA
     return out[:n.value].copy()
 
 
+def _split_covisibility(first, entries):
+    return [entries[first[j]:first[j + 1]].copy() for j in range(len(first) - 1)]
+
+
+def local_map_covisibility_host(obs, obs_feature, point_flags, kf_rows, kf_count, kf_n_cam1, kfs):
+    """orbm_local_map_covisibility_host: KFcounter / KFcounter_cam1 of KeyFrame::UpdateConnections (reference src/KeyFrame.cc:512-552) on
+    plain arrays: obs OBS_DTYPE records with obs_feature their feature indices, kf_rows n_kfs x stride point slots, kf_n_cam1 the
+    camera-1 feature count of every keyframe -> one COVIS_DTYPE array per listed keyframe (all > 0, ascending keyframe slot)."""
+    obs = np.ascontiguousarray(obs, OBS_DTYPE); of = _i32(obs_feature); fl = np.ascontiguousarray(point_flags, np.uint8)
+    rows = np.ascontiguousarray(kf_rows, np.int32); assert rows.ndim == 2
+    cnt = _i32(kf_count); nc = _i32(kf_n_cam1); ks = _i32(kfs)
+    assert len(of) == len(obs) and len(cnt) == rows.shape[0] == len(nc)
+    first = np.zeros(len(ks) + 1, np.int32)
+    cap = max(len(ks) * rows.shape[0], 1)   # a keyframe has at most one entry per other keyframe
+    ent = np.zeros(cap, COVIS_DTYPE)
+    check(_lib.lib().orbm_local_map_covisibility_host(ptr(obs), ptr(of), len(obs), ptr(fl), len(fl), ptr(rows), ptr(cnt), ptr(nc),
+                                                      rows.shape[0], max(rows.shape[1], 1), ptr(ks), len(ks), ptr(first), ptr(ent), cap))
+    return _split_covisibility(first, ent)
+
+
+def local_map_culling_host(obs, obs_feature, point_flags, point_n_obs, kf_rows, kf_count, kf_feature_bytes, kfs, mono=False):
+    """orbm_local_map_culling_host: nMPs and nRedundantObservations of LocalMapping::KeyFrameCulling (reference src/LocalMapping.cc:990-1032)
+    on plain arrays: kf_feature_bytes n_kfs x stride (bits 0-4 the level, bit 7 far), point_n_obs MapPoint::Observations() of every
+    point slot -> counts[len(kfs), 2]."""
+    obs = np.ascontiguousarray(obs, OBS_DTYPE); of = _i32(obs_feature); fl = np.ascontiguousarray(point_flags, np.uint8); no = _i32(point_n_obs)
+    rows = np.ascontiguousarray(kf_rows, np.int32); fb = np.ascontiguousarray(kf_feature_bytes, np.uint8)
+    assert rows.ndim == 2 and fb.shape == rows.shape and len(no) == len(fl) and len(of) == len(obs)
+    cnt = _i32(kf_count); ks = _i32(kfs)
+    assert len(cnt) == rows.shape[0]
+    out = np.zeros((max(len(ks), 1), 2), np.int32)
+    check(_lib.lib().orbm_local_map_culling_host(ptr(obs), ptr(of), len(obs), ptr(fl), ptr(no), len(fl), ptr(rows), ptr(cnt), ptr(fb),
+                                                 rows.shape[0], max(rows.shape[1], 1), ptr(ks), len(ks), int(bool(mono)), ptr(out)))
+    return out[:len(ks)]
+
+
 class ResidentMap:
     """A map resident in HBM under stable slots (orbm_map): one slot per map point (a POINT_DTYPE row + a flag byte, bit 0 = bad),
     per keyframe (mvpMapPoints as point slots) and per observation (OBS_DTYPE), and Tracking::UpdateLocalMap's data-parallel parts
@@ -817,6 +852,52 @@ class ResidentMap:
         points it kept) (orbm_debug_last_local_map)."""
         out = (C.c_int * 4)()
         check(_lib.lib().orbm_debug_last_local_map(self._h, out))
+        return tuple(out)
+
+    def write_observation_features(self, slots, feature):
+        """The feature index of each listed record in its keyframe (orbm_map_write_observation_features)."""
+        slots = _i32(slots); ft = _i32(feature)
+        assert len(ft) == len(slots)
+        check(_lib.lib().orbm_map_write_observation_features(self._m._h, self._h, ptr(slots), len(slots), ptr(ft)))
+
+    def write_keyframe_features(self, kf, feature_bytes, n_cam1):
+        """One byte per feature of keyframe slot kf (bits 0-4 the level, bit 7 far) and its camera-1 feature count
+        (orbm_map_write_keyframe_features)."""
+        fb = np.ascontiguousarray(feature_bytes, np.uint8).reshape(-1)
+        check(_lib.lib().orbm_map_write_keyframe_features(self._m._h, self._h, int(kf), ptr(fb), len(fb), int(n_cam1)))
+
+    def write_point_nobs(self, slots, n_obs):
+        """MapPoint::Observations() of each listed point slot (orbm_map_write_point_nobs)."""
+        slots = _i32(slots); no = _i32(n_obs)
+        assert len(no) == len(slots)
+        check(_lib.lib().orbm_map_write_point_nobs(self._m._h, self._h, ptr(slots), len(slots), ptr(no)))
+
+    def covisibility(self, kfs, entries_cap=None):
+        """orbm_map_covisibility -> one COVIS_DTYPE array per listed keyframe (all > 0, ascending keyframe slot).  entries_cap None:
+        room for every keyframe of the map per listed one, up to 2^20 entries; a call that reports ORB_E_CAPACITY beyond that is
+        repeated once with the room it asked for."""
+        ks = _i32(kfs); first = np.zeros(len(ks) + 1, np.int32)
+        cap = min(len(ks) * max(self.keyframes, 1), 1 << 20) if entries_cap is None else int(entries_cap)
+        for _ in range(2):
+            ent = np.zeros(max(cap, 1), COVIS_DTYPE)
+            rc = _lib.lib().orbm_map_covisibility(self._m._h, self._h, ptr(ks), len(ks), ptr(first), ptr(ent), cap)
+            if rc != _lib.ORB_E_CAPACITY or entries_cap is not None or int(first[len(ks)]) <= cap:
+                break
+            cap = int(first[len(ks)])
+        check(rc)
+        return _split_covisibility(first, ent)
+
+    def culling_counts(self, kfs, mono=False):
+        """orbm_map_culling_counts -> counts[len(kfs), 2]: nMPs, nRedundantObservations."""
+        ks = _i32(kfs); out = np.zeros((max(len(ks), 1), 2), np.int32)
+        check(_lib.lib().orbm_map_culling_counts(self._m._h, self._h, ptr(ks), len(ks), int(bool(mono)), ptr(out)))
+        return out[:len(ks)]
+
+    def last_covisibility(self):
+        """(1 if the last covisibility / culling call ran on the device, 1 if it rebuilt the point -> records index, records indexed,
+        keyframes processed) (orbm_debug_last_covisibility)."""
+        out = (C.c_int * 4)()
+        check(_lib.lib().orbm_debug_last_covisibility(self._h, out))
         return tuple(out)
 
     def close(self):
