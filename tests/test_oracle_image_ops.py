@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import oracle
 from multi_orb_slam_amd import synth
+from extractor_boundary_worlds import plain_resize, plain_scores, resize_taps
 
 RING = [(0, 3), (1, 3), (2, 2), (3, 1), (3, 0), (3, -1), (2, -2), (1, -3), (0, -3), (-1, -3), (-2, -2), (-3, -1), (-3, 0),
         (-3, 1), (-2, 2), (-1, 3)]
@@ -63,6 +64,7 @@ def test_fast_score_equals_threshold_free_definition_on_random_images():
     what lets the GPU serve both thresholds from one score map."""
     rng = synth.hash32(np.arange(64 * 64, dtype=np.uint64) + np.uint64(5))
     img = ((rng % 64) * 4).astype(np.uint8).reshape(64, 64)
+    S = plain_scores(img)   # (the restatement shared with the boundary worlds)
     n = 0
     for y in range(3, 61):
         for x in range(3, 61):
@@ -71,6 +73,7 @@ def test_fast_score_equals_threshold_free_definition_on_random_images():
             sp = max(min(d[(k + i) % 16] for i in range(9)) for k in range(16))
             sm = max(min(-d[(k + i) % 16] for i in range(9)) for k in range(16))
             raw = max(sp, sm) - 1
+            assert raw == S[y, x]
             for t in (7, 20, 50):
                 is_c = oracle.is_corner(img, x, y, t)
                 assert is_c == (raw >= t)
@@ -206,17 +209,7 @@ def test_resize_matches_fixed_point_formula():
     dw, dh = 53, 40
     got = oracle.resize_linear(img, dw, dh)
 
-    def coefs(dn, sn):
-        scale = 1.0 / (dn / sn)
-        out = []
-        for d in range(dn):
-            f = np.float32((d + 0.5) * scale - 0.5)
-            s = int(np.floor(f)); f = np.float32(f - np.float32(s))
-            out.append((s, int(np.rint(np.float32((np.float32(1) - f) * np.float32(2048)))),
-                        int(np.rint(np.float32(f * np.float32(2048))))))
-        return out
-
-    cx, cy = coefs(dw, 64), coefs(dh, 48)
+    cx, cy = resize_taps(dw, 64), resize_taps(dh, 48)   # (the restatement shared with the boundary worlds)
     for y in (0, 1, 17, dh - 1):
         for x in (0, 5, 31, dw - 1):
             sx, a0, a1 = cx[x]; sy, b0, b1 = cy[y]
@@ -224,6 +217,7 @@ def test_resize_matches_fixed_point_formula():
             h1 = int(img[min(sy + 1, 47), sx]) * a0 + int(img[min(sy + 1, 47), min(sx + 1, 63)]) * a1
             exp = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2
             assert got[y, x] == exp
+    assert np.array_equal(got, plain_resize(img, dw, dh))
 
 
 def test_resize_two_level_ramp():
