@@ -82,6 +82,12 @@ int orbm_debug_last_local_map(const orbm_map* map, int* out4);
  * host routines over the mirror), 1 if this call rebuilt the point -> records index (only after an orbm_map_write_observations),
  * records indexed (the record high-water mark), keyframes processed} (inspection only) */
 int orbm_debug_last_covisibility(const orbm_map* map, int* out4);
+/* What the last orbm_map_correct_sim3 / orbm_map_correct_rigid on the map did: {1 if it ran on the device (0: MORB_HOST_RESOLVE=1, the
+ * host routines over the mirror), candidates (row entries of the listed keyframes / point slots looked at), points kept (Sim3) or
+ * changed (rigid: status != 0), keyframes (listed / in the table)} (inspection only) */
+int orbm_debug_last_correction(const orbm_map* map, int* out4);
+/* Rows of the listed point slots as HBM holds them now -- NOT the mirror (inspection only: one copy of the span the slots cover). */
+int orbm_debug_map_read_points(orbm_matcher* m, orbm_map* map, const int32_t* slots, int n, orbm_point* rows);
 /* Where the work of the last orbm_pnp_ransac went: {problems on the device, problems through the host routine because they have more
  * than ORBM_PNP_CAP correspondences, records refined on the device, records refined by the host routine because they lie beyond
  * ORBM_PNP_MAX_RECORDS of a device problem} (inspection only) */

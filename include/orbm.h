@@ -428,6 +428,70 @@ int orbm_local_map_culling_host(const orbm_obs* obs, const int32_t* obs_feature,
                                 const uint8_t* kf_feature_bytes, int n_kfs, int stride, const int32_t* kfs, int n, int mono,
                                 int32_t* counts_out);
 
+/* -- loop correction over the resident map: LoopClosing::CorrectLoop's point pass and the update after global BA ----------
+ * The two passes of the LoopClosing thread that move map points one cv::Mat at a time (reference src/LoopClosing.cc:678-722 and
+ * :953-989), in place over the same resident map: after either only the 12 position bytes of a corrected point's row differ, so the
+ * rows are changed where they lie, in HBM and in the mirror, and no row crosses the bus.  Everything here is additive: what the calls
+ * above read and return is untouched.  The map learns one more fact per point: the keyframe slot of mpRefKF (never written: -1).
+ * A Sim3 is 8 doubles in the layout of orbm_eg_problem::vertex: quaternion x y z w, translation, scale.
+ * Every device call runs on the handle's stream and synchronises it once.  All arithmetic is + - * / in IEEE double and float without
+ * contraction, the same statements on the device and in the host routines; what a NaN, infinite or subnormal INPUT gives is not
+ * specified bit for bit. */
+typedef struct { int32_t point, position; } orbm_correct_entry;   /* a corrected point's slot and the position in kfs of its claimant */
+int orbm_map_points(const orbm_map* map);   /* point high-water mark: one past the last point slot ever written */
+/* The position field alone of point slots slots[0 .. n): pos3[3 i ..] into slot slots[i], HBM and mirror.  A slot named twice takes its
+ * last entry.  A slot outside the capacity: ORB_E_CAPACITY, nothing written.  For callers that already hold the new positions
+ * (orbm_eg_result::point_f, SetWorldPos(mPosGBA)). */
+int orbm_map_write_positions(orbm_matcher* m, orbm_map* map, const int32_t* slots, int n, const float* pos3);
+/* ref_kf[i], the keyframe slot of GetReferenceKeyFrame() (any value; one outside the keyframes given to orbm_map_correct_rigid reads as
+ * "not corrected"), into point slot slots[i].  Shape and errors of orbm_map_write_point_nobs. */
+int orbm_map_write_point_ref(orbm_matcher* m, orbm_map* map, const int32_t* slots, int n, const int32_t* ref_kf);
+/* CorrectLoop's step 4.2 (:678-710) and the poses of step 4.3 (:714-720).  kfs[0 .. n), n <= ORBM_MAP_MAX_LOCAL, are keyframe slots in
+ * CorrectedSim3's iteration order, sim3_before[8 j ..] = NonCorrectedSim3 and sim3_after[8 j ..] = CorrectedSim3 of kfs[j]; already[0 ..
+ * n_already) are the point slots the reference would skip at :696 (negative entries are ignored).
+ * The candidates are the row entries of the listed keyframes in the order (position in kfs, feature index), as in
+ * orbm_map_local_points.  A candidate is kept if its slot is not negative, the point is not bad, the point is not in `already` and no
+ * earlier candidate holds the same point.  A kept candidate at position j moves its point (:701-705):
+ *   P = (double)pos;  w = after[j].inverse().map(before[j].map(P));  pos = (float)w, component by component
+ * (Sim3::map and Sim3::inverse of Thirdparty/g2o/g2o/types/sim3.h; the one definition the essential graph's step 7 runs.)
+ * entries[i] = {point slot, j} and pos_out[3 i ..] the new position, in candidate order; *n_out the number kept; the position field of
+ * every kept point's row is the new one, in HBM and in the mirror.  Tiw_out[16 j ..] is the float 4x4 SetPose receives (:714-720):
+ * toRotationMatrix, t * (1./s), toCvSE3 of after[j] (computed on the host).  entries, pos_out (cap entries) and Tiw_out (n) may not be NULL
+ * unless cap / n is 0.
+ * More than cap kept: ORB_E_CAPACITY, *n_out (and the error text) the number needed, and NO row and no mirror entry has changed (the
+ * reference has no such limit; a caller repeats the call with room).  The list is not bound by ORBM_MAX_POINTS.  Every call starts
+ * unmarked, and the list orbm_map_local_points left for orbm_map_search_local_points is not disturbed. */
+int orbm_map_correct_sim3(orbm_matcher* m, orbm_map* map, const int32_t* kfs, int n, const double* sim3_before, const double* sim3_after,
+                          const int32_t* already, int n_already, orbm_correct_entry* entries, float* pos_out, int cap, int* n_out,
+                          float* Tiw_out);
+/* RunGlobalBundleAdjustment's step 2 (:953-989) over point slots slots[0 .. n), all distinct (a slot named twice: ORB_E_ARG);
+ * slots == NULL: every point slot below the high-water mark, and n must be orbm_map_points(map).  kf_corrected[r] != 0 says
+ * mnBAGlobalForKF == nLoopKF of keyframe slot r < n_kfs; Tcw_before[12 r ..] and Twc_after[12 r ..] are rows 0-2 of its mTcwBefGBA and of
+ * its GetPoseInverse(); gba_slots[0 .. n_gba) are the points with mnBAGlobalForKF == nLoopKF and gba_pos[3 g ..] their mPosGBA (a slot
+ * named twice takes its last entry; negative entries are ignored).  Per point, in this order:
+ *   1. bad: untouched, status 0
+ *   2. listed in gba_slots: the position becomes the given 12 bytes, status 1
+ *   3. r = ref_kf[slot]; r < 0, r >= n_kfs or !kf_corrected[r]: untouched, status 0
+ *   4. Xc = Rcw_before[r]*P + tcw_before[r], pos = Rwc_after[r]*Xc + twc_after[r], each one cv::gemm on its small path with
+ *      alpha = beta = 1 (float products and sums left to right, one double step), status 2
+ * status (n bytes) and pos_out (3 n floats: the position the row holds after the call) may be NULL.  Rows and mirror change in place. */
+int orbm_map_correct_rigid(orbm_matcher* m, orbm_map* map, const int32_t* slots, int n, const uint8_t* kf_corrected,
+                           const float* Tcw_before, const float* Twc_after, int n_kfs, const int32_t* gba_slots, const float* gba_pos,
+                           int n_gba, uint8_t* status, float* pos_out);
+/* Host, on plain arrays, no device and no handle: the fallback (MORB_HOST_RESOLVE=1, over the mirror), the route of a map without a
+ * device and the cross-check of the two calls above.  pos[pos_stride * slot + k], k < 3, is the position of a point (pos_stride 3: a
+ * packed array; 17: the rows of orbm_point), read and written in place; kf_rows / kf_count as in orbm_local_map_points_host.  A row
+ * entry, a listed slot or a keyframe outside the counts given: ORB_E_ARG.  The Sim3 routine counts first: beyond cap it returns
+ * ORB_E_CAPACITY with *n_out the number needed and nothing changed. */
+int orbm_local_map_correct_sim3_host(const int32_t* kf_rows, const int32_t* kf_count, int n_kfs, int stride, const uint8_t* point_flags,
+                                     float* pos, int pos_stride, int n_points, const int32_t* kfs, int n, const double* sim3_before,
+                                     const double* sim3_after, const int32_t* already, int n_already, orbm_correct_entry* entries,
+                                     float* pos_out, int cap, int* n_out, float* Tiw_out);
+int orbm_local_map_correct_rigid_host(float* pos, int pos_stride, const uint8_t* point_flags, const int32_t* point_ref, int n_points,
+                                      const int32_t* slots, int n, const uint8_t* kf_corrected, const float* Tcw_before,
+                                      const float* Twc_after, int n_kfs, const int32_t* gba_slots, const float* gba_pos, int n_gba,
+                                      uint8_t* status, float* pos_out);
+
 /* -- map-point refresh: distinctive descriptor, normal, depth --------------------------------------------------
  * The producer of what an orbm_point row holds beyond the position: MapPoint::ComputeDistinctiveDescriptors (reference
  * src/MapPoint.cc:325-438) and MapPoint::UpdateNormalAndDepth (:480-528), which the reference calls for every point of every

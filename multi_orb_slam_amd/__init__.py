@@ -13,6 +13,8 @@ from .matcher import ResidentMap, local_map_vote_host, local_map_points_host  # 
 from ._lib import OBS_DTYPE, MAX_POINTS, MAP_MAX_KEYFRAMES, MAP_MAX_FEATURES, MAP_MAX_LOCAL, POINT_BAD  # noqa: F401
 from .matcher import local_map_covisibility_host, local_map_culling_host  # noqa: F401
 from ._lib import COVIS_DTYPE, FEATURE_LEVEL_MASK, FEATURE_FAR  # noqa: F401
+from .matcher import local_map_correct_sim3_host, local_map_correct_rigid_host  # noqa: F401
+from ._lib import CORRECT_DTYPE  # noqa: F401
 from .matcher import PoseProblem, pose_optimize_host, pose_sincos  # noqa: F401
 from ._lib import POSE_PROBLEM_DTYPE, POSE_RESULT_DTYPE, POSE_CAM0, POSE_ALL_CAMS, POSE_ORDER_INDEX, POSE_ORDER_DEVICE, POSE_CAP  # noqa: F401
 from .matcher import Sim3Problem, sim3_ransac_host, sim3_walk, sim3_iterations, sim3_atan2  # noqa: F401

@@ -30,6 +30,7 @@ assert OBS_DTYPE.itemsize == 8
 MAX_POINTS, MAP_MAX_KEYFRAMES, MAP_MAX_FEATURES, MAP_MAX_LOCAL, POINT_BAD = 65535, 16384, 8192, 4096, 1
 COVIS_DTYPE = np.dtype([("keyframe", "<i4"), ("all", "<i4"), ("cam1", "<i4")])   # orbm_covis_entry
 assert COVIS_DTYPE.itemsize == 12
+CORRECT_DTYPE = np.dtype([("point", "<i4"), ("position", "<i4")])   # orbm_correct_entry
 FEATURE_LEVEL_MASK, FEATURE_FAR = 0x1f, 0x80
 POSE_PROBLEM_DTYPE = np.dtype([("Tcw", "<f4", (16,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("bf", "<f4"),
                                ("Rcam12", "<f4", (9,)), ("tcam12", "<f4", (3,)), ("inv_level_sigma2", "<f4", (32,)),
@@ -354,6 +355,15 @@ def lib():
     L.orbm_local_map_covisibility_host.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, vp, i32]
     L.orbm_local_map_culling_host.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, i32, vp]
     L.orbm_debug_last_covisibility.argtypes = [vp, vp]
+    L.orbm_map_points.argtypes = [vp]
+    L.orbm_map_write_positions.argtypes = [vp, vp, vp, i32, vp]
+    L.orbm_map_write_point_ref.argtypes = [vp, vp, vp, i32, vp]
+    L.orbm_map_correct_sim3.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
+    L.orbm_map_correct_rigid.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
+    L.orbm_local_map_correct_sim3_host.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
+    L.orbm_local_map_correct_rigid_host.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
+    L.orbm_debug_last_correction.argtypes = [vp, vp]
+    L.orbm_debug_map_read_points.argtypes = [vp, vp, vp, i32, vp]
     L.orbm_refresh_points.argtypes = [vp, vp, vp]
     L.orbm_refresh_points_host.argtypes = [vp, vp]
     L.orbm_debug_last_refresh.argtypes = [vp, vp]

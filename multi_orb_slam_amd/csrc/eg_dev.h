@@ -220,11 +220,7 @@ __host__ __device__ __forceinline__ void eg_correct_point(const double* vertex0,
     Sim3Quat Srw, Siw, Swr;
     if (ref < 0) { eg_identity(Srw); eg_identity(Swr); }
     else { eg_load(vertex0 + 8 * (size_t)ref, Srw); eg_load(final_est + 8 * (size_t)ref, Siw); sim3_inverse(Siw, Swr); }
-    const double p[3] = {(double)P[0], (double)P[1], (double)P[2]};   // Converter::toVector3d
-    double a[3], b[3];
-    sim3_map(Srw, p, a);
-    sim3_map(Swr, a, b);
-    out[0] = x86_nan((float)b[0]); out[1] = x86_nan((float)b[1]); out[2] = x86_nan((float)b[2]);   // Converter::toCvMat
+    sim3_correct_point(Srw, Swr, P, out);
 }
 // step 6: eigR = rotation().toRotationMatrix(), eigt *= (1./s), Converter::toCvSE3
 __host__ __device__ __forceinline__ void eg_Tiw(const double* est8, float* M) {

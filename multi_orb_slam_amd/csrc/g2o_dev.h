@@ -298,6 +298,15 @@ __host__ __device__ inline void sim3_mul(const Sim3Quat& a, const Sim3Quat& b, S
     out.t[0] = a.s * r[0] + a.t[0]; out.t[1] = a.s * r[1] + a.t[1]; out.t[2] = a.s * r[2] + a.t[2];
     out.s = a.s * b.s;
 }
+// Swi.map(Siw.map(P)) on a cv::Mat point: Converter::toVector3d, the two maps, Converter::toCvMat.  Step 7 of the essential graph
+// (eg_dev.h eg_correct_point) and LoopClosing::CorrectLoop (src/LoopClosing.cc:701-705; mapcorrect_dev.h) are this one body.
+__host__ __device__ inline void sim3_correct_point(const Sim3Quat& Siw, const Sim3Quat& Swi, const float* P, float* out) {
+    const double p[3] = {(double)P[0], (double)P[1], (double)P[2]};   // Converter::toVector3d
+    double a[3], b[3];
+    sim3_map(Siw, p, a);
+    sim3_map(Swi, a, b);
+    out[0] = x86_nan((float)b[0]); out[1] = x86_nan((float)b[1]); out[2] = x86_nan((float)b[2]);   // Converter::toCvMat
+}
 // Sim3(const Vector7d& update) (:70-142), all four branches of fabs(sigma) < eps x theta < eps.  order: where sin, cos and exp come
 // from (ORBM_POSE_ORDER_INDEX: the C library; otherwise pose_sincos and pose_exp).  Returns the branch taken.
 __host__ __device__ inline int sim3_exp(const double* update, int order, Sim3Quat& T) {

@@ -8,10 +8,14 @@
 //   orbm_map_covisibility         KFcounter / KFcounter_cam1 of KeyFrame::UpdateConnections (src/KeyFrame.cc:512-552): k_map_covis
 //   orbm_map_culling_counts       nMPs / nRedundantObservations of LocalMapping::KeyFrameCulling (src/LocalMapping.cc:990-1032): k_map_cull
 //   both read the chain from a point to its live records, which k_map_chain builds when a record write has made it stale
+// and the two passes of LoopClosing that move map points, in place over the same map (kernels: mapcorrect_dev.h):
+//   orbm_map_correct_sim3         CorrectLoop's step 4.2 (src/LoopClosing.cc:678-710): the ordered claim above, then k_map_correct_sim3
+//   orbm_map_correct_rigid        the update after global BA (:953-989): k_map_stamp_last, k_map_correct_rigid
 // The kernels are in localmap_dev.h.  The two host routines (orbm_local_map_vote_host, orbm_local_map_points_host) are the
 // reference's loops on plain arrays: the fallback under MORB_HOST_RESOLVE=1, over the mirror, and the cross-check of the tests.
 // K1, K2 and the marks are pointer logic over the covisibility graph and stay with the caller (host/LocalMap.cc).
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 #include <vector>
 
@@ -20,6 +24,7 @@
 #include "orb_common.h"
 #include "matcher_internal.h"
 #include "localmap_dev.h"
+#include "mapcorrect_dev.h"
 
 using namespace morb;
 
@@ -53,6 +58,14 @@ struct orbm_map {
     bool index_dirty = false;
     PinnedBuf<int32_t> h_span, h_counts; PinnedBuf<orbm_covis_entry> h_entries;
     int last_cov[4] = {0, 0, 0, 0};
+    // loop correction: the point's reference keyframe slot (-1: never written), the point high-water mark, the kept entries of a Sim3
+    // correction and what either correction leaves for the host (mapped)
+    DevBuf<int32_t> d_ref; std::vector<int32_t> h_ref;
+    int pt_hw = 0;
+    DevBuf<orbm_correct_entry> d_centries;
+    PinnedBuf<orbm_correct_entry> h_centries; PinnedBuf<float> h_cpos; PinnedBuf<uint8_t> h_cstatus;
+    std::vector<uint32_t> h_seen; uint32_t seen_epoch = 0;   // a listed slot of this call (host; the check that the slots are distinct)
+    int last_cor[4] = {0, 0, 0, 0};
 };
 
 namespace {
@@ -61,6 +74,7 @@ void release_all(orbm_map* p) {
     p->d_rows.release(); p->d_flags.release(); p->d_obs.release(); p->d_kf_rows.release(); p->d_kf_count.release();
     p->d_mult.release(); p->d_first.release(); p->d_mark.release(); p->d_votes.release(); p->d_block.release(); p->d_list.release();
     p->d_obs_feat.release(); p->d_nobs.release(); p->d_kf_ncam1.release(); p->d_kf_feat.release(); p->d_head.release(); p->d_next.release();
+    p->d_ref.release(); p->d_centries.release(); p->h_centries.release(); p->h_cpos.release(); p->h_cstatus.release();
     p->d_cursor.release(); p->h_span.release(); p->h_counts.release(); p->h_entries.release();
     p->d_total.release(); p->h_votes.release(); p->h_list.release(); p->h_total.release(); p->stage.release(); p->scr.h_track.release();
 }
@@ -151,7 +165,8 @@ int orbm_map_create(orbm_matcher* m, int kf_capacity, int point_capacity, int ob
         (rc = p->d_votes.reserve(nk)) || (rc = p->d_list.reserve(ORBM_MAX_POINTS)) || (rc = p->d_total.reserve(4)) ||
         (rc = p->h_votes.reserve(nk)) || (rc = p->h_list.reserve(ORBM_MAX_POINTS)) || (rc = p->h_total.reserve(4)) ||
         (rc = p->d_obs_feat.reserve(no)) || (rc = p->d_nobs.reserve(np)) || (rc = p->d_kf_ncam1.reserve(nk)) || (rc = p->d_kf_feat.reserve(nr)) ||
-        (rc = p->d_head.reserve(np)) || (rc = p->d_next.reserve(no)) || (rc = p->d_cursor.reserve(1))) {
+        (rc = p->d_head.reserve(np)) || (rc = p->d_next.reserve(no)) || (rc = p->d_cursor.reserve(1)) ||
+        (rc = p->d_ref.reserve(np))) {
         release_all(p); delete p;
         return rc;
     }
@@ -167,6 +182,7 @@ int orbm_map_create(orbm_matcher* m, int kf_capacity, int point_capacity, int ob
         hipMemsetAsync(p->d_obs_feat.p, 0, no * sizeof(int32_t), st) != hipSuccess || hipMemsetAsync(p->d_nobs.p, 0, np * sizeof(int32_t), st) != hipSuccess ||
         hipMemsetAsync(p->d_kf_ncam1.p, 0, nk * sizeof(int32_t), st) != hipSuccess || hipMemsetAsync(p->d_kf_feat.p, 0, nr, st) != hipSuccess ||
         hipMemsetAsync(p->d_head.p, 0xff, np * sizeof(int32_t), st) != hipSuccess ||
+        hipMemsetAsync(p->d_ref.p, 0xff, np * sizeof(int32_t), st) != hipSuccess ||
         hipMemsetAsync(p->d_next.p, 0xff, no * sizeof(int32_t), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
         morb::set_error("clearing the resident map failed");
         release_all(p); delete p;
@@ -178,6 +194,7 @@ int orbm_map_create(orbm_matcher* m, int kf_capacity, int point_capacity, int ob
     p->h_kf_rows.assign(nr, -1); p->h_kf_count.assign(nk, 0); p->h_kf_bad.assign(nk, 0);
     p->h_mark.assign((size_t)point_capacity, 0u);
     p->h_obs_feat.assign((size_t)obs_capacity, 0); p->h_nobs.assign((size_t)point_capacity, 0); p->h_kf_ncam1.assign(nk, 0); p->h_kf_feat.assign(nr, 0);
+    p->h_ref.assign((size_t)point_capacity, -1);
     *out = p;
     return ORB_OK;
 }
@@ -211,7 +228,10 @@ int orbm_map_write_points(orbm_matcher* m, orbm_map* p, const int32_t* slots, in
     static_assert(sizeof(orbm_point) == 68, "orbm_point is 17 words");
     const size_t off_rows = (size_t)n * 4, off_flags = off_rows + (size_t)n * sizeof(orbm_point);
     if ((rc = p->stage.reserve(off_flags + (size_t)n + 16))) return rc;
-    for (int i = 0; i < n; ++i) { p->h_rows[(size_t)slots[i]] = rows[i]; p->h_flags[(size_t)slots[i]] = flags ? flags[i] : 0; }
+    for (int i = 0; i < n; ++i) {
+        p->h_rows[(size_t)slots[i]] = rows[i]; p->h_flags[(size_t)slots[i]] = flags ? flags[i] : 0;
+        p->pt_hw = std::max(p->pt_hw, slots[i] + 1);
+    }
     // staged from the mirror: a slot named twice is staged twice with its last entry, so the order of the lanes does not matter
     memcpy(p->stage.p, slots, (size_t)n * 4);
     for (int i = 0; i < n; ++i) {
@@ -689,5 +709,364 @@ int orbm_map_culling_counts(orbm_matcher* m, orbm_map* p, const int32_t* kfs, in
     MORB_HIP(hipGetLastError());
     MORB_HIP(hipStreamSynchronize(m->stream));
     memcpy(counts_out, p->h_counts.p, (size_t)n * 2 * sizeof(int32_t));
+    return ORB_OK;
+}
+
+// ---- loop correction over the resident map (kernels: mapcorrect_dev.h)
+
+namespace {
+
+constexpr int POS_STRIDE_ROWS = (int)(sizeof(orbm_point) / sizeof(float));   // the mirror's rows as a strided array of positions
+static_assert(offsetof(orbm_point, pos) == 0 && sizeof(orbm_point) % sizeof(float) == 0, "a row begins with its position");
+
+inline size_t pad8(size_t n) { return (n + 7) & ~(size_t)7; }
+
+// The positions of the listed slots from the mirror into their rows in HBM (a slot named twice is staged twice with the same bytes).
+// Enqueues only: the caller synchronises.
+int put_positions(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n) {
+    if (n == 0) return ORB_OK;
+    int rc;
+    const size_t off_pos = pad8((size_t)n * 4);
+    if ((rc = p->stage.reserve(off_pos + (size_t)n * 12 + 16))) return rc;
+    memcpy(p->stage.p, slots, (size_t)n * 4);
+    for (int i = 0; i < n; ++i) memcpy(p->stage.p + off_pos + (size_t)i * 12, p->h_rows[(size_t)slots[i]].pos, 12);
+    p->stage.publish();
+    hipLaunchKernelGGL(k_map_put_positions, dim3(blocks_of((long long)n * 3)), dim3(MAP_BLOCK), 0, m->stream,
+                       (const float*)(p->stage.dp + off_pos), (const int32_t*)p->stage.dp, n, p->d_rows.p);
+    MORB_HIP(hipGetLastError());
+    return ORB_OK;
+}
+
+int check_sim3_args(const int32_t* kfs, int n, const double* before, const double* after, const int32_t* already, int n_already,
+                    const orbm_correct_entry* entries, const float* pos_out, int cap, const int* n_out, const float* Tiw_out) {
+    MORB_ARG(n >= 0 && (n == 0 || (kfs && before && after && Tiw_out)) && n_already >= 0 && (n_already == 0 || already) && cap >= 0 &&
+             (cap == 0 || (entries && pos_out)) && n_out);
+    if (n > ORBM_MAP_MAX_LOCAL) { morb::set_error("%d keyframes are more than a call takes (%d)", n, (int)ORBM_MAP_MAX_LOCAL); return ORB_E_CAPACITY; }
+    return ORB_OK;
+}
+
+int check_rigid_args(int n, const uint8_t* kf_corrected, const float* Tcw_before, const float* Twc_after, int n_kfs,
+                     const int32_t* gba_slots, const float* gba_pos, int n_gba, int n_points) {
+    MORB_ARG(n >= 0 && n_kfs >= 0 && (n_kfs == 0 || (kf_corrected && Tcw_before && Twc_after)) && n_gba >= 0 &&
+             (n_gba == 0 || (gba_slots && gba_pos)));
+    if (n_kfs > ORBM_MAP_MAX_KEYFRAMES) { morb::set_error("%d keyframes are more than a map holds (%d)", n_kfs, (int)ORBM_MAP_MAX_KEYFRAMES); return ORB_E_CAPACITY; }
+    for (int g = 0; g < n_gba; ++g) MORB_ARG(gba_slots[g] < n_points);
+    return ORB_OK;
+}
+
+// rows 0-2 of mTcwBefGBA, then rows 0-2 of GetPoseInverse(), per keyframe
+void rigid_table(const float* Tcw_before, const float* Twc_after, int n_kfs, float* table) {
+    for (int r = 0; r < n_kfs; ++r) {
+        memcpy(table + (size_t)MAP_RIGID_TABLE * r, Tcw_before + 12 * (size_t)r, 48);
+        memcpy(table + (size_t)MAP_RIGID_TABLE * r + 12, Twc_after + 12 * (size_t)r, 48);
+    }
+}
+
+}  // namespace
+
+int orbm_local_map_correct_sim3_host(const int32_t* kf_rows, const int32_t* kf_count, int n_kfs, int stride, const uint8_t* point_flags,
+                                     float* pos, int pos_stride, int n_points, const int32_t* kfs, int n, const double* sim3_before,
+                                     const double* sim3_after, const int32_t* already, int n_already, orbm_correct_entry* entries,
+                                     float* pos_out, int cap, int* n_out, float* Tiw_out) {
+    MORB_ARG(n_kfs >= 0 && stride >= 1 && (n_kfs == 0 || (kf_rows && kf_count)) && n_points >= 0 && (n_points == 0 || (point_flags && pos)) &&
+             pos_stride >= 3);
+    int rc;
+    if ((rc = check_sim3_args(kfs, n, sim3_before, sim3_after, already, n_already, entries, pos_out, cap, n_out, Tiw_out))) return rc;
+    *n_out = 0;
+    std::vector<uint8_t> marked((size_t)n_points, 0);   // mnCorrectedByKF == mpCurrentKF->mnId
+    for (int i = 0; i < n_already; ++i) {
+        if (already[i] < 0) continue;
+        MORB_ARG(already[i] < n_points);
+        marked[(size_t)already[i]] = 1;
+    }
+    std::vector<orbm_correct_entry> kept;
+    for (int j = 0; j < n; ++j) {
+        const int kf = kfs[j];
+        MORB_ARG(kf >= 0 && kf < n_kfs && kf_count[kf] >= 0 && kf_count[kf] <= stride);
+        for (int f = 0; f < kf_count[kf]; ++f) {
+            const int s = kf_rows[(size_t)kf * stride + f];
+            if (s < 0) continue;                              // :692
+            MORB_ARG(s < n_points);
+            if (point_flags[s] & ORBM_POINT_BAD) continue;    // :694
+            if (marked[(size_t)s]) continue;                  // :696
+            kept.push_back(orbm_correct_entry{s, j});
+            marked[(size_t)s] = 1;                            // :707
+        }
+    }
+    *n_out = (int)std::min<size_t>(kept.size(), 0x7fffffff);
+    if (kept.size() > (size_t)cap) {
+        morb::set_error("%zu corrected points are more than the list takes (%d)", kept.size(), cap);
+        return ORB_E_CAPACITY;
+    }
+    std::vector<double> table((size_t)n * MAP_SIM3_TABLE);
+    for (int j = 0; j < n; ++j) {
+        map_sim3_table_entry(sim3_before + 8 * (size_t)j, sim3_after + 8 * (size_t)j, table.data() + (size_t)MAP_SIM3_TABLE * j);
+        eg_Tiw(sim3_after + 8 * (size_t)j, Tiw_out + 16 * (size_t)j);   // :714-720
+    }
+    for (size_t i = 0; i < kept.size(); ++i) {
+        float* P = pos + (size_t)pos_stride * (size_t)kept[i].point;
+        float w[3];
+        map_correct_sim3_point(table.data() + (size_t)MAP_SIM3_TABLE * (size_t)kept[i].position, P, w);
+        for (int k = 0; k < 3; ++k) { P[k] = w[k]; pos_out[3 * i + k] = w[k]; }
+        entries[i] = kept[i];
+    }
+    return ORB_OK;
+}
+
+int orbm_local_map_correct_rigid_host(float* pos, int pos_stride, const uint8_t* point_flags, const int32_t* point_ref, int n_points,
+                                      const int32_t* slots, int n, const uint8_t* kf_corrected, const float* Tcw_before,
+                                      const float* Twc_after, int n_kfs, const int32_t* gba_slots, const float* gba_pos, int n_gba,
+                                      uint8_t* status, float* pos_out) {
+    MORB_ARG(n_points >= 0 && (n_points == 0 || (pos && point_flags && point_ref)) && pos_stride >= 3);
+    int rc;
+    if ((rc = check_rigid_args(n, kf_corrected, Tcw_before, Twc_after, n_kfs, gba_slots, gba_pos, n_gba, n_points))) return rc;
+    if (!slots) MORB_ARG(n <= n_points);
+    std::vector<int32_t> given((size_t)n_points, -1);   // mnBAGlobalForKF == nLoopKF: the last entry that names the point
+    for (int g = 0; g < n_gba; ++g)
+        if (gba_slots[g] >= 0) given[(size_t)gba_slots[g]] = g;
+    std::vector<uint8_t> listed(slots ? (size_t)n_points : 0, 0);
+    for (int i = 0; i < n && slots; ++i) {
+        MORB_ARG(slots[i] >= 0 && slots[i] < n_points && !listed[(size_t)slots[i]]);
+        listed[(size_t)slots[i]] = 1;
+    }
+    float T[MAP_RIGID_TABLE];
+    for (int i = 0; i < n; ++i) {
+        const int s = slots ? slots[i] : i;
+        float* P = pos + (size_t)pos_stride * (size_t)s;
+        int st = 0;
+        if (!(point_flags[s] & ORBM_POINT_BAD)) {                          // :961
+            if (given[(size_t)s] >= 0) {                                   // :964-967
+                memcpy(P, gba_pos + 3 * (size_t)given[(size_t)s], 12);
+                st = 1;
+            } else {
+                const int r = point_ref[s];
+                if (r >= 0 && r < n_kfs && kf_corrected[r]) {              // :974
+                    float w[3];
+                    rigid_table(Tcw_before + 12 * (size_t)r, Twc_after + 12 * (size_t)r, 1, T);
+                    map_correct_rigid_point(T, P, w);                      // :978-987
+                    for (int k = 0; k < 3; ++k) P[k] = w[k];
+                    st = 2;
+                }
+            }
+        }
+        if (status) status[i] = (uint8_t)st;
+        if (pos_out) memcpy(pos_out + 3 * (size_t)i, P, 12);
+    }
+    return ORB_OK;
+}
+
+int orbm_map_points(const orbm_map* p) { return p ? p->pt_hw : ORB_E_ARG; }
+
+int orbm_debug_last_correction(const orbm_map* p, int* out4) {
+    MORB_ARG(p && out4);
+    for (int k = 0; k < 4; ++k) out4[k] = p->last_cor[k];
+    return ORB_OK;
+}
+
+int orbm_debug_map_read_points(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n, orbm_point* rows) {
+    MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || (slots && rows)));
+    int rc;
+    if ((rc = check_slots(slots, n, 0, p->pt_cap, "point slot"))) return rc;
+    if (n == 0) return ORB_OK;
+    MORB_HIP(hipSetDevice(m->device));
+    const int lo = *std::min_element(slots, slots + n), hi = *std::max_element(slots, slots + n);
+    std::vector<orbm_point> span((size_t)(hi - lo + 1));
+    MORB_HIP(hipMemcpyAsync(span.data(), p->d_rows.p + lo, span.size() * sizeof(orbm_point), hipMemcpyDeviceToHost, m->stream));
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    for (int i = 0; i < n; ++i) rows[i] = span[(size_t)(slots[i] - lo)];
+    return ORB_OK;
+}
+
+int orbm_map_write_positions(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n, const float* pos3) {
+    MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || (slots && pos3)));
+    int rc;
+    if ((rc = check_slots(slots, n, 0, p->pt_cap, "point slot"))) return rc;
+    if (n == 0) return ORB_OK;
+    MORB_HIP(hipSetDevice(m->device));
+    for (int i = 0; i < n; ++i) {
+        memcpy(p->h_rows[(size_t)slots[i]].pos, pos3 + 3 * (size_t)i, 12);
+        p->pt_hw = std::max(p->pt_hw, slots[i] + 1);
+    }
+    if ((rc = put_positions(m, p, slots, n))) return rc;   // (staged from the mirror: a slot named twice takes its last entry)
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    return ORB_OK;
+}
+
+int orbm_map_write_point_ref(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n, const int32_t* ref_kf) {
+    MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || (slots && ref_kf)));
+    int rc;
+    if ((rc = check_slots(slots, n, 0, p->pt_cap, "point slot"))) return rc;
+    if (n == 0) return ORB_OK;
+    MORB_HIP(hipSetDevice(m->device));
+    const size_t off_val = (size_t)n * 4;
+    if ((rc = p->stage.reserve(off_val + (size_t)n * 4 + 16))) return rc;
+    for (int i = 0; i < n; ++i) { p->h_ref[(size_t)slots[i]] = ref_kf[i]; p->pt_hw = std::max(p->pt_hw, slots[i] + 1); }
+    memcpy(p->stage.p, slots, (size_t)n * 4);
+    for (int i = 0; i < n; ++i) memcpy(p->stage.p + off_val + (size_t)i * 4, &p->h_ref[(size_t)slots[i]], 4);
+    p->stage.publish();
+    hipLaunchKernelGGL(k_map_put_words, dim3(blocks_of(n)), dim3(MAP_BLOCK), 0, m->stream, (const uint32_t*)(p->stage.dp + off_val),
+                       (const int32_t*)p->stage.dp, n, 1, (uint32_t*)p->d_ref.p);
+    MORB_HIP(hipGetLastError());
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    return ORB_OK;
+}
+
+int orbm_map_correct_sim3(orbm_matcher* m, orbm_map* p, const int32_t* kfs, int n, const double* sim3_before, const double* sim3_after,
+                          const int32_t* already, int n_already, orbm_correct_entry* entries, float* pos_out, int cap, int* n_out,
+                          float* Tiw_out) {
+    MORB_ARG(m && p && p->owner == m);
+    int rc;
+    if ((rc = check_sim3_args(kfs, n, sim3_before, sim3_after, already, n_already, entries, pos_out, cap, n_out, Tiw_out))) return rc;
+    *n_out = 0;
+    if (check_slots(kfs, n, 0, p->kf_hw, "keyframe")) return ORB_E_ARG;
+    for (int i = 0; i < n_already; ++i) MORB_ARG(already[i] < p->pt_cap);
+    long long cand = 0; int fmax = 0;
+    for (int j = 0; j < n; ++j) { const int c = p->h_kf_count[(size_t)kfs[j]]; cand += c; fmax = std::max(fmax, c); }
+    p->last_cor[1] = (int)std::min<long long>(cand, 0x7fffffff); p->last_cor[2] = 0; p->last_cor[3] = n;
+    MORB_HIP(hipSetDevice(m->device));
+    if (m->host_resolve) {   // MORB_HOST_RESOLVE=1: the host routine over the mirror, the new positions then sent to their rows
+        p->last_cor[0] = 0;
+        rc = orbm_local_map_correct_sim3_host(p->h_kf_rows.data(), p->h_kf_count.data(), p->kf_hw, p->stride, p->h_flags.data(),
+                                              p->pt_cap ? p->h_rows[0].pos : nullptr, POS_STRIDE_ROWS, p->pt_cap, kfs, n, sim3_before,
+                                              sim3_after, already, n_already, entries, pos_out, cap, n_out, Tiw_out);
+        if (rc) return rc;
+        p->last_cor[2] = *n_out;
+        std::vector<int32_t> moved((size_t)*n_out);
+        for (int i = 0; i < *n_out; ++i) moved[(size_t)i] = entries[i].point;
+        if ((rc = put_positions(m, p, moved.data(), *n_out))) return rc;
+        MORB_HIP(hipStreamSynchronize(m->stream));
+        return ORB_OK;
+    }
+    p->last_cor[0] = 1;
+    for (int j = 0; j < n; ++j) eg_Tiw(sim3_after + 8 * (size_t)j, Tiw_out + 16 * (size_t)j);   // :714-720
+    if (fmax == 0) return ORB_OK;
+    const int bpk = (fmax + MAP_BLOCK - 1) / MAP_BLOCK, nb = n * bpk;
+    const int n_launch = (int)std::min<long long>(cap, cand);
+    const size_t off_table = pad8((size_t)n * 4), off_already = off_table + (size_t)n * MAP_SIM3_TABLE * sizeof(double);
+    if ((rc = p->stage.reserve(off_already + (size_t)n_already * 4 + 16)) || (rc = p->d_block.reserve((size_t)nb)) ||
+        (rc = p->d_centries.reserve((size_t)std::max(n_launch, 1))) || (rc = p->h_centries.reserve((size_t)std::max(n_launch, 1))) ||
+        (rc = p->h_cpos.reserve((size_t)std::max(n_launch, 1) * 3))) return rc;
+    // two epochs: the claim's, and a NEWER one for the points already corrected -- a newer key is smaller than every key of the claim
+    uint32_t e_claim, e_skip;
+    do {
+        if ((rc = next_epoch(m, p))) return rc;
+        e_claim = p->epoch;
+        if ((rc = next_epoch(m, p))) return rc;
+        e_skip = p->epoch;
+    } while (e_skip < e_claim);   // (the counter wrapped in between: both again)
+    memcpy(p->stage.p, kfs, (size_t)n * 4);
+    {
+        double entry[MAP_SIM3_TABLE];
+        for (int j = 0; j < n; ++j) {
+            map_sim3_table_entry(sim3_before + 8 * (size_t)j, sim3_after + 8 * (size_t)j, entry);
+            memcpy(p->stage.p + off_table + (size_t)j * sizeof(entry), entry, sizeof(entry));
+        }
+    }
+    if (n_already) memcpy(p->stage.p + off_already, already, (size_t)n_already * 4);
+    p->stage.publish();
+    const int32_t* d_kfs = (const int32_t*)p->stage.dp;
+    const int32_t *rows = p->d_kf_rows.p, *cnt = p->d_kf_count.p;
+    const uint8_t* fl = p->d_flags.p;
+    if (n_already)
+        hipLaunchKernelGGL(k_map_stamp, dim3(blocks_of(n_already)), dim3(MAP_BLOCK), 0, m->stream, (const int32_t*)(p->stage.dp + off_already),
+                           n_already, p->d_first.p, map_key(e_skip, 0));
+    hipLaunchKernelGGL(k_map_first, dim3(nb), dim3(MAP_BLOCK), 0, m->stream, rows, cnt, d_kfs, p->stride, bpk, fl, p->d_first.p, e_claim);
+    hipLaunchKernelGGL(k_map_count, dim3(nb), dim3(MAP_BLOCK), 0, m->stream, rows, cnt, d_kfs, p->stride, bpk, fl,
+                       (const unsigned long long*)p->d_first.p, e_claim, p->d_block.p);
+    hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(MAP_SCAN_LANES), 0, m->stream, p->d_block.p, nb, p->d_total.p, p->h_total.dp);
+    hipLaunchKernelGGL(k_map_correct_scatter, dim3(nb), dim3(MAP_BLOCK), 0, m->stream, rows, cnt, d_kfs, p->stride, bpk, fl,
+                       (const unsigned long long*)p->d_first.p, e_claim, (const int32_t*)p->d_block.p, (const int32_t*)p->d_total.p,
+                       p->d_centries.p, p->h_centries.dp, n_launch);
+    if (n_launch > 0)
+        hipLaunchKernelGGL(k_map_correct_sim3, dim3(blocks_of(n_launch)), dim3(MAP_BLOCK), 0, m->stream,
+                           (const orbm_correct_entry*)p->d_centries.p, n_launch, (const int32_t*)p->d_total.p, n_launch,
+                           (const double*)(p->stage.dp + off_table), p->d_rows.p, p->h_cpos.dp);
+    MORB_HIP(hipGetLastError());
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    const int total = p->h_total.p[0];
+    *n_out = total;
+    if (total > cap) {   // (beyond n_launch <= cap neither kernel wrote anything)
+        morb::set_error("%d corrected points are more than the list takes (%d)", total, cap);
+        return ORB_E_CAPACITY;
+    }
+    p->last_cor[2] = total;
+    for (int i = 0; i < total; ++i) {
+        entries[i] = p->h_centries.p[i];
+        memcpy(pos_out + 3 * (size_t)i, p->h_cpos.p + 3 * (size_t)i, 12);
+        memcpy(p->h_rows[(size_t)entries[i].point].pos, p->h_cpos.p + 3 * (size_t)i, 12);
+    }
+    return ORB_OK;
+}
+
+int orbm_map_correct_rigid(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n, const uint8_t* kf_corrected,
+                           const float* Tcw_before, const float* Twc_after, int n_kfs, const int32_t* gba_slots, const float* gba_pos,
+                           int n_gba, uint8_t* status, float* pos_out) {
+    MORB_ARG(m && p && p->owner == m);
+    int rc;
+    if ((rc = check_rigid_args(n, kf_corrected, Tcw_before, Twc_after, n_kfs, gba_slots, gba_pos, n_gba, p->pt_cap))) return rc;
+    if (!slots) {
+        if (n != p->pt_hw) { morb::set_error("slots == NULL covers the %d point slots below the high-water mark, not %d", p->pt_hw, n); return ORB_E_ARG; }
+    } else {
+        if ((rc = check_slots(slots, n, 0, p->pt_cap, "point slot"))) return rc;
+        if (p->seen_epoch == 0xffffffffu) { std::fill(p->h_seen.begin(), p->h_seen.end(), 0u); p->seen_epoch = 0; }
+        p->h_seen.resize((size_t)p->pt_cap, 0u);
+        ++p->seen_epoch;
+        for (int i = 0; i < n; ++i) {
+            if (p->h_seen[(size_t)slots[i]] == p->seen_epoch) { morb::set_error("point slot %d is listed twice (entry %d)", slots[i], i); return ORB_E_ARG; }
+            p->h_seen[(size_t)slots[i]] = p->seen_epoch;
+        }
+    }
+    p->last_cor[1] = n; p->last_cor[2] = 0; p->last_cor[3] = n_kfs;
+    MORB_HIP(hipSetDevice(m->device));
+    if (m->host_resolve) {   // MORB_HOST_RESOLVE=1: the host routine over the mirror, the changed positions then sent to their rows
+        p->last_cor[0] = 0;
+        std::vector<uint8_t> st((size_t)std::max(n, 1));
+        rc = orbm_local_map_correct_rigid_host(p->pt_cap ? p->h_rows[0].pos : nullptr, POS_STRIDE_ROWS, p->h_flags.data(), p->h_ref.data(),
+                                               p->pt_cap, slots, n, kf_corrected, Tcw_before, Twc_after, n_kfs, gba_slots, gba_pos, n_gba,
+                                               st.data(), pos_out);
+        if (rc) return rc;
+        std::vector<int32_t> moved;
+        for (int i = 0; i < n; ++i)
+            if (st[(size_t)i]) moved.push_back(slots ? slots[i] : i);
+        p->last_cor[2] = (int)moved.size();
+        if (status) memcpy(status, st.data(), (size_t)n);
+        if ((rc = put_positions(m, p, moved.data(), (int)moved.size()))) return rc;
+        MORB_HIP(hipStreamSynchronize(m->stream));
+        return ORB_OK;
+    }
+    p->last_cor[0] = 1;
+    if (n == 0) return ORB_OK;
+    const size_t off_flag = pad8(slots ? (size_t)n * 4 : 0), off_table = off_flag + pad8((size_t)n_kfs);
+    const size_t off_gslots = off_table + pad8((size_t)n_kfs * MAP_RIGID_TABLE * sizeof(float)), off_gpos = off_gslots + pad8((size_t)n_gba * 4);
+    if ((rc = p->stage.reserve(off_gpos + (size_t)n_gba * 12 + 16)) || (rc = p->h_cstatus.reserve((size_t)n)) ||
+        (rc = p->h_cpos.reserve((size_t)n * 3)) || (rc = next_epoch(m, p))) return rc;
+    if (slots) memcpy(p->stage.p, slots, (size_t)n * 4);
+    if (n_kfs) {
+        memcpy(p->stage.p + off_flag, kf_corrected, (size_t)n_kfs);
+        rigid_table(Tcw_before, Twc_after, n_kfs, (float*)(p->stage.p + off_table));
+    }
+    if (n_gba) {
+        memcpy(p->stage.p + off_gslots, gba_slots, (size_t)n_gba * 4);
+        memcpy(p->stage.p + off_gpos, gba_pos, (size_t)n_gba * 12);
+    }
+    p->stage.publish();
+    if (n_gba)
+        hipLaunchKernelGGL(k_map_stamp_last, dim3(blocks_of(n_gba)), dim3(MAP_BLOCK), 0, m->stream, (const int32_t*)(p->stage.dp + off_gslots),
+                           n_gba, p->d_first.p, p->epoch);
+    hipLaunchKernelGGL(k_map_correct_rigid, dim3(std::min<unsigned>(blocks_of(n), MAP_RIGID_MAX_BLOCKS)), dim3(MAP_BLOCK), 0, m->stream,
+                       slots ? (const int32_t*)p->stage.dp : (const int32_t*)nullptr, n, p->d_rows.p, (const uint8_t*)p->d_flags.p,
+                       (const int32_t*)p->d_ref.p, (const uint8_t*)(p->stage.dp + off_flag), (const float*)(p->stage.dp + off_table), n_kfs,
+                       (const unsigned long long*)p->d_first.p, p->epoch, (const float*)(p->stage.dp + off_gpos), p->h_cstatus.dp,
+                       p->h_cpos.dp);
+    MORB_HIP(hipGetLastError());
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    int changed = 0;
+    for (int i = 0; i < n; ++i) {
+        float* P = p->h_rows[(size_t)(slots ? slots[i] : i)].pos;
+        if (p->h_cstatus.p[i]) { memcpy(P, p->h_cpos.p + 3 * (size_t)i, 12); ++changed; }
+        if (pos_out) memcpy(pos_out + 3 * (size_t)i, P, 12);
+    }
+    if (status) memcpy(status, p->h_cstatus.p, (size_t)n);
+    p->last_cor[2] = changed;
     return ORB_OK;
 }

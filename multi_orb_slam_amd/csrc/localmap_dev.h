@@ -133,23 +133,30 @@ __global__ __launch_bounds__(MAP_SCAN_LANES) void k_map_scan(int32_t* __restrict
     if (threadIdx.x == MAP_SCAN_LANES - 1) { *total = run_sum[threadIdx.x]; *total_out = run_sum[threadIdx.x]; }
 }
 
+// The place of a kept candidate in the compacted list: its block's offset plus the kept candidates before it in the block; -1 for a
+// candidate that is not kept.  Every lane of the workgroup calls it (a barrier inside).
+__device__ inline int map_place(bool keep, const int32_t* __restrict__ block_off) {
+    __shared__ int wave_n[MAP_BLOCK / 64];
+    const unsigned long long b = __ballot(keep);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_n[wave] = __popcll(b);
+    __syncthreads();
+    if (!keep) return -1;
+    int at = block_off[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) at += wave_n[w];
+    return at;
+}
+
 // list and list_out (mapped) have room for list_cap entries; a place beyond it is not written (the caller reports the overflow).
 __global__ __launch_bounds__(MAP_BLOCK) void k_map_scatter(const int32_t* __restrict__ kf_rows, const int32_t* __restrict__ kf_count,
                                                            const int32_t* __restrict__ local_kfs, int stride, int bpk,
                                                            const uint8_t* __restrict__ flags, const unsigned long long* __restrict__ first,
                                                            uint32_t epoch, const int32_t* __restrict__ block_off, int32_t* __restrict__ list,
                                                            int32_t* __restrict__ list_out, int list_cap) {
-    __shared__ int wave_n[MAP_BLOCK / 64];
     const MapCand c = map_candidate(kf_rows, kf_count, local_kfs, stride, bpk, flags);
     const bool keep = c.slot >= 0 && first[c.slot] == map_key(epoch, c.pos);
-    const unsigned long long b = __ballot(keep);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wave_n[wave] = __popcll(b);
-    __syncthreads();
-    if (!keep) return;
-    int at = block_off[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) at += wave_n[w];
-    if (at < list_cap) { list[at] = c.slot; list_out[at] = c.slot; }
+    const int at = map_place(keep, block_off);
+    if (at >= 0 && at < list_cap) { list[at] = c.slot; list_out[at] = c.slot; }
 }
 
 // Scattered writes of orbm_map_write_points / _observations: entry r of the staged block, `words` 32-bit words long, into slot

@@ -59,7 +59,7 @@ int ResidentMap::SlotOf(MapPoint* pMP) {
     if (slot >= mCap.points) { std::fprintf(stderr, "ResidentMap: more than %d map points\n", mCap.points); mbFailed = true; return -1; }
     mvPointOfSlot.push_back(pMP);
     orbm_point zero; std::memset(&zero, 0, sizeof(zero));
-    mvRows.push_back(zero); mvFlags.push_back(0); mvPointNObs.push_back(0);   // what an unwritten slot holds on the device
+    mvRows.push_back(zero); mvFlags.push_back(0); mvPointNObs.push_back(0); mvPointRef.push_back(-1);   // what an unwritten slot holds on the device
     mPoints[pMP] = PointEntry{slot, {}};
     return slot;
 }
@@ -92,6 +92,11 @@ void ResidentMap::LastCovisibility(int out4[4]) const {
     if (mpMap) (void)orbm_debug_last_covisibility(mpMap, out4);
 }
 
+void ResidentMap::LastCorrection(int out4[4]) const {
+    for (int k = 0; k < 4; ++k) out4[k] = 0;
+    if (mpMap) (void)orbm_debug_last_correction(mpMap, out4);
+}
+
 int ResidentMap::Flush() {
     std::lock_guard<std::recursive_mutex> lock_map(mMutexMap);
     mLastFlush = FlushStats();
@@ -108,10 +113,14 @@ int ResidentMap::Flush() {
     std::sort(keyframes.begin(), keyframes.end(), std::less<KeyFrame*>()); keyframes.erase(std::unique(keyframes.begin(), keyframes.end()), keyframes.end());
 
     std::vector<int32_t> row_slots, rec_slots; std::vector<orbm_point> rows; std::vector<uint8_t> flags; std::vector<orbm_obs> recs;
-    std::vector<int32_t> nobs_slots, nobs, feat_slots, feats;
+    std::vector<int32_t> nobs_slots, nobs, feat_slots, feats, ref_slots, refs;
     for (MapPoint* pMP : points) {
         const int slot = SlotOf(pMP);
         if (slot < 0) return -1;
+        KeyFrame* pRefKF = pMP->GetReferenceKeyFrame();        // (what the update after global BA carries the point through)
+        const int ref = pRefKF ? SlotOf(pRefKF) : -1;
+        if (pRefKF && ref < 0) return -1;
+        if (ref != mvPointRef[(size_t)slot]) { mvPointRef[(size_t)slot] = ref; ref_slots.push_back(slot); refs.push_back(ref); }
         const int n_obs = pMP->Observations();                 // (the reference's counter, mirrored as a value)
         if (n_obs != mvPointNObs[(size_t)slot]) { mvPointNObs[(size_t)slot] = n_obs; nobs_slots.push_back(slot); nobs.push_back(n_obs); }
         orbm_point row; pack_point_row(pMP, row);
@@ -192,8 +201,10 @@ int ResidentMap::Flush() {
     }
     mLastFlush.rows = (int)row_slots.size(); mLastFlush.records = (int)rec_slots.size(); mLastFlush.keyframes = (int)kf_send.size();
     mLastFlush.record_features = (int)feat_slots.size(); mLastFlush.point_nobs = (int)nobs_slots.size(); mLastFlush.keyframe_features = (int)kf_feat_send.size();
+    mLastFlush.point_refs = (int)ref_slots.size();
     if (mpMap) {
         int rc;
+        if ((rc = orbm_map_write_point_ref(mpHandle, mpMap, ref_slots.data(), (int)ref_slots.size(), refs.data()))) { report("ResidentMap::Flush", "orbm_map_write_point_ref", rc); mbFailed = true; return -1; }
         if ((rc = orbm_map_write_point_nobs(mpHandle, mpMap, nobs_slots.data(), (int)nobs_slots.size(), nobs.data()))) { report("ResidentMap::Flush", "orbm_map_write_point_nobs", rc); mbFailed = true; return -1; }
         if ((rc = orbm_map_write_observation_features(mpHandle, mpMap, feat_slots.data(), (int)feat_slots.size(), feats.data()))) { report("ResidentMap::Flush", "orbm_map_write_observation_features", rc); mbFailed = true; return -1; }
         for (int slot : kf_feat_send)
@@ -224,6 +235,11 @@ int ResidentMap::Audit(const std::vector<KeyFrame*>& vpKeyFrames, const std::vec
         if (std::memcmp(&row, &mvRows[(size_t)slot], sizeof(row)) != 0) ++differences;
         if ((pMP->isBad() ? ORBM_POINT_BAD : 0) != mvFlags[(size_t)slot]) ++differences;
         if (pMP->Observations() != mvPointNObs[(size_t)slot]) ++differences;
+        {
+            KeyFrame* pRefKF = pMP->GetReferenceKeyFrame();
+            auto r = pRefKF ? mKeyFrames.find(pRefKF) : mKeyFrames.end();
+            if ((pRefKF ? (r == mKeyFrames.end() ? -2 : r->second) : -1) != mvPointRef[(size_t)slot]) ++differences;
+        }
         const std::map<KeyFrame*, size_t> now = pMP->GetObservations();
         const std::map<KeyFrame*, int>& held = it->second.records;
         bool same = now.size() == held.size();

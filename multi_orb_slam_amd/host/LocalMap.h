@@ -54,10 +54,13 @@ public:
     // (rows, records, keyframes: as ever.  The facts the covisibility and culling counts read beyond them (host/Covisibility.h):
     // record_features the records whose feature index was sent, point_nobs the points whose Observations() was, keyframe_features
     // the keyframes whose level / far bytes and camera-1 count were.  Flush's return value stays the sum of the first three.)
-    struct FlushStats { int rows = 0, records = 0, keyframes = 0, record_features = 0, point_nobs = 0, keyframe_features = 0; };
+    // point_refs: the points whose reference keyframe slot was sent (host/LoopCorrection.h reads it on the device).
+    struct FlushStats { int rows = 0, records = 0, keyframes = 0, record_features = 0, point_nobs = 0, keyframe_features = 0, point_refs = 0; };
     FlushStats LastFlush() const { return mLastFlush; }
     // inspection: orbm_debug_last_covisibility of the device map (all zero for a host-only map)
     void LastCovisibility(int out4[4]) const;
+    // inspection: orbm_debug_last_correction of the device map (all zero for a host-only map)
+    void LastCorrection(int out4[4]) const;
 
 private:
     friend void UpdateLocalMap(ResidentMap&, Frame&, std::vector<KeyFrame*>&, std::vector<MapPoint*>&, KeyFrame*&);
@@ -65,6 +68,7 @@ private:
     friend void CovisibilityCounts(ResidentMap&, const std::vector<KeyFrame*>&, std::vector<std::map<KeyFrame*, int> >&,
                                    std::vector<std::map<KeyFrame*, int> >&);
     friend void KeyFrameCulling(ResidentMap&, KeyFrame*, bool);
+    friend struct LoopCorrectionAccess;   // CorrectLoopMap and UpdateMapAfterGlobalBA (host/LoopCorrection.cc)
 
     struct PointEntry { int slot; std::map<KeyFrame*, int> records; };   // the record slot of each observation the mirror holds
     int SlotOf(MapPoint* pMP);      // assigned on first sight; -1 when the map is full (reported)
@@ -76,6 +80,12 @@ private:
     bool SlotsOfSent(const std::vector<KeyFrame*>& vpKFs, size_t begin, size_t end, std::vector<int32_t>& slots);
     int Covisibility(const std::vector<int32_t>& kfs, std::vector<int32_t>& first, std::vector<orbm_covis_entry>& entries);
     int CullingCounts(const std::vector<int32_t>& kfs, bool mono, std::vector<int32_t>& counts);
+    // the two corrections, on the device or over the mirror; either way the mirror's positions are the new ones afterwards
+    int CorrectSim3(const std::vector<int32_t>& kfs, const std::vector<double>& before, const std::vector<double>& after,
+                    const std::vector<int32_t>& already, std::vector<orbm_correct_entry>& entries, std::vector<float>& pos, std::vector<float>& Tiw);
+    int CorrectRigid(const std::vector<int32_t>& slots, const std::vector<uint8_t>& kf_corrected, const std::vector<float>& Tcw_before,
+                     const std::vector<float>& Twc_after, const std::vector<int32_t>& gba_slots, const std::vector<float>& gba_pos,
+                     std::vector<uint8_t>& status, std::vector<float>& pos);
 
     // Everything that touches the device object or the slot tables runs under this: Flush, Audit, the calls of the tracking thread and
     // those of the LocalMapping / LoopClosing threads (an orbm_map is bound to one handle, and one call uses it at a time).
@@ -103,6 +113,7 @@ private:
     std::vector<orbm_obs> mvRecords;
     std::vector<int32_t> mvKeyFrameRows, mvKeyFrameCount;   // mvKeyFrameRows[slot * features_per_keyframe + f]
     std::vector<int32_t> mvRecordFeature, mvPointNObs, mvKeyFrameNCam1;   // per record, per point slot, per keyframe slot
+    std::vector<int32_t> mvPointRef;                        // per point slot: the keyframe slot of GetReferenceKeyFrame(), -1: none
     std::vector<uint8_t> mvKeyFrameFeatures;                // [slot * features_per_keyframe + f]: level | ORBM_FEATURE_FAR
     // the last point list (slots), what SearchLocalPoints searches
     std::vector<int32_t> mvList;

@@ -262,6 +262,12 @@ public:
     // members host/GlobalBA.cc writes when the adjustment belongs to a loop (include/KeyFrame.h: mTcwGBA, mnBAGlobalForKF)
     cv::Mat mTcwGBA;
     long unsigned int mnBAGlobalForKF = 0;
+    // member host/LoopCorrection.cc writes and reads (include/KeyFrame.h: mTcwBefGBA, set by LoopClosing::RunGlobalBundleAdjustment)
+    cv::Mat mTcwBefGBA;
+    // KeyFrame::UpdateConnections (src/KeyFrame.cc:486-668), which LoopClosing::CorrectLoop calls per keyframe: defined behind MapPoint's
+    // late members.  Two statements of the reference cannot run on a keyframe without a camera-1 counter (pKFmax_cam1 is NULL at :618,
+    // front() of an empty vector at :660): they are skipped there.
+    void UpdateConnections();
     // members host/EssentialGraph.cc reads (include/KeyFrame.h:82-96; src/KeyFrame.cc:331-364): the spanning tree, the loop edges and
     // the camera-1 covisibility weights are plain containers the caller fills (mvOrderedWeights_cam1 descending, beside
     // mvpOrderedConnectedKeyFrames_cam1)
@@ -361,6 +367,46 @@ inline void MapPoint::EraseObservationOfBadKeyFrame(KeyFrame* pKF) {   // src/Ma
         if (ob.second < ob.first->mvpMapPoints.size()) ob.first->mvpMapPoints[ob.second] = nullptr;   // EraseMapPointMatch(idx)
 }
 
+inline void KeyFrame::UpdateConnections() {
+    LogCall("UpdateConnections", mnId);
+    std::map<KeyFrame*, int> KFcounter, KFcounter_cam1;
+    for (size_t i = 0; i < mvpMapPoints.size(); ++i) {               // :512-552
+        MapPoint* pMP = mvpMapPoints[i];
+        if (!pMP || pMP->isBad()) continue;
+        for (const auto& ob : pMP->mObservations) {
+            if (ob.first->mnId == mnId) continue;
+            KFcounter[ob.first]++;
+            if ((int)i < N && (int)ob.second < ob.first->N) KFcounter_cam1[ob.first]++;
+        }
+    }
+    if (KFcounter.empty()) return;                                   // :554-667
+    int nmax = 0, nmax_cam1 = 0;
+    KeyFrame *pKFmax = nullptr, *pKFmax_cam1 = nullptr;
+    const int th = 15;
+    std::vector<std::pair<int, KeyFrame*> > vPairs, vPairs_cam1;
+    for (auto& kv : KFcounter) {
+        if (kv.second > nmax) { nmax = kv.second; pKFmax = kv.first; }
+        if (kv.second >= th) { vPairs.push_back(std::make_pair(kv.second, kv.first)); kv.first->AddConnection(this, kv.second); }
+    }
+    for (auto& kv : KFcounter_cam1) {
+        if (kv.second > nmax_cam1) { nmax_cam1 = kv.second; pKFmax_cam1 = kv.first; }
+        if (kv.second >= th) { vPairs_cam1.push_back(std::make_pair(kv.second, kv.first)); kv.first->AddConnection_cam1(this, kv.second); }
+    }
+    if (vPairs.empty()) { vPairs.push_back(std::make_pair(nmax, pKFmax)); pKFmax->AddConnection(this, nmax); }
+    if (vPairs_cam1.empty() && pKFmax_cam1) { vPairs_cam1.push_back(std::make_pair(nmax_cam1, pKFmax_cam1)); pKFmax_cam1->AddConnection_cam1(this, nmax_cam1); }
+    std::sort(vPairs.begin(), vPairs.end());
+    std::sort(vPairs_cam1.begin(), vPairs_cam1.end());
+    mConnectedKeyFrameWeights = KFcounter; mConnectedKeyFrameWeights_cam1 = KFcounter_cam1;
+    mvpOrderedConnectedKeyFrames.clear(); mvOrderedWeights.clear(); mvpOrderedConnectedKeyFrames_cam1.clear(); mvOrderedWeights_cam1.clear();
+    for (size_t i = vPairs.size(); i-- > 0;) { mvpOrderedConnectedKeyFrames.push_back(vPairs[i].second); mvOrderedWeights.push_back(vPairs[i].first); }
+    for (size_t i = vPairs_cam1.size(); i-- > 0;) { mvpOrderedConnectedKeyFrames_cam1.push_back(vPairs_cam1[i].second); mvOrderedWeights_cam1.push_back(vPairs_cam1[i].first); }
+    if (mbFirstConnection && mnId != 0 && !mvpOrderedConnectedKeyFrames_cam1.empty()) {
+        mpParent = mvpOrderedConnectedKeyFrames_cam1.front();
+        mpParent->AddChild(this);
+        mbFirstConnection = false;
+    }
+}
+
 // Map: what host/LocalBA.cc takes of it (include/Map.h).  The stand-in's mutex is a std::mutex that records when it is taken and given back.
 struct LoggedMutex {
     void lock() { m.lock(); LogCall("lock"); }
@@ -379,6 +425,8 @@ public:
     // what host/EssentialGraph.cc takes of it (include/Map.h:58)
     long unsigned int GetMaxKFid() { return mnMaxKFid; }
     long unsigned int mnMaxKFid = 0;
+    // what host/LoopCorrection.cc takes of it (include/Map.h: mvpKeyFrameOrigins)
+    std::vector<KeyFrame*> mvpKeyFrameOrigins;
 };
 
 }  // namespace ORB_SLAM2

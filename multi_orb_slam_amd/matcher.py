@@ -776,6 +776,59 @@ def local_map_culling_host(obs, obs_feature, point_flags, point_n_obs, kf_rows, 
     return out[:len(ks)]
 
 
+def _f32(a, cols):
+    a = np.ascontiguousarray(a, np.float32)
+    return a.reshape(-1, cols)
+
+
+def _f64(a, cols):
+    return np.ascontiguousarray(a, np.float64).reshape(-1, cols)
+
+
+def _raise_needed(rc, needed):
+    """check(rc), the number an ORB_E_CAPACITY call reports attached to the exception as .needed."""
+    if rc != _lib.ORB_OK:
+        e = _lib.OrbError(rc, _lib.lib().orb_last_error().decode("utf-8", "replace"))
+        e.needed = int(needed)
+        raise e
+
+
+def local_map_correct_sim3_host(kf_rows, kf_count, point_flags, pos, kfs, sim3_before, sim3_after, already=(), cap=None):
+    """orbm_local_map_correct_sim3_host: step 4.2 of LoopClosing::CorrectLoop (reference src/LoopClosing.cc:678-710) on plain arrays: pos
+    n_points x 3 float32 (not modified), kfs the keyframes in CorrectedSim3's order with their NonCorrectedSim3 / CorrectedSim3 as rows of
+    8 doubles (quaternion x y z w, translation, scale), already the point slots to skip -> (entries CORRECT_DTYPE, pos_out k x 3, Tiw n x
+    4 x 4, the new n_points x 3 positions).  cap None: room for every candidate.  Beyond cap: OrbError with .needed."""
+    rows = np.ascontiguousarray(kf_rows, np.int32); assert rows.ndim == 2
+    cnt = _i32(kf_count); fl = np.ascontiguousarray(point_flags, np.uint8); ks = _i32(kfs); al = _i32(already)
+    P = _f32(pos, 3).copy(); sb = _f64(sim3_before, 8); sa = _f64(sim3_after, 8)
+    assert len(cnt) == rows.shape[0] and len(P) == len(fl) and len(sb) == len(sa) == len(ks)
+    cap = int(cnt[ks].sum()) if cap is None else int(cap)
+    ent = np.zeros(max(cap, 1), _lib.CORRECT_DTYPE); out = np.zeros((max(cap, 1), 3), np.float32); n = C.c_int()
+    tiw = np.zeros((max(len(ks), 1), 4, 4), np.float32)
+    rc = _lib.lib().orbm_local_map_correct_sim3_host(ptr(rows), ptr(cnt), rows.shape[0], max(rows.shape[1], 1), ptr(fl), ptr(P), 3, len(fl),
+                                                     ptr(ks), len(ks), ptr(sb), ptr(sa), ptr(al), len(al), ptr(ent), ptr(out), cap,
+                                                     C.byref(n), ptr(tiw))
+    _raise_needed(rc, n.value)
+    return ent[:n.value].copy(), out[:n.value].copy(), tiw[:len(ks)], P
+
+
+def local_map_correct_rigid_host(pos, point_flags, point_ref, slots, kf_corrected, Tcw_before, Twc_after, gba_slots=(), gba_pos=()):
+    """orbm_local_map_correct_rigid_host: the map-point update after global BA (reference src/LoopClosing.cc:953-989) on plain arrays: pos
+    n_points x 3 float32 (not modified), point_ref the keyframe slot of every point's reference keyframe, slots the points to visit (None:
+    all), kf_corrected one byte per keyframe, Tcw_before / Twc_after n_kfs x 12 (rows 0-2 of mTcwBefGBA and of GetPoseInverse()),
+    gba_slots / gba_pos the points that take mPosGBA -> (status uint8, pos_out, the new n_points x 3 positions)."""
+    P = _f32(pos, 3).copy(); fl = np.ascontiguousarray(point_flags, np.uint8); rf = _i32(point_ref)
+    sl = None if slots is None else _i32(slots)
+    kc = np.ascontiguousarray(kf_corrected, np.uint8).reshape(-1); tb = _f32(Tcw_before, 12); ta = _f32(Twc_after, 12)
+    gs = _i32(gba_slots); gp = _f32(gba_pos, 3)
+    assert len(P) == len(fl) == len(rf) and len(kc) == len(tb) == len(ta) and len(gs) == len(gp)
+    n = len(P) if sl is None else len(sl)
+    st = np.zeros(max(n, 1), np.uint8); out = np.zeros((max(n, 1), 3), np.float32)
+    check(_lib.lib().orbm_local_map_correct_rigid_host(ptr(P), 3, ptr(fl), ptr(rf), len(P), None if sl is None else ptr(sl), n, ptr(kc),
+                                                       ptr(tb), ptr(ta), len(kc), ptr(gs), ptr(gp), len(gs), ptr(st), ptr(out)))
+    return st[:n], out[:n], P
+
+
 class ResidentMap:
     """A map resident in HBM under stable slots (orbm_map): one slot per map point (a POINT_DTYPE row + a flag byte, bit 0 = bad),
     per keyframe (mvpMapPoints as point slots) and per observation (OBS_DTYPE), and Tracking::UpdateLocalMap's data-parallel parts
@@ -899,6 +952,65 @@ class ResidentMap:
         out = (C.c_int * 4)()
         check(_lib.lib().orbm_debug_last_covisibility(self._h, out))
         return tuple(out)
+
+    @property
+    def points(self):
+        """Point high-water mark (orbm_map_points)."""
+        n = int(_lib.lib().orbm_map_points(self._h))
+        if n < 0:
+            raise _lib.OrbError(n, "orbm_map_points on a closed map")
+        return n
+
+    def write_positions(self, slots, pos):
+        """The position field alone of the listed point slots (orbm_map_write_positions)."""
+        slots = _i32(slots); P = _f32(pos, 3)
+        assert len(P) == len(slots)
+        check(_lib.lib().orbm_map_write_positions(self._m._h, self._h, ptr(slots), len(slots), ptr(P)))
+
+    def write_point_ref(self, slots, ref_kf):
+        """The keyframe slot of each listed point's reference keyframe (orbm_map_write_point_ref)."""
+        slots = _i32(slots); rf = _i32(ref_kf)
+        assert len(rf) == len(slots)
+        check(_lib.lib().orbm_map_write_point_ref(self._m._h, self._h, ptr(slots), len(slots), ptr(rf)))
+
+    def correct_sim3(self, kfs, sim3_before, sim3_after, already=(), cap=None):
+        """orbm_map_correct_sim3 -> (entries CORRECT_DTYPE, pos_out k x 3, Tiw n x 4 x 4); the rows change in place.  cap None: room for
+        every point slot of the map.  Beyond cap: OrbError with .needed, and nothing has changed."""
+        ks = _i32(kfs); al = _i32(already); sb = _f64(sim3_before, 8); sa = _f64(sim3_after, 8)
+        assert len(sb) == len(sa) == len(ks)
+        cap = self.point_capacity if cap is None else int(cap)
+        ent = np.zeros(max(cap, 1), _lib.CORRECT_DTYPE); out = np.zeros((max(cap, 1), 3), np.float32); n = C.c_int()
+        tiw = np.zeros((max(len(ks), 1), 4, 4), np.float32)
+        rc = _lib.lib().orbm_map_correct_sim3(self._m._h, self._h, ptr(ks), len(ks), ptr(sb), ptr(sa), ptr(al), len(al), ptr(ent), ptr(out),
+                                              cap, C.byref(n), ptr(tiw))
+        _raise_needed(rc, n.value)
+        return ent[:n.value].copy(), out[:n.value].copy(), tiw[:len(ks)]
+
+    def correct_rigid(self, slots, kf_corrected, Tcw_before, Twc_after, gba_slots=(), gba_pos=()):
+        """orbm_map_correct_rigid over the listed point slots (None: every slot below the high-water mark) -> (status uint8, pos_out);
+        the rows change in place."""
+        sl = None if slots is None else _i32(slots)
+        kc = np.ascontiguousarray(kf_corrected, np.uint8).reshape(-1); tb = _f32(Tcw_before, 12); ta = _f32(Twc_after, 12)
+        gs = _i32(gba_slots); gp = _f32(gba_pos, 3)
+        assert len(kc) == len(tb) == len(ta) and len(gs) == len(gp)
+        n = self.points if sl is None else len(sl)
+        st = np.zeros(max(n, 1), np.uint8); out = np.zeros((max(n, 1), 3), np.float32)
+        check(_lib.lib().orbm_map_correct_rigid(self._m._h, self._h, None if sl is None else ptr(sl), n, ptr(kc), ptr(tb), ptr(ta), len(kc),
+                                                ptr(gs), ptr(gp), len(gs), ptr(st), ptr(out)))
+        return st[:n], out[:n]
+
+    def last_correction(self):
+        """(1 if the last correct_sim3 / correct_rigid ran on the device, candidates, points kept or changed, keyframes)
+        (orbm_debug_last_correction)."""
+        out = (C.c_int * 4)()
+        check(_lib.lib().orbm_debug_last_correction(self._h, out))
+        return tuple(out)
+
+    def read_points(self, slots):
+        """The rows of the listed point slots as HBM holds them, not the mirror (orbm_debug_map_read_points)."""
+        slots = _i32(slots); rows = np.zeros(max(len(slots), 1), POINT_DTYPE)
+        check(_lib.lib().orbm_debug_map_read_points(self._m._h, self._h, ptr(slots), len(slots), ptr(rows)))
+        return rows[:len(slots)]
 
     def close(self):
         if getattr(self, "_h", None):
