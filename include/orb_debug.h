@@ -51,6 +51,14 @@ int orbm_debug_last_resolve(const orbm_matcher* m, int* out4);
 #define ORBM_FORM_CAMS 8           /* k_resolve_cams: one workgroup per camera */
 #define ORBM_FORM_SWEEPS 9         /* k_rs_sweep + k_rs_owner [+ k_rs_reject] + k_rs_write: one launch per sweep, tables in HBM */
 int orbm_debug_last_resolve_form(const orbm_matcher* m, int* out2);
+/* The frame assembly with the per-camera counts still on the device, as the front end enqueues it behind an extraction it has not
+ * waited for -- with keypoints of the caller's choosing (inspection only; the boundary tests of the assembly reach k_frame_build_small
+ * with device counts, k_frame_fill_head, k_frame_head and k_cams_from_counts through it).  d_counts: n_cams + 1 ints in HBM, the real
+ * counts and then the extractor's status word (0); cams[c].n are CAPACITIES here, 0 <= count <= capacity (checked before anything is
+ * enqueued).  Enqueues what orbm_frame_from_device would, synchronises the handle's stream and sets the counts on the frame as the front
+ * end does after its own synchronisation: orbm_frame_grid, orbm_frame_download and the searches then work on *out. */
+int orbm_debug_frame_from_device_counts(orbm_matcher* m, const orbm_cam_features* cams, int n_cams, const int* d_counts, float mbf,
+                                        float min_x, float min_y, float max_x, float max_y, orbm_frame** out);
 /* Where the points of the last orbm_refresh_points went: {16-lane groups, one wavefront, one workgroup, host routine because the
  * point has more than ORBM_REFRESH_CAP observations, no work (no observations or no job)} (inspection only) */
 int orbm_debug_last_refresh(const orbm_matcher* m, int* out5);
@@ -120,6 +128,12 @@ int orbv_debug_last_keyframe_call(const orbv_workspace* w, int* out4);
  * -- was over before the matching began). */
 int orbf_debug_exchange_timing(orbf_frontend* f, int on);
 int orbf_debug_exchange_us(const orbf_frontend* f, float* out2);
+/* The frame of the last finished step (NULL before the first one), owned by the front end and valid until the next step begins:
+ * orbm_frame_grid / orbm_frame_count read it, nothing may destroy it.  *form says which assembly filled it: 1 the extractor's describe
+ * kernel wrote the per-feature half and the cells through the frame sink (rigs of up to 4 cameras and 8192 features on the asynchronous
+ * path), 2 the matcher's kernels with the counts still on the device (larger rigs), 0 orbm_frame_from_device after a synchronised
+ * extraction (inspection only). */
+const orbm_frame* orbf_debug_last_frame(const orbf_frontend* f, int* form);
 /* steps whose blocks were shipped a second time (a block had gone out before its extraction fell back to the host quadtree) */
 long orbf_debug_exchange_redos(const orbf_frontend* f);
 

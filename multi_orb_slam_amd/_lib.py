@@ -267,6 +267,7 @@ def lib():
     L.orbm_set_stream.argtypes = [vp, vp]
     L.orbm_wait_for_stream.argtypes = [vp, vp]
     L.orbm_frame_from_device.argtypes = [vp, vp, i32, f32, f32, f32, f32, f32, vp]
+    L.orbm_debug_frame_from_device_counts.argtypes = [vp, vp, i32, vp, f32, f32, f32, f32, f32, vp]
     L.orbm_frame_download.argtypes = [vp, vp, vp, vp, vp, vp]
     L.orbm_frame_count.argtypes = [vp]
     L.orbx_debug_last_path.argtypes = [vp]
@@ -298,6 +299,7 @@ def lib():
     L.orbf_debug_exchange_timing.argtypes = [vp, C.c_int]
     L.orbf_debug_exchange_us.argtypes = [vp, C.POINTER(C.c_float)]
     L.orbf_debug_exchange_redos.argtypes = [vp]; L.orbf_debug_exchange_redos.restype = C.c_long
+    L.orbf_debug_last_frame.argtypes = [vp, vp]; L.orbf_debug_last_frame.restype = vp
     L.orbf_exchange_init_loopback.argtypes = [vp, i32, i32, i32]
     L.orbf_exchange_shutdown.argtypes = [vp]
     L.orbf_exchange_peer_handle_bytes.argtypes = []; L.orbf_exchange_peer_handle_bytes.restype = C.c_size_t

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/orbm.h"
+#include "../../include/orb_debug.h"
 #include "orb_common.h"
 #include "frame_sink.h"
 #include "matcher_internal.h"
@@ -662,6 +663,26 @@ int orbm_frame_from_device(orbm_matcher* m, const orbm_cam_features* cams, int n
     MORB_ARG(out != nullptr);
     *out = nullptr;
     return frame_from_device_impl(m, cams, n_cams, mbf, min_x, min_y, max_x, max_y, nullptr, out);
+}
+
+// Inspection only (include/orb_debug.h): the forms that take the counts from the device, with keypoints of the caller's choosing.
+int orbm_debug_frame_from_device_counts(orbm_matcher* m, const orbm_cam_features* cams, int n_cams, const int* d_counts, float mbf,
+                                        float min_x, float min_y, float max_x, float max_y, orbm_frame** out) {
+    MORB_ARG(m && cams && d_counts && out && n_cams >= 1 && n_cams <= 64);
+    *out = nullptr;
+    MORB_HIP(hipSetDevice(m->device));
+    // the kernels trust the counts (the extractor never exceeds its capacities): a caller's array is looked at first
+    int counts[65];
+    MORB_HIP(hipMemcpyAsync(counts, d_counts, (size_t)(n_cams + 1) * sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    for (int c = 0; c < n_cams; ++c) MORB_ARG(counts[c] >= 0 && counts[c] <= cams[c].n);
+    orbm_frame* F = nullptr;
+    int rc = frame_from_device_impl(m, cams, n_cams, mbf, min_x, min_y, max_x, max_y, d_counts, &F);
+    if (rc) return rc;
+    if (hipStreamSynchronize(m->stream) != hipSuccess) { orbm_frame_destroy(F); morb::set_error("the frame assembly failed"); return ORB_E_HIP; }
+    frame_set_counts(F, counts);   // (as the front end does after its own synchronisation)
+    *out = F;
+    return ORB_OK;
 }
 
 

@@ -272,6 +272,13 @@ int orbf_set_calibration(orbf_frontend* f, const orb_calibration* calib) {
     return orbm_set_calibration(f->mt, calib);
 }
 
+// Inspection only (include/orb_debug.h): the last finished step's frame and which assembly filled it.
+const orbm_frame* orbf_debug_last_frame(const orbf_frontend* f, int* form) {
+    if (!f || !f->last_frame) return nullptr;
+    if (form) *form = f->last_frame_owned ? 0 : small_rig(f) ? 1 : 2;
+    return f->last_frame;
+}
+
 int orbf_configure(orbf_frontend* f, float mbf, int th_high, int check_orientation) {
     MORB_ARG(f && th_high >= 0 && th_high <= 256);
     f->mbf = mbf; f->th_high = th_high; f->check_ori = check_orientation ? 1 : 0;

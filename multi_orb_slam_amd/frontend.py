@@ -281,6 +281,20 @@ class NativeFrontEnd:
         return (dict(features=st.features, temporal_matches=st.temporal_matches, cross_accepted=st.cross_accepted,
                      digest=st.digest, seconds=st.seconds), upto.value)
 
+    def last_frame_grid(self):
+        """Inspection only (orbf_debug_last_frame): (form, cell_start, items) of the last finished step's frame -- form 1: filled through
+        the extractor's frame sink, 2: by the matcher's kernels with the counts on the device, 0: after a synchronised extraction.
+        None before the first step."""
+        L = _lib.lib()
+        form = C.c_int(-1)
+        h = L.orbf_debug_last_frame(self._h, C.byref(form))
+        if not h:
+            return None
+        n = L.orbm_frame_count(C.c_void_p(h))
+        cs = np.zeros(self.n_cams * 64 * 48 + 1, np.int32); items = np.zeros(max(n, 1), np.int32)
+        check(L.orbm_frame_grid(C.c_void_p(h), ptr(cs), ptr(items)))
+        return form.value, cs, items[:cs[-1]]
+
     def step(self, images, queries=None, flags=0, copy=True, motion=None):
         """images: [(ptr_or_array, width, height, stride, on_device)] or uint8 arrays.  `queries`: projected map points, or
         `motion` = (du, dv, th): queries built natively from the previous step's features (synthetic-stream driver).

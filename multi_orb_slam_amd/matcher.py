@@ -1203,6 +1203,24 @@ class Matcher:
                                                 C.byref(h)))
         return Frame(self, handle=h, n_total=sum(c[2] for c in cams), n_cams=len(cams))
 
+    def frame_from_device_counts(self, cams, d_counts, counts, mbf, bounds):
+        """Inspection only (orbm_debug_frame_from_device_counts): the assembly as the front end enqueues it, the per-camera counts read on
+        the device.  cams as for frame_from_device, their n being CAPACITIES; d_counts: device pointer to len(cams) + 1 ints (the
+        counts, then a status word of 0); counts: the same numbers on the host (the returned Frame is sized by them)."""
+        arr = (CamFeatures * len(cams))(*[CamFeatures(c[0], c[1], c[2], c[3] or None, c[4]) for c in cams])
+        h = C.c_void_p()
+        check(_lib.lib().orbm_debug_frame_from_device_counts(self._h, arr, len(cams), C.c_void_p(d_counts), mbf, bounds[0], bounds[1],
+                                                             bounds[2], bounds[3], C.byref(h)))
+        return Frame(self, handle=h, n_total=int(sum(counts)), n_cams=len(cams))
+
+    def set_calibration(self, calib):
+        """orbm_set_calibration: the undistortion device-built frames apply (fx, fy, cx, cy, k1, k2, p1, p2[, k3]); None or k1 == 0: off."""
+        if calib is None:
+            check(_lib.lib().orbm_set_calibration(self._h, None))
+        else:
+            c = _lib.Calibration(*([float(v) for v in calib] + [0.0] * (9 - len(calib))))
+            check(_lib.lib().orbm_set_calibration(self._h, C.byref(c)))
+
     def cross_top2_blocks(self, block_ptrs, counts, first_query_block, n_query_blocks):
         """Cross-camera top-2 over HBM-resident descriptor blocks (one per camera of the whole rig)."""
         nb = len(block_ptrs)

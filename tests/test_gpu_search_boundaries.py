@@ -311,6 +311,41 @@ def test_boundary_project_best_and_candidates(matcher, bounds_name):
         assert cnt.max() == 2 * sw.FIRST_CAP + 1 or search == "best"
 
 
+@pytest.mark.parametrize("bounds_name", list(BOUNDS))
+def test_boundary_insertion_on_the_resident_frame(matcher, bounds_name):
+    """The frame built a second time by orbm_frame_create_resident, every camera's descriptors resident: its grid is computed by
+    k_frame_build_small (the host-built frame's by the host), so the k + 0.5 ties of `insert_round` and column 64 / row 48 of
+    `insert_last` reach a kernel.  Same grid, same answers."""
+    import multi_orb_slam_amd as m
+    from multi_orb_slam_amd import rt
+    w = world("frames", bounds_name, "small")
+    fr = w["fr"]
+    cam = np.asarray(fr["cam_of"])
+    assert np.all(np.diff(cam) >= 0) and len(cam) <= 8192 and len(fr["descs"]) <= 4      # (what keeps the resident form on the device)
+    bufs = []
+    for d in fr["descs"]:
+        d = np.ascontiguousarray(d, np.uint8)
+        b = rt.DeviceBuffer(max(d.nbytes, 32)); b.upload(d); bufs.append(b)
+    exp = expected(w, ("frames", True), lambda: oracle.search_by_projection_frames(w["OF"], w["q"], 100, True, w["occ"]))
+    with device_frame(matcher, w) as F:
+        cs, items = F.grid()
+        host_built = matcher.SearchByProjection(F, w["q"], 100, w["occ"])
+    FR = matcher.frame(m.FrameData(**fr), resident=[b.ptr for b in bufs])
+    try:
+        rcs, ritems = FR.grid()
+        resident = matcher.SearchByProjection(FR, w["q"], 100, w["occ"])
+    finally:
+        FR.close()
+        for b in bufs:
+            b.free()
+    ocs, oitems = oracle.grid_csr(w["OF"])
+    assert rcs.tobytes() == cs.tobytes() == ocs.tobytes() and ritems.tobytes() == items.tobytes() == oitems.tobytes()
+    same_matches(w, resident, exp, "resident frame")
+    same_matches(w, resident, host_built, "resident against host-built")
+    probes = np.flatnonzero(np.isin(w["kinds"], ("insert_round", "insert_last")))
+    assert len(probes) >= 8 and np.isin(probes, resident[1]).sum() >= 4           # the insertion probes did find their features
+
+
 def points_of_queries(q, V):
     """Map points whose projection through view V lands where the queries look: back-projected at depth 4 in double, facing the camera
     (radius class 2.5), max_dist = 1.1 x distance (predicted level 1, window of octaves 0 and 1).  The model projects them again in the
