@@ -120,6 +120,19 @@ int orbv_debug_last_join(const orbv_workspace* w, int* out4);
  * orbv_create_new_points_keyframe on the workspace (inspection only; counted on the host where the call enqueues, as last_join is; all
  * zero before the first call and after one that was refused). */
 int orbv_debug_last_keyframe_call(const orbv_workspace* w, int* out4);
+/* {bins (1 + vocabulary nodes at the FeatureVector's level; bin 0 is the root's), chunks of 1024 bins k_fv_offsets scanned, FeatureVector
+ * nodes, largest node (what the joins size their LDS with), items (features whose word is not stopped)} of the last
+ * orbv_keyframe_from_device on the workspace (inspection only; host-side bookkeeping from the sizes and the three counters the call reads
+ * back anyway; all zero before the first call and after one that was refused).  A test written for one chunk count asserts this. */
+int orbv_debug_last_keyframe_build(const orbv_workspace* w, int* out5);
+
+/* ---- keyframe database --------------------------------------------------------------------------------------------------- */
+/* {form of k_db_query, entries per workgroup (epb), workgroups per query, queries} of the last launch behind orbv_db_query /
+ * orbv_db_score on the database (inspection only; host-side bookkeeping of the launch, no kernel knows it; all zero before the first
+ * launch -- a call with no queries or no entries launches nothing and leaves the report as it was). */
+#define ORBV_DB_FORM_LDS 1     /* k_db_query<true>: the longest query of the call has at most 4096 words, queries lie in LDS */
+#define ORBV_DB_FORM_GLOBAL 2  /* k_db_query<false>: queries are read from global memory */
+int orbv_debug_last_db_query(const orbv_database* db, int* out4);
 
 /* ---- front end: probes of the multi-GPU exchange ------------------------------------------------------------------------- */
 /* With on != 0 every step of a handle with an exchange records (HIP events) when its search and when its exchange (all-gather +

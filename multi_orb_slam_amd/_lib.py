@@ -443,6 +443,8 @@ def lib():
     L.orbv_create_new_points_resident.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     L.orbv_create_new_points_keyframe.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     L.orbv_debug_last_keyframe_call.argtypes = [vp, vp]
+    L.orbv_debug_last_keyframe_build.argtypes = [vp, vp]
+    L.orbv_debug_last_db_query.argtypes = [vp, vp]
     L.orbv_db_create.argtypes = [i32, i32, vp]
     L.orbv_db_destroy.argtypes = [vp]; L.orbv_db_destroy.restype = None
     L.orbv_db_add.argtypes = [vp, C.c_uint64, vp, vp, i32]

@@ -890,6 +890,12 @@ int orbv_debug_last_keyframe_call(const orbv_workspace* w, int* out4) {
     return ORB_OK;
 }
 
+int orbv_debug_last_keyframe_build(const orbv_workspace* w, int* out5) {
+    MORB_ARG(w != nullptr && out5 != nullptr);
+    for (int i = 0; i < 5; ++i) out5[i] = w->last_kf_build[i];
+    return ORB_OK;
+}
+
 int orbv_search_by_bow(orbv_workspace* w, const orbv_side* a, const orbv_side* b, int mode, int th_low, float nnratio,
                        int check_orientation, int32_t* match, int* nmatches) {
     MORB_ARG(mode == 0 || mode == 1);
@@ -944,6 +950,7 @@ int orbv_keyframe_from_device(orbv_workspace* w, const orbv_vocabulary* v, const
     const int depths = (int)v->lvl_start.size() - 1;
     const int lvl_nodes = (nid_level >= 1 && nid_level < depths) ? v->lvl_start[nid_level + 1] - v->lvl_start[nid_level] : 0;
     const int nbins = 1 + lvl_nodes;
+    for (int i = 0; i < 5; ++i) w->last_kf_build[i] = 0;   // (host bookkeeping, no kernel reads it)
     if (nbins > 4097) { morb::set_error("%d vocabulary nodes at level %d: build this FeatureVector with orbv_bow_vectors", lvl_nodes, nid_level); return ORB_E_CAPACITY; }
     MORB_HIP(hipSetDevice(w->device));
     const int n = s->n;
@@ -996,6 +1003,8 @@ int orbv_keyframe_from_device(orbv_workspace* w, const orbv_vocabulary* v, const
     D.x = tri ? (const float*)(B + o_x) : nullptr; D.y = tri ? (const float*)(B + o_y) : nullptr;
     D.octave = tri ? (const int32_t*)(B + o_oc) : nullptr; D.cam_of = tri ? (const int32_t*)(B + o_cam) : nullptr;
     k->max_node = std::max(1, meta[1]);
+    w->last_kf_build[0] = nbins; w->last_kf_build[1] = (nbins + 1023) / 1024; w->last_kf_build[2] = meta[0]; w->last_kf_build[3] = meta[1];
+    w->last_kf_build[4] = meta[2];
     k->max_cam = tri ? s->n_cams - 1 : 0; k->max_octave = 0;   // octaves stay on the device: the caller vouches for octave < n_levels
     k->d_word = (const uint32_t*)(B + o_w); k->d_node = (const uint32_t*)(B + o_nd);
     *out = k;

@@ -47,6 +47,8 @@ struct orbv_workspace {
     int last_join[4] = {0, 0, 0, 0};  // {waves per node, largest B node, lds_cand, mode} of the last enqueued join (orbv_debug_last_join)
     morb::DevBuf<uint8_t> d_chain;    // orbv_create_new_points_keyframe: the state byte of every feature of `a`, then the round's flags
     int last_kf_call[4] = {0, 0, 0, 0};  // {rounds given, rounds enqueued, kernel launches, synchronisations} of the last such call
+    int last_kf_build[5] = {0, 0, 0, 0, 0};  // {bins, chunks of 1024, FeatureVector nodes, largest node, items} of the last
+                                             // orbv_keyframe_from_device (orbv_debug_last_keyframe_build)
 };
 
 // One frame / keyframe resident in HBM for any number of searches (descriptors, angles, FeatureVector, and the triangulation

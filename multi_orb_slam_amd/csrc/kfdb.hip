@@ -16,6 +16,7 @@
 #include <unordered_map>
 #include <vector>
 #include "../../include/orbv.h"
+#include "../../include/orb_debug.h"
 #include "orb_common.h"
 #include "stage_pack.h"
 
@@ -125,6 +126,7 @@ struct orbv_database {
     DevBuf<uint4> d_move;
     DevBuf<uint8_t> d_q, d_out;
     PinnedBuf<uint8_t> h_q, h_out;
+    int last_query[4] = {0, 0, 0, 0};   // {form, epb, workgroups per query, queries} of the last k_db_query launch (orbv_debug_last_db_query)
 
     int find(uint64_t seq) const {
         auto it = std::lower_bound(entries.begin(), entries.end(), seq, [](const Entry& a, uint64_t s) { return a.seq < s; });
@@ -223,6 +225,8 @@ int run_query(orbv_database* db, const uint2* d_table, int E, int Q, const uint3
     const uint32_t* dq_id = (const uint32_t*)(db->d_q.p + o_id);
     const double* dq_val = (const double*)(db->d_q.p + o_val);
     const int* dq_off = (const int*)(db->d_q.p + o_off);
+    db->last_query[0] = nmax <= DB_LDS_WORDS ? ORBV_DB_FORM_LDS : ORBV_DB_FORM_GLOBAL; db->last_query[1] = epb;   // (host bookkeeping, no kernel reads it)
+    db->last_query[2] = (int)grid.x; db->last_query[3] = Q;
     if (nmax <= DB_LDS_WORDS)
         hipLaunchKernelGGL(k_db_query<true>, grid, dim3(DB_BLOCK), (size_t)nmax * 12, db->stream, db->d_id, db->d_val, d_table, E, epb, dq_id, dq_val,
                            dq_off, nmax, o_score, o_common, o_first);
@@ -312,6 +316,12 @@ int orbv_db_clear(orbv_database* db) {
 }
 
 int orbv_db_count(const orbv_database* db) { return db ? (int)db->entries.size() : 0; }
+
+int orbv_debug_last_db_query(const orbv_database* db, int* out4) {
+    MORB_ARG(db != nullptr && out4 != nullptr);
+    for (int i = 0; i < 4; ++i) out4[i] = db->last_query[i];
+    return ORB_OK;
+}
 
 int orbv_db_query(orbv_database* db, int n_queries, const uint32_t* const* id, const double* const* val, const int* n, int capacity,
                   uint64_t* key, int32_t* common, double* score, int* n_hits) {

@@ -82,6 +82,9 @@ def _bow(b):
     return np.ascontiguousarray(b[0], np.uint32), np.ascontiguousarray(b[1], np.float64)
 
 
+DB_FORM_LDS, DB_FORM_GLOBAL = 1, 2     # ORBV_DB_FORM_* of include/orb_debug.h
+
+
 class KeyFrameDatabase:
     """Resident keyframe database (orbv_database): BowVectors stay in HBM, a query returns the reference's lKFsSharingWords."""
 
@@ -121,6 +124,13 @@ class KeyFrameDatabase:
         check(_lib.lib().orbv_db_query(self._h, Q, pid, pval, ptr(n), cap, ptr(keys), ptr(common), ptr(score), ptr(hits)))
         return [(keys[q * cap:q * cap + hits[q]].copy(), common[q * cap:q * cap + hits[q]].copy(), score[q * cap:q * cap + hits[q]].copy())
                 for q in range(Q)]
+
+    def last_query(self):
+        """(form: DB_FORM_LDS or DB_FORM_GLOBAL, entries per workgroup, workgroups per query, queries) of the last kernel launch behind
+        query / score (orbv_debug_last_db_query)."""
+        out = (C.c_int * 4)()
+        check(_lib.lib().orbv_debug_last_db_query(self._h, out))
+        return tuple(out)
 
     def score(self, bow, keys):
         """L1 score of `bow` against the named entries."""
@@ -262,6 +272,13 @@ class BowSearch:
         k._h = C.c_void_p(); k.n = feats.n_total; k._search = self
         check(_lib.lib().orbv_keyframe_from_device(self._h, vocabulary._h, C.byref(s), levelsup, C.c_void_p(feats.stream) if feats.stream else None, C.byref(k._h)))
         return k
+
+    def last_keyframe_build(self):
+        """(bins, chunks of 1024 bins, FeatureVector nodes, largest node, items) of the last keyframe_from_device here
+        (orbv_debug_last_keyframe_build); all zero after a refused one."""
+        out = (C.c_int * 5)()
+        check(_lib.lib().orbv_debug_last_keyframe_build(self._h, out))
+        return tuple(out)
 
     def keyframe_download(self, k):
         """-> (word_id, node_of_feature, FeatureVector) of a device-built keyframe."""

@@ -6,6 +6,8 @@ multi_orb_slam_amd.synth at test time; the per-feature (word id, weight, node id
 oracle's descent (the descent itself cannot be built from the reference here), and are stored too.
 Also tests/golden/dbow2_ref_live.npz: the same for the cases of test_oracle_matches_reference_classes_live (LIVE_SEEDS x
 LIVE_LEVELSUP), so that the test needs no reference build.
+And tests/golden/dbow2_ref_boundaries.npz: the same for the `ids`, `stop`, `bins` and `fill` worlds of tests/vocab_boundary_worlds.py
+(hand-built trees, regenerated at test time; keys "<world>_<key>"), a file of its own so that the two above keep their bytes.
 Run from the repo root:  python tests/golden/make_dbow2_golden.py"""
 import ctypes as C
 import os
@@ -71,6 +73,25 @@ def live_vectors(L):
     return out
 
 
+BOUNDARY_GROUPS = ("ids", "stop", "bins", "fill")
+
+
+def boundary_vectors(L):
+    """{"<world>_<key>": array} for the boundary worlds whose FeatureVector has something to get wrong: the oracle's (word, weight, node)
+    triples and the reference classes' vectors built from them"""
+    import vocab_boundary_worlds as vw
+    out, orc = {}, {}
+    for w in vw.worlds():
+        if w["group"] not in BOUNDARY_GROUPS:
+            continue
+        V = orc.setdefault(id(w["tree"]), oracle.Vocabulary(w["tree"]))
+        word, node, weight = V.transform(w["feats"], w["levelsup"])
+        ref = ref_build(L, np.ascontiguousarray(word), np.ascontiguousarray(weight), np.ascontiguousarray(node))
+        for k, v in zip(LIVE_KEYS, (word, node, weight) + ref):
+            out["%s_%s" % (w["name"], k)] = v
+    return out
+
+
 def main():
     L = ref_lib()
     out = {"n_cases": np.int32(len(CASES))}
@@ -85,6 +106,7 @@ def main():
         print("case %d: %d features -> %d words, %d nodes" % (i, c["n"], len(bid), len(fn)))
     np.savez_compressed(os.path.join(ROOT, "tests", "golden", "dbow2_ref_vectors.npz"), **out)
     np.savez_compressed(os.path.join(ROOT, "tests", "golden", "dbow2_ref_live.npz"), **live_vectors(L))
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "dbow2_ref_boundaries.npz"), **boundary_vectors(L))
 
 
 if __name__ == "__main__":

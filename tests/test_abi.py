@@ -80,3 +80,29 @@ def test_last_join_report_of_the_binding_is_the_one_of_the_header():
     assert "orbv_debug_last_join" in doc and [doc.index(k) for k in ("waves per node", "largest node", "staged in LDS", "mode")] == sorted(
         doc.index(k) for k in ("waves per node", "largest node", "staged in LDS", "mode"))
     assert "(ctypes.c_int * 4)" in inspect.getsource(vocabulary.BowSearch.last_join).replace("C.c_int", "ctypes.c_int")
+
+
+def test_keyframe_build_and_database_query_reports_of_the_binding_are_those_of_the_header():
+    """BowSearch.last_keyframe_build() and KeyFrameDatabase.last_query() (what the vocabulary and database boundary tests assert their
+    forms with) against orbv_debug_last_keyframe_build / orbv_debug_last_db_query of include/orb_debug.h: the declarations, the fields in
+    the order the bindings name them, the form codes, the exports and the bindings' argument lists."""
+    import inspect
+    from multi_orb_slam_amd import _lib, vocabulary
+    src = open(os.path.join(ROOT, "include", "orb_debug.h")).read()
+    lib = _lib.lib()
+    for fn, sig, header_keys, method, doc_keys, n in (
+            ("orbv_debug_last_keyframe_build", r"\(const orbv_workspace\* w, int\* out5\)", ("bins", "chunks of 1024", "FeatureVector\n * nodes", "largest node", "items"),
+             vocabulary.BowSearch.last_keyframe_build, ("bins", "chunks of 1024", "FeatureVector nodes", "largest node", "items"), 5),
+            ("orbv_debug_last_db_query", r"\(const orbv_database\* db, int\* out4\)", ("form of k_db_query", "entries per workgroup", "workgroups per query", "queries"),
+             vocabulary.KeyFrameDatabase.last_query, ("form", "entries per workgroup", "workgroups per query", "queries"), 4)):
+        decl = re.search(r"/\*((?:(?!\*/).)*)\*/\s*(?:#define[^\n]*\n)*int %s%s;" % (fn, sig), src, re.S)
+        assert decl, fn
+        fields = re.search(r"\{(.*?)\}", decl.group(1), re.S).group(1)
+        order = [fields.index(k) for k in header_keys]
+        assert order == sorted(order), fn
+        assert hasattr(lib, fn) and len(getattr(lib, fn).argtypes) == 2
+        doc = inspect.getdoc(method)
+        assert fn in doc and [doc.index(k) for k in doc_keys] == sorted(doc.index(k) for k in doc_keys)
+        assert "(ctypes.c_int * %d)" % n in inspect.getsource(method).replace("C.c_int", "ctypes.c_int")
+    header = {name: int(val) for name, val in re.findall(r"#define ORBV_DB_FORM_([A-Z]+)\s+(\d+)", src)}
+    assert header == {"LDS": vocabulary.DB_FORM_LDS, "GLOBAL": vocabulary.DB_FORM_GLOBAL} and len(set(header.values())) == 2
