@@ -11,6 +11,7 @@
 // and the two passes of LoopClosing that move map points, in place over the same map (kernels: mapcorrect_dev.h):
 //   orbm_map_correct_sim3         CorrectLoop's step 4.2 (src/LoopClosing.cc:678-710): the ordered claim above, then k_map_correct_sim3
 //   orbm_map_correct_rigid        the update after global BA (:953-989): k_map_stamp_last, k_map_correct_rigid
+// The six writers of a column by slot are one sequence (write_slots: k_map_put_words, k_map_put_flags).
 // The kernels are in localmap_dev.h.  The two host routines (orbm_local_map_vote_host, orbm_local_map_points_host) are the
 // reference's loops on plain arrays: the fallback under MORB_HOST_RESOLVE=1, over the mirror, and the cross-check of the tests.
 // K1, K2 and the marks are pointer logic over the covisibility graph and stay with the caller (host/LocalMap.cc).
@@ -23,68 +24,131 @@
 #include "../../include/orb_debug.h"
 #include "orb_common.h"
 #include "matcher_internal.h"
+#include "stage_pack.h"
 #include "localmap_dev.h"
 #include "mapcorrect_dev.h"
 
 using namespace morb;
 
+namespace {
+
+// What sizes a buffer of the map when the map is created: its capacities, the longest point list, a few words.  ON_DEMAND: nothing
+// then; the calls that use the buffer reserve it.  FEW is four words: the totals of the scan use them, and the one-word cursor of
+// k_map_covis is sized by it too (three words of room it does not use) rather than by a domain of its own.
+enum Domain { ON_DEMAND, POINTS, RECORDS, KEYFRAMES, FEATURES /* keyframes x stride */, LIST, FEW, N_DOMAINS };
+
+// Every buffer of a map enters orbm_map::all where it is declared.  orbm_map_create and orbm_map_destroy walk that list and nothing
+// else, so a buffer is named once: a column cannot be reserved and not cleared, cleared and not mirrored, or left out of the release.
+struct MapBuffer {
+    virtual int create(const size_t* count, hipStream_t st) = 0;   // count[Domain]; enqueues, the caller synchronises
+    virtual void release() = 0;
+};
+using MapBuffers = std::vector<MapBuffer*>;
+
+// A persistent column: count[D] entries in HBM (d; at least one, so a map of no points still has pointers to pass) and in the host
+// mirror (h), both holding FILL in every byte until written -- 0x00: zero, 0xff: -1, {-1, -1} for a record.
+enum { HBM = 1, MIRROR = 2 };
+template <typename T, Domain D, int FILL, int SIDES = HBM | MIRROR>
+struct Column final : MapBuffer {
+    DevBuf<T> d;
+    std::vector<T> h;
+    explicit Column(MapBuffers& all) { all.push_back(this); }
+    int clear(hipStream_t st) {   // back to the initial state, on both sides
+        if (SIDES & HBM) MORB_HIP(hipMemsetAsync(d.p, FILL, d.cap * sizeof(T), st));
+        T v; memset(&v, FILL, sizeof(v));
+        std::fill(h.begin(), h.end(), v);
+        return ORB_OK;
+    }
+    int create(const size_t* count, hipStream_t st) override {
+        int rc = ORB_OK;
+        if ((SIDES & HBM) && (rc = d.reserve(std::max<size_t>(count[D], 1)))) return rc;
+        if (SIDES & MIRROR) h.resize(count[D]);
+        if (clear(st)) { morb::set_error("clearing the resident map failed"); return ORB_E_HIP; }
+        return ORB_OK;
+    }
+    void release() override { d.release(); }
+};
+
+// Per-call scratch and the mapped buffers the kernels write for the host: a DevBuf / PinnedBuf / StageBuf as it is, sized at creation
+// where D says so, released with the map.
+template <typename B, Domain D = ON_DEMAND>
+struct Owned final : B, MapBuffer {
+    explicit Owned(MapBuffers& all) { all.push_back(this); }
+    int create(const size_t* count, hipStream_t) override {
+        if constexpr (D != ON_DEMAND) return B::reserve(count[D]);
+        return ORB_OK;
+    }
+    void release() override { B::release(); }
+};
+
+struct SearchScratch : FrustumScratch { void release() { h_track.release(); } };
+
+}  // namespace
+
 struct orbm_map {
+    MapBuffers all;                  // every Column and Owned below, in the order declared
     orbm_matcher* owner = nullptr;   // compared, never dereferenced after creation
     int device = 0;
     int kf_cap = 0, pt_cap = 0, obs_cap = 0, stride = 0;
     int kf_hw = 0, obs_hw = 0;       // high-water marks: one past the last keyframe / record slot in use
-    // the map in HBM ...
-    DevBuf<orbm_point> d_rows; DevBuf<uint8_t> d_flags; DevBuf<orbm_obs> d_obs; DevBuf<int32_t> d_kf_rows, d_kf_count;
-    // ... and its host mirror
-    std::vector<orbm_point> h_rows; std::vector<uint8_t> h_flags; std::vector<orbm_obs> h_obs;
-    std::vector<int32_t> h_kf_rows, h_kf_count; std::vector<uint8_t> h_kf_bad;
+    // the map: point rows and their flag bytes, observation records, mvpMapPoints of every keyframe as point slots and its length,
+    // the keyframe's bad flag (host only)
+    Column<orbm_point, POINTS, 0x00> rows{all};
+    Column<uint8_t, POINTS, 0x00> flags{all};
+    Column<orbm_obs, RECORDS, 0xff> obs{all};
+    Column<int32_t, FEATURES, 0xff> kf_rows{all};
+    Column<int32_t, KEYFRAMES, 0x00> kf_count{all};
+    Column<uint8_t, KEYFRAMES, 0x00, MIRROR> kf_bad{all};
     // per-point scratch that stays clean between calls: the frame's multiplicity (zero), the least candidate key and the skip mark
-    // (both carry the epoch of the call that wrote them)
-    DevBuf<int32_t> d_mult; DevBuf<unsigned long long> d_first; DevBuf<uint32_t> d_mark;
-    std::vector<uint32_t> h_mark;    // host twin of d_mark (fallback only)
+    // (both carry the epoch of the call that wrote them; the mark's host twin serves the fallback only)
+    Column<int32_t, POINTS, 0x00, HBM> mult{all};
+    Column<unsigned long long, POINTS, 0xff, HBM> first{all};
+    Column<uint32_t, POINTS, 0x00> mark{all};
     uint32_t epoch = 0;
-    DevBuf<int32_t> d_votes, d_block, d_list, d_total;
-    PinnedBuf<int32_t> h_votes, h_list, h_total;   // what the kernels write for the host: mapped pinned
-    StageBuf stage;                  // the host-written inputs of a call
+    Owned<DevBuf<int32_t>, KEYFRAMES> d_votes{all};
+    Owned<DevBuf<int32_t>, LIST> d_list{all};
+    Owned<DevBuf<int32_t>, FEW> d_total{all};
+    Owned<DevBuf<int32_t>> d_block{all};
+    Owned<PinnedBuf<int32_t>, KEYFRAMES> h_votes{all};   // what the kernels write for the host: mapped pinned
+    Owned<PinnedBuf<int32_t>, LIST> h_list{all};
+    Owned<PinnedBuf<int32_t>, FEW> h_total{all};
+    Owned<StageBuf> stage{all};      // the host-written inputs of a call
     std::vector<int32_t> list;       // the last point list (host copy; the search's fallback reads it)
     int list_n = -1;                 // -1: no list
-    FrustumScratch scr;
+    Owned<SearchScratch> scr{all};
     int last[4] = {0, 0, 0, 0};
-    // covisibility and culling: the record's feature, the feature bytes and camera-1 count of a keyframe, the point's n_obs ...
-    DevBuf<int32_t> d_obs_feat, d_nobs, d_kf_ncam1; DevBuf<uint8_t> d_kf_feat;
-    std::vector<int32_t> h_obs_feat, h_nobs, h_kf_ncam1; std::vector<uint8_t> h_kf_feat;
+    // covisibility and culling: the record's feature, the point's n_obs, the camera-1 count and the feature bytes of a keyframe ...
+    Column<int32_t, RECORDS, 0x00> obs_feat{all};
+    Column<int32_t, POINTS, 0x00> nobs{all};
+    Column<int32_t, KEYFRAMES, 0x00> kf_ncam1{all};
+    Column<uint8_t, FEATURES, 0x00> kf_feat{all};
     // ... and the chain from a point to its live records, stale after any record write
-    DevBuf<int32_t> d_head, d_next, d_cursor;
+    Column<int32_t, POINTS, 0xff, HBM> head{all};
+    Column<int32_t, RECORDS, 0xff, HBM> next{all};
+    Owned<DevBuf<int32_t>, FEW> d_cursor{all};
     bool index_dirty = false;
-    PinnedBuf<int32_t> h_span, h_counts; PinnedBuf<orbm_covis_entry> h_entries;
+    Owned<PinnedBuf<int32_t>> h_span{all}, h_counts{all};
+    Owned<PinnedBuf<orbm_covis_entry>> h_entries{all};
     int last_cov[4] = {0, 0, 0, 0};
     // loop correction: the point's reference keyframe slot (-1: never written), the point high-water mark, the kept entries of a Sim3
     // correction and what either correction leaves for the host (mapped)
-    DevBuf<int32_t> d_ref; std::vector<int32_t> h_ref;
+    Column<int32_t, POINTS, 0xff> ref{all};
     int pt_hw = 0;
-    DevBuf<orbm_correct_entry> d_centries;
-    PinnedBuf<orbm_correct_entry> h_centries; PinnedBuf<float> h_cpos; PinnedBuf<uint8_t> h_cstatus;
+    Owned<DevBuf<orbm_correct_entry>> d_centries{all};
+    Owned<PinnedBuf<orbm_correct_entry>> h_centries{all};
+    Owned<PinnedBuf<float>> h_cpos{all};
+    Owned<PinnedBuf<uint8_t>> h_cstatus{all};
     std::vector<uint32_t> h_seen; uint32_t seen_epoch = 0;   // a listed slot of this call (host; the check that the slots are distinct)
     int last_cor[4] = {0, 0, 0, 0};
 };
 
 namespace {
 
-void release_all(orbm_map* p) {
-    p->d_rows.release(); p->d_flags.release(); p->d_obs.release(); p->d_kf_rows.release(); p->d_kf_count.release();
-    p->d_mult.release(); p->d_first.release(); p->d_mark.release(); p->d_votes.release(); p->d_block.release(); p->d_list.release();
-    p->d_obs_feat.release(); p->d_nobs.release(); p->d_kf_ncam1.release(); p->d_kf_feat.release(); p->d_head.release(); p->d_next.release();
-    p->d_ref.release(); p->d_centries.release(); p->h_centries.release(); p->h_cpos.release(); p->h_cstatus.release();
-    p->d_cursor.release(); p->h_span.release(); p->h_counts.release(); p->h_entries.release();
-    p->d_total.release(); p->h_votes.release(); p->h_list.release(); p->h_total.release(); p->stage.release(); p->scr.h_track.release();
-}
-
 // A new epoch for the keys of k_map_first and the marks of k_map_mark; the arrays are cleared when the counter would wrap.
 int next_epoch(orbm_matcher* m, orbm_map* p) {
     if (p->epoch >= 0xfffffff0u) {
-        MORB_HIP(hipMemsetAsync(p->d_first.p, 0xff, (size_t)std::max(p->pt_cap, 1) * sizeof(unsigned long long), m->stream));
-        MORB_HIP(hipMemsetAsync(p->d_mark.p, 0, (size_t)std::max(p->pt_cap, 1) * sizeof(uint32_t), m->stream));
-        std::fill(p->h_mark.begin(), p->h_mark.end(), 0u);
+        int rc;
+        if ((rc = p->first.clear(m->stream)) || (rc = p->mark.clear(m->stream))) return rc;
         p->epoch = 0;
     }
     ++p->epoch;
@@ -97,7 +161,109 @@ int check_slots(const int32_t* s, int n, int lo, int cap, const char* what) {
     return ORB_OK;
 }
 
+int copy_last(const orbm_map* p, int (orbm_map::*last)[4], int* out4) {   // the three orbm_debug_last_* of a map
+    MORB_ARG(p && out4);
+    for (int k = 0; k < 4; ++k) out4[k] = (p->*last)[k];
+    return ORB_OK;
+}
+
 inline unsigned blocks_of(long long n) { return (unsigned)((n + MAP_BLOCK - 1) / MAP_BLOCK); }
+
+// What one writer asks of write_slots beyond its column, slots and values.
+struct SlotWrite {
+    const char* what;                // the slots' name in an error
+    int* hw = nullptr;               // the high-water mark the write raises (one past the greatest slot), if any
+    bool with_flags = false;         // orbm_map_write_points: the rows' flag bytes ride along (k_map_put_flags) ...
+    const uint8_t* flags = nullptr;  // ... from here, or zeros
+    int offset = 0;                  // the entry's first word in its row
+};
+struct NoCheck { int operator()() const { return ORB_OK; } };
+struct AsGiven { void operator()(int, void*) const {} };
+
+// The one way a column is written by slot: n entries of `words` 32-bit words into words [offset, offset + words) of rows slots[i] of
+// `col`, in HBM and in the mirror, in this order --
+//   1  validate: the slots against the column's capacity, then check_values()
+//   2  reserve the stage: up to here a refused call has changed nothing
+//   3  write the mirror, entry by entry: values[i] (values == NULL: the mirror holds the entries already), then settle(i, the
+//      mirror's entry) for what a writer changes beside the bytes, and *hw raised past the slot
+//   4  stage the slots, and the values FROM THE MIRROR: a slot named twice is staged twice with its last entry, so the order in which
+//      the lanes store does not matter
+//   5  publish, 6  launch k_map_put_words, and synchronise.
+// `words` is a constant so that the copies have a fixed size: the stage is write-combined memory, and a copy whose length is known only
+// at run time made orbm_map_write_points a quarter slower (profiles/r29/notes_resident_map.md, first set).
+// Who raises what:  orbm_map_write_points, _positions, _point_ref raise pt_hw;  _point_nobs raises nothing ("The resident
+// map's columns");  _observations raises obs_hw and, in its settle, kf_hw for a live record;  _observation_features and the host
+// routes of the corrections (put_positions) raise nothing.
+template <int words, typename T, Domain D, int FILL, typename Check = NoCheck, typename Settle = AsGiven>
+int write_slots(orbm_matcher* m, orbm_map* p, Column<T, D, FILL>& col, const int32_t* slots, int n, const void* values, const SlotWrite& w,
+                Check check_values = Check(), Settle settle = Settle()) {
+    static_assert(sizeof(T) % 4 == 0, "a column of 32-bit words");
+    int rc;
+    if ((rc = check_slots(slots, n, 0, (int)col.h.size(), w.what)) || (rc = check_values())) return rc;
+    if (n == 0) return ORB_OK;
+    MORB_HIP(hipSetDevice(m->device));
+    StagePack pk;
+    const int i_slots = pk.add(slots, (size_t)n * 4), i_values = pk.add_in_place((size_t)n * words * 4);
+    const int i_flags = pk.add_in_place(w.with_flags ? (size_t)n : 0);
+    const StagePack::Block blk = pk.open(p->stage, &rc);
+    if (rc) return rc;
+    uint8_t* mirror = (uint8_t*)col.h.data() + (size_t)w.offset * 4;
+    for (int i = 0; i < n; ++i) {
+        uint8_t* entry = mirror + (size_t)slots[i] * sizeof(T);
+        if (values) memcpy(entry, (const uint8_t*)values + (size_t)i * words * 4, (size_t)words * 4);
+        settle(i, entry);
+        if (w.with_flags) p->flags.h[(size_t)slots[i]] = w.flags ? w.flags[i] : 0;
+        if (w.hw) *w.hw = std::max(*w.hw, slots[i] + 1);
+    }
+    uint8_t* staged = blk.host<uint8_t>(i_values); uint8_t* fl = blk.host<uint8_t>(i_flags);
+    for (int i = 0; i < n; ++i) {
+        memcpy(staged + (size_t)i * words * 4, mirror + (size_t)slots[i] * sizeof(T), (size_t)words * 4);
+        if (w.with_flags) fl[i] = p->flags.h[(size_t)slots[i]];
+    }
+    blk.publish();
+    hipLaunchKernelGGL(k_map_put_words, dim3(blocks_of((long long)n * words)), dim3(MAP_BLOCK), 0, m->stream, blk.dev<uint32_t>(i_values),
+                       blk.dev<int32_t>(i_slots), n, words, (int)(sizeof(T) / 4), w.offset, (uint32_t*)col.d.p);
+    if (w.with_flags)
+        hipLaunchKernelGGL(k_map_put_flags, dim3(blocks_of(n)), dim3(MAP_BLOCK), 0, m->stream, blk.dev<uint8_t>(i_flags),
+                           blk.dev<int32_t>(i_slots), n, p->flags.d.p);
+    MORB_HIP(hipGetLastError());
+    MORB_HIP(hipStreamSynchronize(m->stream));
+    return ORB_OK;
+}
+
+// One caller array of slots as the whole staged block of a call: copied, published, *dev its device address.
+int stage_slots(orbm_map* p, const int32_t* v, int n, const int32_t** dev) {
+    int rc;
+    StagePack pk;
+    const int i = pk.add(v, (size_t)n * 4);
+    const StagePack::Block blk = pk.open(p->stage, &rc);
+    if (rc) return rc;
+    blk.publish();
+    *dev = blk.dev<int32_t>(i);
+    return ORB_OK;
+}
+
+// The ordered claim over a list of keyframe slots (UpdateLocalPoints' and CorrectLoop's "the first keyframe that holds a point takes
+// it"): block b covers the features [256 (b % bpk), +256) of listed keyframe b / bpk.  The shape comes from the mirror's row lengths.
+// reserve() goes with the caller's other reserves, before anything is enqueued; enqueue() leaves the least key of every point in
+// `first` and the exclusive prefix sums of the kept candidates in d_block, their total in d_total / h_total, for the scatter of the
+// caller (k_map_scatter, k_map_correct_scatter) to place them.
+struct Claim {
+    long long cand = 0;              // row entries of the listed keyframes
+    int fmax = 0, bpk = 0, nb = 0;   // the longest row, blocks per keyframe, blocks
+    Claim(const orbm_map* p, const int32_t* kfs, int n) {
+        for (int j = 0; j < n; ++j) { const int c = p->kf_count.h[(size_t)kfs[j]]; cand += c; fmax = std::max(fmax, c); }
+        bpk = (fmax + MAP_BLOCK - 1) / MAP_BLOCK; nb = n * bpk;
+    }
+    int reserve(orbm_map* p) const { return p->d_block.reserve((size_t)nb); }
+    void enqueue(orbm_matcher* m, orbm_map* p, const int32_t* d_kfs, uint32_t epoch) const {
+        hipLaunchKernelGGL(k_map_first, dim3(nb), dim3(MAP_BLOCK), 0, m->stream, (const int32_t*)p->kf_rows.d.p, (const int32_t*)p->kf_count.d.p,
+                           d_kfs, p->stride, bpk, (const uint8_t*)p->flags.d.p, p->first.d.p, epoch);
+        hipLaunchKernelGGL(k_map_count, dim3(nb), dim3(MAP_BLOCK), 0, m->stream, (const int32_t*)p->kf_rows.d.p, (const int32_t*)p->kf_count.d.p,
+                           d_kfs, p->stride, bpk, (const uint8_t*)p->flags.d.p, (const unsigned long long*)p->first.d.p, epoch, p->d_block.p);
+        hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(MAP_SCAN_LANES), 0, m->stream, p->d_block.p, nb, p->d_total.p, p->h_total.dp);
+    }
+};
 
 }  // namespace
 
@@ -157,44 +323,15 @@ int orbm_map_create(orbm_matcher* m, int kf_capacity, int point_capacity, int ob
     orbm_map* p = new orbm_map;
     p->owner = m; p->device = m->device;
     p->kf_cap = kf_capacity; p->pt_cap = point_capacity; p->obs_cap = obs_capacity; p->stride = features_per_keyframe;
-    const size_t np = (size_t)std::max(point_capacity, 1), no = (size_t)std::max(obs_capacity, 1);
-    const size_t nk = (size_t)kf_capacity, nr = nk * (size_t)features_per_keyframe;
-    int rc;
-    if ((rc = p->d_rows.reserve(np)) || (rc = p->d_flags.reserve(np)) || (rc = p->d_obs.reserve(no)) || (rc = p->d_kf_rows.reserve(nr)) ||
-        (rc = p->d_kf_count.reserve(nk)) || (rc = p->d_mult.reserve(np)) || (rc = p->d_first.reserve(np)) || (rc = p->d_mark.reserve(np)) ||
-        (rc = p->d_votes.reserve(nk)) || (rc = p->d_list.reserve(ORBM_MAX_POINTS)) || (rc = p->d_total.reserve(4)) ||
-        (rc = p->h_votes.reserve(nk)) || (rc = p->h_list.reserve(ORBM_MAX_POINTS)) || (rc = p->h_total.reserve(4)) ||
-        (rc = p->d_obs_feat.reserve(no)) || (rc = p->d_nobs.reserve(np)) || (rc = p->d_kf_ncam1.reserve(nk)) || (rc = p->d_kf_feat.reserve(nr)) ||
-        (rc = p->d_head.reserve(np)) || (rc = p->d_next.reserve(no)) || (rc = p->d_cursor.reserve(1)) ||
-        (rc = p->d_ref.reserve(np))) {
-        release_all(p); delete p;
-        return rc;
-    }
+    size_t count[N_DOMAINS] = {};
+    count[POINTS] = (size_t)point_capacity; count[RECORDS] = (size_t)obs_capacity; count[KEYFRAMES] = (size_t)kf_capacity;
+    count[FEATURES] = (size_t)kf_capacity * (size_t)features_per_keyframe; count[LIST] = ORBM_MAX_POINTS; count[FEW] = 4;
     // empty on both sides: rows of zeros that are not bad, free records, keyframes without points, clean scratch
-    hipStream_t st = m->stream;
-    if (hipMemsetAsync(p->d_rows.p, 0, np * sizeof(orbm_point), st) != hipSuccess || hipMemsetAsync(p->d_flags.p, 0, np, st) != hipSuccess ||
-        hipMemsetAsync(p->d_obs.p, 0xff, no * sizeof(orbm_obs), st) != hipSuccess ||
-        hipMemsetAsync(p->d_kf_rows.p, 0xff, nr * sizeof(int32_t), st) != hipSuccess ||
-        hipMemsetAsync(p->d_kf_count.p, 0, nk * sizeof(int32_t), st) != hipSuccess ||
-        hipMemsetAsync(p->d_mult.p, 0, np * sizeof(int32_t), st) != hipSuccess ||
-        hipMemsetAsync(p->d_first.p, 0xff, np * sizeof(unsigned long long), st) != hipSuccess ||
-        hipMemsetAsync(p->d_mark.p, 0, np * sizeof(uint32_t), st) != hipSuccess ||
-        hipMemsetAsync(p->d_obs_feat.p, 0, no * sizeof(int32_t), st) != hipSuccess || hipMemsetAsync(p->d_nobs.p, 0, np * sizeof(int32_t), st) != hipSuccess ||
-        hipMemsetAsync(p->d_kf_ncam1.p, 0, nk * sizeof(int32_t), st) != hipSuccess || hipMemsetAsync(p->d_kf_feat.p, 0, nr, st) != hipSuccess ||
-        hipMemsetAsync(p->d_head.p, 0xff, np * sizeof(int32_t), st) != hipSuccess ||
-        hipMemsetAsync(p->d_ref.p, 0xff, np * sizeof(int32_t), st) != hipSuccess ||
-        hipMemsetAsync(p->d_next.p, 0xff, no * sizeof(int32_t), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        morb::set_error("clearing the resident map failed");
-        release_all(p); delete p;
-        return ORB_E_HIP;
-    }
-    orbm_point zero; memset(&zero, 0, sizeof(zero));
-    p->h_rows.assign((size_t)point_capacity, zero); p->h_flags.assign((size_t)point_capacity, 0);
-    p->h_obs.assign((size_t)obs_capacity, orbm_obs{-1, -1});
-    p->h_kf_rows.assign(nr, -1); p->h_kf_count.assign(nk, 0); p->h_kf_bad.assign(nk, 0);
-    p->h_mark.assign((size_t)point_capacity, 0u);
-    p->h_obs_feat.assign((size_t)obs_capacity, 0); p->h_nobs.assign((size_t)point_capacity, 0); p->h_kf_ncam1.assign(nk, 0); p->h_kf_feat.assign(nr, 0);
-    p->h_ref.assign((size_t)point_capacity, -1);
+    int rc = ORB_OK;
+    for (MapBuffer* b : p->all)
+        if ((rc = b->create(count, m->stream))) break;
+    if (!rc && hipStreamSynchronize(m->stream) != hipSuccess) { morb::set_error("clearing the resident map failed"); rc = ORB_E_HIP; }
+    if (rc) { orbm_map_destroy(p); return rc; }
     *out = p;
     return ORB_OK;
 }
@@ -202,7 +339,7 @@ int orbm_map_create(orbm_matcher* m, int kf_capacity, int point_capacity, int ob
 void orbm_map_destroy(orbm_map* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
-    release_all(p);
+    for (MapBuffer* b : p->all) b->release();
     delete p;
 }
 
@@ -210,77 +347,38 @@ int orbm_map_keyframes(const orbm_map* p) { return p ? p->kf_hw : ORB_E_ARG; }
 
 int orbm_map_keyframe_bad(const orbm_map* p, int kf) {
     MORB_ARG(p && kf >= 0 && kf < p->kf_cap);
-    return p->h_kf_bad[(size_t)kf];
+    return p->kf_bad.h[(size_t)kf];
 }
 
-int orbm_debug_last_local_map(const orbm_map* p, int* out4) {
-    MORB_ARG(p && out4);
-    for (int k = 0; k < 4; ++k) out4[k] = p->last[k];
-    return ORB_OK;
-}
+int orbm_debug_last_local_map(const orbm_map* p, int* out4) { return copy_last(p, &orbm_map::last, out4); }
 
 int orbm_map_write_points(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n, const orbm_point* rows, const uint8_t* flags) {
     MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || (slots && rows)));
-    int rc;
-    if ((rc = check_slots(slots, n, 0, p->pt_cap, "point slot"))) return rc;
-    if (n == 0) return ORB_OK;
-    MORB_HIP(hipSetDevice(m->device));
     static_assert(sizeof(orbm_point) == 68, "orbm_point is 17 words");
-    const size_t off_rows = (size_t)n * 4, off_flags = off_rows + (size_t)n * sizeof(orbm_point);
-    if ((rc = p->stage.reserve(off_flags + (size_t)n + 16))) return rc;
-    for (int i = 0; i < n; ++i) {
-        p->h_rows[(size_t)slots[i]] = rows[i]; p->h_flags[(size_t)slots[i]] = flags ? flags[i] : 0;
-        p->pt_hw = std::max(p->pt_hw, slots[i] + 1);
-    }
-    // staged from the mirror: a slot named twice is staged twice with its last entry, so the order of the lanes does not matter
-    memcpy(p->stage.p, slots, (size_t)n * 4);
-    for (int i = 0; i < n; ++i) {
-        memcpy(p->stage.p + off_rows + (size_t)i * sizeof(orbm_point), &p->h_rows[(size_t)slots[i]], sizeof(orbm_point));
-        p->stage.p[off_flags + (size_t)i] = p->h_flags[(size_t)slots[i]];
-    }
-    p->stage.publish();
-    const int words = (int)(sizeof(orbm_point) / 4);
-    hipLaunchKernelGGL(k_map_put_words, dim3(blocks_of((long long)n * words)), dim3(MAP_BLOCK), 0, m->stream,
-                       (const uint32_t*)(p->stage.dp + off_rows), (const int32_t*)p->stage.dp, n, words, (uint32_t*)p->d_rows.p);
-    hipLaunchKernelGGL(k_map_put_flags, dim3(blocks_of(n)), dim3(MAP_BLOCK), 0, m->stream, (const uint8_t*)(p->stage.dp + off_flags),
-                       (const int32_t*)p->stage.dp, n, p->d_flags.p);
-    MORB_HIP(hipGetLastError());
-    MORB_HIP(hipStreamSynchronize(m->stream));
-    return ORB_OK;
+    SlotWrite w{"point slot", &p->pt_hw};
+    w.with_flags = true; w.flags = flags;
+    return write_slots<17>(m, p, p->rows, slots, n, rows, w);
 }
 
 int orbm_map_write_observations(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n, const orbm_obs* records) {
     MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || (slots && records)));
-    int rc;
-    if ((rc = check_slots(slots, n, 0, p->obs_cap, "record slot"))) return rc;
-    for (int i = 0; i < n; ++i) {
-        if (records[i].point < 0) continue;
-        if (records[i].point >= p->pt_cap || records[i].keyframe < 0 || records[i].keyframe >= p->kf_cap) {
-            morb::set_error("record %d names point %d, keyframe %d: outside the map (%d points, %d keyframes)", i, records[i].point,
-                            records[i].keyframe, p->pt_cap, p->kf_cap);
-            return ORB_E_CAPACITY;
+    auto check_records = [&]() {
+        for (int i = 0; i < n; ++i) {
+            if (records[i].point < 0) continue;
+            if (records[i].point >= p->pt_cap || records[i].keyframe < 0 || records[i].keyframe >= p->kf_cap) {
+                morb::set_error("record %d names point %d, keyframe %d: outside the map (%d points, %d keyframes)", i, records[i].point,
+                                records[i].keyframe, p->pt_cap, p->kf_cap);
+                return (int)ORB_E_CAPACITY;
+            }
         }
-    }
-    if (n == 0) return ORB_OK;
-    MORB_HIP(hipSetDevice(m->device));
-    const size_t off_rec = (size_t)n * 4;
-    if ((rc = p->stage.reserve(off_rec + (size_t)n * sizeof(orbm_obs) + 16))) return rc;
-    for (int i = 0; i < n; ++i) {
-        orbm_obs r = records[i];
-        if (r.point < 0) { r.point = -1; r.keyframe = -1; }   // one form of a free record
-        else p->kf_hw = std::max(p->kf_hw, r.keyframe + 1);
-        p->h_obs[(size_t)slots[i]] = r;
-        p->obs_hw = std::max(p->obs_hw, slots[i] + 1);
-    }
-    p->index_dirty = true;   // the chain from a point to its records is rebuilt by the next counting call
-    memcpy(p->stage.p, slots, (size_t)n * 4);
-    for (int i = 0; i < n; ++i) memcpy(p->stage.p + off_rec + (size_t)i * sizeof(orbm_obs), &p->h_obs[(size_t)slots[i]], sizeof(orbm_obs));
-    p->stage.publish();
-    hipLaunchKernelGGL(k_map_put_words, dim3(blocks_of((long long)n * 2)), dim3(MAP_BLOCK), 0, m->stream,
-                       (const uint32_t*)(p->stage.dp + off_rec), (const int32_t*)p->stage.dp, n, 2, (uint32_t*)p->d_obs.p);
-    MORB_HIP(hipGetLastError());
-    MORB_HIP(hipStreamSynchronize(m->stream));
-    return ORB_OK;
+        return (int)ORB_OK;
+    };
+    auto settle = [&](int i, void* entry) {
+        if (records[i].point < 0) memset(entry, 0xff, sizeof(orbm_obs));   // one form of a free record: {-1, -1}
+        else p->kf_hw = std::max(p->kf_hw, records[i].keyframe + 1);
+        p->index_dirty = true;   // the chain from a point to its records is rebuilt by the next counting call
+    };
+    return write_slots<2>(m, p, p->obs, slots, n, records, SlotWrite{"record slot", &p->obs_hw}, check_records, settle);
 }
 
 int orbm_map_write_keyframe(orbm_matcher* m, orbm_map* p, int kf, const int32_t* point_of_feature, int n_features, int bad) {
@@ -292,22 +390,22 @@ int orbm_map_write_keyframe(orbm_matcher* m, orbm_map* p, int kf, const int32_t*
     for (int f = 0; f < n_features; ++f)
         if (point_of_feature[f] >= p->pt_cap) { morb::set_error("feature %d holds point slot %d of %d", f, point_of_feature[f], p->pt_cap); return ORB_E_CAPACITY; }
     MORB_HIP(hipSetDevice(m->device));
-    int32_t* row = p->h_kf_rows.data() + (size_t)kf * p->stride;
+    int32_t* row = p->kf_rows.h.data() + (size_t)kf * p->stride;
     for (int f = 0; f < n_features; ++f) row[f] = point_of_feature[f] < 0 ? -1 : point_of_feature[f];
     for (int f = n_features; f < p->stride; ++f) row[f] = -1;
     // the old row's tail is dead once the count says so: send what the new count covers, and the count
     const int n_send = std::max(n_features, 1);
-    p->h_kf_count[(size_t)kf] = n_features; p->h_kf_bad[(size_t)kf] = bad ? 1 : 0;
+    p->kf_count.h[(size_t)kf] = n_features; p->kf_bad.h[(size_t)kf] = bad ? 1 : 0;
     p->kf_hw = std::max(p->kf_hw, kf + 1);
-    MORB_HIP(hipMemcpyAsync(p->d_kf_rows.p + (size_t)kf * p->stride, row, (size_t)n_send * 4, hipMemcpyHostToDevice, m->stream));
-    MORB_HIP(hipMemcpyAsync(p->d_kf_count.p + kf, &p->h_kf_count[(size_t)kf], 4, hipMemcpyHostToDevice, m->stream));
+    MORB_HIP(hipMemcpyAsync(p->kf_rows.d.p + (size_t)kf * p->stride, row, (size_t)n_send * 4, hipMemcpyHostToDevice, m->stream));
+    MORB_HIP(hipMemcpyAsync(p->kf_count.d.p + kf, &p->kf_count.h[(size_t)kf], 4, hipMemcpyHostToDevice, m->stream));
     MORB_HIP(hipStreamSynchronize(m->stream));
     return ORB_OK;
 }
 
 int orbm_map_set_keyframe_bad(orbm_matcher* m, orbm_map* p, int kf, int bad) {
     MORB_ARG(m && p && p->owner == m && kf >= 0 && kf < p->kf_cap);
-    p->h_kf_bad[(size_t)kf] = bad ? 1 : 0;
+    p->kf_bad.h[(size_t)kf] = bad ? 1 : 0;
     p->kf_hw = std::max(p->kf_hw, kf + 1);
     return ORB_OK;
 }
@@ -320,25 +418,23 @@ int orbm_map_vote(orbm_matcher* m, orbm_map* p, const int32_t* frame_points, int
     p->last[1] = p->obs_hw;
     if (m->host_resolve) {   // MORB_HOST_RESOLVE=1: the host routine over the mirror
         p->last[0] = 0;
-        return orbm_local_map_vote_host(p->h_obs.data(), p->obs_hw, p->h_flags.data(), p->pt_cap, frame_points, n_features, nk, votes);
+        return orbm_local_map_vote_host(p->obs.h.data(), p->obs_hw, p->flags.h.data(), p->pt_cap, frame_points, n_features, nk, votes);
     }
     p->last[0] = 1;
     if (nk == 0) return ORB_OK;
     if (n_features == 0 || p->obs_hw == 0) { for (int k = 0; k < nk; ++k) votes[k] = 0; return ORB_OK; }
     MORB_HIP(hipSetDevice(m->device));
     int rc;
-    if ((rc = p->stage.reserve((size_t)n_features * 4 + 16))) return rc;
-    memcpy(p->stage.p, frame_points, (size_t)n_features * 4);
-    p->stage.publish();
-    const int32_t* d_fp = (const int32_t*)p->stage.dp;
+    const int32_t* d_fp;
+    if ((rc = stage_slots(p, frame_points, n_features, &d_fp))) return rc;
     const unsigned g = blocks_of(std::max(n_features, nk));
-    hipLaunchKernelGGL(k_map_mult, dim3(g), dim3(MAP_BLOCK), 0, m->stream, d_fp, n_features, (const uint8_t*)p->d_flags.p, p->d_mult.p,
+    hipLaunchKernelGGL(k_map_mult, dim3(g), dim3(MAP_BLOCK), 0, m->stream, d_fp, n_features, (const uint8_t*)p->flags.d.p, p->mult.d.p,
                        p->d_votes.p, nk);
     const long long per_block = (long long)MAP_BLOCK * MAP_VOTE_PER_LANE;
     const unsigned gv = (unsigned)std::min<long long>(MAP_VOTE_MAX_BLOCKS, (p->obs_hw + per_block - 1) / per_block);
-    hipLaunchKernelGGL(k_map_vote, dim3(gv), dim3(MAP_BLOCK), (size_t)nk * sizeof(int32_t), m->stream, (const orbm_obs*)p->d_obs.p, p->obs_hw,
-                       (const int32_t*)p->d_mult.p, p->d_votes.p, nk);
-    hipLaunchKernelGGL(k_map_vote_out, dim3(g), dim3(MAP_BLOCK), 0, m->stream, d_fp, n_features, p->d_mult.p, (const int32_t*)p->d_votes.p, nk,
+    hipLaunchKernelGGL(k_map_vote, dim3(gv), dim3(MAP_BLOCK), (size_t)nk * sizeof(int32_t), m->stream, (const orbm_obs*)p->obs.d.p, p->obs_hw,
+                       (const int32_t*)p->mult.d.p, p->d_votes.p, nk);
+    hipLaunchKernelGGL(k_map_vote_out, dim3(g), dim3(MAP_BLOCK), 0, m->stream, d_fp, n_features, p->mult.d.p, (const int32_t*)p->d_votes.p, nk,
                        p->h_votes.dp);
     MORB_HIP(hipGetLastError());
     MORB_HIP(hipStreamSynchronize(m->stream));
@@ -352,33 +448,25 @@ int orbm_map_local_points(orbm_matcher* m, orbm_map* p, const int32_t* local_kfs
     int rc;
     if (check_slots(local_kfs, n_local, 0, p->kf_hw, "local keyframe")) return ORB_E_ARG;
     p->list_n = -1; *n_list = 0;
-    long long cand = 0; int fmax = 0;
-    for (int j = 0; j < n_local; ++j) { const int c = p->h_kf_count[(size_t)local_kfs[j]]; cand += c; fmax = std::max(fmax, c); }
-    p->last[2] = (int)std::min<long long>(cand, 0x7fffffff); p->last[3] = 0;
+    const Claim claim(p, local_kfs, n_local);
+    p->last[2] = (int)std::min<long long>(claim.cand, 0x7fffffff); p->last[3] = 0;
     p->list.resize(ORBM_MAX_POINTS);
     int n = 0;
     if (m->host_resolve) {   // MORB_HOST_RESOLVE=1: the host routine over the mirror (the list still goes to HBM for the search's kernels)
         p->last[0] = 0;
-        rc = orbm_local_map_points_host(p->h_kf_rows.data(), p->h_kf_count.data(), p->kf_hw, p->stride, p->h_flags.data(), p->pt_cap,
+        rc = orbm_local_map_points_host(p->kf_rows.h.data(), p->kf_count.h.data(), p->kf_hw, p->stride, p->flags.h.data(), p->pt_cap,
                                         local_kfs, n_local, p->list.data(), ORBM_MAX_POINTS, &n);
         if (rc) return rc;
     } else {
         p->last[0] = 1;
-        if (fmax > 0) {
+        if (claim.fmax > 0) {
             MORB_HIP(hipSetDevice(m->device));
-            const int bpk = (fmax + MAP_BLOCK - 1) / MAP_BLOCK, nb = n_local * bpk;
-            if ((rc = p->stage.reserve((size_t)n_local * 4 + 16)) || (rc = p->d_block.reserve((size_t)nb)) || (rc = next_epoch(m, p))) return rc;
-            memcpy(p->stage.p, local_kfs, (size_t)n_local * 4);
-            p->stage.publish();
-            const int32_t* d_kfs = (const int32_t*)p->stage.dp;
-            const int32_t *rows = p->d_kf_rows.p, *cnt = p->d_kf_count.p;
-            const uint8_t* fl = p->d_flags.p;
-            hipLaunchKernelGGL(k_map_first, dim3(nb), dim3(MAP_BLOCK), 0, m->stream, rows, cnt, d_kfs, p->stride, bpk, fl, p->d_first.p, p->epoch);
-            hipLaunchKernelGGL(k_map_count, dim3(nb), dim3(MAP_BLOCK), 0, m->stream, rows, cnt, d_kfs, p->stride, bpk, fl,
-                               (const unsigned long long*)p->d_first.p, p->epoch, p->d_block.p);
-            hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(MAP_SCAN_LANES), 0, m->stream, p->d_block.p, nb, p->d_total.p, p->h_total.dp);
-            hipLaunchKernelGGL(k_map_scatter, dim3(nb), dim3(MAP_BLOCK), 0, m->stream, rows, cnt, d_kfs, p->stride, bpk, fl,
-                               (const unsigned long long*)p->d_first.p, p->epoch, (const int32_t*)p->d_block.p, p->d_list.p, p->h_list.dp,
+            const int32_t* d_kfs;
+            if ((rc = stage_slots(p, local_kfs, n_local, &d_kfs)) || (rc = claim.reserve(p)) || (rc = next_epoch(m, p))) return rc;
+            claim.enqueue(m, p, d_kfs, p->epoch);
+            hipLaunchKernelGGL(k_map_scatter, dim3(claim.nb), dim3(MAP_BLOCK), 0, m->stream, (const int32_t*)p->kf_rows.d.p,
+                               (const int32_t*)p->kf_count.d.p, d_kfs, p->stride, claim.bpk, (const uint8_t*)p->flags.d.p,
+                               (const unsigned long long*)p->first.d.p, p->epoch, (const int32_t*)p->d_block.p, p->d_list.p, p->h_list.dp,
                                (int)ORBM_MAX_POINTS);
             MORB_HIP(hipGetLastError());
             MORB_HIP(hipStreamSynchronize(m->stream));
@@ -404,13 +492,13 @@ void host_skip(void* c, uint8_t* out) {   // what k_map_mark + k_frustum<true> d
     orbm_map* p = S->p;
     for (int f = 0; f < S->n_features; ++f) {
         const int s = S->frame_points[f];
-        if (s >= 0 && !(p->h_flags[(size_t)s] & ORBM_POINT_BAD)) p->h_mark[(size_t)s] = p->epoch;
+        if (s >= 0 && !(p->flags.h[(size_t)s] & ORBM_POINT_BAD)) p->mark.h[(size_t)s] = p->epoch;
     }
     for (int i = 0; i < S->n_seen; ++i)
-        if (S->seen[i] >= 0) p->h_mark[(size_t)S->seen[i]] = p->epoch;
+        if (S->seen[i] >= 0) p->mark.h[(size_t)S->seen[i]] = p->epoch;
     for (int i = 0; i < p->list_n; ++i) {
         const size_t s = (size_t)p->list[(size_t)i];
-        out[i] = ((p->h_flags[s] & ORBM_POINT_BAD) || p->h_mark[s] == p->epoch) ? 1 : 0;
+        out[i] = ((p->flags.h[s] & ORBM_POINT_BAD) || p->mark.h[s] == p->epoch) ? 1 : 0;
     }
 }
 }  // namespace
@@ -430,17 +518,17 @@ int orbm_map_search_local_points(orbm_matcher* m, const orbm_frame* cur, orbm_ma
     if ((rc = next_epoch(m, p))) return rc;
     SkipCtx sc{p, frame_points, n_features, seen, n_seen};
     LocalPointSource S{};
-    S.d_rows = p->d_rows.p; S.h_rows = p->h_rows.data(); S.d_index = p->d_list.p; S.h_index = p->list.data();
-    S.d_mark = p->d_mark.p; S.d_flags = p->d_flags.p; S.epoch = p->epoch; S.host_skip = host_skip; S.host_skip_ctx = &sc;
+    S.d_rows = p->rows.d.p; S.h_rows = p->rows.h.data(); S.d_index = p->d_list.p; S.h_index = p->list.data();
+    S.d_mark = p->mark.d.p; S.d_flags = p->flags.d.p; S.epoch = p->epoch; S.host_skip = host_skip; S.host_skip_ctx = &sc;
     if (!m->host_resolve && n > 0 && n_features + n_seen > 0) {
-        const size_t off_seen = (size_t)n_features * 4;
-        if ((rc = p->stage.reserve(off_seen + (size_t)n_seen * 4 + 16))) return rc;
-        if (n_features) memcpy(p->stage.p, frame_points, (size_t)n_features * 4);
-        if (n_seen) memcpy(p->stage.p + off_seen, seen, (size_t)n_seen * 4);
-        p->stage.publish();
+        StagePack pk;
+        const int i_fp = pk.add(frame_points, (size_t)n_features * 4), i_seen = pk.add(seen, (size_t)n_seen * 4);
+        const StagePack::Block blk = pk.open(p->stage, &rc);
+        if (rc) return rc;
+        blk.publish();
         hipLaunchKernelGGL(k_map_mark, dim3(blocks_of((long long)n_features + n_seen)), dim3(MAP_BLOCK), 0, m->stream,
-                           (const int32_t*)p->stage.dp, n_features, (const int32_t*)(p->stage.dp + off_seen), n_seen,
-                           (const uint8_t*)p->d_flags.p, p->d_mark.p, p->epoch);
+                           blk.dev<int32_t>(i_fp), n_features, blk.dev<int32_t>(i_seen), n_seen, (const uint8_t*)p->flags.d.p, p->mark.d.p,
+                           p->epoch);
         MORB_HIP(hipGetLastError());
     }
     return morb::search_local_points_body(m, cur, p->scr, S, n, view, occupied, nnratio, th_high, track, match_of_feature, n_to_match, nmatches);
@@ -479,10 +567,11 @@ int check_rows(const int32_t* kf_rows, const int32_t* kf_count, int n_kfs, int s
 int build_index_if_dirty(orbm_matcher* m, orbm_map* p) {
     p->last_cov[1] = 0; p->last_cov[2] = p->obs_hw;
     if (!p->index_dirty) return ORB_OK;
-    MORB_HIP(hipMemsetAsync(p->d_head.p, 0xff, (size_t)std::max(p->pt_cap, 1) * sizeof(int32_t), m->stream));
+    int rc;
+    if ((rc = p->head.clear(m->stream))) return rc;
     if (p->obs_hw > 0)
-        hipLaunchKernelGGL(k_map_chain, dim3(blocks_of(p->obs_hw)), dim3(MAP_BLOCK), 0, m->stream, (const orbm_obs*)p->d_obs.p, p->obs_hw,
-                           p->d_head.p, p->d_next.p);
+        hipLaunchKernelGGL(k_map_chain, dim3(blocks_of(p->obs_hw)), dim3(MAP_BLOCK), 0, m->stream, (const orbm_obs*)p->obs.d.p, p->obs_hw,
+                           p->head.d.p, p->next.d.p);
     MORB_HIP(hipGetLastError());
     p->index_dirty = false; p->last_cov[1] = 1;
     return ORB_OK;
@@ -570,48 +659,17 @@ int orbm_local_map_culling_host(const orbm_obs* obs, const int32_t* obs_feature,
     return ORB_OK;
 }
 
-int orbm_debug_last_covisibility(const orbm_map* p, int* out4) {
-    MORB_ARG(p && out4);
-    for (int k = 0; k < 4; ++k) out4[k] = p->last_cov[k];
-    return ORB_OK;
-}
+int orbm_debug_last_covisibility(const orbm_map* p, int* out4) { return copy_last(p, &orbm_map::last_cov, out4); }
 
 int orbm_map_write_observation_features(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n, const int32_t* feature) {
     MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || (slots && feature)));
-    int rc;
-    if ((rc = check_slots(slots, n, 0, p->obs_cap, "record slot")) || (rc = check_slots(feature, n, 0, p->stride, "feature index"))) return rc;
-    if (n == 0) return ORB_OK;
-    MORB_HIP(hipSetDevice(m->device));
-    const size_t off_val = (size_t)n * 4;
-    if ((rc = p->stage.reserve(off_val + (size_t)n * 4 + 16))) return rc;
-    for (int i = 0; i < n; ++i) p->h_obs_feat[(size_t)slots[i]] = feature[i];
-    memcpy(p->stage.p, slots, (size_t)n * 4);   // (staged from the mirror, as the records are: a slot named twice takes its last entry)
-    for (int i = 0; i < n; ++i) memcpy(p->stage.p + off_val + (size_t)i * 4, &p->h_obs_feat[(size_t)slots[i]], 4);
-    p->stage.publish();
-    hipLaunchKernelGGL(k_map_put_words, dim3(blocks_of(n)), dim3(MAP_BLOCK), 0, m->stream, (const uint32_t*)(p->stage.dp + off_val),
-                       (const int32_t*)p->stage.dp, n, 1, (uint32_t*)p->d_obs_feat.p);
-    MORB_HIP(hipGetLastError());
-    MORB_HIP(hipStreamSynchronize(m->stream));
-    return ORB_OK;
+    return write_slots<1>(m, p, p->obs_feat, slots, n, feature, SlotWrite{"record slot"},
+                          [&]() { return check_slots(feature, n, 0, p->stride, "feature index"); });
 }
 
 int orbm_map_write_point_nobs(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n, const int32_t* n_obs) {
     MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || (slots && n_obs)));
-    int rc;
-    if ((rc = check_slots(slots, n, 0, p->pt_cap, "point slot"))) return rc;
-    if (n == 0) return ORB_OK;
-    MORB_HIP(hipSetDevice(m->device));
-    const size_t off_val = (size_t)n * 4;
-    if ((rc = p->stage.reserve(off_val + (size_t)n * 4 + 16))) return rc;
-    for (int i = 0; i < n; ++i) p->h_nobs[(size_t)slots[i]] = n_obs[i];
-    memcpy(p->stage.p, slots, (size_t)n * 4);
-    for (int i = 0; i < n; ++i) memcpy(p->stage.p + off_val + (size_t)i * 4, &p->h_nobs[(size_t)slots[i]], 4);
-    p->stage.publish();
-    hipLaunchKernelGGL(k_map_put_words, dim3(blocks_of(n)), dim3(MAP_BLOCK), 0, m->stream, (const uint32_t*)(p->stage.dp + off_val),
-                       (const int32_t*)p->stage.dp, n, 1, (uint32_t*)p->d_nobs.p);
-    MORB_HIP(hipGetLastError());
-    MORB_HIP(hipStreamSynchronize(m->stream));
-    return ORB_OK;
+    return write_slots<1>(m, p, p->nobs, slots, n, n_obs, SlotWrite{"point slot"});
 }
 
 int orbm_map_write_keyframe_features(orbm_matcher* m, orbm_map* p, int kf, const uint8_t* feature_bytes, int n_features, int n_cam1) {
@@ -622,13 +680,13 @@ int orbm_map_write_keyframe_features(orbm_matcher* m, orbm_map* p, int kf, const
         return kf < 0 ? ORB_E_ARG : ORB_E_CAPACITY;
     }
     MORB_HIP(hipSetDevice(m->device));
-    uint8_t* row = p->h_kf_feat.data() + (size_t)kf * p->stride;
+    uint8_t* row = p->kf_feat.h.data() + (size_t)kf * p->stride;
     if (n_features) memcpy(row, feature_bytes, (size_t)n_features);
     memset(row + n_features, 0, (size_t)(p->stride - n_features));
-    p->h_kf_ncam1[(size_t)kf] = n_cam1;
+    p->kf_ncam1.h[(size_t)kf] = n_cam1;
     // the whole row travels: a record of another keyframe's point may name any feature of this one
-    MORB_HIP(hipMemcpyAsync(p->d_kf_feat.p + (size_t)kf * p->stride, row, (size_t)p->stride, hipMemcpyHostToDevice, m->stream));
-    MORB_HIP(hipMemcpyAsync(p->d_kf_ncam1.p + kf, &p->h_kf_ncam1[(size_t)kf], 4, hipMemcpyHostToDevice, m->stream));
+    MORB_HIP(hipMemcpyAsync(p->kf_feat.d.p + (size_t)kf * p->stride, row, (size_t)p->stride, hipMemcpyHostToDevice, m->stream));
+    MORB_HIP(hipMemcpyAsync(p->kf_ncam1.d.p + kf, &p->kf_ncam1.h[(size_t)kf], 4, hipMemcpyHostToDevice, m->stream));
     MORB_HIP(hipStreamSynchronize(m->stream));
     return ORB_OK;
 }
@@ -642,8 +700,8 @@ int orbm_map_covisibility(orbm_matcher* m, orbm_map* p, const int32_t* kfs, int 
     if (m->host_resolve) {   // MORB_HOST_RESOLVE=1: the host routine over the mirror
         p->last_cov[0] = 0; p->last_cov[1] = 0; p->last_cov[2] = p->obs_hw;
         std::vector<orbm_covis_entry> tmp((size_t)std::max(entries_cap, 1));
-        rc = orbm_local_map_covisibility_host(p->h_obs.data(), p->h_obs_feat.data(), p->obs_hw, p->h_flags.data(), p->pt_cap, p->h_kf_rows.data(),
-                                              p->h_kf_count.data(), p->h_kf_ncam1.data(), p->kf_hw, p->stride, kfs, n, first_out, tmp.data(),
+        rc = orbm_local_map_covisibility_host(p->obs.h.data(), p->obs_feat.h.data(), p->obs_hw, p->flags.h.data(), p->pt_cap, p->kf_rows.h.data(),
+                                              p->kf_count.h.data(), p->kf_ncam1.h.data(), p->kf_hw, p->stride, kfs, n, first_out, tmp.data(),
                                               entries_cap);
         if (rc == ORB_E_CAPACITY) { const int32_t need = first_out[n]; for (int j = 0; j < n; ++j) first_out[j] = 0; first_out[n] = need; }
         if (rc == ORB_OK && first_out[n] > 0) memcpy(entries, tmp.data(), (size_t)first_out[n] * sizeof(orbm_covis_entry));
@@ -654,16 +712,15 @@ int orbm_map_covisibility(orbm_matcher* m, orbm_map* p, const int32_t* kfs, int 
     if ((rc = build_index_if_dirty(m, p))) return rc;
     first_out[0] = 0;
     if (n == 0) { MORB_HIP(hipStreamSynchronize(m->stream)); return ORB_OK; }
-    if ((rc = p->stage.reserve((size_t)n * 4 + 16)) || (rc = p->h_span.reserve((size_t)n * 2)) ||
+    const int32_t* d_kfs;
+    if ((rc = stage_slots(p, kfs, n, &d_kfs)) || (rc = p->h_span.reserve((size_t)n * 2)) ||
         (rc = p->h_entries.reserve((size_t)std::max(entries_cap, 1)))) return rc;
-    memcpy(p->stage.p, kfs, (size_t)n * 4);
-    p->stage.publish();
     MORB_HIP(hipMemsetAsync(p->d_cursor.p, 0, sizeof(int32_t), m->stream));
     const int nk = p->kf_hw;
     hipLaunchKernelGGL(k_map_covis, dim3(n), dim3(MAP_BLOCK), ((size_t)nk + MAP_BLOCK / 64 + 1) * sizeof(int32_t), m->stream,
-                       (const int32_t*)p->stage.dp, (const int32_t*)p->d_kf_rows.p, (const int32_t*)p->d_kf_count.p,
-                       (const int32_t*)p->d_kf_ncam1.p, p->stride, (const uint8_t*)p->d_flags.p, (const orbm_obs*)p->d_obs.p,
-                       (const int32_t*)p->d_obs_feat.p, (const int32_t*)p->d_head.p, (const int32_t*)p->d_next.p, nk, p->d_cursor.p,
+                       d_kfs, (const int32_t*)p->kf_rows.d.p, (const int32_t*)p->kf_count.d.p,
+                       (const int32_t*)p->kf_ncam1.d.p, p->stride, (const uint8_t*)p->flags.d.p, (const orbm_obs*)p->obs.d.p,
+                       (const int32_t*)p->obs_feat.d.p, (const int32_t*)p->head.d.p, (const int32_t*)p->next.d.p, nk, p->d_cursor.p,
                        p->h_span.dp, p->h_entries.dp, entries_cap);
     MORB_HIP(hipGetLastError());
     MORB_HIP(hipStreamSynchronize(m->stream));
@@ -691,21 +748,20 @@ int orbm_map_culling_counts(orbm_matcher* m, orbm_map* p, const int32_t* kfs, in
     p->last_cov[3] = n;
     if (m->host_resolve) {   // MORB_HOST_RESOLVE=1: the host routine over the mirror
         p->last_cov[0] = 0; p->last_cov[1] = 0; p->last_cov[2] = p->obs_hw;
-        return orbm_local_map_culling_host(p->h_obs.data(), p->h_obs_feat.data(), p->obs_hw, p->h_flags.data(), p->h_nobs.data(), p->pt_cap,
-                                           p->h_kf_rows.data(), p->h_kf_count.data(), p->h_kf_feat.data(), p->kf_hw, p->stride, kfs, n, mono,
+        return orbm_local_map_culling_host(p->obs.h.data(), p->obs_feat.h.data(), p->obs_hw, p->flags.h.data(), p->nobs.h.data(), p->pt_cap,
+                                           p->kf_rows.h.data(), p->kf_count.h.data(), p->kf_feat.h.data(), p->kf_hw, p->stride, kfs, n, mono,
                                            counts_out);
     }
     p->last_cov[0] = 1;
     MORB_HIP(hipSetDevice(m->device));
     if ((rc = build_index_if_dirty(m, p))) return rc;
     if (n == 0) { MORB_HIP(hipStreamSynchronize(m->stream)); return ORB_OK; }
-    if ((rc = p->stage.reserve((size_t)n * 4 + 16)) || (rc = p->h_counts.reserve((size_t)n * 2))) return rc;
-    memcpy(p->stage.p, kfs, (size_t)n * 4);
-    p->stage.publish();
-    hipLaunchKernelGGL(k_map_cull, dim3(n), dim3(MAP_BLOCK), 0, m->stream, (const int32_t*)p->stage.dp, (const int32_t*)p->d_kf_rows.p,
-                       (const int32_t*)p->d_kf_count.p, (const uint8_t*)p->d_kf_feat.p, p->stride, (const uint8_t*)p->d_flags.p,
-                       (const int32_t*)p->d_nobs.p, (const orbm_obs*)p->d_obs.p, (const int32_t*)p->d_obs_feat.p, (const int32_t*)p->d_head.p,
-                       (const int32_t*)p->d_next.p, mono ? 1 : 0, p->h_counts.dp);
+    const int32_t* d_kfs;
+    if ((rc = stage_slots(p, kfs, n, &d_kfs)) || (rc = p->h_counts.reserve((size_t)n * 2))) return rc;
+    hipLaunchKernelGGL(k_map_cull, dim3(n), dim3(MAP_BLOCK), 0, m->stream, d_kfs, (const int32_t*)p->kf_rows.d.p,
+                       (const int32_t*)p->kf_count.d.p, (const uint8_t*)p->kf_feat.d.p, p->stride, (const uint8_t*)p->flags.d.p,
+                       (const int32_t*)p->nobs.d.p, (const orbm_obs*)p->obs.d.p, (const int32_t*)p->obs_feat.d.p, (const int32_t*)p->head.d.p,
+                       (const int32_t*)p->next.d.p, mono ? 1 : 0, p->h_counts.dp);
     MORB_HIP(hipGetLastError());
     MORB_HIP(hipStreamSynchronize(m->stream));
     memcpy(counts_out, p->h_counts.p, (size_t)n * 2 * sizeof(int32_t));
@@ -719,22 +775,11 @@ namespace {
 constexpr int POS_STRIDE_ROWS = (int)(sizeof(orbm_point) / sizeof(float));   // the mirror's rows as a strided array of positions
 static_assert(offsetof(orbm_point, pos) == 0 && sizeof(orbm_point) % sizeof(float) == 0, "a row begins with its position");
 
-inline size_t pad8(size_t n) { return (n + 7) & ~(size_t)7; }
-
-// The positions of the listed slots from the mirror into their rows in HBM (a slot named twice is staged twice with the same bytes).
-// Enqueues only: the caller synchronises.
+// The positions of the listed slots as the mirror holds them into their rows in HBM, and the stream synchronised (an empty list
+// included): how the host routes of both corrections end, once the host routine has moved the mirror's points.
 int put_positions(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n) {
-    if (n == 0) return ORB_OK;
-    int rc;
-    const size_t off_pos = pad8((size_t)n * 4);
-    if ((rc = p->stage.reserve(off_pos + (size_t)n * 12 + 16))) return rc;
-    memcpy(p->stage.p, slots, (size_t)n * 4);
-    for (int i = 0; i < n; ++i) memcpy(p->stage.p + off_pos + (size_t)i * 12, p->h_rows[(size_t)slots[i]].pos, 12);
-    p->stage.publish();
-    hipLaunchKernelGGL(k_map_put_positions, dim3(blocks_of((long long)n * 3)), dim3(MAP_BLOCK), 0, m->stream,
-                       (const float*)(p->stage.dp + off_pos), (const int32_t*)p->stage.dp, n, p->d_rows.p);
-    MORB_HIP(hipGetLastError());
-    return ORB_OK;
+    if (n == 0) { MORB_HIP(hipStreamSynchronize(m->stream)); return ORB_OK; }
+    return write_slots<3>(m, p, p->rows, slots, n, nullptr, SlotWrite{"point slot"});
 }
 
 int check_sim3_args(const int32_t* kfs, int n, const double* before, const double* after, const int32_t* already, int n_already,
@@ -857,11 +902,7 @@ int orbm_local_map_correct_rigid_host(float* pos, int pos_stride, const uint8_t*
 
 int orbm_map_points(const orbm_map* p) { return p ? p->pt_hw : ORB_E_ARG; }
 
-int orbm_debug_last_correction(const orbm_map* p, int* out4) {
-    MORB_ARG(p && out4);
-    for (int k = 0; k < 4; ++k) out4[k] = p->last_cor[k];
-    return ORB_OK;
-}
+int orbm_debug_last_correction(const orbm_map* p, int* out4) { return copy_last(p, &orbm_map::last_cor, out4); }
 
 int orbm_debug_map_read_points(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n, orbm_point* rows) {
     MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || (slots && rows)));
@@ -871,7 +912,7 @@ int orbm_debug_map_read_points(orbm_matcher* m, orbm_map* p, const int32_t* slot
     MORB_HIP(hipSetDevice(m->device));
     const int lo = *std::min_element(slots, slots + n), hi = *std::max_element(slots, slots + n);
     std::vector<orbm_point> span((size_t)(hi - lo + 1));
-    MORB_HIP(hipMemcpyAsync(span.data(), p->d_rows.p + lo, span.size() * sizeof(orbm_point), hipMemcpyDeviceToHost, m->stream));
+    MORB_HIP(hipMemcpyAsync(span.data(), p->rows.d.p + lo, span.size() * sizeof(orbm_point), hipMemcpyDeviceToHost, m->stream));
     MORB_HIP(hipStreamSynchronize(m->stream));
     for (int i = 0; i < n; ++i) rows[i] = span[(size_t)(slots[i] - lo)];
     return ORB_OK;
@@ -879,36 +920,12 @@ int orbm_debug_map_read_points(orbm_matcher* m, orbm_map* p, const int32_t* slot
 
 int orbm_map_write_positions(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n, const float* pos3) {
     MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || (slots && pos3)));
-    int rc;
-    if ((rc = check_slots(slots, n, 0, p->pt_cap, "point slot"))) return rc;
-    if (n == 0) return ORB_OK;
-    MORB_HIP(hipSetDevice(m->device));
-    for (int i = 0; i < n; ++i) {
-        memcpy(p->h_rows[(size_t)slots[i]].pos, pos3 + 3 * (size_t)i, 12);
-        p->pt_hw = std::max(p->pt_hw, slots[i] + 1);
-    }
-    if ((rc = put_positions(m, p, slots, n))) return rc;   // (staged from the mirror: a slot named twice takes its last entry)
-    MORB_HIP(hipStreamSynchronize(m->stream));
-    return ORB_OK;
+    return write_slots<3>(m, p, p->rows, slots, n, pos3, SlotWrite{"point slot", &p->pt_hw});
 }
 
 int orbm_map_write_point_ref(orbm_matcher* m, orbm_map* p, const int32_t* slots, int n, const int32_t* ref_kf) {
     MORB_ARG(m && p && p->owner == m && n >= 0 && (n == 0 || (slots && ref_kf)));
-    int rc;
-    if ((rc = check_slots(slots, n, 0, p->pt_cap, "point slot"))) return rc;
-    if (n == 0) return ORB_OK;
-    MORB_HIP(hipSetDevice(m->device));
-    const size_t off_val = (size_t)n * 4;
-    if ((rc = p->stage.reserve(off_val + (size_t)n * 4 + 16))) return rc;
-    for (int i = 0; i < n; ++i) { p->h_ref[(size_t)slots[i]] = ref_kf[i]; p->pt_hw = std::max(p->pt_hw, slots[i] + 1); }
-    memcpy(p->stage.p, slots, (size_t)n * 4);
-    for (int i = 0; i < n; ++i) memcpy(p->stage.p + off_val + (size_t)i * 4, &p->h_ref[(size_t)slots[i]], 4);
-    p->stage.publish();
-    hipLaunchKernelGGL(k_map_put_words, dim3(blocks_of(n)), dim3(MAP_BLOCK), 0, m->stream, (const uint32_t*)(p->stage.dp + off_val),
-                       (const int32_t*)p->stage.dp, n, 1, (uint32_t*)p->d_ref.p);
-    MORB_HIP(hipGetLastError());
-    MORB_HIP(hipStreamSynchronize(m->stream));
-    return ORB_OK;
+    return write_slots<1>(m, p, p->ref, slots, n, ref_kf, SlotWrite{"point slot", &p->pt_hw});
 }
 
 int orbm_map_correct_sim3(orbm_matcher* m, orbm_map* p, const int32_t* kfs, int n, const double* sim3_before, const double* sim3_after,
@@ -920,32 +937,30 @@ int orbm_map_correct_sim3(orbm_matcher* m, orbm_map* p, const int32_t* kfs, int 
     *n_out = 0;
     if (check_slots(kfs, n, 0, p->kf_hw, "keyframe")) return ORB_E_ARG;
     for (int i = 0; i < n_already; ++i) MORB_ARG(already[i] < p->pt_cap);
-    long long cand = 0; int fmax = 0;
-    for (int j = 0; j < n; ++j) { const int c = p->h_kf_count[(size_t)kfs[j]]; cand += c; fmax = std::max(fmax, c); }
-    p->last_cor[1] = (int)std::min<long long>(cand, 0x7fffffff); p->last_cor[2] = 0; p->last_cor[3] = n;
+    const Claim claim(p, kfs, n);
+    p->last_cor[1] = (int)std::min<long long>(claim.cand, 0x7fffffff); p->last_cor[2] = 0; p->last_cor[3] = n;
     MORB_HIP(hipSetDevice(m->device));
     if (m->host_resolve) {   // MORB_HOST_RESOLVE=1: the host routine over the mirror, the new positions then sent to their rows
         p->last_cor[0] = 0;
-        rc = orbm_local_map_correct_sim3_host(p->h_kf_rows.data(), p->h_kf_count.data(), p->kf_hw, p->stride, p->h_flags.data(),
-                                              p->pt_cap ? p->h_rows[0].pos : nullptr, POS_STRIDE_ROWS, p->pt_cap, kfs, n, sim3_before,
+        rc = orbm_local_map_correct_sim3_host(p->kf_rows.h.data(), p->kf_count.h.data(), p->kf_hw, p->stride, p->flags.h.data(),
+                                              p->pt_cap ? p->rows.h[0].pos : nullptr, POS_STRIDE_ROWS, p->pt_cap, kfs, n, sim3_before,
                                               sim3_after, already, n_already, entries, pos_out, cap, n_out, Tiw_out);
         if (rc) return rc;
         p->last_cor[2] = *n_out;
         std::vector<int32_t> moved((size_t)*n_out);
         for (int i = 0; i < *n_out; ++i) moved[(size_t)i] = entries[i].point;
-        if ((rc = put_positions(m, p, moved.data(), *n_out))) return rc;
-        MORB_HIP(hipStreamSynchronize(m->stream));
-        return ORB_OK;
+        return put_positions(m, p, moved.data(), *n_out);
     }
     p->last_cor[0] = 1;
     for (int j = 0; j < n; ++j) eg_Tiw(sim3_after + 8 * (size_t)j, Tiw_out + 16 * (size_t)j);   // :714-720
-    if (fmax == 0) return ORB_OK;
-    const int bpk = (fmax + MAP_BLOCK - 1) / MAP_BLOCK, nb = n * bpk;
-    const int n_launch = (int)std::min<long long>(cap, cand);
-    const size_t off_table = pad8((size_t)n * 4), off_already = off_table + (size_t)n * MAP_SIM3_TABLE * sizeof(double);
-    if ((rc = p->stage.reserve(off_already + (size_t)n_already * 4 + 16)) || (rc = p->d_block.reserve((size_t)nb)) ||
-        (rc = p->d_centries.reserve((size_t)std::max(n_launch, 1))) || (rc = p->h_centries.reserve((size_t)std::max(n_launch, 1))) ||
-        (rc = p->h_cpos.reserve((size_t)std::max(n_launch, 1) * 3))) return rc;
+    if (claim.fmax == 0) return ORB_OK;
+    const int n_launch = (int)std::min<long long>(cap, claim.cand);
+    StagePack pk;
+    const int i_kfs = pk.add(kfs, (size_t)n * 4), i_table = pk.add_in_place((size_t)n * MAP_SIM3_TABLE * sizeof(double));
+    const int i_already = pk.add(already, (size_t)n_already * 4);
+    const StagePack::Block blk = pk.open(p->stage, &rc);
+    if (rc || (rc = claim.reserve(p)) || (rc = p->d_centries.reserve((size_t)std::max(n_launch, 1))) ||
+        (rc = p->h_centries.reserve((size_t)std::max(n_launch, 1))) || (rc = p->h_cpos.reserve((size_t)std::max(n_launch, 1) * 3))) return rc;
     // two epochs: the claim's, and a NEWER one for the points already corrected -- a newer key is smaller than every key of the claim
     uint32_t e_claim, e_skip;
     do {
@@ -954,33 +969,25 @@ int orbm_map_correct_sim3(orbm_matcher* m, orbm_map* p, const int32_t* kfs, int 
         if ((rc = next_epoch(m, p))) return rc;
         e_skip = p->epoch;
     } while (e_skip < e_claim);   // (the counter wrapped in between: both again)
-    memcpy(p->stage.p, kfs, (size_t)n * 4);
-    {
-        double entry[MAP_SIM3_TABLE];
-        for (int j = 0; j < n; ++j) {
-            map_sim3_table_entry(sim3_before + 8 * (size_t)j, sim3_after + 8 * (size_t)j, entry);
-            memcpy(p->stage.p + off_table + (size_t)j * sizeof(entry), entry, sizeof(entry));
-        }
+    double entry[MAP_SIM3_TABLE];   // (built here, not in the stage: the host only ever stores to that memory)
+    for (int j = 0; j < n; ++j) {
+        map_sim3_table_entry(sim3_before + 8 * (size_t)j, sim3_after + 8 * (size_t)j, entry);
+        memcpy(blk.host<double>(i_table) + (size_t)MAP_SIM3_TABLE * j, entry, sizeof(entry));
     }
-    if (n_already) memcpy(p->stage.p + off_already, already, (size_t)n_already * 4);
-    p->stage.publish();
-    const int32_t* d_kfs = (const int32_t*)p->stage.dp;
-    const int32_t *rows = p->d_kf_rows.p, *cnt = p->d_kf_count.p;
-    const uint8_t* fl = p->d_flags.p;
+    blk.publish();
+    const int32_t* d_kfs = blk.dev<int32_t>(i_kfs);
     if (n_already)
-        hipLaunchKernelGGL(k_map_stamp, dim3(blocks_of(n_already)), dim3(MAP_BLOCK), 0, m->stream, (const int32_t*)(p->stage.dp + off_already),
-                           n_already, p->d_first.p, map_key(e_skip, 0));
-    hipLaunchKernelGGL(k_map_first, dim3(nb), dim3(MAP_BLOCK), 0, m->stream, rows, cnt, d_kfs, p->stride, bpk, fl, p->d_first.p, e_claim);
-    hipLaunchKernelGGL(k_map_count, dim3(nb), dim3(MAP_BLOCK), 0, m->stream, rows, cnt, d_kfs, p->stride, bpk, fl,
-                       (const unsigned long long*)p->d_first.p, e_claim, p->d_block.p);
-    hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(MAP_SCAN_LANES), 0, m->stream, p->d_block.p, nb, p->d_total.p, p->h_total.dp);
-    hipLaunchKernelGGL(k_map_correct_scatter, dim3(nb), dim3(MAP_BLOCK), 0, m->stream, rows, cnt, d_kfs, p->stride, bpk, fl,
-                       (const unsigned long long*)p->d_first.p, e_claim, (const int32_t*)p->d_block.p, (const int32_t*)p->d_total.p,
+        hipLaunchKernelGGL(k_map_stamp, dim3(blocks_of(n_already)), dim3(MAP_BLOCK), 0, m->stream, blk.dev<int32_t>(i_already), n_already,
+                           p->first.d.p, map_key(e_skip, 0));
+    claim.enqueue(m, p, d_kfs, e_claim);
+    hipLaunchKernelGGL(k_map_correct_scatter, dim3(claim.nb), dim3(MAP_BLOCK), 0, m->stream, (const int32_t*)p->kf_rows.d.p,
+                       (const int32_t*)p->kf_count.d.p, d_kfs, p->stride, claim.bpk, (const uint8_t*)p->flags.d.p,
+                       (const unsigned long long*)p->first.d.p, e_claim, (const int32_t*)p->d_block.p, (const int32_t*)p->d_total.p,
                        p->d_centries.p, p->h_centries.dp, n_launch);
     if (n_launch > 0)
         hipLaunchKernelGGL(k_map_correct_sim3, dim3(blocks_of(n_launch)), dim3(MAP_BLOCK), 0, m->stream,
                            (const orbm_correct_entry*)p->d_centries.p, n_launch, (const int32_t*)p->d_total.p, n_launch,
-                           (const double*)(p->stage.dp + off_table), p->d_rows.p, p->h_cpos.dp);
+                           blk.dev<double>(i_table), p->rows.d.p, p->h_cpos.dp);
     MORB_HIP(hipGetLastError());
     MORB_HIP(hipStreamSynchronize(m->stream));
     const int total = p->h_total.p[0];
@@ -993,7 +1000,7 @@ int orbm_map_correct_sim3(orbm_matcher* m, orbm_map* p, const int32_t* kfs, int 
     for (int i = 0; i < total; ++i) {
         entries[i] = p->h_centries.p[i];
         memcpy(pos_out + 3 * (size_t)i, p->h_cpos.p + 3 * (size_t)i, 12);
-        memcpy(p->h_rows[(size_t)entries[i].point].pos, p->h_cpos.p + 3 * (size_t)i, 12);
+        memcpy(p->rows.h[(size_t)entries[i].point].pos, p->h_cpos.p + 3 * (size_t)i, 12);
     }
     return ORB_OK;
 }
@@ -1021,7 +1028,7 @@ int orbm_map_correct_rigid(orbm_matcher* m, orbm_map* p, const int32_t* slots, i
     if (m->host_resolve) {   // MORB_HOST_RESOLVE=1: the host routine over the mirror, the changed positions then sent to their rows
         p->last_cor[0] = 0;
         std::vector<uint8_t> st((size_t)std::max(n, 1));
-        rc = orbm_local_map_correct_rigid_host(p->pt_cap ? p->h_rows[0].pos : nullptr, POS_STRIDE_ROWS, p->h_flags.data(), p->h_ref.data(),
+        rc = orbm_local_map_correct_rigid_host(p->pt_cap ? p->rows.h[0].pos : nullptr, POS_STRIDE_ROWS, p->flags.h.data(), p->ref.h.data(),
                                                p->pt_cap, slots, n, kf_corrected, Tcw_before, Twc_after, n_kfs, gba_slots, gba_pos, n_gba,
                                                st.data(), pos_out);
         if (rc) return rc;
@@ -1030,39 +1037,30 @@ int orbm_map_correct_rigid(orbm_matcher* m, orbm_map* p, const int32_t* slots, i
             if (st[(size_t)i]) moved.push_back(slots ? slots[i] : i);
         p->last_cor[2] = (int)moved.size();
         if (status) memcpy(status, st.data(), (size_t)n);
-        if ((rc = put_positions(m, p, moved.data(), (int)moved.size()))) return rc;
-        MORB_HIP(hipStreamSynchronize(m->stream));
-        return ORB_OK;
+        return put_positions(m, p, moved.data(), (int)moved.size());
     }
     p->last_cor[0] = 1;
     if (n == 0) return ORB_OK;
-    const size_t off_flag = pad8(slots ? (size_t)n * 4 : 0), off_table = off_flag + pad8((size_t)n_kfs);
-    const size_t off_gslots = off_table + pad8((size_t)n_kfs * MAP_RIGID_TABLE * sizeof(float)), off_gpos = off_gslots + pad8((size_t)n_gba * 4);
-    if ((rc = p->stage.reserve(off_gpos + (size_t)n_gba * 12 + 16)) || (rc = p->h_cstatus.reserve((size_t)n)) ||
-        (rc = p->h_cpos.reserve((size_t)n * 3)) || (rc = next_epoch(m, p))) return rc;
-    if (slots) memcpy(p->stage.p, slots, (size_t)n * 4);
-    if (n_kfs) {
-        memcpy(p->stage.p + off_flag, kf_corrected, (size_t)n_kfs);
-        rigid_table(Tcw_before, Twc_after, n_kfs, (float*)(p->stage.p + off_table));
-    }
-    if (n_gba) {
-        memcpy(p->stage.p + off_gslots, gba_slots, (size_t)n_gba * 4);
-        memcpy(p->stage.p + off_gpos, gba_pos, (size_t)n_gba * 12);
-    }
-    p->stage.publish();
+    StagePack pk;
+    const int i_slots = pk.add(slots, slots ? (size_t)n * 4 : 0), i_flag = pk.add(kf_corrected, (size_t)n_kfs);
+    const int i_table = pk.add_in_place((size_t)n_kfs * MAP_RIGID_TABLE * sizeof(float));
+    const int i_gslots = pk.add(gba_slots, (size_t)n_gba * 4), i_gpos = pk.add(gba_pos, (size_t)n_gba * 12);
+    const StagePack::Block blk = pk.open(p->stage, &rc);
+    if (rc || (rc = p->h_cstatus.reserve((size_t)n)) || (rc = p->h_cpos.reserve((size_t)n * 3)) || (rc = next_epoch(m, p))) return rc;
+    rigid_table(Tcw_before, Twc_after, n_kfs, blk.host<float>(i_table));
+    blk.publish();
     if (n_gba)
-        hipLaunchKernelGGL(k_map_stamp_last, dim3(blocks_of(n_gba)), dim3(MAP_BLOCK), 0, m->stream, (const int32_t*)(p->stage.dp + off_gslots),
-                           n_gba, p->d_first.p, p->epoch);
+        hipLaunchKernelGGL(k_map_stamp_last, dim3(blocks_of(n_gba)), dim3(MAP_BLOCK), 0, m->stream, blk.dev<int32_t>(i_gslots), n_gba,
+                           p->first.d.p, p->epoch);
     hipLaunchKernelGGL(k_map_correct_rigid, dim3(std::min<unsigned>(blocks_of(n), MAP_RIGID_MAX_BLOCKS)), dim3(MAP_BLOCK), 0, m->stream,
-                       slots ? (const int32_t*)p->stage.dp : (const int32_t*)nullptr, n, p->d_rows.p, (const uint8_t*)p->d_flags.p,
-                       (const int32_t*)p->d_ref.p, (const uint8_t*)(p->stage.dp + off_flag), (const float*)(p->stage.dp + off_table), n_kfs,
-                       (const unsigned long long*)p->d_first.p, p->epoch, (const float*)(p->stage.dp + off_gpos), p->h_cstatus.dp,
-                       p->h_cpos.dp);
+                       slots ? blk.dev<int32_t>(i_slots) : (const int32_t*)nullptr, n, p->rows.d.p, (const uint8_t*)p->flags.d.p,
+                       (const int32_t*)p->ref.d.p, blk.dev<uint8_t>(i_flag), blk.dev<float>(i_table), n_kfs,
+                       (const unsigned long long*)p->first.d.p, p->epoch, blk.dev<float>(i_gpos), p->h_cstatus.dp, p->h_cpos.dp);
     MORB_HIP(hipGetLastError());
     MORB_HIP(hipStreamSynchronize(m->stream));
     int changed = 0;
     for (int i = 0; i < n; ++i) {
-        float* P = p->h_rows[(size_t)(slots ? slots[i] : i)].pos;
+        float* P = p->rows.h[(size_t)(slots ? slots[i] : i)].pos;
         if (p->h_cstatus.p[i]) { memcpy(P, p->h_cpos.p + 3 * (size_t)i, 12); ++changed; }
         if (pos_out) memcpy(pos_out + 3 * (size_t)i, P, 12);
     }

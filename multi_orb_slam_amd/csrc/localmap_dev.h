@@ -8,6 +8,8 @@
 //                k_map_count     kept candidates per block of 256
 //                k_map_scan      one workgroup: exclusive prefix sum over the block counts, the total
 //                k_map_scatter   the kept slots to their places
+//   writes:      k_map_put_words one lane per 32-bit word: entry r of the staged block into its words of row slots[r] (every slot writer)
+//                k_map_put_flags one lane per entry: the flag bytes of orbm_map_write_points
 //   search:      k_map_mark      the frame's own points and the `seen` list stamped with the call's epoch (k_frustum<true> reads it)
 //   counting:    k_map_chain     one lane per record: the chain from a point to its live records (an exchange on the point's head)
 //                k_map_covis     one workgroup per keyframe: UpdateConnections' two counters in LDS bins, compacted in slot order
@@ -159,16 +161,18 @@ __global__ __launch_bounds__(MAP_BLOCK) void k_map_scatter(const int32_t* __rest
     if (at >= 0 && at < list_cap) { list[at] = c.slot; list_out[at] = c.slot; }
 }
 
-// Scattered writes of orbm_map_write_points / _observations: entry r of the staged block, `words` 32-bit words long, into slot
-// slots[r]; one lane per word.  (A slot named twice was staged twice with the same bytes.)
+// The scattered write of every slot writer (localmap.hip, write_slots): entry r of the staged block, `words` 32-bit words long, into
+// words [offset, offset + words) of row slots[r] of a column whose rows are `pitch` words apart; one lane per word.  (A slot named
+// twice was staged twice with the same bytes.)
 __global__ __launch_bounds__(MAP_BLOCK) void k_map_put_words(const uint32_t* __restrict__ src, const int32_t* __restrict__ slots, int n,
-                                                             int words, uint32_t* __restrict__ dst) {
+                                                             int words, int pitch, int offset, uint32_t* __restrict__ dst) {
     const long long i = (long long)blockIdx.x * MAP_BLOCK + threadIdx.x;
     if (i >= (long long)n * words) return;
     const int r = (int)(i / words), w = (int)(i % words);
-    dst[(size_t)slots[r] * words + w] = src[i];
+    dst[(size_t)slots[r] * pitch + offset + w] = src[i];
 }
 
+// the flag bytes of orbm_map_write_points, staged next to the rows
 __global__ __launch_bounds__(MAP_BLOCK) void k_map_put_flags(const uint8_t* __restrict__ src, const int32_t* __restrict__ slots, int n,
                                                              uint8_t* __restrict__ dst) {
     const int r = blockIdx.x * MAP_BLOCK + threadIdx.x;

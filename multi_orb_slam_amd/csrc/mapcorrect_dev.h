@@ -9,7 +9,8 @@
 //   LoopClosing::RunGlobalBundleAdjustment, step 2 (:953-989)
 //                k_map_stamp_last      the points that take mPosGBA: the LAST entry that names a slot (64-bit minimum under the call's epoch)
 //                k_map_correct_rigid   one lane per slot, grid-stride: the given bytes, or Rwc*(Rcw_before*P + tcw_before) + twc
-// The per-point statements are __host__ __device__: orbm_local_map_correct_*_host run the same ones.
+// The per-point statements are __host__ __device__: orbm_local_map_correct_*_host run the same ones.  Positions written from the host
+// (orbm_map_write_positions, the host routes of both corrections) go through k_map_put_words of localmap_dev.h.
 #pragma once
 #include "localmap_dev.h"
 #include "eg_dev.h"   // eg_load, eg_Tiw; g2o_dev.h sim3_*; cv_dev.h cv_gemm3
@@ -131,14 +132,6 @@ __global__ __launch_bounds__(MAP_BLOCK) void k_map_correct_rigid(const int32_t* 
         }
         status_out[i] = (uint8_t)st;
     }
-}
-
-// orbm_map_write_positions: the three position words of row slots[r], staged from the mirror; one lane per word
-__global__ __launch_bounds__(MAP_BLOCK) void k_map_put_positions(const float* __restrict__ src, const int32_t* __restrict__ slots, int n,
-                                                                 orbm_point* __restrict__ rows) {
-    const long long i = (long long)blockIdx.x * MAP_BLOCK + threadIdx.x;
-    if (i >= (long long)n * 3) return;
-    rows[slots[i / 3]].pos[i % 3] = src[i];
 }
 
 }  // namespace morb

@@ -203,21 +203,24 @@ int ResidentMap::Flush() {
     mLastFlush.record_features = (int)feat_slots.size(); mLastFlush.point_nobs = (int)nobs_slots.size(); mLastFlush.keyframe_features = (int)kf_feat_send.size();
     mLastFlush.point_refs = (int)ref_slots.size();
     if (mpMap) {
-        int rc;
-        if ((rc = orbm_map_write_point_ref(mpHandle, mpMap, ref_slots.data(), (int)ref_slots.size(), refs.data()))) { report("ResidentMap::Flush", "orbm_map_write_point_ref", rc); mbFailed = true; return -1; }
-        if ((rc = orbm_map_write_point_nobs(mpHandle, mpMap, nobs_slots.data(), (int)nobs_slots.size(), nobs.data()))) { report("ResidentMap::Flush", "orbm_map_write_point_nobs", rc); mbFailed = true; return -1; }
-        if ((rc = orbm_map_write_observation_features(mpHandle, mpMap, feat_slots.data(), (int)feat_slots.size(), feats.data()))) { report("ResidentMap::Flush", "orbm_map_write_observation_features", rc); mbFailed = true; return -1; }
+        // a device call that fails leaves the map loud: reported once, and every later Flush returns -1
+        auto sent = [this](const char* call, int rc) {
+            if (rc) { report("ResidentMap::Flush", call, rc); mbFailed = true; }
+            return rc == 0;
+        };
+        if (!sent("orbm_map_write_point_ref", orbm_map_write_point_ref(mpHandle, mpMap, ref_slots.data(), (int)ref_slots.size(), refs.data()))) return -1;
+        if (!sent("orbm_map_write_point_nobs", orbm_map_write_point_nobs(mpHandle, mpMap, nobs_slots.data(), (int)nobs_slots.size(), nobs.data()))) return -1;
+        if (!sent("orbm_map_write_observation_features",
+                  orbm_map_write_observation_features(mpHandle, mpMap, feat_slots.data(), (int)feat_slots.size(), feats.data()))) return -1;
         for (int slot : kf_feat_send)
-            if ((rc = orbm_map_write_keyframe_features(mpHandle, mpMap, slot, mvKeyFrameFeatures.data() + (size_t)slot * mCap.features_per_keyframe,
-                                                       mCap.features_per_keyframe, mvKeyFrameNCam1[(size_t)slot]))) {
-                report("ResidentMap::Flush", "orbm_map_write_keyframe_features", rc); mbFailed = true; return -1;
-            }
-        if ((rc = orbm_map_write_points(mpHandle, mpMap, row_slots.data(), (int)row_slots.size(), rows.data(), flags.data()))) { report("ResidentMap::Flush", "orbm_map_write_points", rc); mbFailed = true; return -1; }
-        if ((rc = orbm_map_write_observations(mpHandle, mpMap, rec_slots.data(), (int)rec_slots.size(), recs.data()))) { report("ResidentMap::Flush", "orbm_map_write_observations", rc); mbFailed = true; return -1; }
+            if (!sent("orbm_map_write_keyframe_features",
+                      orbm_map_write_keyframe_features(mpHandle, mpMap, slot, mvKeyFrameFeatures.data() + (size_t)slot * mCap.features_per_keyframe,
+                                                       mCap.features_per_keyframe, mvKeyFrameNCam1[(size_t)slot]))) return -1;
+        if (!sent("orbm_map_write_points", orbm_map_write_points(mpHandle, mpMap, row_slots.data(), (int)row_slots.size(), rows.data(), flags.data()))) return -1;
+        if (!sent("orbm_map_write_observations", orbm_map_write_observations(mpHandle, mpMap, rec_slots.data(), (int)rec_slots.size(), recs.data()))) return -1;
         for (const KfSend& k : kf_send)
-            if ((rc = orbm_map_write_keyframe(mpHandle, mpMap, k.slot, mvKeyFrameRows.data() + (size_t)k.slot * mCap.features_per_keyframe, k.n, mvKeyFrameBad[(size_t)k.slot]))) {
-                report("ResidentMap::Flush", "orbm_map_write_keyframe", rc); mbFailed = true; return -1;
-            }
+            if (!sent("orbm_map_write_keyframe", orbm_map_write_keyframe(mpHandle, mpMap, k.slot, mvKeyFrameRows.data() + (size_t)k.slot * mCap.features_per_keyframe,
+                                                                         k.n, mvKeyFrameBad[(size_t)k.slot]))) return -1;
     }
     return mLastFlush.rows + mLastFlush.records + mLastFlush.keyframes;
 }

@@ -841,6 +841,23 @@ class ResidentMap:
         check(_lib.lib().orbm_map_create(matcher._h, self.kf_capacity, self.point_capacity, self.obs_capacity,
                                          self.features_per_keyframe, C.byref(self._h)))
 
+    def _write(self, name, slots, values):
+        """One value per listed slot into a column (orbm_map_write_<name>)."""
+        slots = _i32(slots)
+        assert len(values) == len(slots)
+        check(getattr(_lib.lib(), "orbm_map_write_" + name)(self._m._h, self._h, ptr(slots), len(slots), ptr(values)))
+
+    def _last(self, name):
+        out = (C.c_int * 4)()
+        check(getattr(_lib.lib(), "orbm_debug_last_" + name)(self._h, out))
+        return tuple(out)
+
+    def _high_water(self, name):
+        n = int(getattr(_lib.lib(), name)(self._h))
+        if n < 0:
+            raise _lib.OrbError(n, name + " on a closed map")
+        return n
+
     def write_points(self, slots, rows, flags=None):
         """Rows (POINT_DTYPE) and flag bytes into the listed point slots, one call (orbm_map_write_points)."""
         slots = _i32(slots); rows = np.ascontiguousarray(rows, POINT_DTYPE)
@@ -850,9 +867,7 @@ class ResidentMap:
 
     def write_observations(self, slots, records):
         """Records (OBS_DTYPE; point -1 frees the slot) into the listed record slots (orbm_map_write_observations)."""
-        slots = _i32(slots); rec = np.ascontiguousarray(records, OBS_DTYPE)
-        assert len(rec) == len(slots)
-        check(_lib.lib().orbm_map_write_observations(self._m._h, self._h, ptr(slots), len(slots), ptr(rec)))
+        self._write("observations", slots, np.ascontiguousarray(records, OBS_DTYPE))
 
     def write_keyframe(self, kf, point_of_feature, bad=False):
         pof = _i32(point_of_feature)
@@ -864,10 +879,7 @@ class ResidentMap:
     @property
     def keyframes(self):
         """Keyframe high-water mark (orbm_map_keyframes)."""
-        n = int(_lib.lib().orbm_map_keyframes(self._h))
-        if n < 0:
-            raise _lib.OrbError(n, "orbm_map_keyframes on a closed map")
-        return n
+        return self._high_water("orbm_map_keyframes")
 
     def keyframe_bad(self, kf):
         r = int(_lib.lib().orbm_map_keyframe_bad(self._h, int(kf)))
@@ -903,15 +915,11 @@ class ResidentMap:
     def last_local_map(self):
         """(1 if the last vote / point list ran on the device, records scanned by the last vote, candidates of the last point list,
         points it kept) (orbm_debug_last_local_map)."""
-        out = (C.c_int * 4)()
-        check(_lib.lib().orbm_debug_last_local_map(self._h, out))
-        return tuple(out)
+        return self._last("local_map")
 
     def write_observation_features(self, slots, feature):
         """The feature index of each listed record in its keyframe (orbm_map_write_observation_features)."""
-        slots = _i32(slots); ft = _i32(feature)
-        assert len(ft) == len(slots)
-        check(_lib.lib().orbm_map_write_observation_features(self._m._h, self._h, ptr(slots), len(slots), ptr(ft)))
+        self._write("observation_features", slots, _i32(feature))
 
     def write_keyframe_features(self, kf, feature_bytes, n_cam1):
         """One byte per feature of keyframe slot kf (bits 0-4 the level, bit 7 far) and its camera-1 feature count
@@ -921,9 +929,7 @@ class ResidentMap:
 
     def write_point_nobs(self, slots, n_obs):
         """MapPoint::Observations() of each listed point slot (orbm_map_write_point_nobs)."""
-        slots = _i32(slots); no = _i32(n_obs)
-        assert len(no) == len(slots)
-        check(_lib.lib().orbm_map_write_point_nobs(self._m._h, self._h, ptr(slots), len(slots), ptr(no)))
+        self._write("point_nobs", slots, _i32(n_obs))
 
     def covisibility(self, kfs, entries_cap=None):
         """orbm_map_covisibility -> one COVIS_DTYPE array per listed keyframe (all > 0, ascending keyframe slot).  entries_cap None:
@@ -949,29 +955,20 @@ class ResidentMap:
     def last_covisibility(self):
         """(1 if the last covisibility / culling call ran on the device, 1 if it rebuilt the point -> records index, records indexed,
         keyframes processed) (orbm_debug_last_covisibility)."""
-        out = (C.c_int * 4)()
-        check(_lib.lib().orbm_debug_last_covisibility(self._h, out))
-        return tuple(out)
+        return self._last("covisibility")
 
     @property
     def points(self):
         """Point high-water mark (orbm_map_points)."""
-        n = int(_lib.lib().orbm_map_points(self._h))
-        if n < 0:
-            raise _lib.OrbError(n, "orbm_map_points on a closed map")
-        return n
+        return self._high_water("orbm_map_points")
 
     def write_positions(self, slots, pos):
         """The position field alone of the listed point slots (orbm_map_write_positions)."""
-        slots = _i32(slots); P = _f32(pos, 3)
-        assert len(P) == len(slots)
-        check(_lib.lib().orbm_map_write_positions(self._m._h, self._h, ptr(slots), len(slots), ptr(P)))
+        self._write("positions", slots, _f32(pos, 3))
 
     def write_point_ref(self, slots, ref_kf):
         """The keyframe slot of each listed point's reference keyframe (orbm_map_write_point_ref)."""
-        slots = _i32(slots); rf = _i32(ref_kf)
-        assert len(rf) == len(slots)
-        check(_lib.lib().orbm_map_write_point_ref(self._m._h, self._h, ptr(slots), len(slots), ptr(rf)))
+        self._write("point_ref", slots, _i32(ref_kf))
 
     def correct_sim3(self, kfs, sim3_before, sim3_after, already=(), cap=None):
         """orbm_map_correct_sim3 -> (entries CORRECT_DTYPE, pos_out k x 3, Tiw n x 4 x 4); the rows change in place.  cap None: room for
@@ -1002,9 +999,7 @@ class ResidentMap:
     def last_correction(self):
         """(1 if the last correct_sim3 / correct_rigid ran on the device, candidates, points kept or changed, keyframes)
         (orbm_debug_last_correction)."""
-        out = (C.c_int * 4)()
-        check(_lib.lib().orbm_debug_last_correction(self._h, out))
-        return tuple(out)
+        return self._last("correction")
 
     def read_points(self, slots):
         """The rows of the listed point slots as HBM holds them, not the mirror (orbm_debug_map_read_points)."""
